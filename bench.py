@@ -8,6 +8,12 @@ With N > 1 and no launcher environment (WORLD_SIZE unset) bench.py launches the 
 that WORLD_SIZE == --gpus and refuses to print a line for a different world size.  Every rank builds only
 its own share of the graph (gammagl_amd.synth.rmat_partitioned): no rank holds the edge list.
 
+A plain run sets up, warms up, times --steps steps and prints the headline (metric, value, unit, ms_per_step,
+higher_is_better, dtype, the configuration).  Everything below that needs runs of its own — the other association and
+node order, the route comparison, roofline, cpu_baseline, parity, secondary, the N > 1 exchange report — runs with
+--full only.  --dump-outputs DIR writes what the last timed step handed its caller (the loss, every parameter as the
+optimizer left it, the gradient that step computed) as DIR/<name>.npy; same arguments, same inputs.
+
 * a "step" = one full training step of GCNModel(100 -> 256 -> 256 -> 47, norm='none') on
   precomputed symmetric-normalised edge weights (edge_weight = calc_gcn_norm(edge_index), the
   configuration examples/gcn/gcn_trainer.py:59 sketches) over the whole graph: forward (Linear,
@@ -34,7 +40,7 @@ its own share of the graph (gammagl_amd.synth.rmat_partitioned): no rank holds t
   edge sample of the SAME graph, all host threads, median of 3;
 * parity (N = 1): the HIP aggregate on the SAME graph, weights and features the cpu_baseline leg just ran the reference on,
   compared by oracle/parity.py (`rows_bit_exact_frac`, `max_rel_err`); the run exits 3 when it is outside the criterion;
-* secondary (default command only): one full line (value, ms_per_step, roofline, cpu_baseline, parity) per remaining
+* secondary (--full on the default workload only): one full line (value, ms_per_step, roofline, cpu_baseline, parity) per remaining
   BASELINE config — arxiv, reddit-gat, sage-minibatch, papers-share — from child processes with short step counts;
 * roofline fields are recomputable from the line: `traffic` = fabric-side bytes (FETCH_SIZE / WRITE_SIZE, Infinity-Cache
   hits included) of the row walk + the hub walk beside it, corrections calibrated IN THIS RUN on launches of known byte
@@ -107,12 +113,45 @@ def parse():
                         "step, for tools/scaling_model.sh (papers-share is this with 8 parts built in)")
     p.add_argument("--dry-rank", type=int, default=-1, help="the rank played with --dry-parts (default: parts / 2)")
     p.add_argument("--secondary", default="auto", choices=["auto", "on", "off"],
-                   help="auto: the default run (products, N = 1) also runs the other BASELINE configs — arxiv, reddit-gat, "
+                   help="auto: a --full run of products on N = 1 also runs the other BASELINE configs — arxiv, reddit-gat, "
                         "sage-minibatch, papers-share — as child processes with short step counts and appends their full "
                         "lines as `secondary` (driver-timed figures for every config)")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline, measure and check everything else: the other association and node orders, "
+                        "the route comparison, the roofline (kernel timing, counter passes), the CPU baselines and parity, "
+                        "the secondary configs and the N > 1 exchange report.  Without it a run sets up, warms up, times "
+                        "--steps steps and prints the headline; the options above that tune those extras apply to --full runs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one handed its caller (the loss, every parameter as the "
+                        "optimizer left it, the gradient that step computed) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     p.add_argument("--pmc-probe", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--seed", type=int, default=0)
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:
+        args.no_comparison = args.no_exchange_report = args.no_roofline = args.no_cpu_baseline = True
+        args.pmc_traffic, args.secondary = "off", "off"
+    return args
+
+
+DUMP_LIMIT = 64 << 20      # bytes --dump-outputs writes at most, files in all
+
+
+def dump_outputs(outputs, d):
+    """DIR/<name>.npy per output.  When they would hold more than DUMP_LIMIT, arrays of 1 MB and less stay whole and the
+    larger ones are cut to the same fraction: a fixed, seeded sample of their elements (flattened, in order), so that two
+    runs with the same arguments write the same positions."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: v.numpy() for k, v in outputs.items()}
+    small = sum(a.nbytes for a in arrays.values() if a.nbytes <= 1 << 20)
+    large = sum(a.nbytes for a in arrays.values()) - small
+    room = DUMP_LIMIT - 1024 * len(arrays) - small         # (a .npy header is 128 bytes)
+    keep = 1.0 if large <= room else room / large
+    for name, a in arrays.items():
+        if keep < 1.0 and a.nbytes > 1 << 20:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, int(a.size * keep), replace=False))]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -668,7 +707,7 @@ def run_secondary(args, t_start):
             lines.append({"workload": name, "baseline_config": config,
                           "skipped": f"time budget: {spent:.0f} s of {SECONDARY_BUDGET_S:.0f} s used before it started"})
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", name, "--secondary", "off",
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--workload", name, "--full", "--secondary", "off",
                "--no-comparison", "--seed", str(args.seed), "--hidden", str(args.hidden)] + flags
         if name == "papers-share":
             cmd += ["--pmc-traffic", "off"]    # (two more builds of a 93 GB share: its counters live in profiles/)
@@ -972,6 +1011,9 @@ def main():
         if world > 1:
             diagnostic(err)
         raise
+    outputs = ctx.pop("outputs", None)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(outputs, args.dump_outputs)
     route = (out.get("config") or {}).get("route")
     out["engine"] = ("host-emulation (launcher test, not a measurement)" if emul else
                      ("torch.ops.ggl (dispatcher -> libggl_torch.so -> C ABI -> libggl_mpops_hip.so: the route compat/_torch_ext.py binds)"

@@ -48,6 +48,17 @@ def _sync(dev, world):
         torch.cuda.synchronize()
 
 
+def step_outputs(net, loss):
+    """What a caller of the timed step holds after its last step, on the host (bench.py --dump-outputs): the loss, every
+    parameter as the optimizer left it and the gradient that step computed for it."""
+    out = {"loss": torch.tensor([float(loss)], dtype=torch.float64)}
+    for name, p in net.named_parameters():
+        out[name] = p.detach().float().cpu()
+        if p.grad is not None:
+            out[name + ".grad"] = p.grad.detach().float().cpu()
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # PMC calibration: two launches of KNOWN byte counts in the access patterns of the aggregate, so that the counter
 # corrections applied to the dominant kernel are measured on this part, in this run (MI355X_MICROARCH.md, HBM section:
@@ -396,6 +407,7 @@ def run_gcn(args, dev, rank, world, eng=None):
 
     tr = trainer(af_main)
     dt, lsum = _time_steps(tr, data, args, dev, world)
+    outputs = step_outputs(tr.net, lsum) if getattr(args, "dump_outputs", None) else None
     n_agg = tr.net.agg_per_step     # aggregations the step actually executed (counted by the model's forward)
     graphed = bool(getattr(tr, "graphed", False))
     value = n_agg * e_unit * args.steps / dt
@@ -435,17 +447,19 @@ def run_gcn(args, dev, rank, world, eng=None):
 
     # dominant kernel (K = hidden), hipEvents on the launch stream
     K = args.hidden
-    ms_op, launches, gp_t, rows_t, use_halo = dominant_spmm(pg, eng, K, gen, dev)
-    alg = gp_t.E * (4 * K + 8) + pg.n_local * (4 * K + 8)             # SURVEY §8d, per aggregate
-    b_min = 4 * K * (rows_t + pg.n_local) + 8 * gp_t.E + 8 * pg.n_local   # every row once + ids + rowptr
-    rf = roofline_block(
-        f"row_reduce_kernel<float,4,SUM,SPMM> (CSR SpMM-sum, rank 0's {'halo-source' if use_halo else 'local-source'} "
-        f"edge block: {gp_t.E} edges into {pg.n_local} rows from {rows_t} source rows; the K={K} aggregate runs as "
-        f"{launches} launch(es) over {K // max(launches, 1)}-column blocks"
-        + (f"; the {gp_t.fwd.n_long} rows longer than {gp_t.fwd.chunk} elements are summed in the reference's serial order by "
-           f"hub_rows_f32_kernel on a side stream BESIDE each launch: a launch's duration is the later of the two, its "
-           f"traffic the sum of both" if gp_t.fwd.n_long > 0 else "") + ")",
-        launches, ms_op, alg, b_min, gp_t.E)
+    rf = ms_op = gp_t = None
+    if not getattr(args, "no_roofline", False):
+        ms_op, launches, gp_t, rows_t, use_halo = dominant_spmm(pg, eng, K, gen, dev)
+        alg = gp_t.E * (4 * K + 8) + pg.n_local * (4 * K + 8)             # SURVEY §8d, per aggregate
+        b_min = 4 * K * (rows_t + pg.n_local) + 8 * gp_t.E + 8 * pg.n_local   # every row once + ids + rowptr
+        rf = roofline_block(
+            f"row_reduce_kernel<float,4,SUM,SPMM> (CSR SpMM-sum, rank 0's {'halo-source' if use_halo else 'local-source'} "
+            f"edge block: {gp_t.E} edges into {pg.n_local} rows from {rows_t} source rows; the K={K} aggregate runs as "
+            f"{launches} launch(es) over {K // max(launches, 1)}-column blocks"
+            + (f"; the {gp_t.fwd.n_long} rows longer than {gp_t.fwd.chunk} elements are summed in the reference's serial "
+               f"order by hub_rows_f32_kernel on a side stream BESIDE each launch: a launch's duration is the later of the "
+               f"two, its traffic the sum of both" if gp_t.fwd.n_long > 0 else "") + ")",
+            launches, ms_op, alg, b_min, gp_t.E)
 
     kc = n_cls + (-n_cls) % 4
     per_row = 2 * (args.hidden * max(args.layers - 2, 0) + kc)
@@ -524,6 +538,7 @@ def run_gcn(args, dev, rank, world, eng=None):
             orderings.append(entry)
             del tr, gp_b, pg, data
         out["config"]["orderings"] = orderings
+    ctx["outputs"] = outputs
     return out, ctx
 
 
@@ -602,17 +617,20 @@ def run_gat(args, dev, rank, world, eng=None):
         loss = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    outputs = step_outputs(net, loss) if getattr(args, "dump_outputs", None) else None
     walks = 4     # 2 layers x (forward + backward) walks over every edge (the backward of a layer is two walks — by
     #               destination and by source — counted as one aggregation like a GCN layer's transposed SpMM)
-    # dominant kernel: the forward walk of the 8 x 8 layer
-    xg = torch.randn(n, H, C, generator=g, device=dev)
-    el, er = torch.randn(n, H, generator=g, device=dev), torch.randn(n, H, generator=g, device=dev)
-    with torch.no_grad():
-        ms_k = _event_ms(lambda: eng.gat_fused(ei, el, er, xg, 0.2))
-    alg = E * (4 * H * C + 4 * H + 4) + n * (4 * H * C + 8 * H + 8)
-    b_min = n * (4 * H * C + 4 * H) + n * (4 * H * C + 4 * H) + 4 * E + 8 * n
-    rf = roofline_block("gat_fwd2_kernel (fused edge-softmax + weighted aggregate, forward walk of the 8 x 8 layer; "
-                        "one launch + the hub-chunk combine)", 1, ms_k, alg, b_min, E)
+    rf = ms_k = None
+    if not getattr(args, "no_roofline", False):
+        # dominant kernel: the forward walk of the 8 x 8 layer
+        xg = torch.randn(n, H, C, generator=g, device=dev)
+        el, er = torch.randn(n, H, generator=g, device=dev), torch.randn(n, H, generator=g, device=dev)
+        with torch.no_grad():
+            ms_k = _event_ms(lambda: eng.gat_fused(ei, el, er, xg, 0.2))
+        alg = E * (4 * H * C + 4 * H + 4) + n * (4 * H * C + 8 * H + 8)
+        b_min = n * (4 * H * C + 4 * H) + n * (4 * H * C + 4 * H) + 4 * E + 8 * n
+        rf = roofline_block("gat_fwd2_kernel (fused edge-softmax + weighted aggregate, forward walk of the 8 x 8 layer; "
+                            "one launch + the hub-chunk combine)", 1, ms_k, alg, b_min, E)
     out = {"metric": "edges aggregated/sec, 2-layer 8-head GAT training step, Reddit-sized graph (fused edge-softmax + aggregate)",
            "value": walks * E * args.steps / dt, "unit": "edges/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -623,7 +641,7 @@ def run_gat(args, dev, rank, world, eng=None):
                       "walks_per_step": walks, "fused_gat_forward_ms": ms_k, "setup_s": round(t_gen, 2),
                       "loss": float(loss), "parallelism": "1 GPU"},
            "roofline": rf}
-    return out, {"ei": ei, "n": n}
+    return out, {"ei": ei, "n": n, "outputs": outputs}
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -676,20 +694,23 @@ def run_sage(args, dev, rank, world, eng=None):
     if world > 1:
         dist.all_reduce(dtt, op=dist.ReduceOp.MAX)
     dt = float(dtt)
+    outputs = step_outputs(tr.net, loss) if getattr(args, "dump_outputs", None) else None
     # what one batch aggregates: valid edges of its two blocks (outermost first)
     _, blocks, _ = bs.sample(batches[0], caps=caps)
     valid = [(int(b.counts[0]), int(b.counts[1])) for b in blocks]   # (source rows, edges) per block
     e_batch = sum(v[1] for v in valid)
-    # dominant aggregate: the outer block's mean over 100-wide input rows (layer 1 aggregates before it transforms)
-    blk = blocks[0]
-    xin = torch.randn(blk.n_src_cap, f_in, generator=g, device=dev)
-    yout = torch.empty(blk.n_dst_cap, f_in, device=dev)
-    ms_k = _event_ms(lambda: eng.spmm_epi_into(blk.plan, blk.col, None, xin, yout, mean=True), reps=21)
-    alg = valid[0][1] * (4 * f_in + 4) + blk.n_dst_cap * (4 * f_in + 8)
-    b_min = 4 * f_in * (valid[0][0] + blk.n_dst_cap) + 4 * valid[0][1] + 8 * blk.n_dst_cap
-    rf = roofline_block(f"row_reduce_kernel<float,4,MEAN,SPMM_EPI> (the outer block's mean aggregate: {valid[0][1]} sampled edges, "
-                        f"{f_in}-wide rows; a {ms_k * 1e3:.0f} us kernel — the replayed step is bound by its ~110 small kernels, "
-                        f"not by HBM)", 1, ms_k, alg, b_min, valid[0][1])
+    rf = None
+    if not getattr(args, "no_roofline", False):
+        # dominant aggregate: the outer block's mean over 100-wide input rows (layer 1 aggregates before it transforms)
+        blk = blocks[0]
+        xin = torch.randn(blk.n_src_cap, f_in, generator=g, device=dev)
+        yout = torch.empty(blk.n_dst_cap, f_in, device=dev)
+        ms_k = _event_ms(lambda: eng.spmm_epi_into(blk.plan, blk.col, None, xin, yout, mean=True), reps=21)
+        alg = valid[0][1] * (4 * f_in + 4) + blk.n_dst_cap * (4 * f_in + 8)
+        b_min = 4 * f_in * (valid[0][0] + blk.n_dst_cap) + 4 * valid[0][1] + 8 * blk.n_dst_cap
+        rf = roofline_block(f"row_reduce_kernel<float,4,MEAN,SPMM_EPI> (the outer block's mean aggregate: {valid[0][1]} sampled "
+                            f"edges, {f_in}-wide rows; a {ms_k * 1e3:.0f} us kernel — the replayed step is bound by its ~110 small "
+                            f"kernels, not by HBM)", 1, ms_k, alg, b_min, valid[0][1])
     out = {"metric": "sampled-block edges aggregated/sec, GraphSAGE mini-batch training (2048 seeds, fan-out [25,10]), "
                      "products-sized graph",
            "value": world * e_batch * args.steps / dt, "unit": "edges/s", "n_gpus": world, "steps": args.steps,
@@ -706,7 +727,7 @@ def run_sage(args, dev, rank, world, eng=None):
                       "block_capacities": [list(c) for c in caps], "overflowed_hops": bs.overflow_count(),
                       "parallelism": f"{world} replica(s)", "setup_s": round(t_gen, 2), "loss": float(loss)},
            "roofline": rf}
-    return out, {"blocks": blocks, "valid": valid}
+    return out, {"blocks": blocks, "valid": valid, "outputs": outputs}
 
 
 RUNNERS = {"gcn": run_gcn, "gat": run_gat, "sage": run_sage}

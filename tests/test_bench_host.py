@@ -94,3 +94,57 @@ def test_compact_line_keeps_the_contract_fields_under_the_limit():
     d["roofline"]["traffic_source"] = "x" * 5000
     d["config"]["workload"] = "products: " + "y" * 5000
     assert len(b.compact_line(d)) < b.LINE_LIMIT
+
+
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline alone — none of the side figures, checks
+    or roofline the --full run adds — and --dump-outputs writes the last step's loss, parameters and gradients as .npy
+    files (float32 / float64), the same for two runs with the same arguments (host-emulated kernels, GGL_BENCH_EMUL)."""
+    import subprocess
+
+    import numpy as np
+
+    env = dict(os.environ, GGL_BENCH_EMUL="1", GGL_BENCH_DETAIL=str(tmp_path / "detail.json"))
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--workload", "tiny", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        c = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in c, k
+        assert c["steps"] == 3 and c["warmup"] == 1 and c["ms_per_step"] > 0 and c["value"] > 0
+        for k in ("roofline", "cpu_baseline", "parity", "secondary"):
+            assert k not in c, k
+        for k in ("aggregate_first", "orderings", "routes_ms", "exchange"):
+            assert k not in c["config"], k
+        dumps.append({f[: -len(".npy")]: np.load(d / f) for f in os.listdir(d)})
+    a, b = dumps
+    assert {"loss", "lin.0.weight", "lin.0.weight.grad", "bias.2", "bias.2.grad"} <= set(a)
+    assert a["loss"].shape == (1,) and np.isfinite(a["loss"]).all()
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a)
+
+
+def test_dump_outputs_stays_under_the_limit_with_a_fixed_sample(tmp_path):
+    """Outputs larger than 64 MB in all: small arrays are written whole, large ones as the same seeded sample every time."""
+    import numpy as np
+    import torch
+
+    b = _bench()
+    outs = {"loss": torch.tensor([1.5], dtype=torch.float64), "big": torch.arange(16 << 20, dtype=torch.float32),
+            "mid": torch.arange(3 << 20, dtype=torch.float64)}
+    b.dump_outputs(outs, str(tmp_path / "a"))
+    b.dump_outputs(outs, str(tmp_path / "b"))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["big.npy", "loss.npy", "mid.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    got = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert got["loss.npy"].tolist() == [1.5] and got["big.npy"].dtype == np.float32 and got["mid.npy"].dtype == np.float64
+    assert 0 < got["big.npy"].size < 16 << 20 and np.all(np.diff(got["big.npy"]) > 0)     # element values = positions
+    assert all(np.array_equal(got[f], np.load(tmp_path / "b" / f)) for f in files)

@@ -509,8 +509,8 @@ def test_bench_line_contract_on_the_gpu():
     import sys
 
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--workload", "tiny", "--steps", "5", "--warmup", "2"],
-                       capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "--workload", "tiny", "--steps", "5",
+                        "--warmup", "2"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert lines and lines[-1].startswith("{"), r.stdout[-2000:]

@@ -5,7 +5,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out; mkdir -p $O; : > $O/scaling_model.jsonl
 for P in 2 4 8; do
-  timeout 600 python bench.py --dry-parts $P --no-cpu-baseline --pmc-traffic off --also-relabel none > $O/share_products_$P.json 2> $O/share_products_$P.err
+  timeout 600 python bench.py --full --dry-parts $P --no-cpu-baseline --pmc-traffic off --also-relabel none > $O/share_products_$P.json 2> $O/share_products_$P.err
   python -c "
 import json; d=json.load(open('$O/share_products_$P.json')); c=d['config']
 print(json.dumps({'parts': $P, 'train_step_ms': d['ms_per_step'], 'aggregate_first_ms': (c.get('aggregate_first') or {}).get('ms_per_step'),

@@ -8,7 +8,9 @@ mkdir -p gpurun_out gammagl_amd/tuned
 export PYTORCH_TUNABLEOP_ENABLED=1 PYTORCH_TUNABLEOP_TUNING=1 PYTORCH_TUNABLEOP_FILENAME=gpurun_out/tunableop_$WL.csv
 export PYTORCH_TUNABLEOP_MAX_TUNING_DURATION_MS=100 PYTORCH_TUNABLEOP_VERBOSE=0
 # (--hipgraph off: tuning times each solution with host syncs, which a stream capture does not allow)
-timeout 1500 python bench.py --workload $WL --no-cpu-baseline --pmc-traffic off --no-tuned-gemm --hipgraph off --warmup 4 > gpurun_out/tune_$WL.json 2> gpurun_out/tune_$WL.err
+O=$(dirname "$PYTORCH_TUNABLEOP_FILENAME")
+# (--full: the side trainers of the run have GEMM shapes of their own)
+timeout 1500 python bench.py --full --workload $WL --no-cpu-baseline --pmc-traffic off --no-tuned-gemm --hipgraph off --warmup 4 > $O/tune_$WL.json 2> $O/tune_$WL.err
 F=gammagl_amd/tuned/tunableop_gfx950_${WL//-/_}.csv
 cp gpurun_out/tunableop_${WL}0.csv $F
 cat $F | cut -c1-160
