@@ -13,6 +13,7 @@ reductions"):
   ~0 inside a row whose other elements are O(1) has no meaningful relative error of its own; the row's magnitude is the
   scale its rounding errors live on).  Pass = max_rel_err <= tol.
 """
+import numpy as np
 import torch
 
 TOL = 1e-5
@@ -72,9 +73,10 @@ def check(got, ref, what, tol=TOL, rows_in_one_piece=None, floor_min=0.0):
     return r
 
 
-def gat_truth_f64(ei, el, er, x, go, n, slope=0.2):
+def gat_truth_f64(ei, el, er, x, go, n, slope=0.2, attn_keep=None):
     """gat_conv.py:103-112 + softmax.py:29-35 in float64 with torch on the tensors' device, under autograd: the ground truth
     both f32 evaluations of a GAT layer (the fused HIP kernels, the reference ops composed) are measured against.
+    `attn_keep`: optional [E, H] attention-dropout factor (gat_keep_mask) applied to alpha after the softmax.
     Returns (out, gx, g_el, g_er) as float64."""
     src, dst = ei[0], ei[1]
     xd, eld, erd = (t.detach().double().requires_grad_(True) for t in (x, el, er))
@@ -84,6 +86,8 @@ def gat_truth_f64(ei, el, er, x, go, n, slope=0.2):
     ex = torch.exp(s - m[dst])
     den = torch.zeros_like(m).index_add_(0, dst, ex)
     alpha = ex / (den[dst] + 1e-16)
+    if attn_keep is not None:
+        alpha = alpha * attn_keep.to(device=alpha.device, dtype=alpha.dtype)
     out = torch.zeros(n, *x.shape[1:], dtype=torch.float64, device=x.device).index_add_(0, dst, xd[src] * alpha.unsqueeze(-1))
     out.backward(go.double())
     return out.detach(), xd.grad, eld.grad, erd.grad
@@ -97,6 +101,63 @@ def gat_errors_vs_truth(truth, got):
         floor = float(t64.abs().mean()) if name in ("g_el", "g_er") else 0.0
         out[name] = report(a.double().to(t64.device), t64, tol=1.0, floor_min=floor)["max_rel_err"]
     return out
+
+
+def gat_drop_word(index, offset, seed):
+    """numpy restatement of gat_common.hpp drop_word: the attention-dropout word of counter index = p * H + h."""
+    m64 = (1 << 64) - 1
+    z = (int(seed) + int(offset) * 0x9E3779B97F4A7C15) & m64        # drop_key: splitmix64 of the launch's (seed, offset)
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m64
+    z ^= z >> 31
+    k0, k1 = np.uint64(z & 0xFFFFFFFF), np.uint64(z >> 32)
+    idx = np.asarray(index, dtype=np.uint64)
+    m32 = np.uint64(0xFFFFFFFF)
+    lo, hi = idx & m32, idx >> np.uint64(32)
+    x = ((lo ^ k0) * np.uint64(0x9E3779B1)) & m32
+    x ^= x >> np.uint64(15)
+    x = ((x ^ hi ^ k1) * np.uint64(0x85EBCA77)) & m32
+    x ^= x >> np.uint64(13)
+    x = (x * np.uint64(0xC2B2AE3D)) & m32
+    x ^= x >> np.uint64(16)
+    return x.astype(np.uint32)
+
+
+def gat_keep_mask(perm, E, H, seed, offset, p):
+    """The [E, H] attention-dropout factor one fused GAT launch applied, in ORIGINAL edge order (float32, on the host):
+    keep / (1 - p), 0 where dropped.  The kernels draw the word of counter p_s * H + h for sorted position p_s (the
+    destination-sorted plan) and head h, and keep when it is >= the threshold set_dropout derives from the f32 rate;
+    `perm` (the plan's perm, sorted position -> original edge; None = identity) maps the positions back to edges."""
+    p32 = np.float32(p)
+    thresh = np.uint32(int(float(p32) * 4294967296.0))              # (uint32_t)((double)p_drop * 2^32), p_drop a float
+    scale = np.float32(1.0) / (np.float32(1.0) - p32)                # drop_scale = 1.0f / (1.0f - p_drop)
+    keep = np.zeros((E, H), dtype=np.float32)
+    for a in range(0, E, 1 << 22):                                   # (bounded host temporaries at millions of edges)
+        b = min(E, a + (1 << 22))
+        cnt = (np.arange(a, b, dtype=np.int64)[:, None] * H + np.arange(H)[None, :]).reshape(-1)
+        keep[a:b] = (gat_drop_word(cnt, offset, seed).reshape(b - a, H) >= thresh) * scale
+    if perm is None:
+        return torch.from_numpy(keep)
+    pm = perm.cpu().numpy().astype(np.int64) if isinstance(perm, torch.Tensor) else np.asarray(perm, dtype=np.int64)
+    out = np.empty_like(keep)
+    out[pm] = keep
+    return torch.from_numpy(out)
+
+
+def gat_fused_composed(ei, el, er, x, n, slope=0.2, seg=None, attn_keep=None):
+    """The fused layer's op (gat_conv.py:103-112 + softmax.py:29-35) from its logit terms el [N_src, H], er [N_dst, H] and
+    x [N_src, H, C], composed in the tensors' dtype: `seg` = (segment_max, segment_sum) as in gat_conv_composed (None = torch
+    scatters), `attn_keep` = the [E, H] attention-dropout factor.  Differentiable in el, er, x."""
+    seg_max, seg_sum = seg if seg is not None else _torch_segment_ops(x.dtype)
+    src, dst = ei[0], ei[1]
+    s = torch.nn.functional.leaky_relu(el[src] + er[dst], slope)
+    m = seg_max(s, dst, n)
+    ex = torch.exp(s - m[dst])
+    den = seg_sum(ex, dst, n)
+    alpha = ex / (den[dst] + 1e-16)
+    if attn_keep is not None:
+        alpha = alpha * attn_keep.to(device=alpha.device, dtype=alpha.dtype)
+    return seg_sum(x[src] * alpha.unsqueeze(-1), dst, n)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -116,13 +177,14 @@ def _torch_segment_ops(dtype):
     return seg_max, seg_sum
 
 
-def gat_conv_composed(x, W, att, bias, ei, n, heads, out_channels, concat, slope=0.2, seg=None):
+def gat_conv_composed(x, W, att, bias, ei, n, heads, out_channels, concat, slope=0.2, seg=None, attn_keep=None):
     """GATConv.forward exactly as gat_conv.py:98-122 writes it (attention dropout off): matmul, reshape [N, H, C], gather
     source and destination rows, concat, `(feat * att).sum(-1)`, LeakyReLU, segment_softmax (softmax.py:29-35: segment max,
     exp, segment sum, / (den + 1e-16)), message = x[src] * alpha, segment sum into the destinations, then concat heads
     (:112-113) or `reduce_mean` over them (:115-118) and `+ bias` (:120-121).  `seg` = (segment_max, segment_sum): the
     reference's compiled c_segment_max / c_segment_sum for the f32 composition; None = torch scatters in x's dtype (the
-    float64 truth).  Differentiable in x, W, att, bias."""
+    float64 truth).  `attn_keep`: optional [E, H] attention-dropout factor (gat_keep_mask), multiplied into alpha after the
+    softmax as gat_conv.py:104 applies dropout.  Differentiable in x, W, att, bias."""
     seg_max, seg_sum = seg if seg is not None else _torch_segment_ops(x.dtype)
     src, dst = ei[0], ei[1]
     z = (x @ W).reshape(-1, heads, out_channels)
@@ -132,16 +194,18 @@ def gat_conv_composed(x, W, att, bias, ei, n, heads, out_channels, concat, slope
     ex = torch.exp(e - m[dst])
     den = seg_sum(ex, dst, n)
     alpha = ex / (den[dst] + 1e-16)
+    if attn_keep is not None:
+        alpha = alpha * attn_keep.to(device=alpha.device, dtype=alpha.dtype)
     out = seg_sum(z[src] * alpha.unsqueeze(-1), dst, n)
     out = out.reshape(-1, heads * out_channels) if concat else out.mean(dim=1)
     return out + bias if bias is not None else out
 
 
-def gat_conv_lean(x, W, att, bias, ei, n, heads, out_channels, concat, slope=0.2):
+def gat_conv_lean(x, W, att, bias, ei, n, heads, out_channels, concat, slope=0.2, attn_keep=None):
     """gat_conv_composed's math without the [E, H, 2C] concatenation: (cat(z_src, z_dst) * att).sum(-1) = z_src . a_src +
     z_dst . a_dst, taken per NODE before the gather (algebraically identical; in float64 the two differ by ~1e-16) — the largest
     per-edge tensor is then [E, H, C], which lets a float64 evaluation reach 14 M edges (rows of 19 k edges) in 288 GB.  Torch
-    scatters in x's dtype; differentiable in x, W, att, bias."""
+    scatters in x's dtype; `attn_keep` as in gat_conv_composed; differentiable in x, W, att, bias."""
     seg_max, seg_sum = _torch_segment_ops(x.dtype)
     src, dst = ei[0], ei[1]
     C = out_channels
@@ -152,6 +216,8 @@ def gat_conv_lean(x, W, att, bias, ei, n, heads, out_channels, concat, slope=0.2
     ex = torch.exp(e - m[dst])
     den = seg_sum(ex, dst, n)
     alpha = ex / (den[dst] + 1e-16)
+    if attn_keep is not None:
+        alpha = alpha * attn_keep.to(device=alpha.device, dtype=alpha.dtype)
     out = seg_sum(z[src] * alpha.unsqueeze(-1), dst, n)
     out = out.reshape(-1, heads * C) if concat else out.mean(dim=1)
     return out + bias if bias is not None else out
@@ -170,6 +236,21 @@ def kink_free_edges(ei, x, W, att, heads, out_channels, margin=1e-4):
     el, er = (z * a[:, :, :C]).sum(-1), (z * a[:, :, C:]).sum(-1)
     keep = ((el[ei[0]] + er[ei[1]]).abs() >= margin).all(dim=1)
     return ei[:, keep].contiguous(), int((~keep).sum())
+
+
+def near_kink_rows(ei, x, W, att, heads, out_channels, n, margin=1e-4):
+    """bool [n]: the rows touched (as source or destination) by an edge whose float64 logit lies within `margin` of 0 in any
+    head — where an f32 evaluation that forms the logit differently (x @ (W a) against (x W) . a) may take the other slope.
+    Returns (rows, number of such edges)."""
+    C = out_channels
+    z = (x.double() @ W.double()).reshape(-1, heads, C)
+    a = att.double()
+    el, er = (z * a[:, :, :C]).sum(-1), (z * a[:, :, C:]).sum(-1)
+    near = ((el[ei[0]] + er[ei[1]]).abs() < margin).any(dim=1)
+    rows = torch.zeros(n, dtype=torch.bool, device=ei.device)
+    rows[ei[0][near]] = True
+    rows[ei[1][near]] = True
+    return rows, int(near.sum())
 
 
 def kink_free_edges_logits(ei, el, er, margin=1e-4):
@@ -196,14 +277,19 @@ def kink_free_edges_model(ei, x, params, n, heads, slope=0.2, margin=1e-4):
     return ei, dropped
 
 
-def gat_model_composed(x, params, ei, n, heads, slope=0.2, seg=None):
-    """GATModel.forward (models/gat.py:65-72) in eval mode (dropout = identity): `params` = [(W, att, bias), ...] per layer;
-    every layer but the last concatenates its heads and is followed by ELU, the last one averages them (:49-53;
-    a one-layer model's only layer is built by the `i == 0` branch: concat)."""
+def gat_model_composed(x, params, ei, n, heads, slope=0.2, seg=None, attn_keep=None, feat_keep=None):
+    """GATModel.forward (models/gat.py:65-72): `params` = [(W, att, bias), ...] per layer; every layer but the last concatenates
+    its heads and is followed by ELU, the last one averages them (:49-53; a one-layer model's only layer is built by the
+    `i == 0` branch: concat).  Eval mode (dropout = identity) by default; training mode with recorded masks: `feat_keep` = one
+    factor per layer multiplied into the layer's input (the model's nn.Dropout, keep / (1 - p)), `attn_keep` = one [E, H]
+    attention-dropout factor per layer (gat_keep_mask)."""
     L = len(params)
     for i, (W, att, bias) in enumerate(params):
         C = int(att.shape[-1]) // 2
-        x = gat_conv_composed(x, W, att, bias, ei, n, heads, C, concat=(i == 0 or i < L - 1), slope=slope, seg=seg)
+        if feat_keep is not None:
+            x = x * feat_keep[i].to(device=x.device, dtype=x.dtype)
+        x = gat_conv_composed(x, W, att, bias, ei, n, heads, C, concat=(i == 0 or i < L - 1), slope=slope, seg=seg,
+                              attn_keep=None if attn_keep is None else attn_keep[i])
         if i < L - 1:
             x = torch.nn.functional.elu(x)
     return x

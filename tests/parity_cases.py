@@ -10,6 +10,8 @@ reference) and within 1e-5 relative (north_star) where long rows are split into 
 import numpy as np
 import torch
 
+from oracle.parity import gat_drop_word  # noqa: F401  (the attention-dropout word's host restatement; used below)
+
 DT = {"uint8": torch.uint8, "int8": torch.int8, "int16": torch.int16, "int32": torch.int32,
       "int64": torch.int64, "float16": torch.float16, "bfloat16": torch.bfloat16,
       "float32": torch.float32, "float64": torch.float64}
@@ -569,7 +571,8 @@ def _check_gat(eng, dev, oracle, index, N, H, C, rng):
 
 def _check_gat_separate_buffers(eng, dev, index, N, H, C, rng):
     """C-ABI convention check: alpha / de as two [E,H] arrays give the same gradients as the interleaved
-    [E,H,2] buffer the Engine passes (ggl_gat_fused_bwd_dst / _src accept both)."""
+    [E,H,2] buffer the Engine passes (ggl_gat_fused_bwd_dst / _src accept both).  The direct-entry form for the
+    GPU-only fast and head-mean kernels, with every output and partial inside sentinel guard bands: check_gat_guard_bands."""
     import ctypes
 
     from gammagl_amd.ops import _ptr
@@ -624,6 +627,136 @@ def _check_gat_separate_buffers(eng, dev, index, N, H, C, rng):
     assert torch.equal(ger, er.grad) and torch.equal(gel, el.grad) and torch.equal(gx, x.grad)  # deterministic either way
 
 
+GUARD = 4096          # sentinel bytes on each side of a guarded buffer
+SENTINEL = 0xA5
+
+
+def _guarded(nbytes, dev, bufs):
+    """A uint8 view of exactly `nbytes` inside a buffer with GUARD sentinel bytes on both sides (checked by _guards_intact)."""
+    buf = torch.full((2 * GUARD + nbytes,), SENTINEL, dtype=torch.uint8, device=dev)
+    bufs.append((buf, nbytes))
+    return buf[GUARD:GUARD + nbytes]
+
+
+def _guarded_f32(shape, dev, bufs):
+    n = int(np.prod(shape))
+    return _guarded(4 * n, dev, bufs).view(torch.float32).view(*shape)
+
+
+def _guards_intact(bufs, what):
+    torch.cuda.synchronize()
+    for i, (buf, nb) in enumerate(bufs):
+        lo, hi = buf[:GUARD] != SENTINEL, buf[GUARD + nb:] != SENTINEL
+        assert not bool(lo.any()) and not bool(hi.any()), \
+            f"{what}: buffer {i} ({nb} bytes) written outside its bounds ({int(lo.sum())} bytes below, {int(hi.sum())} above)"
+
+
+def _guard_graph(dev, N=3000, E=60000, seed=5):
+    """Hub rows on both sides: a destination hub and a source hub far longer than the chunk the checks set."""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    ei = torch.randint(0, N, (2, E), generator=g, device=dev)
+    ei[1, :5000] = 17
+    ei[0, 5000:8000] = N - 2
+    ei[1, 8000:8600] = N - 1
+    return ei, N
+
+
+def check_gat_guard_bands(eng, dev, chunk=64):
+    """The direct-entry form of _check_gat_separate_buffers for the GPU-only kernels (gat_fast.hip has no host build, so the
+    AddressSanitizer run never sees them): ggl_gat_fast_fwd / _bwd at every fast head width and ggl_gat_sh_fwd / _bwd, with and
+    without attention dropout, on a graph whose hub rows are chunked.  Every output and every plan->partial is a view inside a
+    larger buffer with GUARD sentinel bytes on both sides, each partial sized exactly as include/ggl_mpops.h documents (no
+    slack); the sentinels must be untouched after the forward and after the backward.  The direct results must be the
+    Engine's own, bit for bit (same kernels, same plan, same RNG state)."""
+    import ctypes
+
+    from gammagl_amd.ops import _DTYPE_CODE, _ptr
+
+    f32 = _DTYPE_CODE[torch.float32]
+    st = eng._stream(dev)
+    old = eng.chunk
+    try:
+        eng.chunk = chunk
+        eng.graph_cache.clear(); eng.seg_cache.clear()
+        it, N = _guard_graph(dev)
+        gp = eng.graph_plan(it, N)
+        assert gp.fwd.n_long > 0 and gp.bwd.n_long > 0, "the guard-band graph must have chunked rows both ways"
+        g = torch.Generator(device=dev).manual_seed(9)
+        for (H, C) in ((16, 4), (8, 8), (16, 16), (8, 32), (4, 64)):
+            assert eng.gat_fast and eng.lib.ggl_gat_fast_supported(H, C)
+            el, er = torch.randn(N, H, generator=g, device=dev), torch.randn(N, H, generator=g, device=dev)
+            x, go = torch.randn(N, H, C, generator=g, device=dev), torch.randn(N, H, C, generator=g, device=dev)
+            for p in (0.0, 0.6):
+                tag = f"fast GAT {H}x{C} p={p}"
+                bufs = []
+                out, rmax, rden = (_guarded_f32(s_, dev, bufs) for s_ in ((N, H, C), (N, H), (N, H)))
+                part = _guarded(eng.lib.ggl_gat_partial_bytes(gp.fwd.n_chunks, H, C), dev, bufs)
+                cs = gp.fwd.c_struct(part)
+                rng = eng._rng_state(dev)
+                used = rng.clone()
+                eng._check(eng.lib.ggl_gat_fast_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(el), _ptr(er), _ptr(x), N, 0.2, H, C,
+                                                    p, _ptr(rng) if p else None, _ptr(out), _ptr(rmax), _ptr(rden), st))
+                _guards_intact(bufs, tag + " forward")
+                stats = _guarded_f32((N, H, 4), dev, bufs)
+                gx, gel, ger = (_guarded_f32(s_, dev, bufs) for s_ in ((N, H, C), (N, H), (N, H)))
+                part_f = _guarded(eng.lib.ggl_partial_bytes(f32, gp.fwd.n_chunks, 8 * H, 0), dev, bufs)
+                part_t = _guarded(eng.lib.ggl_partial_bytes(f32, gp.bwd.n_chunks, H * C + H, 0), dev, bufs)
+                cs, csT = gp.fwd.c_struct(part_f), gp.bwd.c_struct(part_t)
+                eng._check(eng.lib.ggl_gat_fast_bwd(
+                    ctypes.byref(cs), _ptr(gp.col), ctypes.byref(csT), _ptr(gp.colT), _ptr(gp.posT if p else None), _ptr(el),
+                    _ptr(er), _ptr(x), _ptr(go), _ptr(out), _ptr(rmax), _ptr(rden), 0.2, H, C, p, _ptr(used) if p else None,
+                    _ptr(stats), _ptr(gx), _ptr(gel), _ptr(ger), st))
+                _guards_intact(bufs, tag + " backward")
+                eng._rng_state(dev).copy_(used)
+                ela, era, xa = (t.clone().requires_grad_(True) for t in (el, er, x))
+                y = eng.gat_fused(it, ela, era, xa, 0.2, dropout_rate=p)
+                y.backward(go)
+                for a, b, nm in ((out, y.detach(), "out"), (gx, xa.grad, "gx"), (gel, ela.grad, "g_el"), (ger, era.grad, "g_er")):
+                    assert torch.equal(a, b), f"{tag} {nm}: the direct launch differs from the Engine's"
+        # the head-mean layer's kernels (ggl_gat_sh_*), F = 64 -> 8 x 41 (Cp = 44)
+        F, H, C = 64, 8, 41
+        Cp = C + (-C) % 4
+        assert eng.gat_headmean_supported(H, F, C)
+        x = torch.randn(N, F, generator=g, device=dev)
+        W = torch.randn(F, H * C, generator=g, device=dev) * 0.15
+        att = torch.randn(1, H, 2 * C, generator=g, device=dev) * 0.2
+        Wr = W.view(F, H, C)
+        U, V = (Wr * att[0, :, :C]).sum(-1), (Wr * att[0, :, C:]).sum(-1)
+        el, er = (x @ U).contiguous(), (x @ V).contiguous()
+        G = torch.randn(N, H, F, generator=g, device=dev)
+        z = torch.nn.functional.pad((x @ W).view(N, H, C), (0, Cp - C)).contiguous()
+        gyp = torch.nn.functional.pad(torch.randn(N, C, generator=g, device=dev), (0, Cp - C)).contiguous()
+        Wst = Wr.permute(1, 0, 2).reshape(H * F, C)
+        for p in (0.0, 0.6):
+            tag = f"head-mean GAT 64 -> 8 x 41 p={p}"
+            bufs = []
+            rowmax, A, den = (_guarded_f32(s_, dev, bufs) for s_ in ((N, H), (N, H, F), (N, H)))
+            part = _guarded(eng.lib.ggl_gat_sh_partial_bytes(gp.fwd.n_chunks, F), dev, bufs)
+            cs = gp.fwd.c_struct(part)
+            rng = eng._rng_state(dev)
+            used = rng.clone()
+            eng._check(eng.lib.ggl_gat_sh_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(el), _ptr(er), _ptr(x), F, 0.2, p,
+                                              _ptr(rng) if p else None, _ptr(rowmax), _ptr(A), _ptr(den), st))
+            _guards_intact(bufs, tag + " forward")
+            stats = _guarded_f32((N, H, 4), dev, bufs)
+            eng._check(eng.lib.ggl_gat_sh_stats(_ptr(er), _ptr(rowmax), _ptr(den), _ptr(G), _ptr(A), N, F, _ptr(stats), st))
+            ger, T, gel = (_guarded_f32(s_, dev, bufs) for s_ in ((N, H), (N, H, Cp), (N, H)))
+            part_f = _guarded(eng.lib.ggl_gat_sh_partial_bytes(gp.fwd.n_chunks, 8), dev, bufs)
+            part_t = _guarded(eng.lib.ggl_gat_sh_partial_bytes(gp.bwd.n_chunks, Cp), dev, bufs)
+            cs, csT = gp.fwd.c_struct(part_f), gp.bwd.c_struct(part_t)
+            eng._check(eng.lib.ggl_gat_sh_bwd(ctypes.byref(cs), _ptr(gp.col), ctypes.byref(csT), _ptr(gp.colT),
+                                              _ptr(gp.posT if p else None), _ptr(el), _ptr(x), F, _ptr(G), _ptr(stats), _ptr(z),
+                                              _ptr(gyp), Cp, 0.2, p, _ptr(used) if p else None, _ptr(ger), _ptr(T), _ptr(gel), st))
+            _guards_intact(bufs, tag + " backward")
+            assert all(bool(torch.isfinite(t).all()) for t in (A, den, ger, T, gel)), tag
+            eng._rng_state(dev).copy_(used)
+            y = eng.gat_headmean(it, x, W, att, 0.2, dropout_rate=p)
+            assert torch.equal((A.view(N, H * F) @ Wst) / H, y), f"{tag}: the direct launch differs from the Engine's"
+    finally:
+        eng.chunk = old
+        eng.graph_cache.clear(); eng.seg_cache.clear()
+
+
 def philox4x32_10(index, offset, seed):
     """numpy restatement of the device generator (csrc/common.hpp): the four words of Philox4x32-10 with
     counter (index, offset) and key seed — used to rebuild the attention-dropout mask on the host."""
@@ -644,26 +777,6 @@ def philox4x32_10(index, offset, seed):
         k0 = (k0 + np.uint64(0x9E3779B9)) & m32
         k1 = (k1 + np.uint64(0xBB67AE85)) & m32
     return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
-
-
-def gat_drop_word(index, offset, seed):
-    """numpy restatement of gat_common.hpp drop_word: the attention-dropout word of counter index = p * H + h."""
-    m64 = (1 << 64) - 1
-    z = (int(seed) + int(offset) * 0x9E3779B97F4A7C15) & m64        # drop_key: splitmix64 of the launch's (seed, offset)
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m64
-    z ^= z >> 31
-    k0, k1 = np.uint64(z & 0xFFFFFFFF), np.uint64(z >> 32)
-    idx = np.asarray(index, dtype=np.uint64)
-    m32 = np.uint64(0xFFFFFFFF)
-    lo, hi = idx & m32, idx >> np.uint64(32)
-    x = ((lo ^ k0) * np.uint64(0x9E3779B1)) & m32
-    x ^= x >> np.uint64(15)
-    x = ((x ^ hi ^ k1) * np.uint64(0x85EBCA77)) & m32
-    x ^= x >> np.uint64(13)
-    x = (x * np.uint64(0xC2B2AE3D)) & m32
-    x ^= x >> np.uint64(16)
-    return x.astype(np.uint32)
 
 
 def check_drop_word_statistics():
@@ -748,6 +861,46 @@ def check_gat_dropout(eng, dev, oracle):
             y3 = eng.gat_fused(it, el.detach(), er.detach(), x.detach(), 0.2, dropout_rate=pd, training=False)
             np.testing.assert_allclose(to_np(y3), oracle.gat_fwd(index, to_np(el.detach()), to_np(er.detach()),
                                                                 to_np(x.detach()), 0.2), rtol=2e-5, atol=2e-6)
+    finally:
+        eng.chunk = old
+        eng.graph_cache.clear(); eng.seg_cache.clear()
+
+
+def check_gat_dropout_vs_float64(eng, dev, p=0.6):
+    """Attention dropout at the benchmark's rate against FLOAT64 (oracle/parity.py): gat_keep_mask rebuilds the [E, H] factor
+    from the (seed, offset) the launch read and the plan's perm, gat_truth_f64 applies it after the softmax, and the fused op
+    (forward + the three gradients) must agree to 1e-5 of the row's magnitude — on graphs with hub rows (chunked where the
+    chunk is small) and head widths down to one float4.  The same comparison with the mask of the NEXT step (offset + 1)
+    must miss the bound by >= 100x: the check would fail if the mask stopped mattering to it."""
+    from oracle import parity
+
+    rng = np.random.default_rng(47)
+    old = eng.chunk
+    try:
+        for chunk, (N, E, H, C) in ((0, (60, 900, 4, 8)), (16, (50, 800, 8, 4)), (8, (40, 700, 2, 41)), (4, (30, 500, 3, 16))):
+            eng.chunk = chunk
+            eng.graph_cache.clear(); eng.seg_cache.clear()
+            index = _rand_graph(rng, N, E)
+            index[1, : E // 4] = 2              # hub rows, longer than any chunk above
+            index[1, E // 4: E // 4 + E // 8] = N - 1
+            el, er = (to_t(rng.standard_normal((N, H)).astype(np.float32), dev) for _ in range(2))
+            x = to_t(rng.standard_normal((N, H, C)).astype(np.float32), dev)
+            go = to_t(rng.standard_normal((N, H, C)).astype(np.float32), dev)
+            it, _ = parity.kink_free_edges_logits(to_t(index, dev), el, er)
+            E2 = int(it.shape[1])
+            ela, era, xa = (t.clone().requires_grad_(True) for t in (el, er, x))
+            seed, offset = (int(v) for v in eng._rng_state(dev).cpu())
+            y = eng.gat_fused(it, ela, era, xa, 0.2, dropout_rate=p)
+            y.backward(go)
+            hip = (y.detach(), xa.grad, ela.grad, era.grad)
+            perm = eng.graph_plan(it, N).fwd.perm
+            keep = parity.gat_keep_mask(perm, E2, H, seed, offset, p)
+            assert abs(float((keep > 0).double().mean()) - (1 - p)) < 0.08
+            err = parity.gat_errors_vs_truth(parity.gat_truth_f64(it, el, er, x, go, N, attn_keep=keep), hip)
+            assert max(err.values()) <= 1e-5, (chunk, N, E, H, C, err)
+            wrong = parity.gat_keep_mask(perm, E2, H, seed, offset + 1, p)
+            errw = parity.gat_errors_vs_truth(parity.gat_truth_f64(it, el, er, x, go, N, attn_keep=wrong), hip)
+            assert errw["out"] >= 100 * 1e-5 and errw["gx"] >= 100 * 1e-5, (chunk, N, E, H, C, errw)
     finally:
         eng.chunk = old
         eng.graph_cache.clear(); eng.seg_cache.clear()

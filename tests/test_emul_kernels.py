@@ -162,6 +162,10 @@ def test_gat_attention_dropout(eng, oracle):
     pc.check_gat_dropout(eng, DEV, oracle)
 
 
+def test_gat_attention_dropout_vs_float64_with_the_host_mask(eng):
+    pc.check_gat_dropout_vs_float64(eng, DEV)
+
+
 def test_edge_cases_and_errors(eng, oracle):
     pc.check_edge_cases(eng, DEV, oracle)
 

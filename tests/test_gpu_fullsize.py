@@ -148,7 +148,7 @@ def test_reddit_eighth_headmean_layer_vs_float64(eng, dev):
     """The head-mean output layer (ggl_gat_sh_*) against GROUND TRUTH at the largest size a float64 evaluation fits in 288 GB:
     every 8th edge of the Reddit-sized graph (14.4 M edges, hub rows of 19 k edges, hub chunks of 1024) — the layer in float64
     (oracle/parity.py gat_conv_lean: torch scatters) and, as the yardstick, the same composition in float32 (torch ops, none of this
-    library's kernels): err(HIP) <= max(1e-5, 2 err(torch f32)) for y, gx, gW, gatt, gbias."""
+    library's kernels): err(HIP) <= 1e-5 for y, gx, gW, gatt, gbias (the torch f32 composition's error printed beside it)."""
     if not _big(dev):
         pytest.skip("needs > 100 GB of HBM")
     from gammagl_amd import layers
@@ -194,9 +194,10 @@ def test_reddit_eighth_headmean_layer_vs_float64(eng, dev):
     e_hip = parity.layer_errors_vs_truth(truth, hip, names, zero_mean_rows=("gx",))
     e_f32 = parity.layer_errors_vs_truth(truth, f32, names, zero_mean_rows=("gx",))
     for k in names:
-        print(f"head-mean GAT at 14 M edges {k}: err vs fp64 truth — HIP {e_hip[k]:.3e}, torch f32 composition {e_f32[k]:.3e}")
+        print(f"head-mean GAT at 14 M edges {k}: err vs fp64 truth — HIP {e_hip[k]:.3e}, torch f32 composition {e_f32[k]:.3e}, "
+              f"ratio {e_hip[k] / max(e_f32[k], 1e-30):.3f}")
     for k in names:
-        assert e_hip[k] <= max(1e-5, 2.0 * e_f32[k]), (k, e_hip, e_f32)
+        assert e_hip[k] <= 1e-5, (k, e_hip, e_f32)
 
 
 def test_products_size_sampler_and_sage_blocks(eng, dev):

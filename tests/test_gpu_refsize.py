@@ -208,31 +208,29 @@ def test_reddit_size_gat_layer_vs_the_reference_ops(eng, dev, ref):
     x = torch.randn(n, H, C, generator=g, device=dev)
     el, er = torch.randn(n, H, generator=g, device=dev), torch.randn(n, H, generator=g, device=dev)
     go = torch.randn(n, H, C, generator=g, device=dev)
-    ei, _ = parity.kink_free_edges_logits(ei, el, er)      # (logits within 1e-4 of LeakyReLU's kink left out, oracle/parity.py)
-    xa, ela, era = (t.clone().requires_grad_(True) for t in (x, el, er))
-    out = eng.gat_fused(ei, ela, era, xa, 0.2)
-    out.backward(go)
-    xb, elb, erb = (t.cpu().requires_grad_(True) for t in (x, el, er))
-    src, dst = ei[0].cpu(), ei[1].cpu()
-    s = torch.nn.functional.leaky_relu(elb[src] + erb[dst], 0.2)
-    m = ref.c_segment_max(s, dst, n)
-    ex = torch.exp(s - m[dst])
-    den = ref.c_segment_sum(ex, dst, n)
-    alpha = ex / (den[dst] + 1e-16)
-    want = ref.c_segment_sum(xb[src] * alpha.unsqueeze(-1), dst, n)
-    want.backward(go.cpu())
-    parity.check(out.detach(), want.detach(), "fused GAT forward vs the composed reference ops", tol=1e-5)
-    parity.check(xa.grad, xb.grad, "fused GAT gx", tol=2e-5)
-    # (a logit gradient cancels to exactly 0 over a one-edge row: scale floor = the tensor's mean magnitude)
-    parity.check(ela.grad, elb.grad, "fused GAT g_el", tol=2e-5, floor_min=float(elb.grad.abs().mean()))
-    parity.check(era.grad, erb.grad, "fused GAT g_er", tol=2e-5, floor_min=float(erb.grad.abs().mean()))
+    ei_kf, _ = parity.kink_free_edges_logits(ei, el, er)   # (logits within 1e-4 of LeakyReLU's kink left out, oracle/parity.py)
+    # ... and the UNFILTERED graph: both sides form the logit as the same single f32 add el[src] + er[dst], so a near-kink logit
+    # takes the same slope on both and every row is held to the same bounds
+    for graph, tag in ((ei_kf, "kink-free"), (ei, "unfiltered")):
+        xa, ela, era = (t.clone().requires_grad_(True) for t in (x, el, er))
+        out = eng.gat_fused(graph, ela, era, xa, 0.2)
+        out.backward(go)
+        xb, elb, erb = (t.cpu().requires_grad_(True) for t in (x, el, er))
+        want = parity.gat_fused_composed(graph.cpu(), elb, erb, xb, n, seg=_ref_seg(ref))
+        want.backward(go.cpu())
+        parity.check(out.detach(), want.detach(), f"fused GAT forward vs the composed reference ops ({tag})", tol=1e-5)
+        parity.check(xa.grad, xb.grad, f"fused GAT gx ({tag})", tol=2e-5)
+        # (a logit gradient cancels to exactly 0 over a one-edge row: scale floor = the tensor's mean magnitude)
+        parity.check(ela.grad, elb.grad, f"fused GAT g_el ({tag})", tol=2e-5, floor_min=float(elb.grad.abs().mean()))
+        parity.check(era.grad, erb.grad, f"fused GAT g_er ({tag})", tol=2e-5, floor_min=float(erb.grad.abs().mean()))
 
 
 def test_gat_gradients_against_an_fp64_ground_truth(eng, dev, ref):
     """Row G's tolerance, settled with a ground truth (round-4 verdict, weak #2): the fused kernels' gradients agree with the
     reference ops composed in f32 only to ~1e-4 of the row's magnitude — because BOTH are f32 evaluations of a softmax
     gradient (sums of thousands of cancelling terms), not because one of them is wrong.  Measured against the same layer in
-    float64: err(HIP) <= max(1e-5, 2 * err(reference f32 composition)) for out, gx, g_el, g_er on the Reddit-sized subgraph
+    float64: err(HIP) <= 1e-5 (the bound the round-6 measurement supports; the reference f32 composition's error is printed beside
+    it, not used as a bound) for out, gx, g_el, g_er on the Reddit-sized subgraph
     (every 32nd edge, hub rows of thousands of edges).  The errors are printed: bench.py's config-3 `parity` object
     carries the same figures."""
     from gammagl_amd.synth import DATASETS, rmat_graph
@@ -265,8 +263,11 @@ def test_gat_gradients_against_an_fp64_ground_truth(eng, dev, ref):
         reff = (want.detach(), xb.grad, elb.grad, erb.grad)
         e_hip, e_ref = parity.gat_errors_vs_truth(truth, hip), parity.gat_errors_vs_truth(truth, reff)
         for name in e_hip:
-            print(f"GAT {H}x{C} {name}: err vs fp64 truth — HIP {e_hip[name]:.3e}, reference f32 composition {e_ref[name]:.3e}")
-            assert e_hip[name] <= max(1e-5, 2.0 * e_ref[name]), (H, C, name, e_hip, e_ref)
+            print(f"GAT {H}x{C} {name}: err vs fp64 truth — HIP {e_hip[name]:.3e}, reference f32 composition {e_ref[name]:.3e}, "
+                  f"ratio {e_hip[name] / max(e_ref[name], 1e-30):.3f}")
+            # (one figure above 1e-5, a finding: g_el at 1 x 64, 2.31e-5 measured — the fast source walk sums the per-edge terms
+            #  de in f32, tests/test_gpu_gat_training.py; bounded flat at 3e-5 for that shape and tensor only)
+            assert e_hip[name] <= (3e-5 if (H, C, name) == (1, 64, "g_el") else 1e-5), (H, C, name, e_hip, e_ref)
 
 
 def _host_mem_gb():
@@ -298,7 +299,7 @@ def test_reddit_size_headmean_output_layer_vs_the_reference_ops(eng, dev, ref):
     ggl_gat_sh_* kernels (aggregate the 64-float input row per head, transform afterwards; 60 % of the Reddit step) — against
     GATConv.forward as gat_conv.py:98-122 writes it (head mean :115-118, bias :120-121) composed from the reference's own
     c_segment_max / c_segment_sum under autograd, on every 32nd edge of the Reddit-sized graph: y, gx, gW, gatt, gbias.
-    AND against the same layer in float64: err(HIP) <= max(1e-5, 2 err(reference f32 composition)) for all five.
+    AND against the same layer in float64: err(HIP) <= 1e-5 for all five (the reference f32 composition's error printed beside it).
     (Rounds 3-5 checked this path only against the builder's other kernels at 2e-4 of the tensor's maximum.)"""
     from gammagl_amd.layers import FusedGATConv
     from oracle import parity
@@ -315,6 +316,7 @@ def test_reddit_size_headmean_output_layer_vs_the_reference_ops(eng, dev, ref):
     # (edges whose logit lies within 1e-4 of LeakyReLU's kink are left out — oracle/parity.py kink_free_edges: an f32 logit on the
     #  other side of 0 than its float64 value takes the other slope, a jump no precision removes; with them in, HIP and the
     #  reference's composition were BOTH 1.79e-3 from the float64 gx by the same flipped edges)
+    ei_all = ei
     ei, dropped = parity.kink_free_edges(ei, x, W, att, H, C)
     print(f"head-mean refsize test: {dropped} near-kink edges of {int(ei.shape[1]) + dropped} left out")
     layer = FusedGATConv(F, C, heads=H, concat=False).to(dev)
@@ -353,9 +355,10 @@ def test_reddit_size_headmean_output_layer_vs_the_reference_ops(eng, dev, ref):
     e_hip = parity.layer_errors_vs_truth(truth, hip, names, zero_mean_rows=("gx",))
     e_ref = parity.layer_errors_vs_truth(truth, reff, names, zero_mean_rows=("gx",))
     for k in names:
-        print(f"head-mean GAT 64 -> 8 x 41 {k}: err vs fp64 truth — HIP {e_hip[k]:.3e}, reference f32 composition {e_ref[k]:.3e}")
+        print(f"head-mean GAT 64 -> 8 x 41 {k}: err vs fp64 truth — HIP {e_hip[k]:.3e}, reference f32 composition {e_ref[k]:.3e}, "
+              f"ratio {e_hip[k] / max(e_ref[k], 1e-30):.3f}")
     for k in names:
-        assert e_hip[k] <= max(1e-5, 2.0 * e_ref[k]), (k, e_hip, e_ref)
+        assert e_hip[k] <= 1e-5, (k, e_hip, e_ref)
     # and f32 against f32, the north_star's figure: 1e-5 of the row's magnitude forward, 2e-5 for the gradients
     parity.check(hip[0], reff[0], "head-mean GAT forward vs the composed reference ops", tol=1e-5)
     parity.check(hip[1], reff[1], "head-mean GAT gx", tol=2e-5, floor_min=float(reff[1].abs().mean()))
@@ -364,6 +367,31 @@ def test_reddit_size_headmean_output_layer_vs_the_reference_ops(eng, dev, ref):
     for a, b, k in zip(hip[2:], reff[2:], names[2:]):
         a2, b2 = (t.reshape(t.shape[0], -1) if t.dim() > 1 else t.reshape(1, -1) for t in (a, b))
         parity.check(a2, b2.to(dev), f"head-mean GAT {k}", tol=max(2e-5, e_hip[k] + e_ref[k]))
+    # f32 against f32 on the UNFILTERED graph.  HIP forms the logits as x @ (W a) (ops.py GATHeadMean), the composition as
+    # (x W) . a: a logit within rounding of 0 can take the other slope on one side, so the rows an edge with a float64 logit
+    # within 1e-4 of 0 touches are left out of the row comparison (counted: 2017 of 232 965 rows measured, each such edge touches
+    # two rows; bounded at 1 %); the parameter gradients are compared over the whole graph at the bounds above
+    tols = {k: max(2e-5, e_hip[k] + e_ref[k]) for k in names[2:]}
+    layer.zero_grad()
+    xa = x.clone().requires_grad_(True)
+    y = layer(xa, ei_all, n)
+    y.backward(go)
+    hip = (y.detach(), xa.grad, layer.w.grad, layer.att.grad, layer.bias.grad)
+    xb, Wb, ab, bb = (t.detach().cpu().requires_grad_(True) for t in (x, W, att, bias))
+    yb = parity.gat_conv_composed(xb, Wb, ab, bb, ei_all.cpu(), n, H, C, concat=False, slope=0.2, seg=_ref_seg(ref))
+    yb.backward(go.cpu())
+    reff = (yb.detach(), xb.grad, Wb.grad, ab.grad, bb.grad)
+    near, n_edges = parity.near_kink_rows(ei_all, x, W, att, H, C, n)
+    keep = ~near
+    print(f"head-mean refsize test, unfiltered graph: {n_edges} near-kink edges touch {int(near.sum())} of {n} rows "
+          f"(left out of the row comparison)")
+    assert int(near.sum()) < 1e-2 * n, int(near.sum())
+    parity.check(hip[0][keep], reff[0].to(dev)[keep], "head-mean GAT forward (unfiltered graph)", tol=1e-5)
+    parity.check(hip[1][keep], reff[1].to(dev)[keep], "head-mean GAT gx (unfiltered graph)", tol=2e-5,
+                 floor_min=float(reff[1].abs().mean()))
+    for a, b, k in zip(hip[2:], reff[2:], names[2:]):
+        a2, b2 = (t.reshape(t.shape[0], -1) if t.dim() > 1 else t.reshape(1, -1) for t in (a, b))
+        parity.check(a2, b2.to(dev), f"head-mean GAT {k} (unfiltered graph)", tol=tols[k])
 
 
 def test_reddit_size_gat_model_vs_the_reference_ops(eng, dev, ref):
@@ -384,6 +412,7 @@ def test_reddit_size_gat_model_vs_the_reference_ops(eng, dev, ref):
     x = torch.randn(n, 602, generator=g, device=dev)
     go = torch.randn(n, 41, generator=g, device=dev)
     params = [(l.w, l.att, l.bias) for l in model.gat_list]
+    ei_all = ei
     with torch.no_grad():        # (near-kink edges of either layer left out: oracle/parity.py kink_free_edges)
         ei, dropped = parity.kink_free_edges_model(ei, x, [tuple(p.detach() for p in tpl) for tpl in params], n, 8)
     print(f"GAT model refsize test: {dropped} near-kink edges of {int(ei.shape[1]) + dropped} left out")
@@ -392,9 +421,9 @@ def test_reddit_size_gat_model_vs_the_reference_ops(eng, dev, ref):
     hip = [y.detach()] + [p.grad for tpl in params for p in tpl]
     names = ["y"] + [f"g{nm}{li}" for li in range(2) for nm in ("W", "att", "b")]
 
-    def run(dtype, device, seg):
+    def run(dtype, device, seg, graph=ei):
         ps = [tuple(p.detach().to(device=device, dtype=dtype).requires_grad_(True) for p in tpl) for tpl in params]
-        out = parity.gat_model_composed(x.to(device=device, dtype=dtype), ps, ei.to(device), n, 8, slope=0.2, seg=seg)
+        out = parity.gat_model_composed(x.to(device=device, dtype=dtype), ps, graph.to(device), n, 8, slope=0.2, seg=seg)
         out.backward(go.to(device=device, dtype=dtype))
         return [out.detach()] + [p.grad for tpl in ps for p in tpl]
 
@@ -403,8 +432,39 @@ def test_reddit_size_gat_model_vs_the_reference_ops(eng, dev, ref):
     e_hip = parity.layer_errors_vs_truth(truth, hip, names)
     e_ref = parity.layer_errors_vs_truth(truth, reff, names)
     for k in names:
-        print(f"GAT model {k}: err vs fp64 truth — HIP {e_hip[k]:.3e}, reference f32 composition {e_ref[k]:.3e}")
-        assert e_hip[k] <= max(1e-5, 2.0 * e_ref[k]), (k, e_hip, e_ref)
+        print(f"GAT model {k}: err vs fp64 truth — HIP {e_hip[k]:.3e}, reference f32 composition {e_ref[k]:.3e}, "
+              f"ratio {e_hip[k] / max(e_ref[k], 1e-30):.3f}")
+    for k in names:
+        assert e_hip[k] <= 1e-5, (k, e_hip, e_ref)
+    # f32 against f32, on the filtered and on the UNFILTERED graph: y within 1e-5 of the row's magnitude, every parameter gradient
+    # within the sum of the two sides' float64 errors (at least 2e-5).  On the unfiltered graph every row of y is compared: y is
+    # continuous at LeakyReLU's kink (a logit within f32 rounding of 0 moves it by ~1e-7 whichever slope it takes), and the
+    # near-kink edges of either layer (HIP forms the logits as x @ (W a)) are counted and printed
+    tols = {k: max(2e-5, e_hip[k] + e_ref[k]) for k in names[1:]}
+
+    def compare(h_, r_, rows, tag):
+        parity.check(h_[0][rows], r_[0].to(dev)[rows], f"GAT model y ({tag})", tol=1e-5)
+        for a, b, k in zip(h_[1:], r_[1:], names[1:]):
+            a2, b2 = (t.reshape(t.shape[0], -1) if t.dim() > 1 else t.reshape(1, -1) for t in (a, b))
+            parity.check(a2, b2.to(dev), f"GAT model {k} ({tag})", tol=tols[k])
+
+    compare(hip, reff, torch.ones(n, dtype=torch.bool, device=dev), "kink-free graph")
+    with torch.no_grad():
+        p64 = [tuple(t.detach().double() for t in tpl) for tpl in params]
+        near0, k0 = parity.near_kink_rows(ei_all, x, p64[0][0], p64[0][1], 8, 8, n)
+        h = torch.nn.functional.elu(parity.gat_conv_lean(x.double(), *p64[0], ei_all, n, 8, 8, concat=True))
+        near1, k1 = parity.near_kink_rows(ei_all, h, p64[1][0], p64[1][1], 8, 41, n)
+        del h
+    near = near0 | near1
+    print(f"GAT model refsize test, unfiltered graph: {k0} + {k1} near-kink edges touch {int(near.sum())} of {n} rows "
+          f"(all rows compared)")
+    for p in model.parameters():
+        p.grad = None
+    y = model(x, ei_all, n)
+    y.backward(go)
+    hip = [y.detach()] + [p.grad for tpl in params for p in tpl]
+    compare(hip, run(torch.float32, "cpu", _ref_seg(ref), ei_all), torch.ones(n, dtype=torch.bool, device=dev),
+            "unfiltered graph")
 
 
 @pytest.mark.parametrize("K", [16, 64, 256])
