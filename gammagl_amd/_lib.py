@@ -15,7 +15,7 @@ HIP_LIB_PATH = os.path.join(_HERE, "lib", "libggl_mpops_hip.so")
 HOST_LIB_PATH = os.path.join(_HERE, "lib", "libggl_mpops_host.so")
 
 GGL_OK, GGL_EINVAL, GGL_EINDEX, GGL_EDTYPE, GGL_EHIP, GGL_EWORKSPACE = 0, -1, -2, -3, -4, -5
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class SegPlanC(ctypes.Structure):
@@ -106,6 +106,10 @@ SIGNATURES = {
     "ggl_gat_sh_stats": (c_int, [_V, _V, _V, _V, _V, c_int64, c_int64, _V, _V]),
     "ggl_gat_sh_bwd": (c_int, [_P, _V, _P, _V, _V, _V, _V, c_int64, _V, _V, _V, _V, c_int64, c_float, c_float, _V,
                                _V, _V, _V, _V]),
+    "ggl_segment_softmax_supported": (c_int, [c_int64]),
+    "ggl_segment_softmax_partial_bytes": (c_size_t, [c_int64, c_int64]),
+    "ggl_segment_softmax_fwd": (c_int, [_V, _P, c_int64, _V, _V]),
+    "ggl_segment_softmax_bwd": (c_int, [_V, _V, _P, c_int64, _V, _V]),
     "ggl_sample_count": (c_int, [_V, _V, c_int64, c_int64, c_int64, c_int, _V, _V]),
     "ggl_sample_pick": (c_int, [_V, _V, _V, c_int64, c_int64, c_int, _V, _V, _V, _V, _V]),
     "ggl_sample_hop_workspace_bytes": (c_size_t, [c_int64, c_int64]),
@@ -125,6 +129,7 @@ SIGNATURES = {
     "ggl_policy_maxbwd_form": (c_int, [c_int64, c_int64, c_int64]),
     "ggl_policy_xcd_run_rows": (c_int64, [c_int64, ctypes.c_double]),
     "ggl_policy_row_order": (c_int, [POINTER(c_int64), POINTER(c_int64)]),
+    "ggl_policy_softmax_sublanes": (c_int64, [c_int64, c_int64, c_int64]),
     "ggl_calib_stream": (c_int, [_V, _V, c_int64, c_int, _V]),
     "ggl_time_spmm_sum": (c_int, [_P, _V, _V, c_int, _V, c_int64, _V, _V, c_int, POINTER(c_float)]),
 }

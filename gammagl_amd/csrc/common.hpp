@@ -137,6 +137,7 @@ struct Options {
   // LOSES (dry 8-way share 14.3 -> 16.9 ms, 4-way 26.1 -> 29.3: profiles/r5_priority_ab.txt)
   int64_t hub_priority = 0;
   int64_t hub_pipe = 1;           // hub walk's consumer with its LDS reads software-pipelined (0 = round 4's: A/B, heavy configuration only)
+  int64_t softmax_sublanes = 0;   // edge softmax (gat.hip): lanes that share a (row, column), GPU build (0 = ggl_policy_softmax_sublanes)
   int64_t hub_one_launch = 2;     // hub walk once per aggregate over the full width: 1 = always, 0 = once per column block, 2 = where the long rows lead the ids
 };
 Options &options();

@@ -785,3 +785,505 @@ extern "C" int ggl_gat_fused_bwd_src(const ggl_segplan_t *planT, const int32_t *
   }
   return GGL_OK;
 }
+
+// =====================================================================================================================
+// Edge softmax as an op of its own: ggl_segment_softmax_fwd / _bwd (gammagl/utils/softmax.py:29-35, the function every
+// attention layer calls on its [E, H] logits).  Replaces, per direction, the chain segment_max -> gather -> sub / exp ->
+// segment_sum -> gather -> add / div (8+ launches, four [E, H] temporaries, two narrow-K segment reductions) by one walk
+// kernel, plus a chunk pass and a per-row merge in front (and, backward, a winner fix-up behind) when the plan has long rows.
+//
+// Shape: one or more lanes per (work item, column); work item = a row of at most plan->chunk elements, or one chunk of a
+// longer row.  The K lanes of an item sit next to each other, so a gathered record x[perm[p], 0:K] is ONE 4K-byte access
+// of the group and perm[p] a broadcast.  No LDS, no barriers, no atomics.  With one lane per (item, column) — the host
+// build's only form — a lane walks its item's sorted positions serially and 64 / K rows share a wavefront; the GPU build
+// may split an item's positions between S lanes (see "Sub-lanes" below).
+//   forward : walk 1 m = max x;  walk 2 D = sum exp(x - m) in double;  walk 3 y = exp(x - m) / (f32(D) + 1e-16f).
+//             Walk 1 fetches the row's records from HBM; walks 2 and 3 find them in L2 (a wavefront's 64 / K rows of mean
+//             length L hold 256 L bytes: 25-130 KiB at L = 100-500) or, for rows that fell out of it, in the MALL.
+//             For a row walked in one piece the numerators of walk 3 and the terms of walk 2 are the SAME rounded exp
+//             values, which keeps its y summing to 1 within 3 x 2^-24 — an online (one-walk) max / sum would evaluate
+//             them at different maxima.  (Long rows DO: their D is merged from chunk-local maxima, see below; their sum
+//             is held to the tested 1e-6, not to that derived bound.)
+//   backward: walk 1 S = sum y g in double and the winner (largest y, first among equals);  walk 2 gx = y * f32(g - S) for
+//             everyone else, their double sum T on the way, then gx[winner] = f32(-T).
+//   long rows: ssm_*_chunk_kernel leaves chunk-local (m_c, D_c) / (S_c, ymax_c, p_c) in plan->partial; ssm_*_merge_kernel
+//             merges them ONCE per (row, column) in chunk order (m = max m_c, D = sum D_c exp(m_c - m), the factor in
+//             double; S = sum S_c, winner = largest ymax_c, first chunk among equals) into a per-row slot; the chunk items
+//             of the walk kernel read that slot and write their chunk; backward, ssm_bwd_final_kernel adds the chunks' T_c
+//             in chunk order and writes the winner.  A long row costs one more read of its elements than a short one.
+// =====================================================================================================================
+#ifndef GGL_EMULATE
+#define GGL_EXPD(x) exp(x)
+#else
+#define GGL_EXPD(x) std::exp(x)
+#endif
+
+namespace ggl {
+
+constexpr int kSsmU = 4;  // gathered loads a lane keeps in flight
+
+struct SsmDims {
+  int64_t N, K, chunk, n_long, n_chunks;
+};
+
+__device__ __forceinline__ int64_t ssm_elem(const int32_t *__restrict__ perm, int64_t p) {
+  return perm ? (int64_t)perm[p] : p;
+}
+
+// long-row slot of chunk `cid`: the last j with chunk_ptr[j] <= cid
+__device__ __forceinline__ int64_t ssm_long_slot(const int64_t *__restrict__ chunk_ptr, int64_t n_long, int64_t cid) {
+  int64_t lo = 0, hi = n_long - 1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) >> 1;
+    if (chunk_ptr[mid] <= cid) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// positions [beg, end) of chunk `cid` (long-row slot *slot)
+__device__ __forceinline__ void ssm_chunk_range(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ long_rows,
+                                                const int64_t *__restrict__ chunk_ptr, const SsmDims &d, int64_t cid,
+                                                int64_t &slot, int64_t &beg, int64_t &end) {
+  slot = ssm_long_slot(chunk_ptr, d.n_long, cid);
+  const int64_t row = long_rows[slot];
+  beg = rowptr[row] + (cid - chunk_ptr[slot]) * d.chunk;
+  const int64_t rend = rowptr[row + 1];
+  end = (beg + d.chunk < rend) ? beg + d.chunk : rend;
+}
+
+// Sub-lanes (GPU build only).  With LOGS > 0 a work item's column is shared by S = 2^LOGS lanes that take every S-th
+// sorted position (lane s: beg + s, beg + s + S, ...): for K = 1 a 64-lane load of perm is 64 consecutive entries, a row
+// of 500 elements is 8 steps of a wavefront instead of 500 of a lane, and the lanes of a wavefront finish together.
+// Thread t -> (item, s, k) = (t / (S K), (t / K) % S, t % K); K is a power of two with S K <= 64, so the S lanes of an
+// (item, column) sit K apart inside ONE wavefront and combine their maxima / double sums / winners with an xor butterfly
+// (every lane ends with the same bits, and the same bits every run).  The host build has no cross-lane exchange and
+// instantiates LOGS = 0 only, where these are the identity.
+#ifndef GGL_EMULATE
+template <int LOGS> __device__ __forceinline__ float ssm_all_max(float v, int K) {
+#pragma unroll
+  for (int i = 0; i < LOGS; ++i) {
+    const float o = __shfl_xor(v, K << i, 64);
+    if (v < o) v = o;
+  }
+  return v;
+}
+template <int LOGS> __device__ __forceinline__ double ssm_all_sum(double v, int K) {
+#pragma unroll
+  for (int i = 0; i < LOGS; ++i) v = __dadd_rn(v, __shfl_xor(v, K << i, 64));
+  return v;
+}
+// largest y, smallest position among equals
+template <int LOGS> __device__ __forceinline__ void ssm_all_winner(float &ym, int64_t &pw, int K) {
+#pragma unroll
+  for (int i = 0; i < LOGS; ++i) {
+    const float oy = __shfl_xor(ym, K << i, 64);
+    const int64_t op = (int64_t)__shfl_xor((long long)pw, K << i, 64);
+    if (ym < oy || (ym == oy && op < pw)) { ym = oy; pw = op; }
+  }
+}
+#else
+template <int LOGS> __device__ __forceinline__ float ssm_all_max(float v, int) { return v; }
+template <int LOGS> __device__ __forceinline__ double ssm_all_sum(double v, int) { return v; }
+template <int LOGS> __device__ __forceinline__ void ssm_all_winner(float &, int64_t &, int) {}
+#endif
+
+template <int LOGS>
+__device__ __forceinline__ void ssm_decode(int64_t K, int64_t &item, int64_t &k, int64_t &s) {
+  const int64_t t = thread_id();
+  const int64_t q = t / K;
+  k = t - q * K;
+  s = q & (((int64_t)1 << LOGS) - 1);
+  item = q >> LOGS;
+}
+
+// One walk over the sorted positions beg, beg + step, ... < end for column k with kSsmU gathered loads in flight:
+// f(p, e, a[e, k]) resp. f(p, e, a[e, k], b[e, k]) in position order.
+template <typename F>
+__device__ __forceinline__ void ssm_walk1(const float *__restrict__ a, const int32_t *__restrict__ perm, int64_t K,
+                                          int64_t k, int64_t beg, int64_t end, int64_t step, F &&f) {
+  constexpr int U = kSsmU;
+  int64_t p = beg;
+  for (; p + (U - 1) * step < end; p += U * step) {
+    int64_t e[U];
+    float v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) e[u] = ssm_elem(perm, p + u * step);
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = a[e[u] * K + k];
+#pragma unroll
+    for (int u = 0; u < U; ++u) f(p + u * step, e[u], v[u]);
+  }
+  for (; p < end; p += step) {
+    const int64_t e0 = ssm_elem(perm, p);
+    f(p, e0, a[e0 * K + k]);
+  }
+}
+template <typename F>
+__device__ __forceinline__ void ssm_walk2(const float *__restrict__ a, const float *__restrict__ b,
+                                          const int32_t *__restrict__ perm, int64_t K, int64_t k, int64_t beg,
+                                          int64_t end, int64_t step, F &&f) {
+  constexpr int U = kSsmU;
+  int64_t p = beg;
+  for (; p + (U - 1) * step < end; p += U * step) {
+    int64_t e[U];
+    float v[U], w[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) e[u] = ssm_elem(perm, p + u * step);
+#pragma unroll
+    for (int u = 0; u < U; ++u) { v[u] = a[e[u] * K + k]; w[u] = b[e[u] * K + k]; }
+#pragma unroll
+    for (int u = 0; u < U; ++u) f(p + u * step, e[u], v[u], w[u]);
+  }
+  for (; p < end; p += step) {
+    const int64_t e0 = ssm_elem(perm, p);
+    f(p, e0, a[e0 * K + k], b[e0 * K + k]);
+  }
+}
+
+// m = max x, D = sum exp(x - m) (double) over [beg, end), the item's lanes together
+template <int LOGS>
+__device__ __forceinline__ void ssm_max_den(const float *__restrict__ x, const int32_t *__restrict__ perm, int64_t K,
+                                            int64_t k, int64_t s, int64_t beg, int64_t end, float &m, double &D) {
+  constexpr int64_t S = (int64_t)1 << LOGS;
+  float mm = -FLT_MAX;  // unsorted_segment_max: lowest() fill, strict <
+  ssm_walk1(x, perm, K, k, beg + s, end, S, [&](int64_t, int64_t, float v) { if (mm < v) mm = v; });
+  mm = ssm_all_max<LOGS>(mm, (int)K);
+  double dd = 0.0;
+  ssm_walk1(x, perm, K, k, beg + s, end, S,
+            [&](int64_t, int64_t, float v) { dd = __dadd_rn(dd, (double)GGL_EXPF(__fadd_rn(v, -mm))); });
+  m = mm;
+  D = ssm_all_sum<LOGS>(dd, (int)K);
+}
+
+// forward partials of one chunk and column: part[(cid * K + k) * 2 + {0, 1}] = {m_c, D_c}
+template <int LOGS>
+__global__ __launch_bounds__(kBlock) void ssm_fwd_chunk_kernel(const int64_t *__restrict__ rowptr,
+                                                               const int32_t *__restrict__ perm,
+                                                               const int32_t *__restrict__ long_rows,
+                                                               const int64_t *__restrict__ chunk_ptr,
+                                                               const float *__restrict__ x, double *__restrict__ part,
+                                                               const SsmDims d) {
+  int64_t cid, k, s;
+  ssm_decode<LOGS>(d.K, cid, k, s);
+  if (cid >= d.n_chunks) return;  // whole lane groups leave together: the butterflies stay inside a group
+  int64_t slot, beg, end;
+  ssm_chunk_range(rowptr, long_rows, chunk_ptr, d, cid, slot, beg, end);
+  float m;
+  double D;
+  ssm_max_den<LOGS>(x, perm, d.K, k, s, beg, end, m, D);
+  if (s == 0) {
+    part[(cid * d.K + k) * 2] = (double)m;
+    part[(cid * d.K + k) * 2 + 1] = D;
+  }
+}
+
+// long rows, once per (row, column): the chunks' (m_c, D_c) merged in chunk order by the online-softmax identity
+// (m = max m_c, D = sum D_c exp(m_c - m), the factor in double) into rowp[(j * K + k) * 2 + {0, 1}] = {m, D}
+__global__ __launch_bounds__(kBlock) void ssm_fwd_merge_kernel(const int64_t *__restrict__ chunk_ptr,
+                                                               const double *__restrict__ part,
+                                                               double *__restrict__ rowp, const SsmDims d) {
+  const int64_t t = thread_id();
+  const int64_t j = t / d.K, k = t - j * d.K;
+  if (j >= d.n_long) return;
+  const int64_t c0 = chunk_ptr[j], c1 = chunk_ptr[j + 1];
+  float m = -FLT_MAX;
+  for (int64_t c = c0; c < c1; ++c) {
+    const float mc = (float)part[(c * d.K + k) * 2];
+    if (m < mc) m = mc;
+  }
+  double D = 0.0;
+  for (int64_t c = c0; c < c1; ++c)
+    D = __dadd_rn(D, part[(c * d.K + k) * 2 + 1] * GGL_EXPD(part[(c * d.K + k) * 2] - (double)m));
+  rowp[(j * d.K + k) * 2] = (double)m;
+  rowp[(j * d.K + k) * 2 + 1] = D;
+}
+
+template <int LOGS>
+__global__ __launch_bounds__(kBlock) void ssm_fwd_kernel(const int64_t *__restrict__ rowptr,
+                                                         const int32_t *__restrict__ perm,
+                                                         const int32_t *__restrict__ row_order,
+                                                         const int32_t *__restrict__ long_rows,
+                                                         const int64_t *__restrict__ chunk_ptr,
+                                                         const float *__restrict__ x, float *__restrict__ y,
+                                                         const double *__restrict__ rowp, const SsmDims d) {
+  constexpr int64_t S = (int64_t)1 << LOGS;
+  int64_t item, k, s;
+  ssm_decode<LOGS>(d.K, item, k, s);
+  if (item >= d.n_chunks + d.N) return;
+  int64_t beg, end;
+  float m;
+  double D;
+  if (item < d.n_chunks) {  // chunks carry the lowest item ids: the hub work is dispatched first
+    int64_t slot;
+    ssm_chunk_range(rowptr, long_rows, chunk_ptr, d, item, slot, beg, end);
+    m = (float)rowp[(slot * d.K + k) * 2];  // merged once per row by ssm_fwd_merge_kernel
+    D = rowp[(slot * d.K + k) * 2 + 1];
+  } else {
+    const int64_t slot = item - d.n_chunks;
+    const int64_t row = row_order ? (int64_t)row_order[slot] : slot;
+    beg = rowptr[row];
+    end = rowptr[row + 1];
+    if (end == beg || end - beg > d.chunk) return;  // empty: nothing to write; long: its chunks are separate items
+    ssm_max_den<LOGS>(x, perm, d.K, k, s, beg, end, m, D);
+  }
+  const float den = __fadd_rn((float)D, 1e-16f);  // softmax.py:35: exp / (sum + 1e-16)
+  ssm_walk1(x, perm, d.K, k, beg + s, end, S, [&](int64_t, int64_t e, float v) {
+    y[e * d.K + k] = __fdiv_rn(GGL_EXPF(__fadd_rn(v, -m)), den);
+  });
+}
+
+// S = sum y g (double), the winner's y and sorted position (largest y, first among equals) over [beg, end)
+template <int LOGS>
+__device__ __forceinline__ void ssm_bwd_stats(const float *__restrict__ y, const float *__restrict__ g,
+                                              const int32_t *__restrict__ perm, int64_t K, int64_t k, int64_t s,
+                                              int64_t beg, int64_t end, double &Ssum, float &ymax, int64_t &pwin) {
+  constexpr int64_t S = (int64_t)1 << LOGS;
+  double ss = 0.0;
+  float ym = -1.0f;  // y >= 0: the first element wins an all-zero column
+  int64_t pw = beg + s < end ? beg + s : INT64_MAX;
+  ssm_walk2(y, g, perm, K, k, beg + s, end, S, [&](int64_t p, int64_t, float yv, float gv) {
+    ss = __dadd_rn(ss, (double)yv * (double)gv);
+    if (ym < yv) { ym = yv; pw = p; }
+  });
+  ssm_all_winner<LOGS>(ym, pw, (int)K);
+  Ssum = ssm_all_sum<LOGS>(ss, (int)K);
+  ymax = ym;
+  pwin = pw;
+}
+
+// gx = y * f32(g - S) for this lane's positions of [beg, end) but pwin; returns the double sum of what the item's lanes wrote
+template <int LOGS>
+__device__ __forceinline__ double ssm_bwd_write(const float *__restrict__ y, const float *__restrict__ g,
+                                                const int32_t *__restrict__ perm, int64_t K, int64_t k, int64_t s,
+                                                int64_t beg, int64_t end, double Ssum, int64_t pwin,
+                                                float *__restrict__ gx) {
+  constexpr int64_t S = (int64_t)1 << LOGS;
+  double T = 0.0;
+  ssm_walk2(y, g, perm, K, k, beg + s, end, S, [&](int64_t p, int64_t e, float yv, float gv) {
+    if (p == pwin) return;
+    const float r = __fmul_rn(yv, (float)((double)gv - Ssum));
+    gx[e * K + k] = r;
+    T = __dadd_rn(T, (double)r);
+  });
+  return ssm_all_sum<LOGS>(T, (int)K);
+}
+
+// backward partials of one chunk and column: part[(cid * K + k) * 4 + {0, 1, 2}] = {S_c, ymax_c, p_c}; slot 3 (T_c) is the
+// walk kernel's
+template <int LOGS>
+__global__ __launch_bounds__(kBlock) void ssm_bwd_chunk_kernel(const int64_t *__restrict__ rowptr,
+                                                               const int32_t *__restrict__ perm,
+                                                               const int32_t *__restrict__ long_rows,
+                                                               const int64_t *__restrict__ chunk_ptr,
+                                                               const float *__restrict__ y, const float *__restrict__ g,
+                                                               double *__restrict__ part, const SsmDims d) {
+  int64_t cid, k, s;
+  ssm_decode<LOGS>(d.K, cid, k, s);
+  if (cid >= d.n_chunks) return;
+  int64_t slot, beg, end;
+  ssm_chunk_range(rowptr, long_rows, chunk_ptr, d, cid, slot, beg, end);
+  double Ssum;
+  float ym;
+  int64_t pw;
+  ssm_bwd_stats<LOGS>(y, g, perm, d.K, k, s, beg, end, Ssum, ym, pw);
+  if (s == 0) {
+    double *q = part + (cid * d.K + k) * 4;
+    q[0] = Ssum;
+    q[1] = (double)ym;
+    q[2] = (double)pw;  // positions < 2^53: exact
+  }
+}
+
+// the row's S and winner position from its chunks' partials, chunk order
+__device__ __forceinline__ void ssm_bwd_merge(const double *__restrict__ part, int64_t K, int64_t k, int64_t c0,
+                                              int64_t c1, double &Ssum, int64_t &pwin) {
+  double ss = 0.0, ym = -1.0, pw = 0.0;
+  for (int64_t c = c0; c < c1; ++c) {
+    const double *q = part + (c * K + k) * 4;
+    ss = __dadd_rn(ss, q[0]);
+    if (c == c0 || ym < q[1]) { ym = q[1]; pw = q[2]; }
+  }
+  Ssum = ss;
+  pwin = (int64_t)pw;
+}
+
+// long rows, once per (row, column): rowp[(j * K + k) * 2 + {0, 1}] = {S, winner position}
+__global__ __launch_bounds__(kBlock) void ssm_bwd_merge_kernel(const int64_t *__restrict__ chunk_ptr,
+                                                               const double *__restrict__ part,
+                                                               double *__restrict__ rowp, const SsmDims d) {
+  const int64_t t = thread_id();
+  const int64_t j = t / d.K, k = t - j * d.K;
+  if (j >= d.n_long) return;
+  double Ssum;
+  int64_t pwin;
+  ssm_bwd_merge(part, d.K, k, chunk_ptr[j], chunk_ptr[j + 1], Ssum, pwin);
+  rowp[(j * d.K + k) * 2] = Ssum;
+  rowp[(j * d.K + k) * 2 + 1] = (double)pwin;
+}
+
+template <int LOGS>
+__global__ __launch_bounds__(kBlock) void ssm_bwd_kernel(const int64_t *__restrict__ rowptr,
+                                                         const int32_t *__restrict__ perm,
+                                                         const int32_t *__restrict__ row_order,
+                                                         const int32_t *__restrict__ long_rows,
+                                                         const int64_t *__restrict__ chunk_ptr,
+                                                         const float *__restrict__ y, const float *__restrict__ g,
+                                                         float *__restrict__ gx, double *__restrict__ part,
+                                                         const double *__restrict__ rowp, const SsmDims d) {
+  int64_t item, k, s;
+  ssm_decode<LOGS>(d.K, item, k, s);
+  if (item >= d.n_chunks + d.N) return;
+  if (item < d.n_chunks) {
+    int64_t slot, beg, end;
+    ssm_chunk_range(rowptr, long_rows, chunk_ptr, d, item, slot, beg, end);
+    const double Ssum = rowp[(slot * d.K + k) * 2];  // merged once per row by ssm_bwd_merge_kernel
+    const int64_t pwin = (int64_t)rowp[(slot * d.K + k) * 2 + 1];
+    const double T = ssm_bwd_write<LOGS>(y, g, perm, d.K, k, s, beg, end, Ssum, pwin, gx);
+    if (s == 0) part[(item * d.K + k) * 4 + 3] = T;
+    return;
+  }
+  const int64_t slot = item - d.n_chunks;
+  const int64_t row = row_order ? (int64_t)row_order[slot] : slot;
+  const int64_t beg = rowptr[row], end = rowptr[row + 1];
+  if (end == beg || end - beg > d.chunk) return;
+  double Ssum;
+  float ym;
+  int64_t pwin;
+  ssm_bwd_stats<LOGS>(y, g, perm, d.K, k, s, beg, end, Ssum, ym, pwin);
+  const double T = ssm_bwd_write<LOGS>(y, g, perm, d.K, k, s, beg, end, Ssum, pwin, gx);
+  if (s == 0) gx[ssm_elem(perm, pwin) * d.K + k] = (float)(0.0 - T);
+}
+
+// long rows: the winner's gradient = -(sum of the chunks' T_c, chunk order)
+__global__ __launch_bounds__(kBlock) void ssm_bwd_final_kernel(const int32_t *__restrict__ perm,
+                                                               const int64_t *__restrict__ chunk_ptr,
+                                                               const double *__restrict__ part,
+                                                               const double *__restrict__ rowp, float *__restrict__ gx,
+                                                               const SsmDims d) {
+  const int64_t t = thread_id();
+  const int64_t j = t / d.K, k = t - j * d.K;
+  if (j >= d.n_long) return;
+  const int64_t c0 = chunk_ptr[j], c1 = chunk_ptr[j + 1];
+  const int64_t pwin = (int64_t)rowp[(j * d.K + k) * 2 + 1];
+  double T = 0.0;
+  for (int64_t c = c0; c < c1; ++c) T = __dadd_rn(T, part[(c * d.K + k) * 4 + 3]);
+  gx[ssm_elem(perm, pwin) * d.K + k] = (float)(0.0 - T);
+}
+
+// lanes per (item, column) as log2: the library's policy on the GPU, one lane on the host
+static inline int ssm_logs(const ggl_segplan_t *plan, int64_t K) {
+#ifndef GGL_EMULATE
+  int64_t S = ggl_policy_softmax_sublanes(K, plan->E, plan->N);
+  if (S < 1 || (K & (K - 1)) != 0) S = 1;
+  int l = 0;
+  while (l < 6 && ((int64_t)2 << l) <= S && (((int64_t)2 << l) * K) <= kWave) ++l;
+  return l;
+#else
+  (void)plan; (void)K;
+  return 0;
+#endif
+}
+
+static inline int ssm_setup(const ggl_segplan_t *plan, int64_t K, SsmDims &d, double *&part, int &logs) {
+  GGL_REQUIRE(plan && plan->rowptr, GGL_EINVAL, "plan is NULL");
+  GGL_REQUIRE(ggl_segment_softmax_supported(K), GGL_EINVAL, "segment_softmax: K = %lld is outside [1, 64]", (long long)K);
+  GGL_REQUIRE(plan->chunk > 0, GGL_EINVAL, "chunk must be positive");
+  d.N = plan->N; d.K = K;
+  d.n_long = plan->n_long > 0 ? plan->n_long : 0;
+  d.n_chunks = d.n_long > 0 ? plan->n_chunks : 0;
+  d.chunk = d.n_long > 0 ? plan->chunk : INT64_MAX;  // no long-row table: every row in one piece
+  part = nullptr;
+  if (d.n_long > 0) {
+    GGL_REQUIRE(plan->long_rows && plan->chunk_ptr && plan->partial, GGL_EWORKSPACE,
+                "plan has long rows but long_rows/chunk_ptr/partial is NULL");
+    part = reinterpret_cast<double *>((reinterpret_cast<uintptr_t>(plan->partial) + 7u) & ~(uintptr_t)7u);
+  }
+  logs = ssm_logs(plan, K);
+  GGL_REQUIRE(ceil_div(((d.n_chunks + d.N) * K) << logs, kBlock) < ((int64_t)1 << 31), GGL_EINVAL,
+              "too many rows for one launch");
+  return GGL_OK;
+}
+
+}  // namespace ggl
+
+// KERN<LOGS> for the run-time `logs`; the host build has LOGS = 0 only
+#ifndef GGL_EMULATE
+#define GGL_SSM_LAUNCH(KERN, GRID, ...)                                              \
+  do {                                                                               \
+    switch (logs) {                                                                  \
+      case 1: GGL_LAUNCH((KERN<1>), GRID, kBlock, s, __VA_ARGS__); break;            \
+      case 2: GGL_LAUNCH((KERN<2>), GRID, kBlock, s, __VA_ARGS__); break;            \
+      case 3: GGL_LAUNCH((KERN<3>), GRID, kBlock, s, __VA_ARGS__); break;            \
+      case 4: GGL_LAUNCH((KERN<4>), GRID, kBlock, s, __VA_ARGS__); break;            \
+      case 5: GGL_LAUNCH((KERN<5>), GRID, kBlock, s, __VA_ARGS__); break;            \
+      case 6: GGL_LAUNCH((KERN<6>), GRID, kBlock, s, __VA_ARGS__); break;            \
+      default: GGL_LAUNCH((KERN<0>), GRID, kBlock, s, __VA_ARGS__); break;           \
+    }                                                                                \
+  } while (0)
+#else
+#define GGL_SSM_LAUNCH(KERN, GRID, ...) GGL_LAUNCH((KERN<0>), GRID, kBlock, s, __VA_ARGS__)
+#endif
+
+extern "C" int ggl_segment_softmax_supported(int64_t K) { return (K >= 1 && K <= 64) ? 1 : 0; }
+
+extern "C" size_t ggl_segment_softmax_partial_bytes(int64_t n_chunks, int64_t K) {
+  if (n_chunks <= 0 || K <= 0) return 0;
+  // per chunk and column {S, ymax, p, T} (forward: {m, D}), then per long row and column {S, p} ({m, D}); n_long <= n_chunks
+  return (size_t)n_chunks * (size_t)K * 6 * sizeof(double) + 64;
+}
+
+extern "C" int ggl_segment_softmax_fwd(const float *x, const ggl_segplan_t *plan, int64_t K, float *y, void *stream) {
+  SsmDims d{};
+  double *part = nullptr;
+  int logs = 0;
+  const int rc = ssm_setup(plan, K, d, part, logs);
+  if (rc) return rc;
+  if (plan->E == 0 || d.N == 0) return GGL_OK;
+  GGL_REQUIRE(x && y, GGL_EINVAL, "NULL pointer");
+  const int32_t *order = options().row_order ? plan->row_order : nullptr;
+  double *rowp = part ? part + d.n_chunks * K * 4 : nullptr;  // the long rows' merged statistics
+  hipStream_t s = as_stream(stream);
+  if (d.n_chunks > 0) {
+    GGL_SSM_LAUNCH(ssm_fwd_chunk_kernel, ceil_div((d.n_chunks * K) << logs, kBlock), plan->rowptr, plan->perm,
+                   plan->long_rows, plan->chunk_ptr, x, part, d);
+    GGL_LAUNCH_CHECK();
+    GGL_LAUNCH((ssm_fwd_merge_kernel), ceil_div(d.n_long * K, kBlock), kBlock, s, plan->chunk_ptr, (const double *)part,
+               rowp, d);
+    GGL_LAUNCH_CHECK();
+  }
+  GGL_SSM_LAUNCH(ssm_fwd_kernel, ceil_div(((d.n_chunks + d.N) * K) << logs, kBlock), plan->rowptr, plan->perm, order,
+                 plan->long_rows, plan->chunk_ptr, x, y, (const double *)rowp, d);
+  GGL_LAUNCH_CHECK();
+  return GGL_OK;
+}
+
+extern "C" int ggl_segment_softmax_bwd(const float *y, const float *g, const ggl_segplan_t *plan, int64_t K, float *gx,
+                                       void *stream) {
+  SsmDims d{};
+  double *part = nullptr;
+  int logs = 0;
+  const int rc = ssm_setup(plan, K, d, part, logs);
+  if (rc) return rc;
+  if (plan->E == 0 || d.N == 0) return GGL_OK;
+  GGL_REQUIRE(y && g && gx, GGL_EINVAL, "NULL pointer");
+  const int32_t *order = options().row_order ? plan->row_order : nullptr;
+  double *rowp = part ? part + d.n_chunks * K * 4 : nullptr;
+  hipStream_t s = as_stream(stream);
+  if (d.n_chunks > 0) {
+    GGL_SSM_LAUNCH(ssm_bwd_chunk_kernel, ceil_div((d.n_chunks * K) << logs, kBlock), plan->rowptr, plan->perm,
+                   plan->long_rows, plan->chunk_ptr, y, g, part, d);
+    GGL_LAUNCH_CHECK();
+    GGL_LAUNCH((ssm_bwd_merge_kernel), ceil_div(d.n_long * K, kBlock), kBlock, s, plan->chunk_ptr, (const double *)part,
+               rowp, d);
+    GGL_LAUNCH_CHECK();
+  }
+  GGL_SSM_LAUNCH(ssm_bwd_kernel, ceil_div(((d.n_chunks + d.N) * K) << logs, kBlock), plan->rowptr, plan->perm, order,
+                 plan->long_rows, plan->chunk_ptr, y, g, gx, part, (const double *)rowp, d);
+  GGL_LAUNCH_CHECK();
+  if (d.n_long > 0) {
+    GGL_LAUNCH((ssm_bwd_final_kernel), ceil_div(d.n_long * K, kBlock), kBlock, s, plan->perm, plan->chunk_ptr,
+               (const double *)part, (const double *)rowp, gx, d);
+    GGL_LAUNCH_CHECK();
+  }
+  return GGL_OK;
+}

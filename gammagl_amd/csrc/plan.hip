@@ -327,6 +327,7 @@ extern "C" int ggl_set_option(const char *name, int64_t value) {
   else if (!strcmp(name, "maxbwd_mask_scatter")) o.maxbwd_mask_scatter = value;
   else if (!strcmp(name, "maxbwd_mask_wlane")) o.maxbwd_mask_wlane = value;
   else if (!strcmp(name, "maxbwd_mask_cols")) o.maxbwd_mask_cols = value;
+  else if (!strcmp(name, "softmax_sublanes")) o.softmax_sublanes = value;
   else { set_error("unknown option %s", name); return GGL_EINVAL; }
   return GGL_OK;
 }
@@ -365,6 +366,7 @@ extern "C" int64_t ggl_get_option(const char *name) {
   if (!strcmp(name, "maxbwd_mask_scatter")) return o.maxbwd_mask_scatter;
   if (!strcmp(name, "maxbwd_mask_wlane")) return o.maxbwd_mask_wlane;
   if (!strcmp(name, "maxbwd_mask_cols")) return o.maxbwd_mask_cols;
+  if (!strcmp(name, "softmax_sublanes")) return o.softmax_sublanes;
   return -1;
 }
 
@@ -399,6 +401,17 @@ extern "C" int64_t ggl_policy_xcd_run_rows(int64_t E, double locality) {
   static const int64_t forced = env_i64("GGL_XCD_RUN_ROWS", -1);
   if (forced >= 0) return forced;
   return (E >= ((int64_t)1 << 22) && locality > 0.5) ? 2048 : 0;
+}
+// One lane per (row, column): the form profiles/segment_softmax.txt was measured with and that beats the composition at K = 4 and 8
+// (2-4x forward, 11-13x forward + backward).  More lanes (the option) are an A/B the same file's sweep lines record; they become
+// the default for a shape only once a measurement puts them ahead there.
+extern "C" int64_t ggl_policy_softmax_sublanes(int64_t K, int64_t E, int64_t N) {
+  (void)E; (void)N;
+  if (K < 1 || K > 64 || (K & (K - 1)) != 0) return 1;
+  const int64_t S = options().softmax_sublanes, cap = 64 / K;
+  int64_t r = 1;
+  while (2 * r <= S && 2 * r <= cap) r *= 2;
+  return r;
 }
 extern "C" int ggl_policy_row_order(int64_t *window_host, int64_t *heavy_host) {
   static const int64_t window = env_i64("GGL_ROW_ORDER_WINDOW", 2048);

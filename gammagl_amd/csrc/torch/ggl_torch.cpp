@@ -5,6 +5,7 @@
 //
 //   ggl::segment_sum / segment_mean (Tensor x, Tensor index, int N) -> Tensor         src/segment_{sum,mean}.cpp
 //   ggl::segment_max                (Tensor x, Tensor index, int N) -> (Tensor, Tensor)  src/segment_max.cpp (+ argmax)
+//   ggl::segment_softmax            (Tensor x, Tensor index, int N) -> Tensor         utils/softmax.py:10-36 as one op
 //   ggl::spmm_sum / spmm_mean / spmm_max (Tensor index, Tensor? weight, Tensor x) -> Tensor   src/gspmm.cpp:26-202
 //   ggl::bspmm_sum                  (Tensor index, Tensor weight, Tensor x) -> Tensor   src/gspmm.cpp:204-260
 //
@@ -65,7 +66,9 @@ using torch::autograd::variable_list;
   X(ggl_policy_chunk) X(ggl_policy_spmm_width) X(ggl_policy_head_channels) X(ggl_policy_mean_bwd_prescale)            \
   X(ggl_policy_gradw_sorted) X(ggl_policy_xcd_run_rows) X(ggl_policy_row_order)                                     \
   X(ggl_spmm_max_mask_bytes) X(ggl_spmm_max_mask) X(ggl_spmm_max_bwd_mask) X(ggl_invert_perm) X(ggl_get_option)      \
-  X(ggl_spmm_max_bwd32) X(ggl_policy_maxbwd_form)
+  X(ggl_spmm_max_bwd32) X(ggl_policy_maxbwd_form)                                                                   \
+  X(ggl_segment_softmax_supported) X(ggl_segment_softmax_partial_bytes) X(ggl_segment_softmax_fwd) X(ggl_segment_softmax_bwd) \
+  X(ggl_policy_softmax_sublanes)
 
 struct Api {
   void *handle = nullptr;
@@ -649,6 +652,52 @@ static std::tuple<Tensor, Tensor> segment_max_kernel(const Tensor &x, const Tens
   c10::OptionalDeviceGuard guard(x.device());
   auto r = segment_fwd(Red::Max, x.contiguous(), *seg_plan(index, N));
   return {r.first, r.second};
+}
+
+// Edge softmax (utils/softmax.py:29-35) as one op each way: ggl_segment_softmax_fwd / _bwd over the id vector's cached plan.
+// y and gx come back in the caller's element order; the backward needs y and grad only.
+static Tensor softmax_partial(const Api &a, const SegPlan &p, const Tensor &like, int64_t K) {
+  if (p.n_long == 0) return Tensor();
+  const size_t nb = a.ggl_segment_softmax_partial_bytes(p.n_chunks, K);
+  return at::empty({static_cast<int64_t>(nb) + 16}, like.options().dtype(at::kByte));
+}
+static int64_t softmax_width(const Api &a, const Tensor &x, const SegPlan &p) {
+  TORCH_CHECK_INDEX(x.size(0) == p.E, "fisrt dimension of x and index should be same");
+  f32("x", x);
+  int64_t K = 1;
+  for (int64_t d = 1; d < x.dim(); ++d) K *= x.size(d);
+  TORCH_CHECK(a.ggl_segment_softmax_supported(K) != 0, "segment_softmax: no kernel for rows of ", K,
+              " columns (ggl_segment_softmax_supported); gammagl_amd.utils.segment_softmax composes such rows from the segment ops");
+  return K;
+}
+static Tensor segment_softmax_kernel(const Tensor &x_, const Tensor &index, int64_t N) {
+  seg_args(x_, index);
+  c10::OptionalDeviceGuard guard(x_.device());
+  const Api &a = api_for(x_.device());
+  Tensor x = x_.contiguous();
+  auto plan = seg_plan(index, N);
+  const int64_t K = softmax_width(a, x, *plan);
+  Tensor y = at::empty_like(x);
+  Tensor part = softmax_partial(a, *plan, x, K);
+  ggl_segplan_t cs = plan->c(part);
+  check(a, a.ggl_segment_softmax_fwd(x.data_ptr<float>(), &cs, K, y.data_ptr<float>(), stream_of(x.device())));
+  return y;
+}
+static Tensor segment_softmax_backward_kernel(const Tensor &grad, const Tensor &y_, const Tensor &index, int64_t N) {
+  same_device({&grad, &y_, &index});
+  c10::OptionalDeviceGuard guard(y_.device());
+  const Api &a = api_for(y_.device());
+  Tensor y = y_.contiguous(), g = grad.contiguous();
+  TORCH_CHECK(g.sizes() == y.sizes(), "segment_softmax backward: grad and y differ in shape");
+  f32("grad", g);
+  auto plan = seg_plan(index, N);    // (the forward's plan: a cache hit)
+  const int64_t K = softmax_width(a, y, *plan);
+  Tensor gx = at::empty_like(y);
+  Tensor part = softmax_partial(a, *plan, y, K);
+  ggl_segplan_t cs = plan->c(part);
+  check(a, a.ggl_segment_softmax_bwd(y.data_ptr<float>(), g.data_ptr<float>(), &cs, K, gx.data_ptr<float>(),
+                                     stream_of(y.device())));
+  return gx;
 }
 
 struct SpArgs {
@@ -1244,6 +1293,22 @@ struct SegmentFn : public torch::autograd::Function<SegmentFn<OP>> {
   }
 };
 
+struct SegmentSoftmaxFn : public torch::autograd::Function<SegmentSoftmaxFn> {
+  static Tensor forward(AutogradContext *ctx, const Tensor &x, const Tensor &index, int64_t N) {
+    at::AutoDispatchBelowADInplaceOrView below;
+    static auto op = op_handle<SegSig>("ggl::segment_softmax");
+    Tensor y = op.call(x, index, N);
+    ctx->saved_data["N"] = N;
+    ctx->save_for_backward({y, index});
+    return y;
+  }
+  static variable_list backward(AutogradContext *ctx, variable_list grads) {
+    auto saved = ctx->get_saved_variables();
+    static auto op = op_handle<Tensor(const Tensor &, const Tensor &, const Tensor &, int64_t)>("ggl::segment_softmax_backward");
+    return {op.call(grads[0], saved[0], saved[1], ctx->saved_data["N"].toInt()), Tensor(), Tensor()};
+  }
+};
+
 template <SpOp OP>
 struct SpMMFn : public torch::autograd::Function<SpMMFn<OP>> {
   static Tensor forward(AutogradContext *ctx, const Tensor &index, const OptT &weight, const Tensor &x) {
@@ -1297,6 +1362,7 @@ static std::tuple<Tensor, Tensor> segment_max_autograd(const Tensor &x, const Te
   auto r = SegmentFn<Red::Max>::apply(x, i, N);
   return {r[0], r[1]};
 }
+static Tensor segment_softmax_autograd(const Tensor &x, const Tensor &i, int64_t N) { return SegmentSoftmaxFn::apply(x, i, N); }
 static Tensor spmm_sum_autograd(const Tensor &i, const OptT &w, const Tensor &x) { return SpMMFn<SpOp::Sum>::apply(i, w, x); }
 static Tensor spmm_mean_autograd(const Tensor &i, const OptT &w, const Tensor &x) { return SpMMFn<SpOp::Mean>::apply(i, w, x); }
 static Tensor spmm_max_autograd(const Tensor &i, const OptT &w, const Tensor &x) { return SpMMFn<SpOp::Max>::apply(i, w, x); }
@@ -1499,6 +1565,8 @@ static std::tuple<Tensor, Tensor> spmm_max_arg_meta(const Tensor &, const OptT &
   return {at::empty_like(x), at::empty(x.sizes(), x.options().dtype(at::kLong))};
 }
 static Tensor bspmm_meta(const Tensor &, const Tensor &, const Tensor &x) { return at::empty_like(x); }
+static Tensor softmax_meta(const Tensor &x, const Tensor &, int64_t) { return at::empty_like(x); }
+static Tensor softmax_bwd_meta(const Tensor &, const Tensor &y, const Tensor &, int64_t) { return at::empty_like(y); }
 static Tensor seg_bwd_meta(const Tensor &g, const Tensor &, c10::IntArrayRef shape) { return at::empty(shape, g.options()); }
 static Tensor seg_mean_bwd_meta(const Tensor &g, const Tensor &, int64_t, c10::IntArrayRef shape) {
   return at::empty(shape, g.options());
@@ -1574,6 +1642,8 @@ TORCH_LIBRARY(ggl, m) {
   m.def("segment_sum(Tensor x, Tensor index, int N) -> Tensor");
   m.def("segment_mean(Tensor x, Tensor index, int N) -> Tensor");
   m.def("segment_max(Tensor x, Tensor index, int N) -> (Tensor, Tensor)");
+  m.def("segment_softmax(Tensor x, Tensor index, int N) -> Tensor");
+  m.def("segment_softmax_backward(Tensor grad, Tensor y, Tensor index, int N) -> Tensor");
   m.def("spmm_sum(Tensor index, Tensor? weight, Tensor x) -> Tensor");
   m.def("spmm_mean(Tensor index, Tensor? weight, Tensor x) -> Tensor");
   m.def("spmm_max(Tensor index, Tensor? weight, Tensor x) -> Tensor");
@@ -1624,6 +1694,8 @@ TORCH_LIBRARY(ggl, m) {
     m.impl("segment_sum", ggl_torch::segment_sum_kernel);    \
     m.impl("segment_mean", ggl_torch::segment_mean_kernel);  \
     m.impl("segment_max", ggl_torch::segment_max_kernel);    \
+    m.impl("segment_softmax", ggl_torch::segment_softmax_kernel);                    \
+    m.impl("segment_softmax_backward", ggl_torch::segment_softmax_backward_kernel);  \
     m.impl("spmm_sum", ggl_torch::spmm_sum_kernel);          \
     m.impl("spmm_mean", ggl_torch::spmm_mean_kernel);        \
     m.impl("spmm_max", ggl_torch::spmm_max_kernel);          \
@@ -1653,6 +1725,7 @@ TORCH_LIBRARY_IMPL(ggl, Autograd, m) {
   m.impl("segment_sum", ggl_torch::segment_sum_autograd);
   m.impl("segment_mean", ggl_torch::segment_mean_autograd);
   m.impl("segment_max", ggl_torch::segment_max_autograd);
+  m.impl("segment_softmax", ggl_torch::segment_softmax_autograd);
   m.impl("spmm_sum", ggl_torch::spmm_sum_autograd);
   m.impl("spmm_mean", ggl_torch::spmm_mean_autograd);
   m.impl("spmm_max", ggl_torch::spmm_max_autograd);
@@ -1668,6 +1741,8 @@ TORCH_LIBRARY_IMPL(ggl, Meta, m) {
   m.impl("segment_sum", ggl_torch::seg_meta);
   m.impl("segment_mean", ggl_torch::seg_meta);
   m.impl("segment_max", ggl_torch::seg_max_meta);
+  m.impl("segment_softmax", ggl_torch::softmax_meta);
+  m.impl("segment_softmax_backward", ggl_torch::softmax_bwd_meta);
   m.impl("spmm_sum", ggl_torch::like_x_meta);
   m.impl("spmm_mean", ggl_torch::like_x_meta);
   m.impl("spmm_max", ggl_torch::like_x_meta);

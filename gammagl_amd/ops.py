@@ -21,6 +21,7 @@ import os
 from collections import OrderedDict
 
 import torch
+from torch.autograd.function import once_differentiable
 from torch.multiprocessing.reductions import StorageWeakRef
 
 from . import _lib
@@ -567,6 +568,44 @@ class Engine:
         nb = self.lib.ggl_partial_bytes(_DTYPE_CODE[dtype], plan.n_chunks, K, 1 if with_arg else 0)
         return torch.empty(nb + 16, dtype=torch.uint8, device=dev)
 
+    def _softmax_partial(self, plan, K, dev):
+        if plan.n_long == 0:
+            return None
+        nb = self.lib.ggl_segment_softmax_partial_bytes(plan.n_chunks, K)
+        return torch.empty(nb + 16, dtype=torch.uint8, device=dev)
+
+    def _softmax_width(self, x, plan):
+        E = int(x.shape[0])
+        if E != plan.E:
+            raise IndexError("fisrt dimension of x and index should be same")
+        self._check_f32("x", x)
+        K = int(math.prod(x.shape[1:]))
+        if not self.lib.ggl_segment_softmax_supported(K):
+            raise RuntimeError(f"segment_softmax: no kernel for rows of {K} columns (ggl_segment_softmax_supported); "
+                               "gammagl_amd.utils.segment_softmax composes such rows from the segment ops")
+        return K
+
+    def _softmax_fwd(self, x, plan):
+        """y = softmax of x[E, ...] over the plan's segments (ggl_segment_softmax_fwd), caller's element order."""
+        K = self._softmax_width(x, plan)
+        dev = x.device
+        y = torch.empty_like(x)
+        part = self._softmax_partial(plan, K, dev)   # must outlive the launch
+        cs = plan.c_struct(part)
+        self._check(self.lib.ggl_segment_softmax_fwd(_ptr(x), ctypes.byref(cs), K, _ptr(y), self._stream(dev)))
+        return y
+
+    def _softmax_bwd(self, y, g, plan):
+        """gx from y and g alone (ggl_segment_softmax_bwd)."""
+        K = self._softmax_width(y, plan)
+        dev = y.device
+        g = g.contiguous()
+        gx = torch.empty_like(y)
+        part = self._softmax_partial(plan, K, dev)
+        cs = plan.c_struct(part)
+        self._check(self.lib.ggl_segment_softmax_bwd(_ptr(y), _ptr(g), ctypes.byref(cs), K, _ptr(gx), self._stream(dev)))
+        return gx
+
     # ---- raw (non-autograd) forward launches -------------------------------------------------
     def _segment_fwd(self, op, x, plan):
         dev = x.device
@@ -874,6 +913,20 @@ class Engine:
                                                        int(arg.shape[0]), K, _ptr(gin),
                                                        eng._stream(g.device)))
                 return gin, None, None
+
+        class SegmentSoftmax(torch.autograd.Function):  # utils/softmax.py:29-35 as one op each way
+            @staticmethod
+            def forward(ctx, x, plan):
+                y = eng._softmax_fwd(x, plan)
+                ctx.save_for_backward(y)
+                ctx.plan = plan
+                return y
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, g):
+                (y,) = ctx.saved_tensors
+                return eng._softmax_bwd(y, g, ctx.plan), None
 
         class SpMMSum(torch.autograd.Function):  # src/gspmm.cpp:26-80
             @staticmethod
@@ -1330,6 +1383,7 @@ class Engine:
         self.BiasAct = BiasAct
         self.BiasAdd = BiasAdd
         self.SegmentSum, self.SegmentMean, self.SegmentMax = SegmentSum, SegmentMean, SegmentMax
+        self.SegmentSoftmax = SegmentSoftmax
         self.SpMMSum, self.SpMMMean, self.SpMMMax = SpMMSum, SpMMMean, SpMMMax
         self.BSpMMSum, self.GATFused = BSpMMSum, GATFused
 
@@ -1355,6 +1409,22 @@ class Engine:
 
     def segment_max_with_arg(self, x, index, N):
         return self.SegmentMax.apply(*self._seg_args(x, index, N))
+
+    def segment_softmax_supported(self, x):
+        """Does the native edge softmax take `x` (f32, rows of a width the library has a kernel for)?"""
+        K = int(math.prod(x.shape[1:]))
+        return x.dtype == torch.float32 and x.dim() >= 1 and bool(self.lib.ggl_segment_softmax_supported(K))
+
+    def segment_softmax(self, x, index, N=None):
+        """utils/softmax.py:10-36 as ONE op with its own backward: y[e] = exp(x[e] - max) / (sum + 1e-16) over the
+        elements that share a segment id, per trailing column.  x: [E], [E, H] or [E, H, C] f32; `index`: int64 ids
+        [E] (plan from the cache) or a SegPlan built with build_plan / plan_from_rowptr (explicit-plan form, as
+        segment_reduce is for the sums)."""
+        if isinstance(index, SegPlan):
+            self._dev(x)
+            return self.SegmentSoftmax.apply(x.contiguous(), index)
+        x, index, N = self._seg_args(x, index, N)
+        return self.SegmentSoftmax.apply(x, self.seg_plan(index, N))
 
     def _spmm_args(self, index, weight, x):
         self._dev(index, weight, x)

@@ -7,6 +7,7 @@ points (+ the fused GAT op and the fused epilogue) are dispatcher ops:
     torch.ops.gammagl_amd.segment_sum(x, index, N)        -> Tensor          c_segment_sum
     torch.ops.gammagl_amd.segment_mean(x, index, N)       -> Tensor          c_segment_mean
     torch.ops.gammagl_amd.segment_max(x, index, N)        -> (Tensor, Tensor) c_segment_max (+ argmax)
+    torch.ops.gammagl_amd.segment_softmax(x, index, N)    -> Tensor          utils/softmax.py segment_softmax
     torch.ops.gammagl_amd.spmm_sum(index, weight, x)      -> Tensor          c_spmm_sum
     torch.ops.gammagl_amd.spmm_mean(index, weight, x)     -> Tensor          c_spmm_mean
     torch.ops.gammagl_amd.spmm_max(index, weight, x)      -> Tensor          c_spmm_max
@@ -32,6 +33,7 @@ _SCHEMAS = {
     "segment_sum": "(Tensor x, Tensor index, int N) -> Tensor",
     "segment_mean": "(Tensor x, Tensor index, int N) -> Tensor",
     "segment_max": "(Tensor x, Tensor index, int N) -> (Tensor, Tensor)",
+    "segment_softmax": "(Tensor x, Tensor index, int N) -> Tensor",
     "spmm_sum": "(Tensor index, Tensor? weight, Tensor x) -> Tensor",
     "spmm_mean": "(Tensor index, Tensor? weight, Tensor x) -> Tensor",
     "spmm_max": "(Tensor index, Tensor? weight, Tensor x) -> Tensor",
@@ -54,6 +56,7 @@ def _kernels(get_engine):
         "segment_sum": lambda x, index, N: get_engine().c_segment_sum(x, index, N),
         "segment_mean": lambda x, index, N: get_engine().c_segment_mean(x, index, N),
         "segment_max": lambda x, index, N: get_engine().segment_max_with_arg(x, index, N),
+        "segment_softmax": lambda x, index, N: get_engine().segment_softmax(x, index, N),
         "spmm_sum": lambda index, weight, x: get_engine().c_spmm_sum(index, weight, x),
         "spmm_mean": lambda index, weight, x: get_engine().c_spmm_mean(index, weight, x),
         "spmm_max": lambda index, weight, x: get_engine().c_spmm_max(index, weight, x),
@@ -102,6 +105,7 @@ def _register_fakes():
         return x.new_empty((n,) + tuple(x.shape[1:]))
 
     for name, fn in (("segment_sum", seg), ("segment_mean", seg), ("segment_max", seg_max),
+                     ("segment_softmax", lambda x, index, N: torch.empty_like(x)),
                      ("spmm_sum", like_x), ("spmm_mean", like_x), ("spmm_max", like_x),
                      ("bspmm_sum", like_x), ("gat_fused", gat),
                      ("bias_act", lambda a, bias, relu, p_drop: torch.empty_like(a))):

@@ -50,7 +50,9 @@ extern "C" {
 /* 9 (round 6): + ggl_policy_maxbwd_form (the gspmm-max backward's form gated on the winner mask's footprint; option
  *   maxbwd_mask_kmax), ggl_gat_sh_bwd's forward-plan partial holds four doubles per chunk and head, + ggl_spmm_col_blocks_plan (128-column blocks for plans whose node order carries locality), option gat_sh_pk.
  *   No struct change. */
-#define GGL_ABI_VERSION 9
+/* 10: + ggl_segment_softmax_{fwd,bwd,supported,partial_bytes} (the edge softmax of utils/softmax.py as one op each way),
+ *   ggl_policy_softmax_sublanes, option softmax_sublanes.  No struct change. */
+#define GGL_ABI_VERSION 10
 
 /* dtype codes (AT_DISPATCH_ALL_TYPES_AND2(Half, BFloat16), segment_sum_cpu.cpp:32-33) */
 enum {
@@ -445,6 +447,30 @@ int ggl_gat_sh_stats(const float *er, const float *rowmax, const float *den, con
                      int64_t F, float *stats, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Edge softmax — supersedes the composition gammagl/utils/softmax.py:29-35 runs on the segment ops
+ * (segment_max -> gather -> sub / exp -> segment_sum -> gather -> add / div, and the same chain backwards under
+ * autograd) for the [E, H] logits of every attention layer.  f32; K = product of the trailing dims; x, y, g, gx are
+ * [E, K] in the CALLER's element order (the kernels go through plan->perm); nothing [N, K] is returned or saved.
+ *   fwd, per segment s and column k:  m = max x (start value -FLT_MAX, strict <, NaN never wins: segment_max_cpu.cpp:40-62),
+ *        D = sum exp(x[e] - m) accumulated in DOUBLE and rounded to f32 once,  y[e] = exp(x[e] - m) / (D + 1e-16f).
+ *        An all -inf column gives y = 0; empty segments write nothing; E == 0 is a no-op.
+ *   bwd, from y and g alone:  S = sum y[e] g[e] in DOUBLE,  gx[e] = y[e] * f32(g[e] - S)  (the difference formed in
+ *        double), except for the element with the largest y of its (segment, column) (smallest element index among
+ *        equals): gx = -(sum of the other elements' gx, in double), so that a row's gradients sum to 0 as they do in
+ *        exact arithmetic.  Without it a row dominated by one logit loses its gradient to the cancellation in g - S.
+ * No atomics, no host synchronisation, every element of y / gx written exactly once.  Rows longer than plan->chunk go
+ * through the long-row table: chunk-local (m, D) — resp. (S, winner) — in plan->partial
+ * (ggl_segment_softmax_partial_bytes(n_chunks, K) bytes, 8-byte aligned), merged in chunk order.  A plan presented
+ * WITHOUT its long-row table (n_long == 0) has every row walked in one piece.
+ * ggl_segment_softmax_supported(K): 1 <= K <= 64 (one or more lanes per (row, column)); wider rows are the caller's to compose.
+ * ---------------------------------------------------------------------------------------------- */
+int ggl_segment_softmax_supported(int64_t K);
+size_t ggl_segment_softmax_partial_bytes(int64_t n_chunks, int64_t K);
+int ggl_segment_softmax_fwd(const float *x, const ggl_segplan_t *plan, int64_t K, float *y, void *stream);
+int ggl_segment_softmax_bwd(const float *y, const float *g, const ggl_segplan_t *plan, int64_t K, float *gx,
+                            void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Uniform neighbour sampling — supersedes ops/sparse sample_adj
  * (cpu/sample.cpp:10-135).  CSR (rowptr [M+1], col [nnz]) int64; seeds [B] int64 row ids.
  *   ggl_sample_count: out_deg[i] = deg (fanout < 0) | fanout if deg > 0 (replace) | min(deg, fanout)
@@ -533,6 +559,11 @@ int64_t ggl_policy_xcd_run_rows(int64_t E, double locality);
 /* the row hand-out order: rows of >= *heavy elements first, longest first; the rest by length inside windows of
  * *window consecutive ids (0: one global sort).  GGL_ROW_ORDER_WINDOW overrides the window. */
 int ggl_policy_row_order(int64_t *window_host, int64_t *heavy_host);
+/* lanes of the GPU build that share one (row, column) of the edge-softmax walks (a power of two, lanes x K <= 64) for rows of K
+ * columns, E elements in N segments.  1 = a lane walks its row alone: the default (the measured form, profiles/segment_softmax.txt),
+ * the only form for widths that are not a power of two and on the host build.  Option softmax_sublanes > 0 asks for more (A/B;
+ * same formulas, double sums in another association). */
+int64_t ggl_policy_softmax_sublanes(int64_t K, int64_t E, int64_t N);
 
 /* Measurement aid (bench.py's roofline leg): a grid-stride pass over `n_vec4` 16-byte vectors of `src`, 16 bytes per
  * lane and four independent loads in flight — mode 0: read-only (every wavefront folds what it read into ONE float of
