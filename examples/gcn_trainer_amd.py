@@ -9,11 +9,13 @@ features + neighbourhood); --data points at an .npz with x, y, edge_index, train
 
     python examples/gcn_trainer_amd.py --n_epoch 50 --hidden_dim 16
     python examples/gcn_trainer_amd.py --gpu -1 --n_epoch 20       # BASELINE config 1: TL_BACKEND=torch on the CPU
+    python examples/gcn_trainer_amd.py --amp bf16                  # mixed precision (not in the reference trainer)
 
 With --gpu -1 (gcn_trainer.py's own flag for "no GPU") every tensor stays on the host and the same ops dispatch to the
 host build of the kernel sources (CPU dispatch key, libggl_mpops_host.so) — the plumbing configuration of BASELINE.json.
 """
 import argparse
+import contextlib
 import os
 import sys
 
@@ -50,6 +52,9 @@ def main():
     p.add_argument("--l2_coef", type=float, default=5e-4)
     p.add_argument("--data", type=str, default="")
     p.add_argument("--gpu", type=int, default=0)
+    # mixed precision: f32 parameters and optimizer state, the forward under torch.autocast (16-bit activations, summed in f32
+    # by the aggregate and rounded once), the loss in f32, a GradScaler for f16
+    p.add_argument("--amp", choices=["none", "bf16", "f16"], default="none")
     args = p.parse_args()
     dev = torch.device("cuda", args.gpu) if args.gpu >= 0 else torch.device("cpu")
     x, y, edge_index, train_idx, val_idx, test_idx = load(args, dev)
@@ -59,14 +64,24 @@ def main():
     net = GCNModel(x.shape[1], args.hidden_dim, int(y.max()) + 1, args.drop_rate, args.num_layers, args.norm).to(dev)
     opt = torch.optim.Adam(net.parameters(), lr=args.lr, weight_decay=args.l2_coef)
     best_val, best_state = 0.0, None
+    amp_dtype = {"none": None, "bf16": torch.bfloat16, "f16": torch.float16}[args.amp]
+    amp = (lambda: torch.autocast(dev.type, dtype=amp_dtype)) if amp_dtype is not None else contextlib.nullcontext
+    scaler = torch.amp.GradScaler(dev.type) if amp_dtype == torch.float16 else None
     for epoch in range(args.n_epoch):
         net.train()
         opt.zero_grad(set_to_none=True)
-        loss = F.cross_entropy(net(x, edge_index, None, n)[train_idx], y[train_idx])
-        loss.backward()
-        opt.step()
+        with amp():
+            out = net(x, edge_index, None, n)
+        loss = F.cross_entropy(out[train_idx].float(), y[train_idx])
+        if scaler is not None:
+            scaler.scale(loss).backward()
+            scaler.step(opt)
+            scaler.update()
+        else:
+            loss.backward()
+            opt.step()
         net.eval()
-        with torch.no_grad():
+        with torch.no_grad(), amp():
             logits = net(x, edge_index, None, n)
         val_acc = float((logits[val_idx].argmax(1) == y[val_idx]).float().mean())
         if epoch % 10 == 0 or epoch == args.n_epoch - 1:
@@ -75,7 +90,7 @@ def main():
             best_val, best_state = val_acc, {k: v.clone() for k, v in net.state_dict().items()}
     net.load_state_dict(best_state)
     net.eval()
-    with torch.no_grad():
+    with torch.no_grad(), amp():
         logits = net(x, edge_index, None, n)
     print("Test acc:  {:.4f}".format(float((logits[test_idx].argmax(1) == y[test_idx]).float().mean())))
 

@@ -72,6 +72,10 @@ SIGNATURES = {
     "ggl_spmm_mean": (c_int, [_P, _V, _V, c_int, _V, c_int64, _V, _V]),
     "ggl_spmm_max": (c_int, [_P, _V, _V, c_int, _V, c_int64, _V, _V, _V]),
     "ggl_spmm_mean_bwd": (c_int, [_P, _V, _V, c_int, _V, _V, c_int64, _V, _V]),
+    "ggl_spmm_sum_x16": (c_int, [_P, _V, _V, c_int, c_int, _V, c_int64, c_int64, c_int, _V, c_int64, _V]),
+    "ggl_spmm_mean_x16": (c_int, [_P, _V, _V, c_int, c_int, _V, c_int64, c_int64, c_int, _V, c_int64, _V]),
+    "ggl_spmm_mean_bwd_x16": (c_int, [_P, _V, _V, c_int, c_int, _V, _V, c_int64, c_int, _V, _V]),
+    "ggl_spmm_col_blocks_x16": (c_int64, [c_void_p, c_int64]),
     "ggl_spmm_max_bwd": (c_int, [_P, _V, _V, c_int, _V, _V, c_int64, _V, _V]),
     "ggl_spmm_max_bwd32": (c_int, [_P, _V, _V, c_int, _V, _V, c_int64, _V, _V]),
     "ggl_spmm_max_mask_bytes": (c_size_t, [c_int64, c_int64]),

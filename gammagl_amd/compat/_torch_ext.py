@@ -59,12 +59,12 @@ def c_segment_max(x, index, N):
 
 
 def c_spmm_sum(index, weight, x):
-    """SpMMSum::apply (src/gspmm.cpp:26-80)."""
+    """SpMMSum::apply (src/gspmm.cpp:26-80).  Beyond the reference: bf16 / f16 `x` is summed in f32, rounded once."""
     return _ops.spmm_sum(index, weight, x)
 
 
 def c_spmm_mean(index, weight, x):
-    """SpMMMean::apply (src/gspmm.cpp:82-141)."""
+    """SpMMMean::apply (src/gspmm.cpp:82-141).  Beyond the reference: bf16 / f16 `x` is summed in f32, rounded once."""
     return _ops.spmm_mean(index, weight, x)
 
 

@@ -139,6 +139,9 @@ struct Options {
   int64_t hub_pipe = 1;           // hub walk's consumer with its LDS reads software-pipelined (0 = round 4's: A/B, heavy configuration only)
   int64_t softmax_sublanes = 0;   // edge softmax (gat.hip): lanes that share a (row, column), GPU build (0 = ggl_policy_softmax_sublanes)
   int64_t hub_one_launch = 2;     // hub walk once per aggregate over the full width: 1 = always, 0 = once per column block, 2 = where the long rows lead the ids
+  // wide 16-bit-storage SpMM-sum / mean (ggl_spmm_*_x16): column blocks of this width (0 = one launch).  128 columns of 16 bits are
+  // the 256-byte slices the f32 launches gather at col_block = 64 (sweep: profiles/spmm16.txt, DESIGN.md "Mixed-precision aggregate")
+  int64_t col_block16 = 128;
 };
 Options &options();
 
@@ -183,6 +186,8 @@ struct HubF32Args {
   float *partial;           // [n_long, K]
   int64_t avg_long_len;     // average length of the long rows (picks the stage size)
   int f64;                  // segment sums of doubles: x / x_ld / K / partial in 4-byte WORDS (2 per element), see hubf32.hip
+  int x16;                  // 0, or GGL_BF16 / GGL_F16: x holds 16-bit elements (x_ld / K in elements), widened before the multiply;
+                            // tile, consumer and partial stay f32 (SpMM modes without heads only)
 };
 int hub_f32_launch(const HubF32Args &a, hipStream_t stream, bool beside, int *forked);   // *forked: 0 or the join token
 int hub_f32_join(hipStream_t stream, int token);
@@ -294,6 +299,63 @@ template <> struct TT<bf16_t> {
   static __device__ __forceinline__ bool gt1(A c) { return c > 1.0f; }
   static __device__ __forceinline__ A div(A a, A c) { return bf16_to_f32(f32_to_bf16(__fdiv_rn(a, c))); }
 };
+
+// ---- mixed precision: 16-bit STORAGE, f32 ARITHMETIC (ggl_spmm_*_x16) ---------------------------------------------------
+// The element is widened at the load (exact), every product and add is the f32 one the float kernels make, in the same
+// order, and the sum is rounded ONCE, at the store: out == f32_op(x.float()).to(x.dtype) bit for bit.  Not the traits
+// above: the segment ops keep the reference's storage-type running sums (a bf16 sum of ones stalls at 256).
+struct mxbf16_t {};
+struct mxf16_t {};
+template <typename T> struct f32out {};     // T's rows, result stored as f32 (no rounding at all)
+#define GGL_MX_TT(T, LOAD, STORE)                                                        \
+  template <> struct TT<T> {                                                             \
+    using S = uint16_t;                                                                  \
+    using A = float;                                                                     \
+    static __device__ __forceinline__ A load(S v) { return LOAD(v); }                    \
+    static __device__ __forceinline__ S store(A v) { return STORE(v); }                  \
+    static __device__ __forceinline__ A add(A a, A b) { return __fadd_rn(a, b); }        \
+    static __device__ __forceinline__ bool less(A a, A b) { return a < b; }              \
+    static __device__ __forceinline__ A lowest() { return -FLT_MAX; }                    \
+    static __device__ __forceinline__ A zero() { return 0.0f; }                          \
+    static __device__ __forceinline__ A count(int64_t c) { return TT<float>::count(c); } \
+    static __device__ __forceinline__ bool gt1(A c) { return c > 1.0f; }                 \
+    static __device__ __forceinline__ A div(A a, A c) { return __fdiv_rn(a, c); }        \
+  };
+GGL_MX_TT(mxbf16_t, bf16_to_f32, f32_to_bf16)
+GGL_MX_TT(mxf16_t, f16_to_f32, f32_to_f16)
+#undef GGL_MX_TT
+template <typename T> struct TT<f32out<T>> : TT<T> {};
+template <typename T> struct mx_code { static constexpr int value = 0; };     // 0 = not a mixed-precision type
+template <> struct mx_code<mxbf16_t> { static constexpr int value = GGL_BF16; };
+template <> struct mx_code<mxf16_t> { static constexpr int value = GGL_F16; };
+template <typename T> struct mx_code<f32out<T>> : mx_code<T> {};
+
+// Where a row kernel's results go: O = element type of `out`, P = of the chunk partials.  The storage type itself for every
+// type but the mixed-precision ones, whose partials are f32 (a 16-bit partial would round twice) and whose output is 16-bit
+// or f32 (f32out<>).
+template <typename T> struct TO {
+  using O = typename TT<T>::S;
+  using P = typename TT<T>::S;
+  static __device__ __forceinline__ O ostore(typename TT<T>::A v) { return TT<T>::store(v); }
+  static __device__ __forceinline__ typename TT<T>::A oload(O v) { return TT<T>::load(v); }
+  static __device__ __forceinline__ P pstore(typename TT<T>::A v) { return TT<T>::store(v); }
+  static __device__ __forceinline__ typename TT<T>::A pload(P v) { return TT<T>::load(v); }
+};
+template <typename T, typename OT> struct TOmx {
+  using O = OT;
+  using P = float;
+  static __device__ __forceinline__ O ostore(float v) {
+    if constexpr (std::is_same<OT, float>::value) return v; else return TT<T>::store(v);
+  }
+  static __device__ __forceinline__ float oload(O v) {
+    if constexpr (std::is_same<OT, float>::value) return v; else return TT<T>::load(v);
+  }
+  static __device__ __forceinline__ P pstore(float v) { return v; }
+  static __device__ __forceinline__ float pload(P v) { return v; }
+};
+template <> struct TO<mxbf16_t> : TOmx<mxbf16_t, uint16_t> {};
+template <> struct TO<mxf16_t> : TOmx<mxf16_t, uint16_t> {};
+template <typename T> struct TO<f32out<T>> : TOmx<T, float> {};
 
 // eight 16-bit elements at a 2-byte aligned address as ONE 16-byte access (the backend emits global_load_dwordx4 for the
 // packed struct: unaligned access mode) — rows of f16 / bf16 whose width is not a multiple of 8 (reduce.hip, hub16.hip)

@@ -82,9 +82,14 @@ template <int PER> struct HfIds { int32_t row[PER], wi[PER]; };       // source 
 // F64 (segment sums of doubles: the two segment modes, no weights): the producers move the row as 4-byte words — a row of
 // K doubles is a row of 2 K words, `a.K` / `a.x_ld` / `a.x` arrive in words — and only the consumer knows better: a lane
 // owns a DOUBLE (two adjacent words of the tile) and adds with __dadd_rn.  Same pipeline, same order of adds.
-template <int MODE, bool VEC4, bool WPC, int PER, int LOG_LPE, bool F64 = false, bool PIPE = true>
+// X16 (GGL_BF16 / GGL_F16; the mixed-precision SpMM, reduce.hip): the SOURCE rows are 16-bit — a producer lane gathers its
+// four columns as one 8-byte load (VEC4) or four 2-byte loads, keeps the raw bits in the stage's registers (no ALU between
+// the gathers: the vmcnt counting below stays what it is) and widens them where it parks them, before the rounded multiply.
+// Tile, consumer and partial are the f32 ones: the same adds in the same order as on x.float().
+template <int MODE, bool VEC4, bool WPC, int PER, int LOG_LPE, bool F64 = false, bool PIPE = true, int X16 = 0>
 __global__ __launch_bounds__(kHfBlock) void hub_rows_f32_kernel(const HubF32Args a) {
   static_assert(!F64 || hub_seg(MODE), "doubles: segment sums only (the SpMMs are f32 in the reference)");
+  static_assert(!X16 || (!F64 && !WPC && !hub_seg(MODE) && !hub_heads(MODE)), "16-bit source rows: SpMM-sum / mean only");
   constexpr int kLpe = 1 << LOG_LPE, kEpl = kWave / kLpe;          // lanes per element, elements per load instruction
   constexpr int kHfCols = kLpe * 4;                                 // columns per slab
   constexpr int kHfPer = PER, kHfStage = kHfProd * PER * kEpl;      // elements per LDS half
@@ -110,6 +115,7 @@ __global__ __launch_bounds__(kHfBlock) void hub_rows_f32_kernel(const HubF32Args
     const int cl = live ? piece * 4 : 0;                        // first of this lane's four columns inside the slab
     const int e0 = pw * (kHfPer * kEpl) + eg;                   // this lane's elements of a stage: e0 + kEpl i
     const float *xs = a.x + c0 + cl;
+    const uint16_t *xs16 = reinterpret_cast<const uint16_t *>(a.x) + c0 + cl;
     int64_t hd[NW];                                             // head of each weight this lane applies
 #pragma unroll
     for (int c = 0; c < NW; ++c) {
@@ -137,7 +143,20 @@ __global__ __launch_bounds__(kHfBlock) void hub_rows_f32_kernel(const HubF32Args
 #pragma unroll
       for (int i = 0; i < kHfPer; ++i) {
         const float *g = xs + (int64_t)t.row[i] * a.x_ld;
-        if (VEC4) {
+        if (X16) {                                                // raw bits: two columns per word (VEC4) or one
+          const uint16_t *h = xs16 + (int64_t)t.row[i] * a.x_ld;
+          if (VEC4) {
+            const uint2 u = *reinterpret_cast<const uint2 *>(h);
+            d.r[i].x = __uint_as_float(u.x);
+            d.r[i].y = __uint_as_float(u.y);
+          } else {
+            const int last = ncol - 1 - cl;
+            d.r[i].x = __uint_as_float((uint32_t)h[0]);
+            d.r[i].y = __uint_as_float((uint32_t)h[last < 1 ? last : 1]);
+            d.r[i].z = __uint_as_float((uint32_t)h[last < 2 ? last : 2]);
+            d.r[i].w = __uint_as_float((uint32_t)h[last < 3 ? last : 3]);
+          }
+        } else if (VEC4) {
           d.r[i] = *reinterpret_cast<const float4 *>(g);
         } else {                                                  // (columns past the slab's end: the last valid one again)
           const int last = ncol - 1 - cl;
@@ -157,6 +176,23 @@ __global__ __launch_bounds__(kHfBlock) void hub_rows_f32_kernel(const HubF32Args
 #pragma unroll
       for (int i = 0; i < kHfPer; ++i) {
         float4 v = d.r[i];
+        if (X16) {
+          uint32_t b0, b1, b2, b3;
+          if (VEC4) {
+            const uint32_t u0 = __float_as_uint(d.r[i].x), u1 = __float_as_uint(d.r[i].y);
+            b0 = u0 & 0xffffu; b1 = u0 >> 16; b2 = u1 & 0xffffu; b3 = u1 >> 16;
+          } else {
+            b0 = __float_as_uint(d.r[i].x); b1 = __float_as_uint(d.r[i].y);
+            b2 = __float_as_uint(d.r[i].z); b3 = __float_as_uint(d.r[i].w);
+          }
+          if (X16 == GGL_BF16) {
+            v.x = bf16_to_f32((uint16_t)b0); v.y = bf16_to_f32((uint16_t)b1);
+            v.z = bf16_to_f32((uint16_t)b2); v.w = bf16_to_f32((uint16_t)b3);
+          } else {
+            v.x = f16_to_f32((uint16_t)b0); v.y = f16_to_f32((uint16_t)b1);
+            v.z = f16_to_f32((uint16_t)b2); v.w = f16_to_f32((uint16_t)b3);
+          }
+        }
         if (hub_has_w(MODE)) {
           v.x = __fmul_rn(wv.w[i][0], v.x);
           v.y = __fmul_rn(wv.w[i][WPC ? 1 : 0], v.y);
@@ -354,7 +390,8 @@ int hub_f32_launch(const HubF32Args &a, hipStream_t stream, bool beside, int *fo
   const bool narrow = a.K <= 16;                       // 16-column slabs, 4 lanes per element
   const int64_t slabs = ceil_div(a.K, (int64_t)(narrow ? 16 : 64));
   const int64_t grid = a.n_long * slabs;
-  const bool vec4 = a.K % 4 == 0 && a.x_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15u) == 0;
+  // (16-bit source rows: a lane's four columns are 8 bytes)
+  const bool vec4 = a.K % 4 == 0 && a.x_ld % 4 == 0 && (reinterpret_cast<uintptr_t>(a.x) & (a.x16 ? 7u : 15u)) == 0;
   const bool seg = a.col == nullptr, has_w = !seg && a.w != nullptr;
   const bool w_perm = has_w && !a.w_by_pos && a.perm != nullptr;
   const bool heads = has_w && a.C > 0, wpc = heads && a.C % 4 != 0;
@@ -374,7 +411,34 @@ int hub_f32_launch(const HubF32Args &a, hipStream_t stream, bool beside, int *fo
     if (vec4) GGL_HF2(M, W, true);                     \
     else GGL_HF2(M, W, false);                         \
   } while (0)
-  if (seg && a.f64) {   // (light stages: one instantiation per index mode and width class is enough for this rare dtype)
+  if (a.x16) {          // 16-bit source rows (mixed-precision SpMM-sum / mean): the three weight forms, three stage shapes
+    if (seg || heads || a.f64 || (a.x16 != GGL_BF16 && a.x16 != GGL_F16)) {
+      set_error("hub walk: 16-bit source rows are for SpMM-sum / mean only");
+      return GGL_EINVAL;
+    }
+#define GGL_HF16_3(M, V, X)                                                                                  \
+  do {                                                                                                        \
+    if (narrow) GGL_LAUNCH((hub_rows_f32_kernel<M, V, false, 2, 2, false, true, X>), grid, kHfBlock, s, a);   \
+    else if (heavy) GGL_LAUNCH((hub_rows_f32_kernel<M, V, false, 4, 4, false, true, X>), grid, kHfBlock, s, a); \
+    else GGL_LAUNCH((hub_rows_f32_kernel<M, V, false, 2, 4, false, true, X>), grid, kHfBlock, s, a);          \
+  } while (0)
+#define GGL_HF16_2(M, X)                                 \
+  do {                                                   \
+    if (vec4) GGL_HF16_3(M, true, X);                    \
+    else GGL_HF16_3(M, false, X);                        \
+  } while (0)
+#define GGL_HF16(M)                                      \
+  do {                                                   \
+    if (a.x16 == GGL_BF16) GGL_HF16_2(M, GGL_BF16);      \
+    else GGL_HF16_2(M, GGL_F16);                         \
+  } while (0)
+    if (!has_w) GGL_HF16(HUB_SPMM);
+    else if (w_perm) GGL_HF16(HUB_SPMM_WP);
+    else GGL_HF16(HUB_SPMM_W);
+#undef GGL_HF16
+#undef GGL_HF16_2
+#undef GGL_HF16_3
+  } else if (seg && a.f64) {   // (light stages: one instantiation per index mode and width class is enough for this rare dtype)
 #define GGL_HF64(M)                                                                                       \
   do {                                                                                                     \
     if (narrow) {                                                                                          \

@@ -47,6 +47,7 @@ Options &options() {
     t.force_generic = env_i64("GGL_FORCE_GENERIC", t.force_generic);
     t.ragged4 = env_i64("GGL_RAGGED4", t.ragged4);
     t.col_block = env_i64("GGL_COL_BLOCK", t.col_block);
+    t.col_block16 = env_i64("GGL_COL_BLOCK16", t.col_block16);
     t.col_block_min_edges = env_i64("GGL_COL_BLOCK_MIN_EDGES", t.col_block_min_edges);
     t.col_block_min_degree = env_i64("GGL_COL_BLOCK_MIN_DEGREE", t.col_block_min_degree);
     t.row_order = env_i64("GGL_ROW_ORDER", t.row_order);
@@ -303,6 +304,7 @@ extern "C" int ggl_set_option(const char *name, int64_t value) {
   else if (!strcmp(name, "ragged4")) o.ragged4 = value;
   else if (!strcmp(name, "ragged_max")) o.ragged_max = value;
   else if (!strcmp(name, "col_block")) o.col_block = value;
+  else if (!strcmp(name, "col_block16")) o.col_block16 = value;
   else if (!strcmp(name, "col_block_min_edges")) o.col_block_min_edges = value;
   else if (!strcmp(name, "col_block_min_degree")) o.col_block_min_degree = value;
   else if (!strcmp(name, "row_order")) o.row_order = value;
@@ -342,6 +344,7 @@ extern "C" int64_t ggl_get_option(const char *name) {
   if (!strcmp(name, "ragged4")) return o.ragged4;
   if (!strcmp(name, "ragged_max")) return o.ragged_max;
   if (!strcmp(name, "col_block")) return o.col_block;
+  if (!strcmp(name, "col_block16")) return o.col_block16;
   if (!strcmp(name, "col_block_min_edges")) return o.col_block_min_edges;
   if (!strcmp(name, "col_block_min_degree")) return o.col_block_min_degree;
   if (!strcmp(name, "row_order")) return o.row_order;

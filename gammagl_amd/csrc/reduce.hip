@@ -123,6 +123,19 @@ template <> struct VecIO<float, 4> {
   }
 };
 
+// eight f32 results of a lane that walks eight 16-bit elements (the mixed-precision SpMM: f32 partials, f32 output)
+template <> struct VecIO<float, 8> {
+  static __device__ __forceinline__ void load(const float *__restrict__ p, float (&v)[8]) {
+    const float4 t = *reinterpret_cast<const float4 *>(p), u = *reinterpret_cast<const float4 *>(p + 4);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; v[4] = u.x; v[5] = u.y; v[6] = u.z; v[7] = u.w;
+  }
+  static __device__ __forceinline__ void store(float *__restrict__ p, const float (&v)[8]) {
+    float4 t, u;
+    t.x = v[0]; t.y = v[1]; t.z = v[2]; t.w = v[3]; u.x = v[4]; u.y = v[5]; u.z = v[6]; u.w = v[7];
+    *reinterpret_cast<float4 *>(p) = t;
+    *reinterpret_cast<float4 *>(p + 4) = u;
+  }
+};
 // 16-byte accesses for the 16-bit float storage types (8 elements) and for f64 (2 elements)
 template <> struct VecIO<uint16_t, 8> {
   static __device__ __forceinline__ void load(const uint16_t *__restrict__ p, uint16_t (&v)[8]) {
@@ -192,6 +205,18 @@ template <> struct RowIO<float, 4, true> {
     F4U t;
     t.x = v[0]; t.y = v[1]; t.z = v[2]; t.w = v[3];
     *reinterpret_cast<F4U *>(p) = t;
+  }
+};
+template <> struct RowIO<float, 8, true> {
+  static __device__ __forceinline__ void load(const float *__restrict__ p, float (&v)[8], int) {
+    const F4U t = *reinterpret_cast<const F4U *>(p), u = *reinterpret_cast<const F4U *>(p + 4);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; v[4] = u.x; v[5] = u.y; v[6] = u.z; v[7] = u.w;
+  }
+  static __device__ __forceinline__ void store(float *__restrict__ p, const float (&v)[8], int) {
+    F4U t, u;
+    t.x = v[0]; t.y = v[1]; t.z = v[2]; t.w = v[3]; u.x = v[4]; u.y = v[5]; u.z = v[6]; u.w = v[7];
+    *reinterpret_cast<F4U *>(p) = t;
+    *reinterpret_cast<F4U *>(p + 4) = u;
   }
 };
 template <> struct RowIO<uint16_t, 8, true> {
@@ -361,13 +386,13 @@ __device__ __forceinline__ void init_acc(typename TT<T>::A (&acc)[VEC], argreg_t
 
 // accumulate mode: the row starts from what `out` already holds (sum only)
 template <typename T, int VEC, int OP, bool RAG = false>
-__device__ __forceinline__ void seed_acc(const ReduceDims &d, const typename TT<T>::S *__restrict__ out,
+__device__ __forceinline__ void seed_acc(const ReduceDims &d, const typename TO<T>::O *__restrict__ out,
                                          int64_t row, int64_t kk, typename TT<T>::A (&acc)[VEC]) {
   if (OP == OP_SUM && d.accumulate) {
-    typename TT<T>::S o[VEC];
-    RowIO<typename TT<T>::S, VEC, RAG>::load(out + row * d.out_ld + kk, o, valid_lanes<VEC, RAG>(d.K, kk));
+    typename TO<T>::O o[VEC];
+    RowIO<typename TO<T>::O, VEC, RAG>::load(out + row * d.out_ld + kk, o, valid_lanes<VEC, RAG>(d.K, kk));
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) acc[i] = TT<T>::load(o[i]);
+    for (int i = 0; i < VEC; ++i) acc[i] = TO<T>::oload(o[i]);
   }
 }
 
@@ -407,11 +432,11 @@ __device__ __forceinline__ void epi_prefetch(const RPtrs<typename TT<T>::S> &q, 
 // mean / store epilogue of a finished row
 template <typename T, int VEC, int OP, int MODE, bool RAG = false>
 __device__ __forceinline__ void finish_row(const RPtrs<typename TT<T>::S> &q, const ReduceDims &d,
-                                           typename TT<T>::S *__restrict__ out,
+                                           typename TO<T>::O *__restrict__ out,
                                            int64_t *__restrict__ argout, int64_t K, int64_t row,
                                            int64_t len, int64_t kk, typename TT<T>::A (&acc)[VEC],
                                            const argreg_t (&arg)[VEC], const EpiPre<VEC> &pre) {
-  using S = typename TT<T>::S;
+  using O = typename TO<T>::O;
   const int nv = valid_lanes<VEC, RAG>(K, kk);
   if (OP == OP_MEAN) {
     if (seg_like(MODE)) {
@@ -444,10 +469,10 @@ __device__ __forceinline__ void finish_row(const RPtrs<typename TT<T>::S> &q, co
       acc[i] = (typename TT<T>::A)v;
     }
   }
-  S o[VEC];
+  O o[VEC];
 #pragma unroll
-  for (int i = 0; i < VEC; ++i) o[i] = TT<T>::store(acc[i]);
-  RowIO<S, VEC, RAG>::store(out + row * d.out_ld + kk, o, nv);
+  for (int i = 0; i < VEC; ++i) o[i] = TO<T>::ostore(acc[i]);
+  RowIO<O, VEC, RAG>::store(out + row * d.out_ld + kk, o, nv);
   if (OP == OP_MAX) {
 #pragma unroll
     for (int i = 0; i < VEC; ++i)
@@ -486,12 +511,13 @@ __global__ __launch_bounds__(kBlock) GGL_RR_WAVES(T, VEC, OP, U, RAG) void row_r
                                                             const int32_t *__restrict__ row_order,
                                                             const int32_t *__restrict__ long_rows,
                                                             const int64_t *__restrict__ chunk_ptr,
-                                                            typename TT<T>::S *__restrict__ partial,
+                                                            typename TO<T>::P *__restrict__ partial,
                                                             int64_t *__restrict__ partial_arg,
-                                                            typename TT<T>::S *__restrict__ out,
+                                                            typename TO<T>::O *__restrict__ out,
                                                             int64_t *__restrict__ argout,
                                                             const ReduceDims d) {
   using S = typename TT<T>::S;
+  using P = typename TO<T>::P;
   using A = typename TT<T>::A;
   GGL_RPTR_PACK(S);
   const int lane = threadIdx.x & (kWave - 1);
@@ -517,11 +543,11 @@ __global__ __launch_bounds__(kBlock) GGL_RR_WAVES(T, VEC, OP, U, RAG) void row_r
       argreg_t arg[VEC];
       init_acc<T, VEC, OP>(acc, arg, d.arg_fill);
       reduce_range<T, VEC, OP, MODE, IDX, U, RAG>(q, d, row, beg, end, kk, acc, arg);
-      S o[VEC];
+      P o[VEC];
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) o[i] = TT<T>::store(acc[i]);
+      for (int i = 0; i < VEC; ++i) o[i] = TO<T>::pstore(acc[i]);
       const int nv = valid_lanes<VEC, RAG>(d.K, kk);
-      RowIO<S, VEC, RAG>::store(partial + cid * d.K + kk, o, nv);
+      RowIO<P, VEC, RAG>::store(partial + cid * d.K + kk, o, nv);
       if (OP == OP_MAX) {
 #pragma unroll
         for (int i = 0; i < VEC; ++i)
@@ -568,9 +594,9 @@ template <typename T, int OP, int MODE>
 __global__ __launch_bounds__(kBlock) void long_final_kernel(const int64_t *__restrict__ rowptr,
                                                             const int32_t *__restrict__ long_rows,
                                                             const int64_t *__restrict__ chunk_ptr,
-                                                            const typename TT<T>::S *__restrict__ partial,
+                                                            const typename TO<T>::P *__restrict__ partial,
                                                             const int64_t *__restrict__ partial_arg,
-                                                            typename TT<T>::S *__restrict__ out,
+                                                            typename TO<T>::O *__restrict__ out,
                                                             int64_t *__restrict__ argout,
                                                             const float *__restrict__ epi_bias,
                                                             const int64_t *__restrict__ epi_rng,
@@ -592,7 +618,7 @@ __global__ __launch_bounds__(kBlock) void long_final_kernel(const int64_t *__res
     init_acc<T, 1, OP>(acc, arg, d.arg_fill);
     seed_acc<T, 1, OP>(d, out, row, k, acc);
     for (int64_t c = c0; c < c1; ++c) {
-      const A v = TT<T>::load(partial[c * d.K + k]);
+      const A v = TO<T>::pload(partial[c * d.K + k]);
       if (OP == OP_MAX) {
         if (TT<T>::less(acc[0], v)) {  // strict <: the earliest chunk (smallest e) keeps ties
           acc[0] = v;
@@ -665,7 +691,8 @@ static inline int pow2_ceil_log2(int64_t v) {
 // epilogue.  (max has no rounding; the mean / max backward walks keep their chunks.)
 template <typename T, int OP, int MODE> constexpr bool exact_long_mode() {
   return OP != OP_MAX && ((std::is_same<T, float>::value && (seg_like(MODE) || spmm_like(MODE) || MODE == MODE_BSPMM)) ||
-                          (std::is_same<T, double>::value && (MODE == MODE_SEG)));
+                          (std::is_same<T, double>::value && (MODE == MODE_SEG)) ||
+                          (mx_code<T>::value != 0 && MODE == MODE_SPMM));   // 16-bit storage, f32 sums: the f32 walk's conditions
 }
 
 // ... and whether this launch takes it (positions travel as int32 in the hub kernel's registers, like the plan's own perm
@@ -686,6 +713,7 @@ template <typename T, int MODE> static HubF32Args hub_args_of(const ReduceArgs &
   HubF32Args h{};
   constexpr int kWords = std::is_same<T, double>::value ? 2 : 1;   // doubles travel as pairs of 4-byte words (hubf32.hip)
   h.f64 = kWords == 2 ? 1 : 0;
+  h.x16 = mx_code<T>::value;      // (16-bit source rows: x_ld / K stay in elements, the partial rows are f32)
   h.x = reinterpret_cast<const float *>(a.x);
   h.x_ld = x_ld * kWords;
   h.perm = a.perm;
@@ -708,9 +736,11 @@ template <typename T, int MODE> static HubF32Args hub_args_of(const ReduceArgs &
 template <typename T, int VEC, int OP, int MODE, int IDX, bool RAG = false>
 static int launch_idx(const ReduceArgs &a_in, ReduceDims d, hipStream_t stream) {
   using S = typename TT<T>::S;
+  using O = typename TO<T>::O;
+  using P = typename TO<T>::P;
   ReduceArgs a = a_in;
   const bool uniform = !RAG && (d.logL == 6) && std::is_same<T, float>::value;   // (ragged rows: K <= 128 only)
-  S *out = static_cast<S *>(a.out);
+  O *out = static_cast<O *>(a.out);
   int forked = a.phase == 2 ? a.hub_forked : 0;     // the hub launch's join token (0 = nothing to join)
   const bool exact = exact_long_applies<T, OP, MODE>(a);
 #ifdef GGL_EMULATE
@@ -739,7 +769,7 @@ static int launch_idx(const ReduceArgs &a_in, ReduceDims d, hipStream_t stream) 
   const int64_t grid = d.chunk_blocks + d.nblocks;
   GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "grid too large");
   const int32_t *order = (options().row_order && (!uniform || options().row_order > 1)) ? a.row_order : nullptr;
-#define GGL_RR_ARGS GGL_RPTR_ARGS(S), order, a.long_rows, a.chunk_ptr, static_cast<S *>(a.partial), a.partial_arg, out, a.arg, d
+#define GGL_RR_ARGS GGL_RPTR_ARGS(S), order, a.long_rows, a.chunk_ptr, static_cast<P *>(a.partial), a.partial_arg, out, a.arg, d
   if (a.phase == 2) {
     // (join + long_final only)
   } else if (uniform) {
@@ -774,7 +804,7 @@ static int launch_idx(const ReduceArgs &a_in, ReduceDims d, hipStream_t stream) 
 #endif
   if (a.n_long > 0) {
     GGL_LAUNCH((long_final_kernel<T, OP, MODE>), a.n_long, kBlock, stream, a.rowptr, a.long_rows,
-               a.chunk_ptr, static_cast<const S *>(a.partial), (const int64_t *)a.partial_arg, out,
+               a.chunk_ptr, static_cast<const P *>(a.partial), (const int64_t *)a.partial_arg, out,
                a.arg, a.epi_bias, a.epi_rng, a.epi_add, d);
     GGL_LAUNCH_CHECK();
   }
@@ -1007,6 +1037,85 @@ static int launch_seg(int dtype, const ReduceArgs &a, hipStream_t stream) {
       return launch_typed<int64_t, 1, OP, MODE_SEG, false>(a, stream);
     default: set_error("unsupported dtype code %d", dtype); return GGL_EDTYPE;
   }
+}
+
+// ---- mixed-precision SpMM: rows stored as bf16 / f16, every product and add in f32, one rounding at the store ----------
+// The walk is the f32 one: same element order per column, same __fmul_rn / __fadd_rn, hub rows through the same serial
+// hub walk (hubf32.hip, 16-bit source form), chunk partials in f32 — so out == f32_op(x.float()).to(dtype) bit for bit
+// wherever the f32 op itself is the serial sum.  A lane moves 16 bytes = EIGHT columns and keeps eight f32 sums.
+template <typename T, int OP, int MODE>
+static int launch_x16_typed(const ReduceArgs &a, hipStream_t stream) {
+  constexpr bool kStatic = MODE == MODE_SPMM;
+  // (rows of <= 8 columns: one element per lane, as the 16-bit segment sums do — eight per lane would leave one lane per row)
+  if (wide_ok(a, 8) && a.K > 8) return launch_typed<T, 8, OP, MODE, kStatic>(a, stream);
+  if (ragged16_ok<OP>(a)) return launch_typed<T, 8, OP, MODE, false, true>(a, stream);
+  return launch_typed<T, 1, OP, MODE, false>(a, stream);
+}
+template <int OP, int MODE>
+static int launch_x16(int xd, int od, const ReduceArgs &a, hipStream_t stream) {
+  if (xd == GGL_BF16) {
+    if (od == GGL_F32) return launch_x16_typed<f32out<mxbf16_t>, OP, MODE>(a, stream);
+    return launch_x16_typed<mxbf16_t, OP, MODE>(a, stream);
+  }
+  if (od == GGL_F32) return launch_x16_typed<f32out<mxf16_t>, OP, MODE>(a, stream);
+  return launch_x16_typed<mxf16_t, OP, MODE>(a, stream);
+}
+
+// Column blocks of the 16-bit launches: their own width (option col_block16).  64 columns — the f32 default — are ONE
+// 128-byte line at 16 bits, the slice width that loses at f32 (col_block_width above); the sweep over 64 / 128 / 256 / one
+// launch is in profiles/spmm16.txt.  Blocks are multiples of 8 columns (16-byte lanes) and tile the row exactly unless the
+// row is wider than one pass of a lane group (512 columns).
+static int64_t col_block_width16(int64_t E, int64_t K, int64_t N) {   // 0 = one launch
+  if (N > 0 && E < options().col_block_min_degree * N) return 0;
+  int64_t bw = options().col_block16;
+  if (bw > 0 && E < options().col_block_min_edges) bw *= 2;
+  if (bw <= 0 || bw % 8 != 0 || K < 2 * bw || K % 8 != 0) return 0;
+  if (K % bw != 0 && K <= 512) return 0;
+  return bw;
+}
+extern "C" int64_t ggl_spmm_col_blocks_x16(const ggl_segplan_t *plan, int64_t K) {
+  if (plan == nullptr) return 1;
+  const int64_t bw = col_block_width16(plan->E, K, plan->N);
+  return bw > 0 ? (K + bw - 1) / bw : 1;
+}
+
+template <int OP>
+static int launch_x16_cols(int xd, int od, const ReduceArgs &a0, hipStream_t stream) {
+  const int64_t bw = col_block_width16(a0.E, a0.K, a0.N);
+  if (bw <= 0 || a0.N <= 0) return launch_x16<OP, MODE_SPMM>(xd, od, a0, stream);
+  // (the hub launch, its side stream and the join are the f32 path's: launch_f32_cols)
+  bool one_hub = false;
+  int forked = 0;
+#ifndef GGL_EMULATE
+  const int64_t ohl = options().hub_one_launch;
+  if ((ohl == 1 || (ohl == 2 && a0.xcd_run_rows < 0)) && exact_long_applies<mxbf16_t, OP, MODE_SPMM>(a0)) {
+    GGL_REQUIRE(a0.partial != nullptr, GGL_EWORKSPACE, "plan has long rows but no partial buffer");
+    const int64_t ld = a0.x_ld > 0 ? a0.x_ld : a0.K;
+    const HubF32Args h = xd == GGL_BF16 ? hub_args_of<mxbf16_t, MODE_SPMM>(a0, ld) : hub_args_of<mxf16_t, MODE_SPMM>(a0, ld);
+    const int rc = hub_f32_launch(h, stream, options().exact_side_stream != 0, &forked);
+    if (rc) return rc;
+    one_hub = true;
+  }
+#endif
+  const size_t osz = dtype_size(od);
+  for (int64_t c0 = 0; c0 < a0.K; c0 += bw) {
+    ReduceArgs a = a0;
+    a.phase = one_hub ? 1 : 0;
+    a.K = (a0.K - c0) < bw ? (a0.K - c0) : bw;
+    a.x = static_cast<const uint16_t *>(a0.x) + c0;
+    a.out = static_cast<char *>(a0.out) + (size_t)c0 * osz;
+    a.x_ld = a0.x_ld > 0 ? a0.x_ld : a0.K;
+    a.out_ld = a0.out_ld > 0 ? a0.out_ld : a0.K;
+    const int rc = launch_x16<OP, MODE_SPMM>(xd, od, a, stream);
+    if (rc) return rc;
+  }
+  if (one_hub) {
+    ReduceArgs a = a0;
+    a.phase = 2;
+    a.hub_forked = forked;
+    return launch_x16<OP, MODE_SPMM>(xd, od, a, stream);
+  }
+  return GGL_OK;
 }
 
 static int fill_plan(ReduceArgs &a, const ggl_segplan_t *plan, int dtype, int64_t K, bool with_arg) {
@@ -1266,6 +1375,58 @@ extern "C" int ggl_spmm_mean_bwd(const ggl_segplan_t *planT, const int32_t *colT
   GGL_REQUIRE(fwd_rowptr != nullptr, GGL_EINVAL, "fwd_rowptr is NULL");
   a.aux_rowptr = fwd_rowptr;
   return launch_f32<OP_SUM, MODE_MEANBWD>(a, as_stream(stream));
+}
+
+// ---- gspmm, 16-bit storage / f32 arithmetic (include/ggl_mpops.h: "Mixed-precision aggregate") ---------------------------
+static int spmm16_common(ReduceArgs &a, const ggl_segplan_t *plan, const int32_t *col, const float *w, int w_by_pos,
+                         int x_dtype, const void *x, int64_t x_ld, int64_t K, int out_dtype, void *out, int64_t out_ld) {
+  if ((x_dtype != GGL_F16 && x_dtype != GGL_BF16) || (out_dtype != x_dtype && out_dtype != GGL_F32)) {
+    set_error("x16: x must be f16 or bf16 and out the same or f32 (got dtype codes %d -> %d)", x_dtype, out_dtype);
+    return GGL_EDTYPE;
+  }
+  int rc = fill_plan(a, plan, GGL_F32, K, false);     // (chunk / hub partials are f32: ggl_partial_bytes(GGL_F32, ...))
+  if (rc) return rc;
+  GGL_REQUIRE(col || plan->E == 0, GGL_EINVAL, "col is NULL");
+  GGL_REQUIRE((x || plan->E * K == 0) && (out || plan->N * K == 0), GGL_EINVAL, "x/out is NULL");
+  GGL_REQUIRE((x_ld == 0 || x_ld >= K) && (out_ld == 0 || out_ld >= K), GGL_EINVAL, "row stride < K");
+  a.x = x;
+  a.col = col;
+  a.w = w;
+  a.w_by_pos = w_by_pos;
+  a.out = out;
+  a.x_ld = x_ld;
+  a.out_ld = out_ld;
+  return GGL_OK;
+}
+
+extern "C" int ggl_spmm_sum_x16(const ggl_segplan_t *plan, const int32_t *col, const float *w, int w_by_pos, int x_dtype,
+                                const void *x, int64_t x_ld, int64_t K, int out_dtype, void *out, int64_t out_ld,
+                                void *stream) {
+  ReduceArgs a{};
+  int rc = spmm16_common(a, plan, col, w, w_by_pos, x_dtype, x, x_ld, K, out_dtype, out, out_ld);
+  if (rc) return rc;
+  return launch_x16_cols<OP_SUM>(x_dtype, out_dtype, a, as_stream(stream));
+}
+
+extern "C" int ggl_spmm_mean_x16(const ggl_segplan_t *plan, const int32_t *col, const float *w, int w_by_pos, int x_dtype,
+                                 const void *x, int64_t x_ld, int64_t K, int out_dtype, void *out, int64_t out_ld,
+                                 void *stream) {
+  ReduceArgs a{};
+  int rc = spmm16_common(a, plan, col, w, w_by_pos, x_dtype, x, x_ld, K, out_dtype, out, out_ld);
+  if (rc) return rc;
+  return launch_x16_cols<OP_MEAN>(x_dtype, out_dtype, a, as_stream(stream));
+}
+
+// gx[src] += g[dst] / count[dst] * w, divide and multiply in f32 as ggl_spmm_mean_bwd makes them, on a 16-bit g
+extern "C" int ggl_spmm_mean_bwd_x16(const ggl_segplan_t *planT, const int32_t *colT, const float *w, int w_by_pos,
+                                     int g_dtype, const void *g, const int64_t *fwd_rowptr, int64_t K, int gx_dtype,
+                                     void *gx, void *stream) {
+  ReduceArgs a{};
+  int rc = spmm16_common(a, planT, colT, w, w_by_pos, g_dtype, g, 0, K, gx_dtype, gx, 0);
+  if (rc) return rc;
+  GGL_REQUIRE(fwd_rowptr != nullptr, GGL_EINVAL, "fwd_rowptr is NULL");
+  a.aux_rowptr = fwd_rowptr;
+  return launch_x16<OP_SUM, MODE_MEANBWD>(g_dtype, gx_dtype, a, as_stream(stream));
 }
 
 extern "C" int ggl_spmm_max_bwd(const ggl_segplan_t *planT, const int32_t *colT, const float *w,

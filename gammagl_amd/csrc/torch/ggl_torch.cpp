@@ -68,7 +68,7 @@ using torch::autograd::variable_list;
   X(ggl_spmm_max_mask_bytes) X(ggl_spmm_max_mask) X(ggl_spmm_max_bwd_mask) X(ggl_invert_perm) X(ggl_get_option)      \
   X(ggl_spmm_max_bwd32) X(ggl_policy_maxbwd_form)                                                                   \
   X(ggl_segment_softmax_supported) X(ggl_segment_softmax_partial_bytes) X(ggl_segment_softmax_fwd) X(ggl_segment_softmax_bwd) \
-  X(ggl_policy_softmax_sublanes)
+  X(ggl_policy_softmax_sublanes) X(ggl_spmm_sum_x16) X(ggl_spmm_mean_x16) X(ggl_spmm_mean_bwd_x16)
 
 struct Api {
   void *handle = nullptr;
@@ -526,9 +526,44 @@ static std::pair<const float *, int> weights_for(const Api &a, GraphPlan &gp, co
 
 enum class SpOp { Sum, Mean, Max, MeanBwd, MaxBwd };
 
+static bool is_x16(const Tensor &t) { return t.scalar_type() == at::kHalf || t.scalar_type() == at::kBFloat16; }
+
+// sum / mean / mean backward on rows STORED as f16 / bf16 (ggl_spmm_*_x16): widened at the load, the f32 op's products and adds
+// in its order, rounded once at the store — or not at all with out_f32.  Any width, nothing padded; f32 partials.
+static Tensor spmm_fwd16(SpOp op, GraphPlan &gp, const SegPlan &p, const Tensor &col, const Tensor &w, const Tensor &x,
+                         int64_t n_out, const Tensor &aux, bool out_f32) {
+  const auto dev = x.device();
+  const Api &a = api_for(dev);
+  int64_t K = 1;
+  for (int64_t d = 1; d < x.dim(); ++d) K *= x.size(d);
+  Tensor out = at::empty(out_shape(x, n_out), out_f32 ? x.options().dtype(at::kFloat) : x.options());
+  void *st = stream_of(dev);
+  Tensor part;
+  if (p.n_long > 0) {
+    const size_t nb = a.ggl_partial_bytes(GGL_F32, p.n_chunks, K, 0);
+    part = at::empty({static_cast<int64_t>(nb) + 16}, x.options().dtype(at::kByte));
+  }
+  ggl_segplan_t cs = p.c(part);
+  Tensor keep;
+  auto [wp, by_pos] = weights_for(a, gp, p, w, keep);
+  const int32_t *c = col.data_ptr<int32_t>();
+  const int xc = dtype_code(x), oc = out_f32 ? GGL_F32 : xc;
+  switch (op) {
+    case SpOp::Sum: check(a, a.ggl_spmm_sum_x16(&cs, c, wp, by_pos, xc, x.data_ptr(), 0, K, oc, out.data_ptr(), 0, st)); break;
+    case SpOp::Mean: check(a, a.ggl_spmm_mean_x16(&cs, c, wp, by_pos, xc, x.data_ptr(), 0, K, oc, out.data_ptr(), 0, st)); break;
+    case SpOp::MeanBwd:
+      check(a, a.ggl_spmm_mean_bwd_x16(&cs, c, wp, by_pos, xc, x.data_ptr(), aux.data_ptr<int64_t>(), K, oc, out.data_ptr(), st));
+      break;
+    default: TORCH_CHECK(false, "expected scalar type Float but found ", x.scalar_type(), " (gspmm max is f32 only)");
+  }
+  return out;
+}
+
 static std::pair<Tensor, Tensor> spmm_fwd(SpOp op, GraphPlan &gp, const SegPlan &p, const Tensor &col, const Tensor &w,
                                           const Tensor &x, int64_t n_out, const Tensor &aux = Tensor(),
-                                          const Tensor &tpos = Tensor()) {
+                                          const Tensor &tpos = Tensor(), bool out_f32 = false) {
+  if (is_x16(x) && (op == SpOp::Sum || op == SpOp::Mean || op == SpOp::MeanBwd))
+    return {spmm_fwd16(op, gp, p, col, w, x, n_out, aux, out_f32), Tensor()};
   const auto dev = x.device();
   const Api &a = api_for(dev);
   int64_t K = 1;
@@ -704,10 +739,11 @@ struct SpArgs {
   std::shared_ptr<GraphPlan> gp;
   Tensor w, x;
 };
-static SpArgs spmm_args(const Tensor &index, const c10::optional<Tensor> &weight, const Tensor &x) {
+// x16: the op also takes rows stored as f16 / bf16 (sum and mean: an extension over the reference, which is f32 only)
+static SpArgs spmm_args(const Tensor &index, const c10::optional<Tensor> &weight, const Tensor &x, bool x16 = false) {
   Tensor w = opt(weight);
   same_device({&index, &w, &x});
-  f32("x", x);
+  if (!(x16 && is_x16(x))) f32("x", x);
   if (w.defined()) f32("weight", w);
   TORCH_CHECK(x.dim() >= 1, "x must have a node dimension");
   SpArgs s;
@@ -720,10 +756,11 @@ static SpArgs spmm_args(const Tensor &index, const c10::optional<Tensor> &weight
 }
 
 static Tensor spmm_kernel(SpOp op, const Tensor &index, const c10::optional<Tensor> &weight, const Tensor &x,
-                          Tensor *arg = nullptr) {
+                          Tensor *arg = nullptr, bool out_f32 = false) {
   c10::OptionalDeviceGuard guard(x.device());
-  SpArgs s = spmm_args(index, weight, x);
-  auto r = spmm_fwd(op, *s.gp, *s.gp->fwd, s.gp->col, s.w, s.x, s.gp->N_dst);
+  SpArgs s = spmm_args(index, weight, x, op != SpOp::Max);
+  TORCH_CHECK(!out_f32 || is_x16(s.x), "out_f32 is for f16 / bf16 rows (x is ", x.scalar_type(), ")");
+  auto r = spmm_fwd(op, *s.gp, *s.gp->fwd, s.gp->col, s.w, s.x, s.gp->N_dst, Tensor(), Tensor(), out_f32);
   if (arg != nullptr) *arg = r.second;
   return r.first;
 }
@@ -735,6 +772,15 @@ static Tensor spmm_mean_kernel(const Tensor &i, const c10::optional<Tensor> &w, 
 }
 static Tensor spmm_max_kernel(const Tensor &i, const c10::optional<Tensor> &w, const Tensor &x) {
   return spmm_kernel(SpOp::Max, i, w, x);
+}
+// f16 / bf16 rows, the f32 sums as they are (out_f32) or rounded once to x's dtype (= spmm_sum / spmm_mean on such rows)
+static Tensor spmm_sum_x16_kernel(const Tensor &i, const c10::optional<Tensor> &w, const Tensor &x, bool out_f32) {
+  TORCH_CHECK(is_x16(x), "spmm_sum_x16 takes f16 / bf16 rows (x is ", x.scalar_type(), ")");
+  return spmm_kernel(SpOp::Sum, i, w, x, nullptr, out_f32);
+}
+static Tensor spmm_mean_x16_kernel(const Tensor &i, const c10::optional<Tensor> &w, const Tensor &x, bool out_f32) {
+  TORCH_CHECK(is_x16(x), "spmm_mean_x16 takes f16 / bf16 rows (x is ", x.scalar_type(), ")");
+  return spmm_kernel(SpOp::Mean, i, w, x, nullptr, out_f32);
 }
 
 static int64_t head_pad(const GraphPlan &gp, const Tensor &x) {   // channels to append per head (ggl_policy_head_channels)
@@ -810,12 +856,16 @@ static std::shared_ptr<GraphPlan> bwd_plan(const Tensor &index, int64_t n) {
 // gx[src] += w[e] * g[dst]: the same walk on the transposed plan          (spmm_sum_cpu.cpp:43-80)
 static Tensor spmm_sum_backward_kernel(const Tensor &index, const c10::optional<Tensor> &weight, const Tensor &grad) {
   Tensor g = grad.contiguous(), w = opt_dense(weight);
+  if (!is_x16(g)) f32("grad", g);
+  if (w.defined()) f32("weight", w);
   c10::OptionalDeviceGuard guard(g.device());
   auto gp = bwd_plan(index, g.size(0));
   return spmm_fwd(SpOp::Sum, *gp, *gp->bwd, gp->colT, w, g, gp->N_src).first;
 }
 static Tensor spmm_mean_backward_kernel(const Tensor &index, const c10::optional<Tensor> &weight, const Tensor &grad) {
   Tensor g = grad.contiguous(), w = opt_dense(weight);
+  if (!is_x16(g)) f32("grad", g);
+  if (w.defined()) f32("weight", w);
   c10::OptionalDeviceGuard guard(g.device());
   auto gp = bwd_plan(index, g.size(0));
   return spmm_fwd(SpOp::MeanBwd, *gp, *gp->bwd, gp->colT, w, g, gp->N_src, gp->fwd->rowptr).first;
@@ -1363,6 +1413,28 @@ static std::tuple<Tensor, Tensor> segment_max_autograd(const Tensor &x, const Te
   return {r[0], r[1]};
 }
 static Tensor segment_softmax_autograd(const Tensor &x, const Tensor &i, int64_t N) { return SegmentSoftmaxFn::apply(x, i, N); }
+// f16 / bf16 rows with an f32 result: the gradient arrives in f32, is walked in f32 and rounded once to x's dtype
+template <SpOp OP>
+struct SpMMX16Fn : public torch::autograd::Function<SpMMX16Fn<OP>> {
+  using Sig16 = Tensor(const Tensor &, const OptT &, const Tensor &, bool);
+  static Tensor forward(AutogradContext *ctx, const Tensor &index, const OptT &weight, const Tensor &x, bool out_f32) {
+    at::AutoDispatchBelowADInplaceOrView below;
+    static auto op = op_handle<Sig16>(OP == SpOp::Sum ? "ggl::spmm_sum_x16" : "ggl::spmm_mean_x16");
+    ctx->save_for_backward({index, opt(weight)});
+    ctx->saved_data["x_dtype"] = static_cast<int64_t>(x.scalar_type());
+    return op.call(index, weight, x, out_f32);
+  }
+  static variable_list backward(AutogradContext *ctx, variable_list grads) {
+    auto saved = ctx->get_saved_variables();
+    OptT w = saved[1].defined() ? OptT(saved[1]) : OptT();
+    static auto op = op_handle<SpSig>(OP == SpOp::Sum ? "ggl::spmm_sum_backward" : "ggl::spmm_mean_backward");
+    Tensor gx = op.call(saved[0], w, grads[0]);
+    const auto xt = static_cast<at::ScalarType>(ctx->saved_data["x_dtype"].toInt());
+    return {Tensor(), Tensor(), gx.scalar_type() == xt ? gx : gx.to(xt), Tensor()};
+  }
+};
+static Tensor spmm_sum_x16_autograd(const Tensor &i, const OptT &w, const Tensor &x, bool f) { return SpMMX16Fn<SpOp::Sum>::apply(i, w, x, f); }
+static Tensor spmm_mean_x16_autograd(const Tensor &i, const OptT &w, const Tensor &x, bool f) { return SpMMX16Fn<SpOp::Mean>::apply(i, w, x, f); }
 static Tensor spmm_sum_autograd(const Tensor &i, const OptT &w, const Tensor &x) { return SpMMFn<SpOp::Sum>::apply(i, w, x); }
 static Tensor spmm_mean_autograd(const Tensor &i, const OptT &w, const Tensor &x) { return SpMMFn<SpOp::Mean>::apply(i, w, x); }
 static Tensor spmm_max_autograd(const Tensor &i, const OptT &w, const Tensor &x) { return SpMMFn<SpOp::Max>::apply(i, w, x); }
@@ -1561,6 +1633,9 @@ static std::tuple<Tensor, Tensor> seg_max_meta(const Tensor &x, const Tensor &, 
   return {at::empty(out_shape(x, N), x.options()), at::empty(out_shape(x, N), x.options().dtype(at::kLong))};
 }
 static Tensor like_x_meta(const Tensor &, const OptT &, const Tensor &x) { return at::empty_like(x); }
+static Tensor x16_meta(const Tensor &, const OptT &, const Tensor &x, bool out_f32) {
+  return out_f32 ? at::empty(x.sizes(), x.options().dtype(at::kFloat)) : at::empty_like(x);
+}
 static std::tuple<Tensor, Tensor> spmm_max_arg_meta(const Tensor &, const OptT &, const Tensor &x) {
   return {at::empty_like(x), at::empty(x.sizes(), x.options().dtype(at::kLong))};
 }
@@ -1648,6 +1723,9 @@ TORCH_LIBRARY(ggl, m) {
   m.def("spmm_mean(Tensor index, Tensor? weight, Tensor x) -> Tensor");
   m.def("spmm_max(Tensor index, Tensor? weight, Tensor x) -> Tensor");
   m.def("bspmm_sum(Tensor index, Tensor weight, Tensor x) -> Tensor");
+  // not in the reference: rows stored as f16 / bf16, summed in f32; out_f32 keeps the f32 sums (a last layer's logits)
+  m.def("spmm_sum_x16(Tensor index, Tensor? weight, Tensor x, bool out_f32=False) -> Tensor");
+  m.def("spmm_mean_x16(Tensor index, Tensor? weight, Tensor x, bool out_f32=False) -> Tensor");
   // backward passes and the arg-returning max (what the autograd formulas call; usable on their own)
   m.def("segment_sum_backward(Tensor grad, Tensor index, int[] x_shape) -> Tensor");
   m.def("segment_mean_backward(Tensor grad, Tensor index, int N, int[] x_shape) -> Tensor");
@@ -1700,6 +1778,8 @@ TORCH_LIBRARY(ggl, m) {
     m.impl("spmm_mean", ggl_torch::spmm_mean_kernel);        \
     m.impl("spmm_max", ggl_torch::spmm_max_kernel);          \
     m.impl("bspmm_sum", ggl_torch::bspmm_sum_kernel);        \
+    m.impl("spmm_sum_x16", ggl_torch::spmm_sum_x16_kernel);  \
+    m.impl("spmm_mean_x16", ggl_torch::spmm_mean_x16_kernel); \
     m.impl("segment_sum_backward", ggl_torch::segment_sum_backward_kernel);    \
     m.impl("segment_mean_backward", ggl_torch::segment_mean_backward_kernel);  \
     m.impl("segment_max_backward", ggl_torch::segment_max_backward_kernel);    \
@@ -1730,6 +1810,8 @@ TORCH_LIBRARY_IMPL(ggl, Autograd, m) {
   m.impl("spmm_mean", ggl_torch::spmm_mean_autograd);
   m.impl("spmm_max", ggl_torch::spmm_max_autograd);
   m.impl("bspmm_sum", ggl_torch::bspmm_sum_autograd);
+  m.impl("spmm_sum_x16", ggl_torch::spmm_sum_x16_autograd);
+  m.impl("spmm_mean_x16", ggl_torch::spmm_mean_x16_autograd);
   m.impl("gat_fused", ggl_torch::gat_fused_autograd);
   m.impl("gat_fused_csr", ggl_torch::gat_fused_csr_autograd);
   m.impl("bias_act", ggl_torch::bias_act_autograd);
@@ -1747,6 +1829,8 @@ TORCH_LIBRARY_IMPL(ggl, Meta, m) {
   m.impl("spmm_mean", ggl_torch::like_x_meta);
   m.impl("spmm_max", ggl_torch::like_x_meta);
   m.impl("bspmm_sum", ggl_torch::bspmm_meta);
+  m.impl("spmm_sum_x16", ggl_torch::x16_meta);
+  m.impl("spmm_mean_x16", ggl_torch::x16_meta);
   m.impl("segment_sum_backward", ggl_torch::seg_bwd_meta);
   m.impl("segment_mean_backward", ggl_torch::seg_mean_bwd_meta);
   m.impl("segment_max_backward", ggl_torch::seg_bwd_meta);

@@ -71,7 +71,8 @@ class Linear(torch.nn.Linear):
     """torch.nn.Linear (same parameters / state_dict) whose weight gradient uses `wgrad` for 2-D inputs."""
 
     def forward(self, x):
-        if x.dim() != 2 or not x.is_contiguous():
+        # (under torch.autocast the built-in linear: it casts its operands and its backward runs in the forward's dtype)
+        if x.dim() != 2 or not x.is_contiguous() or torch.is_autocast_enabled(x.device.type):
             return super().forward(x)
         y = _LinearFn.apply(x, self.weight)
         return y if self.bias is None else y + self.bias

@@ -103,8 +103,11 @@ class MessagePassing(nn.Module):
             kwargs['num_nodes'] = x.shape[0]
         if 'message_aggregate' in self.__class__.__dict__:  # message_passing.py:144
             x = self.message_aggregate(x, edge_index, edge_weight=kwargs.get('edge_weight'), aggr=aggr)
-        elif (aggr in ('sum', 'mean') and edge_index.shape[1] >= FUSED_MIN_EDGES and x.dim() == 2
-              and x.dtype == torch.float32 and type(self).message is MessagePassing.message
+        elif (aggr in ('sum', 'mean') and x.dim() == 2
+              # (bf16 / f16 rows take the SpMM whatever the size: it sums in f32, the segment route in the storage type)
+              and ((x.dtype == torch.float32 and edge_index.shape[1] >= FUSED_MIN_EDGES)
+                   or x.dtype in (torch.bfloat16, torch.float16))
+              and type(self).message is MessagePassing.message
               and type(self).aggregate is MessagePassing.aggregate
               # gspmm treats the edge weight as a constant (gspmm.cpp:30); a weight that needs a gradient
               # must stay on the message() route, which differentiates through the multiply — and so must a
@@ -182,7 +185,11 @@ class GCNConv(MessagePassing):
         n_out = self.linear.weight.shape[0]
         pad = (-n_out) % 4 if n_out >= 8 else 0
         if pad and x.dim() == 2:  # class-count widths: 47 -> 48 columns inside the GEMM, dropped at the end
-            x = _LinearFn.apply(x.contiguous(), torch.nn.functional.pad(self.linear.weight, (0, 0, 0, pad)))
+            wp = torch.nn.functional.pad(self.linear.weight, (0, 0, 0, pad))
+            if torch.is_autocast_enabled(x.device.type):   # the built-in linear casts its operands (dense.Linear does the same)
+                x = torch.nn.functional.linear(x, wp)
+            else:
+                x = _LinearFn.apply(x.contiguous(), wp)
         else:
             x = self.linear(x)
         num_nodes = x.shape[0]
@@ -211,7 +218,13 @@ class GCNConv(MessagePassing):
                                     p_drop=p_drop, training=training)
         else:
             out = self.propagate(x, edge_index, edge_weight=weights, num_nodes=num_nodes)
-            if bias is not None or relu or p_drop > 0:
+            if out.dtype != torch.float32:
+                # bf16 / f16 activations (torch.autocast): the mixed-precision aggregate (f32 sums, rounded once), then the
+                # epilogue in torch — bias_act is f32 only
+                out = out + bias.to(out.dtype) if bias is not None else out
+                out = torch.relu(out) if relu else out
+                out = torch.nn.functional.dropout(out, p_drop, training) if p_drop > 0 else out
+            elif bias is not None or relu or p_drop > 0:
                 out = _engine(out).bias_act(out, bias, relu=relu, p_drop=p_drop, training=training)
         return out[:, :n_out] if pad else out
 

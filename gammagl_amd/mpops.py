@@ -94,7 +94,12 @@ def segment_sum(x, segment_ids, num_segments=None):
 
 
 def gspmm(index, weight=None, x=None, reduce='sum'):
-    """Generalized SpMM: out[dst] = reduce_e weight[e] * x[src] (torch.py:302-351)."""
+    """Generalized SpMM: out[dst] = reduce_e weight[e] * x[src] (torch.py:302-351).
+
+    An extension over the reference, which is f32 only: for 'sum' and 'mean', ``x`` may be STORED as bfloat16 / float16
+    (what a preceding Linear produces under ``torch.autocast``).  Every product and add is then made in f32, in the f32
+    op's order, and the result is rounded once to x's dtype: ``gspmm(i, w, x16) == gspmm(i, w, x16.float()).to(x16.dtype)``
+    bit for bit; the gradient w.r.t. x follows the same rule.  ``weight`` stays f32.  'max' and ``bspmm`` are f32 only."""
     _engine(x)._dev(index, weight, x)
     _ops = _ops_for(x)
     # weight=None: torch.py:332-333 builds ones([E]) f32; w * x == x exactly, so the kernels simply skip

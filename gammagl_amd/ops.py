@@ -32,6 +32,8 @@ _DTYPE_CODE = {
     torch.float16: 5, torch.bfloat16: 6, torch.float32: 7, torch.float64: 8,
 }
 _FLOAT_DTYPES = (torch.float16, torch.bfloat16, torch.float32, torch.float64)
+# gspmm sum / mean also take rows STORED in these (f32 arithmetic, one rounding at the store: ggl_spmm_*_x16)
+_X16_DTYPES = (torch.float16, torch.bfloat16)
 
 DEFAULT_CHUNK = int(os.environ.get("GGL_LONG_ROW", "0"))  # 0 = automatic, see Engine.auto_chunk
 
@@ -717,8 +719,40 @@ class Engine:
                                                 self._stream(dev)))
         return out
 
-    def _spmm_fwd(self, op, plan, col, w, x, n_out, perm_override=None, aux=None, gp=None):
+    def _spmm_fwd16(self, op, plan, col, w, x, n_out, perm_override=None, aux=None, out_dtype=None):
+        """sum / mean / mean_bwd on rows stored as bf16 / f16 (ggl_spmm_*_x16): widened at the load, the f32 op's products
+        and adds in its order, rounded once at the store — or not at all with out_dtype=torch.float32.  Any width: rows
+        that are not multiples of 8 columns take the ragged / one-element-per-lane kernels, nothing is padded."""
+        dev = x.device
+        K = int(math.prod(x.shape[1:]))
+        out_dtype = x.dtype if out_dtype is None else out_dtype
+        if out_dtype not in (x.dtype, torch.float32):
+            raise RuntimeError(f"gspmm on {x.dtype} rows returns {x.dtype} or torch.float32, not {out_dtype}")
+        out = torch.empty((n_out,) + tuple(x.shape[1:]), dtype=out_dtype, device=dev)
+        st = self._stream(dev)
+        part = self._partial(plan, torch.float32, K, False, dev)      # f32 partials: a 16-bit one would round twice
+        w, w_by_pos, wp = self._weights(plan, w, perm_override)
+        cs = plan.c_struct(part, wp)
+        L = self.lib
+        xc, oc = _DTYPE_CODE[x.dtype], _DTYPE_CODE[out_dtype]
+        if op == "sum":
+            self._check(L.ggl_spmm_sum_x16(ctypes.byref(cs), _ptr(col), _ptr(w), w_by_pos, xc, _ptr(x), 0, K, oc,
+                                           _ptr(out), 0, st))
+        elif op == "mean":
+            self._check(L.ggl_spmm_mean_x16(ctypes.byref(cs), _ptr(col), _ptr(w), w_by_pos, xc, _ptr(x), 0, K, oc,
+                                            _ptr(out), 0, st))
+        elif op == "mean_bwd":
+            # (no pre-scaled copy of g as on the f32 route: it would be an f32 [N, K] pass, the bytes this path saves)
+            self._check(L.ggl_spmm_mean_bwd_x16(ctypes.byref(cs), _ptr(col), _ptr(w), w_by_pos, xc, _ptr(x), _ptr(aux),
+                                                K, oc, _ptr(out), st))
+        else:
+            raise ValueError(op)
+        return out, None
+
+    def _spmm_fwd(self, op, plan, col, w, x, n_out, perm_override=None, aux=None, gp=None, out_dtype=None):
         """op in sum/mean/max/mean_bwd/max_bwd.  x [N_in, *]; returns out [n_out, *] (+argsrc)."""
+        if x.dtype in _X16_DTYPES and op in ("sum", "mean", "mean_bwd"):
+            return self._spmm_fwd16(op, plan, col, w, x, n_out, perm_override, aux, out_dtype)
         dev = x.device
         K = int(math.prod(x.shape[1:]))
         if op in ("sum", "mean", "max") and x.dim() == 2:
@@ -846,6 +880,19 @@ class Engine:
             # spmm_sum_cpu.cpp:22 data_ptr<float>() on a non-float tensor
             raise RuntimeError(f"expected scalar type Float but found {t.dtype} for {name}")
 
+    @staticmethod
+    def _check_f32_or_x16(name, t):
+        """gspmm sum / mean: f32 as the reference, or bf16 / f16 storage (an extension: f32 sums, rounded once)."""
+        if t.dtype != torch.float32 and t.dtype not in _X16_DTYPES:
+            raise RuntimeError(f"expected scalar type Float (or Half / BFloat16 storage) but found {t.dtype} for {name}")
+
+    def _spmm_bwd_x(self, op, gp, w, g, x_dtype, aux=None):
+        """gx of sum / mean in x's dtype: the transposed walk on g as it arrives.  An f32 g for 16-bit rows (the forward
+        returned f32: out_dtype) is walked in f32 and rounded once."""
+        g = g.contiguous()
+        gx, _ = self._spmm_fwd(op, gp.bwd, gp.colT, w, g, gp.N_src, aux=aux)
+        return gx if gx.dtype == x_dtype else gx.to(x_dtype)
+
     # ---- autograd Functions (closures over this engine) ---------------------------------------
     def _make_functions(self):
         eng = self
@@ -930,30 +977,27 @@ class Engine:
 
         class SpMMSum(torch.autograd.Function):  # src/gspmm.cpp:26-80
             @staticmethod
-            def forward(ctx, gp, w, x):
-                out, _ = eng._spmm_fwd("sum", gp.fwd, gp.col, w, x, gp.N_dst)
-                ctx.gp, ctx.w = gp, w
+            def forward(ctx, gp, w, x, out_dtype=None):
+                out, _ = eng._spmm_fwd("sum", gp.fwd, gp.col, w, x, gp.N_dst, out_dtype=out_dtype)
+                ctx.gp, ctx.w, ctx.x_dtype = gp, w, x.dtype
                 return out
 
             @staticmethod
             def backward(ctx, g):
-                gp = ctx.gp
-                gx, _ = eng._spmm_fwd("sum", gp.bwd, gp.colT, ctx.w, g.contiguous(), gp.N_src)
-                return None, None, gx  # weight is non-differentiable in the reference (gspmm.cpp:30)
+                gx = eng._spmm_bwd_x("sum", ctx.gp, ctx.w, g, ctx.x_dtype)
+                return None, None, gx, None  # weight is non-differentiable in the reference (gspmm.cpp:30)
 
         class SpMMMean(torch.autograd.Function):  # src/gspmm.cpp:82-141
             @staticmethod
-            def forward(ctx, gp, w, x):
-                out, _ = eng._spmm_fwd("mean", gp.fwd, gp.col, w, x, gp.N_dst)
-                ctx.gp, ctx.w = gp, w
+            def forward(ctx, gp, w, x, out_dtype=None):
+                out, _ = eng._spmm_fwd("mean", gp.fwd, gp.col, w, x, gp.N_dst, out_dtype=out_dtype)
+                ctx.gp, ctx.w, ctx.x_dtype = gp, w, x.dtype
                 return out
 
             @staticmethod
             def backward(ctx, g):
-                gp = ctx.gp
-                gx, _ = eng._spmm_fwd("mean_bwd", gp.bwd, gp.colT, ctx.w, g.contiguous(), gp.N_src,
-                                      aux=gp.fwd.rowptr)
-                return None, None, gx
+                gx = eng._spmm_bwd_x("mean_bwd", ctx.gp, ctx.w, g, ctx.x_dtype, aux=ctx.gp.fwd.rowptr)
+                return None, None, gx, None
 
         class SpMMMax(torch.autograd.Function):  # src/gspmm.cpp:143-202
             @staticmethod
@@ -1426,20 +1470,30 @@ class Engine:
         x, index, N = self._seg_args(x, index, N)
         return self.SegmentSoftmax.apply(x, self.seg_plan(index, N))
 
-    def _spmm_args(self, index, weight, x):
+    def _spmm_args(self, index, weight, x, x16=False):
         self._dev(index, weight, x)
-        self._check_f32("x", x)
+        (self._check_f32_or_x16 if x16 else self._check_f32)("x", x)
         if weight is not None:
             self._check_f32("weight", weight)
             weight = weight.contiguous()
         gp = self.graph_plan(index, x.shape[0])
         return gp, weight, x.contiguous()
 
-    def c_spmm_sum(self, index, weight, x):
-        return self.SpMMSum.apply(*self._spmm_args(index, weight, x))
+    def c_spmm_sum(self, index, weight, x, out_dtype=None):
+        """c_spmm_sum of the reference for f32 x; bf16 / f16 x (an extension) is summed in f32 and returned in x's dtype,
+        or unrounded with out_dtype=torch.float32."""
+        return self.SpMMSum.apply(*self._spmm_args(index, weight, x, True), self._out_dtype(x, out_dtype))
 
-    def c_spmm_mean(self, index, weight, x):
-        return self.SpMMMean.apply(*self._spmm_args(index, weight, x))
+    def c_spmm_mean(self, index, weight, x, out_dtype=None):
+        return self.SpMMMean.apply(*self._spmm_args(index, weight, x, True), self._out_dtype(x, out_dtype))
+
+    @staticmethod
+    def _out_dtype(x, out_dtype):
+        if out_dtype is None or out_dtype == x.dtype:
+            return None
+        if x.dtype not in _X16_DTYPES or out_dtype != torch.float32:
+            raise RuntimeError(f"out_dtype={out_dtype}: only torch.float32 from bf16 / f16 rows (x is {x.dtype})")
+        return out_dtype
 
     def c_spmm_max(self, index, weight, x):
         return self.SpMMMax.apply(*self._spmm_args(index, weight, x))
@@ -1493,12 +1547,18 @@ class Engine:
         return weight.reshape(-1).contiguous()
 
     # rectangular / explicit-plan variants used by the harness and the multi-GPU layer
-    def spmm(self, gp, weight, x, reduce="sum"):
+    def spmm(self, gp, weight, x, reduce="sum", out_dtype=None):
+        """sum / mean also take bf16 / f16 rows (f32 arithmetic, the result rounded once to x's dtype, or returned as
+        f32 with out_dtype=torch.float32 — a last layer's logits); max is f32 only."""
         self._dev(x, weight)
-        self._check_f32("x", x)
+        (self._check_f32 if reduce == "max" else self._check_f32_or_x16)("x", x)
         weight = self._check_weight(weight, gp)
         fn = {"sum": self.SpMMSum, "mean": self.SpMMMean, "max": self.SpMMMax}[reduce]
-        return fn.apply(gp, weight, x.contiguous())
+        if reduce == "max":
+            if out_dtype not in (None, x.dtype):
+                raise RuntimeError("spmm(max) returns x's dtype")
+            return fn.apply(gp, weight, x.contiguous())
+        return fn.apply(gp, weight, x.contiguous(), self._out_dtype(x, out_dtype))
 
     def colsum(self, g):
         """out[k] = sum_r g[r, k] for a row-major f32 [N, K] matrix (deterministic two-stage kernel)."""

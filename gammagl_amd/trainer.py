@@ -11,22 +11,38 @@ from .layers import GCNModel, GraphSAGESampleModel
 
 class GCNTrainer:
     def __init__(self, feature_dim, hidden_dim, num_class, num_layers=3, drop_rate=0.5, lr=0.01,
-                 l2_coef=5e-4, norm="both", seed=0, device="cuda"):
+                 l2_coef=5e-4, norm="both", seed=0, device="cuda", amp_dtype=None):
+        """`amp_dtype` = torch.bfloat16 / torch.float16: mixed precision — parameters and Adam state stay f32, the forward
+        runs under torch.autocast (the Linears produce 16-bit activations, every aggregate sums them in f32 and rounds
+        once), the loss is taken in f32, and f16 gradients go through a GradScaler.  None: the f32 step, unchanged."""
+        if amp_dtype not in (None, torch.bfloat16, torch.float16):
+            raise ValueError("amp_dtype must be None, torch.bfloat16 or torch.float16")
         torch.manual_seed(seed)
         self.net = GCNModel(feature_dim, hidden_dim, num_class, drop_rate=drop_rate,
                             num_layers=num_layers, norm=norm).to(device)
         self.opt = torch.optim.Adam(self.net.parameters(), lr=lr, weight_decay=l2_coef)
+        self.amp_dtype = amp_dtype
+        self.scaler = torch.amp.GradScaler(torch.device(device).type) if amp_dtype == torch.float16 else None
 
     def loss(self, x, edge_index, y, train_idx, num_nodes):
-        logits = self.net(x, edge_index, None, num_nodes)
-        return F.cross_entropy(logits[train_idx], y[train_idx])
+        if self.amp_dtype is None:
+            logits = self.net(x, edge_index, None, num_nodes)
+            return F.cross_entropy(logits[train_idx], y[train_idx])
+        with torch.autocast(x.device.type, dtype=self.amp_dtype):
+            logits = self.net(x, edge_index, None, num_nodes)
+        return F.cross_entropy(logits[train_idx].float(), y[train_idx])
 
     def step(self, x, edge_index, y, train_idx, num_nodes):
         self.net.train()
         self.opt.zero_grad(set_to_none=True)
         loss = self.loss(x, edge_index, y, train_idx, num_nodes)
-        loss.backward()
-        self.opt.step()
+        if self.scaler is not None:
+            self.scaler.scale(loss).backward()
+            self.scaler.step(self.opt)
+            self.scaler.update()
+        else:
+            loss.backward()
+            self.opt.step()
         return loss.detach()
 
 

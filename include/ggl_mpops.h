@@ -52,6 +52,9 @@ extern "C" {
  *   No struct change. */
 /* 10: + ggl_segment_softmax_{fwd,bwd,supported,partial_bytes} (the edge softmax of utils/softmax.py as one op each way),
  *   ggl_policy_softmax_sublanes, option softmax_sublanes.  No struct change. */
+/* still 10: + ggl_spmm_{sum,mean,mean_bwd}_x16, ggl_spmm_col_blocks_x16, option col_block16 (the mixed-precision aggregate).
+ *   Purely ADDITIVE symbols: no struct, no existing signature and no existing behaviour changed, so a caller built against 10
+ *   keeps working and the number stays (hosts that want the new entry points look them up by name). */
 #define GGL_ABI_VERSION 10
 
 /* dtype codes (AT_DISPATCH_ALL_TYPES_AND2(Half, BFloat16), segment_sum_cpu.cpp:32-33) */
@@ -255,6 +258,24 @@ int ggl_spmm_mean_bwd(const ggl_segplan_t *planT, const int32_t *colT, const flo
                       void *stream);
 int ggl_spmm_max_bwd(const ggl_segplan_t *planT, const int32_t *colT, const float *w, int w_by_pos,
                      const float *g, const int64_t *argsrc, int64_t K, float *gx, void *stream);
+/* Mixed-precision aggregate (an extension: the reference's gspmm is f32 only).  x [N_in, K] is stored as GGL_BF16 or
+ * GGL_F16, w stays f32; every element is widened at the load (exact), every product and add is the f32 one of
+ * ggl_spmm_sum / ggl_spmm_mean in the same order, and the finished sum is rounded to nearest-even ONCE, at the store
+ * (out_dtype == x_dtype), or not at all (out_dtype == GGL_F32).  With F = the f32 entry point on the same plan and weights:
+ *     out_dtype == x_dtype : out == round(F(widen(x)))      out_dtype == GGL_F32 : out == F(widen(x))
+ * bit for bit, under the conditions under which F itself is the serial sum (host build: always; GPU: hub rows through the
+ * exact walk, i.e. E < 2^31 and max_len <= option exact_long_max; chunked otherwise, with F32 partials like F's).  Any other
+ * dtype pair returns GGL_EDTYPE.  x_ld / out_ld: row strides in elements (0 = K).  plan->partial holds F32 partials:
+ * ggl_partial_bytes(GGL_F32, n_chunks, K, 0).  ggl_spmm_mean_bwd_x16 is ggl_spmm_mean_bwd on a 16-bit g (divide and
+ * multiply in f32); the backward of the sum is ggl_spmm_sum_x16 on the transposed plan.
+ * Wide rows are cut into column blocks of option "col_block16" columns: ggl_spmm_col_blocks_x16 = launches per call. */
+int ggl_spmm_sum_x16(const ggl_segplan_t *plan, const int32_t *col, const float *w, int w_by_pos, int x_dtype,
+                     const void *x, int64_t x_ld, int64_t K, int out_dtype, void *out, int64_t out_ld, void *stream);
+int ggl_spmm_mean_x16(const ggl_segplan_t *plan, const int32_t *col, const float *w, int w_by_pos, int x_dtype,
+                      const void *x, int64_t x_ld, int64_t K, int out_dtype, void *out, int64_t out_ld, void *stream);
+int ggl_spmm_mean_bwd_x16(const ggl_segplan_t *planT, const int32_t *colT, const float *w, int w_by_pos, int g_dtype,
+                          const void *g, const int64_t *fwd_rowptr, int64_t K, int gx_dtype, void *gx, void *stream);
+int64_t ggl_spmm_col_blocks_x16(const ggl_segplan_t *plan, int64_t K);
 /* the same walk with the witnesses in a compact int32 copy of argsrc (node ids index int32 arrays everywhere in this
  * library): the lookup is per edge AND column, 8 of the walk's 12 bytes per element with int64 witnesses.  NOT yet the
  * hosts' default: unmeasured on the GPU (the Engine takes it with the option `maxbwd_arg32`; results identical). */
