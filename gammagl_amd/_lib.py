@@ -45,6 +45,13 @@ SIGNATURES = {
     "ggl_plan_long_count": (c_int, [_V, c_int64, c_int64, _V, c_size_t, _V, POINTER(c_int64),
                                     POINTER(c_int64)]),
     "ggl_plan_long_fill": (c_int, [_V, c_int64, c_int64, c_int64, _V, _V, _V, c_size_t, _V]),
+    "ggl_plan_rows_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "ggl_plan_rows_rank": (c_int, [_V, c_int64, c_int64, _V, _V, c_size_t, _V]),
+    "ggl_plan_rows_fwd_rowptr": (c_int, [_V, _V, c_int64, _V, _V, c_size_t, _V, POINTER(c_int64)]),
+    "ggl_plan_rows_fwd_fill": (c_int, [_V, _V, _V, _V, _V, c_int64, _V, c_int64, _V, _V, _V]),
+    "ggl_plan_rows_bwd_rowptr": (c_int, [_V, _V, c_int64, c_int64, _V, _V, _V, _V, c_size_t, _V, POINTER(c_int64)]),
+    "ggl_plan_rows_bwd_fill": (c_int, [_V, _V, _V, c_int64, _V, _V, _V, _V, _V]),
+    "ggl_bias_grad_rows": (c_int, [_V, _V, c_int64, c_int64, c_int64, _V, _V, c_size_t, _V]),
     "ggl_partial_bytes": (c_size_t, [c_int, c_int64, c_int64, c_int]),
     "ggl_fill_i64": (c_int, [_V, c_int64, c_int64, _V]),
     "ggl_gather_i64_to_i32": (c_int, [_V, _V, c_int64, _V, _V]),

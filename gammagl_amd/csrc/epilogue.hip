@@ -180,6 +180,41 @@ static inline void geometry(int64_t N, int64_t K, bool vec4, int *kp, int *group
   *rpb = ceil_div(N > 0 ? N : 1, b);
 }
 
+// The first stage of bias_act_bwd_kernel<4, 0> for a gradient that is zero outside a sorted list of rows, from the
+// compact [R, K] rows alone: slot (block b, group j) of the SAME geometry(N, K) adds the listed rows r of the block's
+// range with (r - r0) % groups == j, ascending — the rows the full kernel adds there minus its +0 ones, so every partial
+// (and the column sum ggl_colsum_f32 makes of them) is the number the full pass over the scattered [N, K] matrix gives.
+__global__ __launch_bounds__(kBlock) void bias_grad_rows_kernel(const float *__restrict__ g, const int64_t *__restrict__ rows,
+                                                                int64_t R, int64_t N, int64_t K, int64_t nblocks,
+                                                                int64_t rows_per_block, int kp, int groups,
+                                                                float *__restrict__ partial) {
+  const int j = threadIdx.x / kp;
+  const int c0 = threadIdx.x - j * kp;
+  if (j >= groups || block_id() >= nblocks) return;
+  const int64_t KV = K / 4;
+  const int64_t r0 = block_id() * rows_per_block;
+  const int64_t r1 = (r0 + rows_per_block < N) ? r0 + rows_per_block : N;
+  int64_t lo = 0, hi = R;   // first listed position with rows[i] >= r0
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (rows[mid] < r0) lo = mid + 1; else hi = mid;
+  }
+  for (int64_t c = c0; c < KV; c += kp) {
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int64_t i = lo; i < R; ++i) {
+      const int64_t r = rows[i];
+      if (r >= r1) break;
+      if ((int)(r - r0) % groups != j) continue;   // (r - r0 < rows_per_block: fits an int)
+      float gv[4];
+      ldv<4>(g + i * K + c * 4, gv);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) acc[k] = __fadd_rn(acc[k], gv[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) partial[(block_id() * groups + j) * K + c * 4 + k] = acc[k];
+  }
+}
+
 int rng_advance(int64_t *rng_state, void *stream) {
   GGL_LAUNCH((rng_advance_kernel), 1, 64, as_stream(stream), rng_state, (int64_t)1);
   GGL_LAUNCH_CHECK();
@@ -275,4 +310,23 @@ extern "C" int ggl_bias_act_bwd(const float *g, const float *y, int64_t N, int64
                           workspace_bytes - part, stream);
   }
   return GGL_OK;
+}
+
+extern "C" int ggl_bias_grad_rows(const float *g, const int64_t *rows, int64_t R, int64_t N, int64_t K, float *gbias,
+                                  void *workspace, size_t workspace_bytes, void *stream) {
+  GGL_REQUIRE(R >= 0 && N >= 0 && R <= N && K > 0 && K % 4 == 0, GGL_EINVAL,
+              "bias_grad_rows needs R <= N rows of a multiple of 4 columns");
+  GGL_REQUIRE(gbias && ((g && rows) || R == 0), GGL_EINVAL, "NULL pointer");
+  GGL_REQUIRE((reinterpret_cast<uintptr_t>(g) & 15u) == 0, GGL_EINVAL, "g must be 16-byte aligned");
+  GGL_REQUIRE(workspace && workspace_bytes >= ggl_bias_act_bwd_workspace_bytes(N, K), GGL_EWORKSPACE,
+              "bias_grad_rows workspace too small (ggl_bias_act_bwd_workspace_bytes(N, K))");
+  int kp, groups;
+  int64_t blocks, rpb;
+  geometry(N, K, true, &kp, &groups, &blocks, &rpb);   // the float4 geometry of ggl_bias_act_bwd on the full [N, K] gradient
+  float *partial = static_cast<float *>(workspace);
+  GGL_LAUNCH((bias_grad_rows_kernel), blocks, kBlock, as_stream(stream), g, rows, R, N, K, blocks, rpb, kp, groups, partial);
+  GGL_LAUNCH_CHECK();
+  const size_t part = bwd_partial_bytes(N, K);
+  return ggl_colsum_f32(partial, blocks * groups, K, gbias, static_cast<char *>(workspace) + part, workspace_bytes - part,
+                        stream);
 }

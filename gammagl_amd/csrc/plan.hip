@@ -638,6 +638,213 @@ extern "C" int ggl_gather_rows_f32(const float *src, const int32_t *perm, int64_
   return GGL_OK;
 }
 
+// ---- restricted plan pair (ggl_plan_rows_*): the plans of a graph cut down to a list of destination rows --------------
+// Forward R x N_src: row r = the slice rowptr[rows[r]] .. rowptr[rows[r] + 1] of the full plan (a segmented copy).
+// Transposed N_src x R: the full transposed plan FILTERED to the elements whose destination is listed (flag, exclusive
+// scan, compact), destinations renamed to their rank in the list.  Neither sorts: the order inside every row is the full
+// plan's, which is what keeps the row sums' bits.  Weights are copied into sorted order on the way (w_by_pos = 1).
+namespace ggl {
+
+// flags[0] = some row id out of [0, N); flags[1] = ids not strictly ascending (unsorted or repeated)
+__global__ __launch_bounds__(kBlock) void rows_check_kernel(const int64_t *rows, int64_t R, int64_t N, int32_t *flags) {
+  const int64_t stride = grid_threads();
+  for (int64_t i = thread_id(); i < R; i += stride) {
+    const int64_t v = rows[i];
+    if (v < 0 || v >= N) flags[0] = 1;  // benign race: every writer stores the same value
+    if (i > 0 && rows[i - 1] >= v) flags[1] = 1;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void fill_i32_kernel(int32_t *p, int64_t n, int32_t v) {
+  const int64_t stride = grid_threads();
+  for (int64_t i = thread_id(); i < n; i += stride) p[i] = v;
+}
+
+__global__ __launch_bounds__(kBlock) void rows_rank_kernel(const int64_t *rows, int64_t R, int32_t *rank) {
+  const int64_t stride = grid_threads();
+  for (int64_t i = thread_id(); i < R; i += stride) rank[rows[i]] = (int32_t)i;
+}
+
+// len[r] = elements of listed row r (r < R), len[R] = 0: the scan over R + 1 entries then ends on the total
+__global__ __launch_bounds__(kBlock) void rows_len_kernel(const int64_t *rowptr, const int64_t *rows, int64_t R, int64_t *len) {
+  const int64_t stride = grid_threads();
+  for (int64_t r = thread_id(); r <= R; r += stride) len[r] = r < R ? rowptr[rows[r] + 1] - rowptr[rows[r]] : 0;
+}
+
+// element q of the restricted forward plan = element rowptr[rows[r]] + (q - rowptr_r[r]) of the full one, r = its row
+__global__ __launch_bounds__(kBlock) void rows_fwd_fill_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                                               const float *__restrict__ w, const int32_t *__restrict__ wperm,
+                                                               const int64_t *__restrict__ rows, int64_t R,
+                                                               const int64_t *__restrict__ rowptr_r, int64_t E_r,
+                                                               int32_t *__restrict__ col_r, float *__restrict__ w_r) {
+  const int64_t stride = grid_threads();
+  for (int64_t q = thread_id(); q < E_r; q += stride) {
+    int64_t lo = 0, hi = R;  // first r with rowptr_r[r + 1] > q
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (rowptr_r[mid + 1] <= q) lo = mid + 1; else hi = mid;
+    }
+    const int64_t p = rowptr[rows[lo]] + (q - rowptr_r[lo]);
+    col_r[q] = col[p];
+    if (w) w_r[q] = w[wperm ? (int64_t)wperm[p] : p];
+  }
+}
+
+// keep flag of transposed position i (0 past the end: the scan runs over E + 1 entries and ends on the total)
+struct RowsKeep {
+  const int32_t *colT;
+  const int32_t *rank;
+  int64_t E;
+  __host__ __device__ int32_t operator()(int64_t i) const { return (i < E && rank[colT[i]] >= 0) ? 1 : 0; }
+};
+
+__global__ __launch_bounds__(kBlock) void rows_bwd_rowptr_kernel(const int64_t *rowptrT, int64_t N_src, const int32_t *pos,
+                                                                 int64_t *rowptrT_r) {
+  const int64_t stride = grid_threads();
+  for (int64_t j = thread_id(); j <= N_src; j += stride) rowptrT_r[j] = (int64_t)pos[rowptrT[j]];
+}
+
+__global__ __launch_bounds__(kBlock) void rows_bwd_fill_kernel(const int32_t *__restrict__ colT, const float *__restrict__ w,
+                                                               const int32_t *__restrict__ wperm, int64_t E,
+                                                               const int32_t *__restrict__ rank, const int32_t *__restrict__ pos,
+                                                               int32_t *__restrict__ colT_r, float *__restrict__ w_r) {
+  const int64_t stride = grid_threads();
+  for (int64_t p = thread_id(); p < E; p += stride) {
+    const int32_t c = rank[colT[p]];
+    if (c < 0) continue;
+    const int64_t q = pos[p];
+    colT_r[q] = c;
+    if (w) w_r[q] = w[wperm ? (int64_t)wperm[p] : p];
+  }
+}
+
+#ifndef GGL_EMULATE
+static size_t rows_scan_temp_bytes(int64_t E, int64_t R) {
+  size_t a = 0, b = 0;
+  (void)rocprim::exclusive_scan(nullptr, a, (const int64_t *)nullptr, (int64_t *)nullptr, (int64_t)0, (size_t)(R + 1),
+                                rocprim::plus<int64_t>(), (hipStream_t)0);
+  auto flags = rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), RowsKeep{nullptr, nullptr, 0});
+  (void)rocprim::exclusive_scan(nullptr, b, flags, (int32_t *)nullptr, (int32_t)0, (size_t)(E + 1), rocprim::plus<int32_t>(),
+                                (hipStream_t)0);
+  return a > b ? a : b;
+}
+#endif
+
+}  // namespace ggl
+
+extern "C" size_t ggl_plan_rows_workspace_bytes(int64_t E, int64_t N, int64_t R) {
+  (void)N;
+  if (E < 0 || R < 0) return 0;
+  size_t b = 256 + align_up((size_t)(R + 1) * 8, 256);   // flags, row lengths
+#ifndef GGL_EMULATE
+  b += align_up(rows_scan_temp_bytes(E, R), 256);
+#endif
+  return b;
+}
+
+extern "C" int ggl_plan_rows_rank(const int64_t *rows, int64_t R, int64_t N, int32_t *rank, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+  GGL_REQUIRE(R >= 0 && N >= 0 && N < ((int64_t)1 << 31) && R <= N, GGL_EINVAL, "row list: %lld rows for %lld destinations",
+              (long long)R, (long long)N);
+  GGL_REQUIRE((rows || R == 0) && (rank || N == 0), GGL_EINVAL, "NULL pointer");
+  GGL_REQUIRE(workspace && workspace_bytes >= 256, GGL_EWORKSPACE, "row-list workspace too small");
+  hipStream_t s = as_stream(stream);
+  int32_t *flags = static_cast<int32_t *>(workspace);
+  int32_t flags_host[2] = {0, 0};
+  GGL_HIP_CHECK(hipMemsetAsync(flags, 0, 256, s));
+  if (R > 0) {
+    GGL_LAUNCH((rows_check_kernel), grid_for(R), kBlock, s, rows, R, N, flags);
+    GGL_LAUNCH_CHECK();
+  }
+  GGL_HIP_CHECK(hipMemcpyAsync(flags_host, flags, 8, hipMemcpyDeviceToHost, s));
+  GGL_HIP_CHECK(hipStreamSynchronize(s));   // the rank map is only written from a list known to be in range
+  GGL_REQUIRE(flags_host[0] == 0, GGL_EINDEX, "row id out of range [0, %lld)", (long long)N);
+  GGL_REQUIRE(flags_host[1] == 0, GGL_EINVAL, "the row list must be sorted ascending without duplicates");
+  if (N > 0) {
+    GGL_LAUNCH((fill_i32_kernel), grid_for(N), kBlock, s, rank, N, (int32_t)-1);
+    GGL_LAUNCH_CHECK();
+  }
+  if (R > 0) {
+    GGL_LAUNCH((rows_rank_kernel), grid_for(R), kBlock, s, rows, R, rank);
+    GGL_LAUNCH_CHECK();
+  }
+  return GGL_OK;
+}
+
+extern "C" int ggl_plan_rows_fwd_rowptr(const int64_t *rowptr, const int64_t *rows, int64_t R, int64_t *rowptr_r,
+                                        void *workspace, size_t workspace_bytes, void *stream, int64_t *E_r_host) {
+  GGL_REQUIRE(R >= 0 && rowptr && rowptr_r && (rows || R == 0), GGL_EINVAL, "bad arguments");
+  GGL_REQUIRE(workspace && workspace_bytes >= ggl_plan_rows_workspace_bytes(0, 0, R), GGL_EWORKSPACE,
+              "row-list workspace too small");
+  hipStream_t s = as_stream(stream);
+  char *ws = static_cast<char *>(workspace);
+  int64_t *len = reinterpret_cast<int64_t *>(ws + 256);
+  GGL_LAUNCH((rows_len_kernel), grid_for(R + 1), kBlock, s, rowptr, rows, R, len);
+  GGL_LAUNCH_CHECK();
+#ifndef GGL_EMULATE
+  size_t tmp = workspace_bytes - 256 - align_up((size_t)(R + 1) * 8, 256);
+  GGL_HIP_CHECK(rocprim::exclusive_scan(ws + 256 + align_up((size_t)(R + 1) * 8, 256), tmp, (const int64_t *)len, rowptr_r,
+                                        (int64_t)0, (size_t)(R + 1), rocprim::plus<int64_t>(), s));
+#else
+  int64_t acc = 0;
+  for (int64_t r = 0; r <= R; ++r) { rowptr_r[r] = acc; acc += len[r]; }
+#endif
+  int64_t total = 0;
+  GGL_HIP_CHECK(hipMemcpyAsync(&total, rowptr_r + R, 8, hipMemcpyDeviceToHost, s));
+  GGL_HIP_CHECK(hipStreamSynchronize(s));
+  if (E_r_host) *E_r_host = total;
+  return GGL_OK;
+}
+
+extern "C" int ggl_plan_rows_fwd_fill(const int64_t *rowptr, const int32_t *col, const float *w, const int32_t *wperm,
+                                      const int64_t *rows, int64_t R, const int64_t *rowptr_r, int64_t E_r, int32_t *col_r,
+                                      float *w_r, void *stream) {
+  GGL_REQUIRE(R >= 0 && E_r >= 0 && E_r < ((int64_t)1 << 31), GGL_EINVAL, "bad sizes");
+  if (E_r == 0) return GGL_OK;
+  GGL_REQUIRE(rowptr && col && rows && rowptr_r && col_r && (w_r || !w), GGL_EINVAL, "NULL pointer");
+  GGL_LAUNCH((rows_fwd_fill_kernel), grid_for(E_r), kBlock, as_stream(stream), rowptr, col, w, wperm, rows, R, rowptr_r, E_r,
+             col_r, w_r);
+  GGL_LAUNCH_CHECK();
+  return GGL_OK;
+}
+
+extern "C" int ggl_plan_rows_bwd_rowptr(const int64_t *rowptrT, const int32_t *colT, int64_t N_src, int64_t E,
+                                        const int32_t *rank, int32_t *pos, int64_t *rowptrT_r, void *workspace,
+                                        size_t workspace_bytes, void *stream, int64_t *E_r_host) {
+  GGL_REQUIRE(N_src >= 0 && E >= 0 && E < ((int64_t)1 << 31) - 1, GGL_EINVAL, "bad sizes");
+  GGL_REQUIRE(rowptrT && pos && rowptrT_r && ((colT && rank) || E == 0), GGL_EINVAL, "NULL pointer");
+  GGL_REQUIRE(workspace && workspace_bytes >= ggl_plan_rows_workspace_bytes(E, 0, 0), GGL_EWORKSPACE,
+              "row-list workspace too small");
+  hipStream_t s = as_stream(stream);
+  const RowsKeep keep{colT, rank, E};
+#ifndef GGL_EMULATE
+  char *ws = static_cast<char *>(workspace);
+  size_t tmp = workspace_bytes - 256;
+  auto flags = rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), keep);
+  GGL_HIP_CHECK(rocprim::exclusive_scan(ws + 256, tmp, flags, pos, (int32_t)0, (size_t)(E + 1), rocprim::plus<int32_t>(), s));
+#else
+  int32_t acc = 0;
+  for (int64_t i = 0; i <= E; ++i) { pos[i] = acc; acc += keep(i); }
+#endif
+  GGL_LAUNCH((rows_bwd_rowptr_kernel), grid_for(N_src + 1), kBlock, s, rowptrT, N_src, (const int32_t *)pos, rowptrT_r);
+  GGL_LAUNCH_CHECK();
+  int32_t total = 0;
+  GGL_HIP_CHECK(hipMemcpyAsync(&total, pos + E, 4, hipMemcpyDeviceToHost, s));
+  GGL_HIP_CHECK(hipStreamSynchronize(s));
+  if (E_r_host) *E_r_host = total;
+  return GGL_OK;
+}
+
+extern "C" int ggl_plan_rows_bwd_fill(const int32_t *colT, const float *w, const int32_t *wperm, int64_t E,
+                                      const int32_t *rank, const int32_t *pos, int32_t *colT_r, float *w_r, void *stream) {
+  GGL_REQUIRE(E >= 0 && E < ((int64_t)1 << 31) - 1, GGL_EINVAL, "bad sizes");
+  if (E == 0) return GGL_OK;
+  GGL_REQUIRE(colT && rank && pos, GGL_EINVAL, "NULL pointer");   // (colT_r / w_r may be NULL when no element is kept)
+  GGL_LAUNCH((rows_bwd_fill_kernel), grid_for(E), kBlock, as_stream(stream), colT, w, wperm, E, rank, pos, colT_r, w_r);
+  GGL_LAUNCH_CHECK();
+  return GGL_OK;
+}
+
 // ---- ggl_calib_stream: the streaming yardstick of bench.py's roofline leg ------------------------------------------
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void calib_stream_kernel(const float4 *__restrict__ src, float4 *__restrict__ dst,

@@ -68,7 +68,9 @@ using torch::autograd::variable_list;
   X(ggl_spmm_max_mask_bytes) X(ggl_spmm_max_mask) X(ggl_spmm_max_bwd_mask) X(ggl_invert_perm) X(ggl_get_option)      \
   X(ggl_spmm_max_bwd32) X(ggl_policy_maxbwd_form)                                                                   \
   X(ggl_segment_softmax_supported) X(ggl_segment_softmax_partial_bytes) X(ggl_segment_softmax_fwd) X(ggl_segment_softmax_bwd) \
-  X(ggl_policy_softmax_sublanes) X(ggl_spmm_sum_x16) X(ggl_spmm_mean_x16) X(ggl_spmm_mean_bwd_x16)
+  X(ggl_policy_softmax_sublanes) X(ggl_spmm_sum_x16) X(ggl_spmm_mean_x16) X(ggl_spmm_mean_bwd_x16)                    \
+  X(ggl_plan_rows_workspace_bytes) X(ggl_plan_rows_rank) X(ggl_plan_rows_fwd_rowptr) X(ggl_plan_rows_fwd_fill)        \
+  X(ggl_plan_rows_bwd_rowptr) X(ggl_plan_rows_bwd_fill) X(ggl_bias_grad_rows)
 
 struct Api {
   void *handle = nullptr;
@@ -1236,6 +1238,161 @@ static std::tuple<Tensor, Tensor> spmm_epi_forward_kernel(const Tensor &index, c
   return {y, used};
 }
 
+// ---- spmm_rows: (A x + bias)[rows] on the restricted plan pair (include/ggl_mpops.h ggl_plan_rows_*; ops.py Engine.rows_plan) ----
+struct RowsPlan {
+  int64_t R = 0, N_dst = 0, N_src = 0;
+  Tensor rows, col, colT, w_fwd, w_bwd;
+  std::shared_ptr<SegPlan> fwd, bwd;
+  bool has_w = false;
+  // the weights the pair was built from: storage, offset and version each compared on a hit; an entry whose weights
+  // died is a miss (address reuse)
+  const void *w_storage = nullptr;
+  int64_t w_offset = 0, w_version = 0;
+  c10::optional<c10::weak_intrusive_ptr<c10::StorageImpl>> w_ref;
+};
+
+static Cache<RowsPlan> &rows_cache() {
+  static Cache<RowsPlan> c(8);
+  return c;
+}
+
+// a plan over elements already grouped by row (ops.py Engine.plan_from_rowptr): one host read for the longest row
+// `chunk`: the long-row threshold of the plan the rows were cut from, so the same rows are long in both
+static std::shared_ptr<SegPlan> plan_from_rowptr(const Api &a, const Tensor &rowptr, int64_t E, int64_t chunk, void *st) {
+  auto p = std::make_shared<SegPlan>();
+  p->N = rowptr.size(0) - 1;
+  p->E = E;
+  p->chunk = chunk;
+  p->rowptr = rowptr;
+  p->sorted = true;
+  p->max_len = p->N > 0 ? p->counts().max().item<int64_t>() : 0;
+  fill_long_rows(a, *p, st);
+  p->uid = ++g_plans_built;
+  return p;
+}
+
+static std::shared_ptr<RowsPlan> rows_plan(GraphPlan &gp, const Tensor &index, const Tensor &w, const Tensor &rows_in) {
+  TORCH_CHECK(rows_in.dim() == 1 && rows_in.scalar_type() == at::kLong, "rows must be a 1-D int64 tensor, got ", rows_in.sizes(),
+              " ", rows_in.scalar_type());
+  const void *w_storage = w.defined() ? w.storage().unsafeGetStorageImpl() : nullptr;
+  const int64_t w_offset = w.defined() ? w.storage_offset() : 0;
+  const int64_t w_version = (w.defined() && !w.is_inference()) ? static_cast<int64_t>(w._version()) : 0;
+  TensorKey k = TensorKey::of(rows_in, static_cast<int64_t>(gp.fwd->uid),
+                              static_cast<int64_t>(reinterpret_cast<uintptr_t>(w_storage)));
+  if (auto hit = rows_cache().get(k)) {
+    if (hit->has_w == w.defined() && hit->w_storage == w_storage && hit->w_offset == w_offset && hit->w_version == w_version &&
+        (!hit->has_w || !hit->w_ref->expired())) {
+      ++g_plan_hits;
+      return hit;
+    }
+  }
+  const auto dev = rows_in.device();
+  TORCH_CHECK(!capturing(dev), "spmm_rows: the restricted plan of this row list must be built before a hipGraph capture "
+                               "(run one eager step first)");
+  const Api &a = api_for(dev);
+  void *st = stream_of(dev);
+  gp.need_bwd(index);
+  Tensor rows = rows_in.contiguous();
+  const int64_t R = rows.size(0), N = gp.N_dst, E = gp.E;
+  auto i64 = rows.options(), i32 = rows.options().dtype(at::kInt), f32o = rows.options().dtype(at::kFloat);
+  const size_t wsb = a.ggl_plan_rows_workspace_bytes(E, std::max(gp.N_dst, gp.N_src), R);
+  Tensor ws = at::empty({static_cast<int64_t>(wsb)}, rows.options().dtype(at::kByte));
+  Tensor rank = at::empty({std::max<int64_t>(N, 1)}, i32);
+  check(a, a.ggl_plan_rows_rank(rows.data_ptr<int64_t>(), R, N, rank.data_ptr<int32_t>(), ws.data_ptr(), wsb, st));
+  auto rp = std::make_shared<RowsPlan>();
+  rp->R = R;
+  rp->N_dst = gp.N_dst;
+  rp->N_src = gp.N_src;
+  rp->rows = rows;
+  rp->has_w = w.defined();
+  rp->w_storage = w_storage;
+  rp->w_offset = w_offset;
+  rp->w_version = w_version;
+  if (w.defined()) rp->w_ref = w.storage().getWeakStorageImpl();
+  const float *wp = w.defined() ? w.data_ptr<float>() : nullptr;
+  auto i32p = [](const Tensor &t) { return t.defined() ? t.data_ptr<int32_t>() : nullptr; };
+  auto f32p = [](const Tensor &t) { return t.defined() ? t.data_ptr<float>() : nullptr; };
+  // forward: a segmented copy of the listed rows' slices
+  Tensor rowptr_r = at::empty({R + 1}, i64);
+  int64_t E_r = 0, E_t = 0;
+  check(a, a.ggl_plan_rows_fwd_rowptr(gp.fwd->rowptr.data_ptr<int64_t>(), rows.data_ptr<int64_t>(), R,
+                                      rowptr_r.data_ptr<int64_t>(), ws.data_ptr(), wsb, st, &E_r));
+  rp->col = at::empty({E_r}, i32);
+  if (w.defined()) rp->w_fwd = at::empty({E_r}, f32o);
+  check(a, a.ggl_plan_rows_fwd_fill(gp.fwd->rowptr.data_ptr<int64_t>(), gp.col.data_ptr<int32_t>(), wp, i32p(gp.fwd->perm),
+                                    rows.data_ptr<int64_t>(), R, rowptr_r.data_ptr<int64_t>(), E_r, rp->col.data_ptr<int32_t>(),
+                                    f32p(rp->w_fwd), st));
+  rp->fwd = plan_from_rowptr(a, rowptr_r, E_r, gp.fwd->chunk, st);
+  // transposed: the full transposed plan filtered to the listed destinations (flag, scan, compact)
+  Tensor pos = at::empty({E + 1}, i32), rowptrT_r = at::empty({gp.N_src + 1}, i64);
+  check(a, a.ggl_plan_rows_bwd_rowptr(gp.bwd->rowptr.data_ptr<int64_t>(), gp.colT.data_ptr<int32_t>(), gp.N_src, E,
+                                      rank.data_ptr<int32_t>(), pos.data_ptr<int32_t>(), rowptrT_r.data_ptr<int64_t>(),
+                                      ws.data_ptr(), wsb, st, &E_t));
+  TORCH_CHECK(E_t == E_r, "restricted plans disagree: ", E_r, " forward elements, ", E_t, " transposed");
+  rp->colT = at::empty({E_r}, i32);
+  if (w.defined()) rp->w_bwd = at::empty({E_r}, f32o);
+  check(a, a.ggl_plan_rows_bwd_fill(gp.colT.data_ptr<int32_t>(), wp, i32p(gp.bwd->perm), E, rank.data_ptr<int32_t>(),
+                                    pos.data_ptr<int32_t>(), rp->colT.data_ptr<int32_t>(), f32p(rp->w_bwd), st));
+  rp->bwd = plan_from_rowptr(a, rowptrT_r, E_r, gp.bwd->chunk, st);
+  rows_cache().put(rows_in, k, rp);
+  return rp;
+}
+
+static Tensor spmm_rows_forward_kernel(const Tensor &index, const OptT_ &weight, const Tensor &x, const Tensor &rows,
+                                       const OptT_ &bias_) {
+  c10::OptionalDeviceGuard guard(x.device());
+  SpArgs s = spmm_args(index, weight, x);
+  Tensor bias = opt(bias_);
+  same_device({&x, &rows, &bias});
+  TORCH_CHECK(s.x.dim() == 2 && s.x.size(1) > 0 && s.x.size(1) % 4 == 0,
+              "spmm_rows needs a 2-D f32 x whose width is a multiple of 4, got ", x.sizes());
+  const Api &a = api_for(x.device());
+  const int64_t K = s.x.size(1);
+  if (bias.defined()) {
+    f32("bias", bias);
+    bias = bias.contiguous().reshape({-1});
+    TORCH_CHECK(bias.numel() == K, "bias must hold one value per column");
+  }
+  auto rp = rows_plan(*s.gp, index, s.w, rows);
+  const SegPlan &p_ = *rp->fwd;
+  Tensor y = at::empty({rp->R, K}, s.x.options());
+  Tensor part = partial_for(a, p_, s.x, K, false);
+  ggl_segplan_t cs = p_.c(part);
+  check(a, a.ggl_spmm_epi_ex(&cs, rp->col.data_ptr<int32_t>(), rp->has_w ? rp->w_fwd.data_ptr<float>() : nullptr, 1,
+                             s.x.data_ptr<float>(), K, K, y.data_ptr<float>(), K, 0, 0, nullptr, 0,
+                             bias.defined() ? bias.data_ptr<float>() : nullptr, 0, 0.0f, nullptr, 0, 0, 1, stream_of(x.device())));
+  return y;
+}
+
+// (gx [N_src, K], gbias [K] or empty): the transposed restricted walk over the compact gradient; ggl_bias_grad_rows
+static std::tuple<Tensor, Tensor> spmm_rows_backward_kernel(const Tensor &index, const OptT_ &weight, const Tensor &grad,
+                                                            const Tensor &rows, int64_t n_src, bool has_bias) {
+  Tensor g = grad.contiguous(), w = opt_dense(weight);
+  f32("grad", g);
+  if (w.defined()) f32("weight", w);
+  c10::OptionalDeviceGuard guard(g.device());
+  const Api &a = api_for(g.device());
+  auto gp = bwd_plan(index, n_src);
+  auto rp = rows_plan(*gp, index, w, rows);
+  TORCH_CHECK(g.dim() == 2 && g.size(0) == rp->R && g.size(1) % 4 == 0, "grad must be [len(rows), K], K a multiple of 4");
+  const int64_t K = g.size(1);
+  void *st = stream_of(g.device());
+  Tensor gb = at::empty({has_bias ? K : 0}, g.options());
+  if (has_bias) {
+    const size_t wsb = a.ggl_bias_act_bwd_workspace_bytes(rp->N_dst, K);
+    Tensor ws = at::empty({static_cast<int64_t>(std::max<size_t>(wsb, 4))}, g.options().dtype(at::kByte));
+    check(a, a.ggl_bias_grad_rows(g.data_ptr<float>(), rp->rows.data_ptr<int64_t>(), rp->R, rp->N_dst, K, gb.data_ptr<float>(),
+                                  ws.data_ptr(), wsb, st));
+  }
+  const SegPlan &p_ = *rp->bwd;
+  Tensor gx = at::empty({rp->N_src, K}, g.options());
+  Tensor part = partial_for(a, p_, g, K, false);
+  ggl_segplan_t cs = p_.c(part);
+  check(a, a.ggl_spmm_sum(&cs, rp->colT.data_ptr<int32_t>(), rp->has_w ? rp->w_bwd.data_ptr<float>() : nullptr, 1,
+                          g.data_ptr<float>(), K, gx.data_ptr<float>(), st));
+  return {gx, gb};
+}
+
 // relu(segment_{sum,mean}(x, ids, N) + add + bias) for f32 messages [E, K] in one kernel (sage_conv.py:100-108)
 static Tensor segment_epi_forward_kernel(const Tensor &x_, const Tensor &index, int64_t N, bool mean, const OptT_ &add_,
                                          const OptT_ &bias_, bool relu) {
@@ -1584,6 +1741,38 @@ static Tensor spmm_epi_autograd(const Tensor &index, const OptT_ &weight, const 
   return BiasActFn::apply(out, bias, relu, p);
 }
 
+// (A x + bias)[rows] computed on the listed rows alone; the edge weights carry no gradient here (bspmm_sum is that op)
+struct SpMMRowsFn : public torch::autograd::Function<SpMMRowsFn> {
+  static Tensor forward(AutogradContext *ctx, const Tensor &index, const OptT_ &weight, const Tensor &x, const Tensor &rows,
+                        const OptT_ &bias) {
+    at::AutoDispatchBelowADInplaceOrView below;
+    static auto op = op_handle<Tensor(const Tensor &, const OptT_ &, const Tensor &, const Tensor &, const OptT_ &)>(
+        "ggl::spmm_rows_forward");
+    Tensor y = op.call(index, weight, x, rows, bias);
+    ctx->save_for_backward({index, opt(weight), rows});
+    ctx->saved_data["n_src"] = x.size(0);
+    ctx->saved_data["has_bias"] = opt(bias).defined();
+    ctx->saved_data["bias_shape"] = opt(bias).defined() ? opt(bias).sizes().vec() : std::vector<int64_t>{};
+    return y;
+  }
+  static variable_list backward(AutogradContext *ctx, variable_list grads) {
+    auto s = ctx->get_saved_variables();
+    static auto op = op_handle<std::tuple<Tensor, Tensor>(const Tensor &, const OptT_ &, const Tensor &, const Tensor &, int64_t,
+                                                          bool)>("ggl::spmm_rows_backward");
+    const bool hb = ctx->saved_data["has_bias"].toBool();
+    OptT_ w = s[1].defined() ? OptT_(s[1]) : OptT_();
+    auto r = op.call(s[0], w, grads[0], s[2], ctx->saved_data["n_src"].toInt(), hb);
+    Tensor gb = hb ? std::get<1>(r).reshape(ctx->saved_data["bias_shape"].toIntVector()) : Tensor();
+    return {Tensor(), Tensor(), std::get<0>(r), Tensor(), gb};
+  }
+};
+static Tensor spmm_rows_autograd(const Tensor &index, const OptT_ &weight, const Tensor &x, const Tensor &rows,
+                                 const OptT_ &bias) {
+  TORCH_CHECK(!(opt(weight).defined() && opt(weight).requires_grad()),
+              "spmm_rows has no gradient for the edge weights: pass detached weights (bspmm_sum is the op with a weight gradient)");
+  return SpMMRowsFn::apply(index, weight, x, rows, bias);
+}
+
 struct SegEpiFn : public torch::autograd::Function<SegEpiFn> {
   static Tensor forward(AutogradContext *ctx, const Tensor &x, const Tensor &index, int64_t N, bool mean, const OptT_ &add,
                         const OptT_ &bias, bool relu) {
@@ -1698,6 +1887,13 @@ static std::tuple<Tensor, Tensor> epi_fwd_meta(const Tensor &, const OptT_ &, co
 static Tensor epi_meta(const Tensor &, const OptT_ &, const Tensor &x, bool, const OptT_ &, const OptT_ &, bool, double) {
   return at::empty_like(x);
 }
+static Tensor rows_meta(const Tensor &, const OptT_ &, const Tensor &x, const Tensor &rows, const OptT_ &) {
+  return at::empty({rows.size(0), x.size(1)}, x.options());
+}
+static std::tuple<Tensor, Tensor> rows_bwd_meta(const Tensor &, const OptT_ &, const Tensor &g, const Tensor &, int64_t n_src,
+                                                bool hb) {
+  return {at::empty({n_src, g.size(1)}, g.options()), at::empty({hb ? g.size(1) : 0}, g.options())};
+}
 static Tensor seg_epi_meta(const Tensor &x, const Tensor &, int64_t N, bool, const OptT_ &, const OptT_ &, bool) {
   return at::empty(out_shape(x, N), x.options());
 }
@@ -1706,6 +1902,7 @@ static void clear_caches() {
   seg_cache().clear();
   graph_cache().clear();
   csr_cache().clear();
+  rows_cache().clear();
 }
 static std::vector<int64_t> plan_stats() {
   return {static_cast<int64_t>(g_plans_built.load()), static_cast<int64_t>(g_plan_hits.load())};
@@ -1758,6 +1955,10 @@ TORCH_LIBRARY(ggl, m) {
         "bool relu=False, float p_drop=0.0) -> Tensor");
   m.def("spmm_epi_forward(Tensor index, Tensor? weight, Tensor x, bool mean, Tensor? add, Tensor? bias, bool relu, "
         "float p_drop) -> (Tensor, Tensor)");
+  // (A x + bias)[rows] on the rows alone: rows = a sorted, duplicate-free int64 list of destination rows; K % 4 == 0
+  m.def("spmm_rows(Tensor index, Tensor? weight, Tensor x, Tensor rows, Tensor? bias=None) -> Tensor");
+  m.def("spmm_rows_forward(Tensor index, Tensor? weight, Tensor x, Tensor rows, Tensor? bias) -> Tensor");
+  m.def("spmm_rows_backward(Tensor index, Tensor? weight, Tensor grad, Tensor rows, int n_src, bool has_bias) -> (Tensor, Tensor)");
   m.def("segment_epi(Tensor x, Tensor index, int N, bool mean=True, Tensor? add=None, Tensor? bias=None, bool relu=False) -> Tensor");
   m.def("segment_epi_forward(Tensor x, Tensor index, int N, bool mean, Tensor? add, Tensor? bias, bool relu) -> Tensor");
   m.def("sample_hop(Tensor rowptr, Tensor col, Tensor seeds, Tensor n_seeds, int num_nodes, int fanout, int e_cap, int s_cap, "
@@ -1796,6 +1997,8 @@ TORCH_LIBRARY(ggl, m) {
     m.impl("bias_act_backward", ggl_torch::bias_act_backward_kernel);          \
     m.impl("spmm_epi_forward", ggl_torch::spmm_epi_forward_kernel);            \
     m.impl("segment_epi_forward", ggl_torch::segment_epi_forward_kernel);      \
+    m.impl("spmm_rows_forward", ggl_torch::spmm_rows_forward_kernel);          \
+    m.impl("spmm_rows_backward", ggl_torch::spmm_rows_backward_kernel);        \
     m.impl("sample_hop", ggl_torch::sample_hop_kernel);                        \
   }
 GGL_BACKEND(CPU)
@@ -1817,6 +2020,7 @@ TORCH_LIBRARY_IMPL(ggl, Autograd, m) {
   m.impl("bias_act", ggl_torch::bias_act_autograd);
   m.impl("spmm_epi", ggl_torch::spmm_epi_autograd);
   m.impl("segment_epi", ggl_torch::segment_epi_autograd);
+  m.impl("spmm_rows", ggl_torch::spmm_rows_autograd);
 }
 
 TORCH_LIBRARY_IMPL(ggl, Meta, m) {
@@ -1851,5 +2055,8 @@ TORCH_LIBRARY_IMPL(ggl, Meta, m) {
   m.impl("spmm_epi", ggl_torch::epi_meta);
   m.impl("spmm_epi_forward", ggl_torch::epi_fwd_meta);
   m.impl("segment_epi", ggl_torch::seg_epi_meta);
+  m.impl("spmm_rows", ggl_torch::rows_meta);
+  m.impl("spmm_rows_forward", ggl_torch::rows_meta);
+  m.impl("spmm_rows_backward", ggl_torch::rows_bwd_meta);
   m.impl("segment_epi_forward", ggl_torch::seg_epi_meta);
 }

@@ -40,6 +40,9 @@ from .ops import _ptr
 HALO_CHUNKS = int(os.environ.get("GGL_HALO_CHUNKS", "0"))  # 0 = automatic (4 at K >= 256, 2 at K >= 128)
 DIST_EXACT = os.environ.get("GGL_DIST_EXACT", "1") == "1"   # 0: partitioned aggregates walk their hub rows chunk by chunk (A/B)
 A2A_MODE = os.environ.get("GGL_HALO_A2A", "a2a")            # "a2a": all_to_all_single | "p2p": grouped isend / irecv per peer
+# 1: the output layer of a one-GPU training step aggregates only the rows the loss reads (spmm_rows on the restricted plan
+# pair of the train list); 0: every row, indexed afterwards (A/B runs and the equality tests; same results either way)
+OUT_ROWS = os.environ.get("GGL_OUT_ROWS", "1") != "0"
 
 
 def balanced_bounds(dst, num_nodes, world):
@@ -292,13 +295,22 @@ class PartitionedGraph:
         """Undo what constructing this graph changed process-wide (the GGL_DIST_EXACT=0 switch of `exact_long_rows`)."""
         _restore_dist_exact(self)
 
-    def aggregate(self, h, bias=None, relu=False, p_drop=0.0, training=True, halo_included=False):
+    def aggregate(self, h, bias=None, relu=False, p_drop=0.0, training=True, halo_included=False, out_rows=None):
         """out[i] = dropout(relu(sum_{j->i} w_ij h[j] + bias)) for the local rows i (autograd-aware).  The
         epilogue (gcn_conv.py:105-106, models/gcn.py:55-59) rides on the store of the LAST edge block added:
         the local SpMM when this rank has no halo, the halo-source SpMM otherwise.  `halo_included`: `h` holds
         n_local + n_halo rows, the halo rows already in place behind the local ones (`with_halo`, or rows this rank
-        computed from them): nothing is exchanged, and the gradient comes back with the same n_local + n_halo rows."""
+        computed from them): nothing is exchanged, and the gradient comes back with the same n_local + n_halo rows.
+        `out_rows` (one GPU, no halo, a layer without ReLU / dropout): a sorted, duplicate-free int64 list of local rows —
+        only those rows are aggregated and returned ([len(out_rows), K], equal to the full result indexed by them)."""
         p = float(p_drop) if training else 0.0
+        if out_rows is not None:
+            if self.comm or halo_included or relu or p > 0 or h.shape[1] % 4 != 0:
+                raise RuntimeError("aggregate(out_rows=...) is the one-GPU output layer's form: no halo, no ReLU / dropout, "
+                                   "a feature width that is a multiple of 4")
+            if self.route == "cpp":
+                return _cpp_ops().spmm_rows(self.ei_loc, self.w_loc, h, out_rows, bias)
+            return self.eng.spmm_rows(self.gp_loc, self.w_loc, h, out_rows, bias)
         if self.route == "cpp" and not self.comm and not halo_included and h.shape[1] % 4 == 0:
             # ONE GPU, no halo: the aggregate through the operator the zero-edit drop-in binds — torch.ops.ggl.spmm_epi, i.e.
             # dispatcher -> libggl_torch.so (plan cache + autograd in C++) -> C ABI -> libggl_mpops_hip.so (round-5 verdict: the
@@ -627,7 +639,11 @@ class DistGCN(torch.nn.Module):
                 w.grad.add_(gw)
         self._sink.clear()
 
-    def forward(self, x, pg):
+    def forward(self, x, pg, out_rows=None):
+        """`out_rows` (a sorted, duplicate-free int64 list of local rows, e.g. the train nodes): return the logits of those
+        rows only, [len(out_rows), num_class] — equal to forward(x, pg)[out_rows].  On one GPU without a halo the output
+        layer then aggregates only those rows (PartitionedGraph.aggregate); partitioned and dry graphs, and the
+        aggregate-first association, compute every row and index afterwards."""
         n = len(self.lin)
         if x.is_cuda and self.side is None and self.overlap_wgrad:
             self.side = torch.cuda.Stream(device=x.device)
@@ -662,12 +678,19 @@ class DistGCN(torch.nn.Module):
                     h = _LinearSideWgrad.apply(x, self.lin[i].weight, self.side, self._sink, pad)
                     # + bias, ReLU and dropout ride on the store of the last edge block added to a row: the local SpMM
                     # on one GPU, the halo-source SpMM behind the exchange otherwise (reduce.hip MODE_SPMM_EPI)
-                    x = pg.aggregate(h, bias, relu=hidden, p_drop=p, training=self.training, halo_included=pre)
+                    rows = out_rows if (i == n - 1 and out_rows is not None and not pg.comm and not pre
+                                        and (n_out + pad) % 4 == 0) else None
+                    x = pg.aggregate(h, bias, relu=hidden, p_drop=p, training=self.training, halo_included=pre, out_rows=rows)
+                    if rows is not None:
+                        out_rows = None   # applied: what follows sees the listed rows only
+                        if pad:
+                            x = x[:, :n_out].contiguous()   # (what indexing the [N, n_out] view hands the loss: a contiguous matrix)
+                        continue
             pre = False
             if pad:
                 x = x[:, :n_out]
         self.agg_per_step = n_agg
-        return x
+        return x if out_rows is None else x[out_rows]
 
 
 class DistGCNTrainer:
@@ -686,14 +709,41 @@ class DistGCNTrainer:
         except (RuntimeError, TypeError):
             self.opt = torch.optim.Adam(self.net.parameters(), lr=lr, weight_decay=l2_coef)
         self.graph = None
+        from .ops import _PlanCache
+
+        # train lists already checked for the restricted output layer (sorted, unique int64); an entry dies with its storage
+        self._rows_ok = _PlanCache(cap=16)
         torch.manual_seed(seed + 1000 * (pg.rank + 1))  # independent dropout masks per rank
+
+    def _out_rows(self, train_local):
+        """`train_local` if the output layer may be restricted to it (GGL_OUT_ROWS, one GPU without a halo, a sorted
+        duplicate-free int64 list: checked once per list, on its first step, with up to three host reads — any other index keeps
+        the full-row path)."""
+        if not OUT_ROWS or self.pg.comm or not torch.is_tensor(train_local) or train_local.dtype != torch.int64 \
+                or train_local.dim() != 1:
+            return None
+        if int(self.pg.ei_loc.shape[1]) >= 2**31 - 1:
+            return None   # the restricted pair is cut with 32-bit scan positions; the full plans take 64-bit offsets
+        ok = self._rows_ok.get(train_local, ())
+        if ok is None:
+            if train_local.is_cuda and torch.cuda.is_current_stream_capturing():
+                return None
+            t = train_local
+            ok = bool(t.numel() == 0 or (int(t[0]) >= 0 and int(t[-1]) < self.pg.n_local and
+                                         (t.numel() == 1 or bool((t[1:] > t[:-1]).all()))))
+            self._rows_ok.put(train_local, (), ok)
+        return train_local if ok else None
 
     def step(self, x_local, y_local, train_local, n_train_global):
         pg = self.pg
         self.net.train()
         self.opt.zero_grad(set_to_none=True)
-        logits = self.net(x_local, pg)
-        loss = F.cross_entropy(logits[train_local], y_local[train_local], reduction="sum") / n_train_global
+        rows = self._out_rows(train_local)
+        if rows is not None:   # the loss reads these rows only: the output layer aggregates nothing else
+            logits = self.net(x_local, pg, out_rows=rows)
+        else:
+            logits = self.net(x_local, pg)[train_local]
+        loss = F.cross_entropy(logits, y_local[train_local], reduction="sum") / n_train_global
         loss.backward()
         self.net.join()
         if pg.world > 1:  # one flat bucket: 3 small weight matrices + biases

@@ -217,6 +217,14 @@ class GraphPlan:
         return self._tpos
 
 
+class RowsPlan:
+    """A GraphPlan cut down to a sorted list of destination rows (Engine.rows_plan): `fwd` R x N_src and `bwd` N_src x R
+    SegPlans with their column arrays and the edge weights in sorted order.  `w_ref`: the weight tensor's storage (an
+    entry whose weights died is a miss: the address may have been handed to another tensor)."""
+
+    __slots__ = ("R", "N_dst", "N_src", "rows", "fwd", "col", "w_fwd", "bwd", "colT", "w_bwd", "w_ref")
+
+
 class _PlanCache:
     """LRU keyed on the identity of the id tensor's storage + its version counter, bounded by entry count AND
     by the bytes its plans hold (a products-sized GraphPlan is ~2.5 GB of HBM: a caller that builds a fresh
@@ -315,6 +323,7 @@ class Engine:
         self.seg_cache = _PlanCache()
         self.graph_cache = _PlanCache()
         self.w_cache = _PlanCache(cap=8)
+        self.rows_cache = _PlanCache(cap=8)   # restricted plan pairs (rows_plan), keyed on the row list
         self._rng = {}
         self.stats = {"plans_built": 0, "plan_hits": 0}
         self.chunk = DEFAULT_CHUNK  # long-row threshold == elements per chunk; 0 = auto_chunk(E)
@@ -339,6 +348,7 @@ class Engine:
         self.seg_cache.clear()
         self.graph_cache.clear()
         self.w_cache.clear()
+        self.rows_cache.clear()
 
     # ---- plumbing ----------------------------------------------------------------------------
     def _check(self, rc):
@@ -473,12 +483,13 @@ class Engine:
         key = (group << 32) | ((1 << 31) - counts.clamp(max=(1 << 31) - 1))
         return torch.argsort(key, stable=True).to(torch.int32)
 
-    def plan_from_rowptr(self, rowptr, E, max_len=None):
+    def plan_from_rowptr(self, rowptr, E, max_len=None, chunk=None):
         """SegPlan for elements that are ALREADY grouped by segment (CSR: a sampler's block, a sorted edge
-        list): no sort, and no host sync when the caller knows ``max_len`` (e.g. the fan-out)."""
+        list): no sort, and no host sync when the caller knows ``max_len`` (e.g. the fan-out).  ``chunk``: the
+        long-row threshold of the plan these rows were cut from (rows_plan), instead of the policy's for this E."""
         dev = self._dev(rowptr)
         p = SegPlan()
-        p.N, p.E, p.chunk, p.device = int(rowptr.shape[0]) - 1, int(E), int(self.chunk or self.auto_chunk(E)), dev
+        p.N, p.E, p.chunk, p.device = int(rowptr.shape[0]) - 1, int(E), int(chunk or self.chunk or self.auto_chunk(E)), dev
         p.rowptr = rowptr.contiguous().to(torch.int64)
         p.perm, p.is_sorted = None, True
         p.max_len = int(max_len) if max_len is not None else (int(p.counts().max()) if p.N > 0 else 0)
@@ -554,6 +565,83 @@ class Engine:
         else:
             self.stats["plan_hits"] += 1
         return gp
+
+    def rows_plan(self, gp, weight, rows):
+        """The restricted plan pair of `gp` for the sorted, duplicate-free destination list `rows` (int64 [R]) with the
+        edge weights `weight` (or None) copied into sorted order: cached next to the full plan on the identity + version
+        of `rows` (and of the weights), so it is built once per (graph, weights, row list) — in warm-up, never inside a
+        hipGraph capture (the build reads sizes back)."""
+        if rows.dim() != 1 or rows.dtype != torch.int64:
+            raise RuntimeError(f"rows must be a 1-D int64 tensor, got {tuple(rows.shape)} {rows.dtype}")
+        self._dev(rows, weight)
+        extra = ("rows", gp.fwd.uid, gp.N_dst, gp.N_src) + (_PlanCache.key(weight, ()) if weight is not None else (None,))
+        rp = self.rows_cache.get(rows, extra)
+        if rp is not None and (rp.w_ref is None or not rp.w_ref.expired()):
+            self.stats["plan_hits"] += 1
+            return rp
+        if rows.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("spmm_rows: the restricted plan of this row list must be built before a hipGraph capture "
+                               "(run one eager step first)")
+        rows = rows.contiguous()
+        dev, L, st = rows.device, self.lib, self._stream(rows.device)
+        R, N, E = int(rows.shape[0]), gp.N_dst, gp.E
+        wsb = L.ggl_plan_rows_workspace_bytes(E, max(gp.N_dst, gp.N_src), R)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        rank = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
+        self._check(L.ggl_plan_rows_rank(_ptr(rows), R, N, _ptr(rank), _ptr(ws), wsb, st))
+        bwd, colT = gp.bwd, gp.colT
+        w = weight
+        rp = RowsPlan()
+        rp.R, rp.N_dst, rp.N_src, rp.rows = R, gp.N_dst, gp.N_src, rows
+        rp.w_ref = StorageWeakRef(weight.untyped_storage()) if weight is not None else None
+        # forward: a segmented copy of the listed rows' slices
+        rowptr_r = torch.empty(R + 1, dtype=torch.int64, device=dev)
+        n = ctypes.c_int64(0)
+        self._check(L.ggl_plan_rows_fwd_rowptr(_ptr(gp.fwd.rowptr), _ptr(rows), R, _ptr(rowptr_r), _ptr(ws), wsb, st,
+                                               ctypes.byref(n)))
+        E_r = int(n.value)
+        rp.col = torch.empty(E_r, dtype=torch.int32, device=dev)
+        rp.w_fwd = torch.empty(E_r, dtype=torch.float32, device=dev) if w is not None else None
+        wperm = gp.fwd.perm if gp.fwd.perm is not None else getattr(gp.fwd, "wperm", None)
+        self._check(L.ggl_plan_rows_fwd_fill(_ptr(gp.fwd.rowptr), _ptr(gp.col), _ptr(w), _ptr(wperm), _ptr(rows), R,
+                                             _ptr(rowptr_r), E_r, _ptr(rp.col), _ptr(rp.w_fwd), st))
+        rp.fwd = self.plan_from_rowptr(rowptr_r, E_r, chunk=gp.fwd.chunk)   # the full plan's threshold: the same rows are long
+        # transposed: the full transposed plan filtered to the listed destinations (flag, scan, compact)
+        pos = torch.empty(E + 1, dtype=torch.int32, device=dev)
+        rowptrT_r = torch.empty(gp.N_src + 1, dtype=torch.int64, device=dev)
+        self._check(L.ggl_plan_rows_bwd_rowptr(_ptr(bwd.rowptr), _ptr(colT), gp.N_src, E, _ptr(rank), _ptr(pos),
+                                               _ptr(rowptrT_r), _ptr(ws), wsb, st, ctypes.byref(n)))
+        if int(n.value) != E_r:
+            raise RuntimeError(f"restricted plans disagree: {E_r} forward elements, {int(n.value)} transposed")
+        rp.colT = torch.empty(E_r, dtype=torch.int32, device=dev)
+        rp.w_bwd = torch.empty(E_r, dtype=torch.float32, device=dev) if w is not None else None
+        wpermT = bwd.perm if bwd.perm is not None else getattr(bwd, "wperm", None)
+        self._check(L.ggl_plan_rows_bwd_fill(_ptr(colT), _ptr(w), _ptr(wpermT), E, _ptr(rank), _ptr(pos), _ptr(rp.colT),
+                                             _ptr(rp.w_bwd), st))
+        rp.bwd = self.plan_from_rowptr(rowptrT_r, E_r, chunk=bwd.chunk)
+        del pos, rank, ws
+        self.rows_cache.put(rows, extra, rp)
+        return rp
+
+    def spmm_rows(self, gp, weight, x, rows, bias=None):
+        """(A x + bias)[rows] for a sorted, duplicate-free int64 row list, computed on the rows alone: [R, K] f32,
+        K % 4 == 0.  Equal to spmm_epi(gp, weight, x, bias=bias)[rows], gradients included.  A weight that requires grad
+        is refused (c_bspmm_sum is the op with a weight gradient)."""
+        self._dev(x, weight, bias, rows)
+        self._check_f32("x", x)
+        if x.dim() != 2 or x.shape[1] % 4 != 0 or x.shape[1] == 0:
+            raise RuntimeError(f"spmm_rows needs a 2-D f32 x whose width is a multiple of 4, got {tuple(x.shape)}")
+        if int(x.shape[0]) != gp.N_src:
+            raise RuntimeError(f"spmm_rows: x has {int(x.shape[0])} rows, the graph {gp.N_src} source nodes")
+        if weight is not None and weight.requires_grad:
+            raise RuntimeError("spmm_rows has no gradient for the edge weights: pass detached weights (c_bspmm_sum is the "
+                               "op with a weight gradient)")
+        weight = self._check_weight(weight, gp)
+        if bias is not None:
+            self._check_f32("bias", bias)
+            if bias.numel() != x.shape[1]:
+                raise RuntimeError("bias must hold one value per column")
+        return self.SpMMRows.apply(gp, weight, x.contiguous(), rows, bias)
 
     def gather_i32(self, src_i64, perm):
         dev = src_i64.device
@@ -1422,6 +1510,44 @@ class Engine:
                 return gx, None, (ga if ctx.has_add else None), gb, None
 
         self.BlockMeanEpi = BlockMeanEpi
+        class SpMMRows(torch.autograd.Function):
+            """y[r] = sum_{j -> rows[r]} w x_j + bias for a sorted list of destination rows: the aggregate of a layer whose
+            consumer reads only those rows (the loss over the training nodes), on the restricted plan pair
+            (Engine.rows_plan).  Backward: gx = the transposed restricted walk over the compact [R, K] gradient, written
+            into a full [N_src, K] result; gbias = ggl_bias_grad_rows.  Same bits as spmm_epi(...)[rows] and its backward."""
+
+            @staticmethod
+            def forward(ctx, gp, w, x, rows, bias):
+                dev = x.device
+                K = int(x.shape[1])
+                rp = eng.rows_plan(gp, w, rows)
+                y = torch.empty((rp.R, K), dtype=torch.float32, device=dev)
+                b = bias.contiguous().reshape(-1) if bias is not None else None
+                eng.spmm_epi_into(rp.fwd, rp.col, rp.w_fwd, x, y, bias=b)
+                ctx.rp, ctx.bshape, ctx.K = rp, (None if bias is None else bias.shape), K
+                return y
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, g):
+                rp, K = ctx.rp, ctx.K
+                g = g.contiguous()
+                dev = g.device
+                gb = None
+                if ctx.bshape is not None and ctx.needs_input_grad[4]:
+                    gb = torch.empty(K, dtype=torch.float32, device=dev)
+                    wsb = eng.lib.ggl_bias_act_bwd_workspace_bytes(rp.N_dst, K)
+                    ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=dev)
+                    eng._check(eng.lib.ggl_bias_grad_rows(_ptr(g), _ptr(rp.rows), rp.R, rp.N_dst, K, _ptr(gb), _ptr(ws), wsb,
+                                                          eng._stream(dev)))
+                    gb = gb.reshape(ctx.bshape)
+                gx = None
+                if ctx.needs_input_grad[2]:
+                    gx = torch.empty((rp.N_src, K), dtype=torch.float32, device=dev)
+                    eng.spmm_sum_into(rp.bwd, rp.colT, rp.w_bwd, g, gx)
+                return None, None, gx, None, gb
+
+        self.SpMMRows = SpMMRows
         self.SpMMEpi, self.SegmentEpi = SpMMEpi, SegmentEpi
         self.SpMMSumBiasAct = SpMMSumBiasAct
         self.BiasAct = BiasAct

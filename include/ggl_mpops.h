@@ -139,6 +139,41 @@ int ggl_plan_long_count(const int64_t *rowptr, int64_t N, int64_t chunk, void *w
 int ggl_plan_long_fill(const int64_t *rowptr, int64_t N, int64_t chunk, int64_t n_long,
                        int32_t *long_rows, int64_t *chunk_ptr, void *workspace,
                        size_t workspace_bytes, void *stream);
+/* ------------------------------------------------------------------------------------------------
+ * Restricted plan pair (still ABI 10: additive) — the plans of a graph cut down to a SORTED, DUPLICATE-FREE list
+ * rows[R] (int64) of destination rows, built from the full pair without a sort.  An aggregate whose consumer reads
+ * only those rows (a loss over the training nodes) then walks only the edges that end in them, and its backward
+ * gathers a compact [R, K] gradient instead of an [N_dst, K] one that is zero elsewhere:
+ *   forward   R x N_src : row r = the slice rowptr[rows[r]] .. rowptr[rows[r] + 1] of the full plan's col / weights;
+ *   transposed N_src x R: the full transposed plan filtered to the elements whose destination is listed (flag,
+ *                         exclusive scan, compact), colT_r = rank of the destination in rows[].
+ * Every row keeps its elements in the full plan's order, so its sum has the same bits; the skipped terms are w * (+0).
+ * col_r / colT_r / w_r are in sorted order (launch with w_by_pos = 1, perm = NULL); long-row bookkeeping as for any
+ * plan (ggl_plan_long_count / _fill on rowptr_r / rowptrT_r).  w (or NULL) is read at wperm[p] when wperm != NULL (the
+ * plan's perm: caller's edge order), at p otherwise.
+ *   ggl_plan_rows_rank       SYNCHRONOUS: validates rows (GGL_EINDEX out of [0, N); GGL_EINVAL unsorted / repeated) and
+ *                            writes rank[N] (int32: position in rows[], -1 = not listed)
+ *   ggl_plan_rows_fwd_rowptr SYNCHRONOUS: rowptr_r[R + 1], *E_r_host = elements kept
+ *   ggl_plan_rows_fwd_fill   col_r[E_r], w_r[E_r]
+ *   ggl_plan_rows_bwd_rowptr SYNCHRONOUS: pos[E + 1] (int32 scratch: exclusive scan of the keep flags) and
+ *                            rowptrT_r[N_src + 1] read off it at the old row boundaries; *E_r_host = elements kept
+ *   ggl_plan_rows_bwd_fill   colT_r[E_r], w_r[E_r]
+ * workspace: ggl_plan_rows_workspace_bytes(E, N, R) bytes serve every call above.
+ * ---------------------------------------------------------------------------------------------- */
+size_t ggl_plan_rows_workspace_bytes(int64_t E, int64_t N, int64_t R);
+int ggl_plan_rows_rank(const int64_t *rows, int64_t R, int64_t N, int32_t *rank, void *workspace,
+                       size_t workspace_bytes, void *stream);
+int ggl_plan_rows_fwd_rowptr(const int64_t *rowptr, const int64_t *rows, int64_t R, int64_t *rowptr_r, void *workspace,
+                             size_t workspace_bytes, void *stream, int64_t *E_r_host);
+int ggl_plan_rows_fwd_fill(const int64_t *rowptr, const int32_t *col, const float *w, const int32_t *wperm,
+                           const int64_t *rows, int64_t R, const int64_t *rowptr_r, int64_t E_r, int32_t *col_r,
+                           float *w_r, void *stream);
+int ggl_plan_rows_bwd_rowptr(const int64_t *rowptrT, const int32_t *colT, int64_t N_src, int64_t E, const int32_t *rank,
+                             int32_t *pos, int64_t *rowptrT_r, void *workspace, size_t workspace_bytes, void *stream,
+                             int64_t *E_r_host);
+int ggl_plan_rows_bwd_fill(const int32_t *colT, const float *w, const int32_t *wperm, int64_t E, const int32_t *rank,
+                           const int32_t *pos, int32_t *colT_r, float *w_r, void *stream);
+
 /* bytes of `partial` for n_chunks chunks of K features of dtype (value + int64 arg for max) */
 size_t ggl_partial_bytes(int dtype, int64_t n_chunks, int64_t K, int with_arg);
 
@@ -356,6 +391,13 @@ size_t ggl_bias_act_bwd_workspace_bytes(int64_t N, int64_t K);
 int ggl_bias_act_bwd(const float *g, const float *y, int64_t N, int64_t K, int relu, float p_drop,
                      const int64_t *rng_used, float *ga, float *gbias, void *workspace,
                      size_t workspace_bytes, void *stream);
+/* The bias gradient of ggl_bias_act_bwd(relu = 0, p_drop = 0) for a gradient that is zero outside the sorted rows[R] of
+ * an [N, K] matrix, from the compact g[R, K] alone (K % 4 == 0, g 16-byte aligned): the same partial matrix — same
+ * geometry, every listed row added into the slot and at the position its id gives it — reduced by the same
+ * ggl_colsum_f32, so gbias[K] is the number the pass over the scattered [N, K] gradient gives (it only adds +0 rows
+ * more).  workspace: ggl_bias_act_bwd_workspace_bytes(N, K). */
+int ggl_bias_grad_rows(const float *g, const int64_t *rows, int64_t R, int64_t N, int64_t K, float *gbias,
+                       void *workspace, size_t workspace_bytes, void *stream);
 /* General form of the fused epilogue (sage_conv.py:100-108, gcn_conv.py:105-106):
  *   out[i, 0:K] = dropout(relu(reduce_{p in row i} w * x[col[p], 0:K] (+ out[i, 0:K] if accumulate)
  *                              + add[i, 0:K] + bias[0:K]))
