@@ -77,71 +77,57 @@ __device__ __forceinline__ int64_t block_id() { return (int64_t)blockIdx.y * (in
 __device__ __forceinline__ int64_t thread_id() { return block_id() * (int64_t)blockDim.x + (int64_t)threadIdx.x; }
 __device__ __forceinline__ int64_t grid_threads() { return (int64_t)gridDim.x * (int64_t)gridDim.y * (int64_t)blockDim.x; }
 
+// The library's options, declared ONCE: X(name, default) /* what it selects, and the measurement behind the default */.
+// The Options fields, the environment read (GGL_ + the upper-cased name, once, at first use), ggl_set_option,
+// ggl_get_option and ggl_option_name (plan.hip) are all generated from this list.  Forms that were measured, lost and
+// removed in ABI 11 are recorded in DESIGN.md ("Forms removed in ABI 11"); they were last present in 992473a.
+#define GGL_OPTIONS(X)                                                                                                      \
+  X(unroll, 4)               /* neighbour loads in flight per lane in the f32 fast path (4 or 8) */                         \
+  X(unroll_narrow, 16)       /* ... and where a row owns <= 4 lanes (K <= 16 floats): 4 or 16 */                            \
+  X(unroll_narrow_max, 0)    /* ... for max too (lost with 64-bit argmax registers in round 1; re-measured in round 4) */   \
+  /* 1 = give each XCD a contiguous range of row blocks (private-L2 locality).  OFF by default: measured on MI355X          \
+     (profiles/kbench_r1.txt) it changes nothing on a randomly ordered graph and is 4x SLOWER on a degree-ordered one       \
+     (one XCD inherits all the hub rows); round-robin is the load balancer. */                                              \
+  X(xcd_swizzle, 0)                                                                                                         \
+  X(force_generic, 0)        /* route f32 through the VEC=1 generic kernel (tests force the path) */                        \
+  X(col_block, 64)           /* wide f32 SpMM-sum / mean: launches over column blocks of this width (0 = one launch) */     \
+  X(col_block_min_degree, 24)     /* ... and only where a row averages at least this many edges (reuse to find) */          \
+  X(col_block_min_edges, 8000000) /* below this many edges the blocks are twice as wide (launch-bound graphs) */            \
+  X(ragged4, 1)              /* f32 rows that are not aligned float4s (K % 4 != 0): 4 floats per lane + ragged last lane */ \
+  X(ragged_max, 1)           /* ... for segment_max as well (0 = the one-element-per-lane kernels of rounds 2-3) */         \
+  /* 0 = natural row order; 1 = length-sorted rows where several rows share a wavefront (balances the lanes of a wave);     \
+     2 = also for the wave-per-row kernels (heavy rows first) */                                                            \
+  X(row_order, 1)                                                                                                           \
+  X(max_grid_x, 1 << 22)     /* blocks per grid row before a launch is folded into 2-D (tests lower it; set clamps to >= 1) */ \
+  /* f32 sums: rows longer than the plan's chunk are added up in the reference's serial order (hubf32.hip: bit-identical    \
+     to the CPU extension on EVERY row) instead of chunk by chunk (within rounding of it); 0 = the chunked walk */          \
+  X(exact_long_rows, 1)                                                                                                     \
+  /* hosts: gspmm max backward (products-sized graph, forward + backward in ms, profiles/r5_max_backward.txt):              \
+                 int64 witnesses   int32 witnesses   winner mask, forward-order records                                     \
+       K =  64        16.8              12.7                        14.0                                                    \
+       K = 128        32.4              25.0                        21.6                                                    \
+       K = 256        67.1              53.0                        41.1                                                    \
+     (removed in ABI 11: records assembled with selects instead of v_writelane, 44.4 ms at K = 256; records scattered to    \
+      transposed positions, 41.7 ms; the masked walk in 64-column blocks, 46.8-54.6 ms) */                                  \
+  X(maxbwd_arg32, 1)         /* witnesses from a compact int32 copy (ggl_spmm_max_bwd32) ... */                             \
+  X(maxbwd_mask, 128)        /* ... and from this many columns up a 1-bit winner mask instead (0 = never) */                \
+  /* ... up to this many columns (the mask is an E x K/8-byte transient; K = 602 measured slower AND 12 GiB on the          \
+     Reddit-sized graph: ggl_policy_maxbwd_form; 0 = no upper bound: tests force the mask at any width) */                  \
+  X(maxbwd_mask_kmax, 256)                                                                                                  \
+  X(exact_long_max, (int64_t)1 << 21) /* exact_long_rows: unless the plan's longest row is longer than this (0 = no limit) */ \
+  X(exact_side_stream, 1)    /* ... launched beside the walk over the other rows (0 = in front of it, same stream) */       \
+  X(softmax_sublanes, 0)     /* edge softmax (gat.hip): lanes that share a (row, column), GPU build (0 = ggl_policy_softmax_sublanes) */ \
+  /* hub walk once per aggregate over the full width: 1 = always, 0 = once per column block, 2 = where the long rows lead the ids */ \
+  X(hub_one_launch, 2)                                                                                                      \
+  /* wide 16-bit-storage SpMM-sum / mean (ggl_spmm_*_x16): column blocks of this width (0 = one launch).  128 columns of    \
+     16 bits are the 256-byte slices the f32 launches gather at col_block = 64 (sweep: profiles/spmm16.txt, DESIGN.md       \
+     "Mixed-precision aggregate") */                                                                                        \
+  X(col_block16, 128)
+
 struct Options {
-  int64_t unroll = 4;        // neighbour loads in flight per lane in the f32 fast path (4 or 8)
-  int64_t unroll_narrow = 16; // ... and where a row owns <= 4 lanes (K <= 16 floats): 4 or 16
-  int64_t unroll_narrow_max = 0;  // ... for max too (A/B knob: lost with 64-bit argmax registers in round 1; re-measured in round 4)
-  // 1 = give each XCD a contiguous range of row blocks (private-L2 locality).  OFF by default: measured
-  // on MI355X (profiles/kbench_r1.txt) it changes nothing on a randomly ordered graph and is 4x SLOWER
-  // on a degree-ordered one (one XCD inherits all the hub rows); round-robin is the load balancer.
-  int64_t xcd_swizzle = 0;
-  int64_t force_generic = 0; // route f32 through the VEC=1 generic kernel (A/B aid)
-  int64_t col_block = 64;    // wide f32 SpMM-sum / mean: launches over column blocks of this width (0 = one launch)
-  int64_t col_block_min_degree = 24;      // ... and only where a row averages at least this many edges (reuse to find)
-  int64_t col_block_min_edges = 8000000;  // below this many edges the blocks are twice as wide (launch-bound graphs)
-  int64_t ragged4 = 1;       // f32 rows that are not aligned float4s (K % 4 != 0): 4 floats per lane + ragged last lane
-  int64_t ragged_max = 1;    // ... for segment_max as well (0 = the one-element-per-lane kernels of rounds 2-3: an A/B knob)
-  // 0 = natural row order; 1 = length-sorted rows where several rows share a wavefront (balances
-  // the lanes of a wave); 2 = also for the wave-per-row kernels (heavy rows first)
-  int64_t row_order = 1;
-  int64_t max_grid_x = 1 << 22;  // blocks per grid row before a launch is folded into 2-D (tests lower it)
-  // f32 sums: rows longer than the plan's chunk are added up in the reference's serial order (hubf32.hip: bit-identical to
-  // the CPU extension on EVERY row) instead of chunk by chunk (within rounding of it); 0 = the chunked walk (A/B switch)
-  int64_t exact_long_rows = 1;
-  // hosts: gspmm max backward (products-sized graph, forward + backward in ms, profiles/r5_max_backward.txt):
-  //             int64 witnesses   int32 witnesses   winner mask: forward order (writelane / select)   scattered
-  //   K =  64        16.8              12.7                        14.0 / 14.4                           15.4
-  //   K = 128        32.4              25.0                        21.6 / 23.1                           22.2
-  //   K = 256        67.1              53.0                        41.1 / 44.4                           41.7
-  int64_t maxbwd_arg32 = 1;        // witnesses from a compact int32 copy (ggl_spmm_max_bwd32) ...
-  int64_t maxbwd_mask = 128;       // ... and from this many columns up a 1-bit winner mask instead (0 = never)
-  int64_t maxbwd_mask_kmax = 256;  // ... up to this many columns (the mask is an E x K/8-byte transient; K = 602 measured slower AND 12 GiB on the
-                                   //     Reddit-sized graph: ggl_policy_maxbwd_form; 0 = no upper bound: tests force the mask at any width)
-  int64_t maxbwd_mask_wlane = 1;   // ... its forward-order records assembled with v_writelane (inline asm; 0 = selects)
-  int64_t maxbwd_mask_cols = 0;    // ... its walk in 64-column blocks like the plain sum's (A/B: loses, the record is re-read per block)
-  int64_t maxbwd_mask_scatter = 0; // ... its records scattered to transposed positions instead of kept in forward order (A/B)
-  int64_t exact_long_max = (int64_t)1 << 21;   // exact_long_rows: unless the plan's longest row is longer than this (0 = no limit)
-  int64_t exact_side_stream = 1;  // ... launched beside the walk over the other rows (0 = in front of it, same stream)
-  // the head-mean (output-layer) GAT walks, round 5 (Reddit-sized graph, profiles/r5_gat_sh_forms.txt: layer fwd 5.13 -> 4.64 ms,
-  // fwd + bwd 20.9 -> 18.6 ms, 2-layer step 32.0 -> 29.6 ms):
-  int64_t gat_sh_pk = 1;          // backward walks of the head-mean GAT: dots packed over head pairs (v_pk_fma_f32), select-free reduce-scatter (round 6)
-  int64_t gat_sh_pipe = 0;        // source walk of the head-mean backward with its gathers software-pipelined one step ahead (A/B, round 6)
-  int64_t gat_sh_glds = 0;        // destination walk of the backward: the row's G in per-lane LDS slots too (A/B)
-  int64_t gat_sh_prefetch = 1;    // forward / destination walks request the next step's ids before this step's gathers
-  int64_t gat_sh_zlds = 1;        // source walk of the backward: the row's z_j in per-lane LDS slots instead of 32 registers (140 -> 125:
-                                  // 4 wavefronts per SIMD without spills) + the same id prefetch
-  int64_t gat_sh_waves = 0;       // >= 4: the output-layer GAT backward's source walk (dropout form) built for 4 wavefronts per SIMD (A/B)
-  // static-shape sampler hop: count / flag + scan (+ clamp) as ONE launch each (single-pass chained scan).  Measured (round 5,
-  // profiles/r5_sage_fused_scans.txt): 76 -> 63 launches per replayed step, but the same 0.17 ms for the two hops — the fused
-  // kernels take the 13-33 us their look-back chains need where five 5-us launches stood.  OFF: no gain to set against a
-  // kernel that spins on its predecessors (an A/B knob only: its look-back assumes lower-numbered blocks are resident or
-  // will be scheduled, and its slots are told apart by a tag of (seed, offset, scan, block) instead of being zeroed per hop).
-  int64_t hop_fused_scans = 0;
-  // small hops (round 6, A/B): the first scan + clamp + clamp_last as ONE single-workgroup launch (<= 65 536 rows: both hops of the reference's
-  // [25, 10] mini-batch), the flag scan likewise while it covers <= 32 768 positions.  Measured in three forms (values computed inside the
-  // workgroup: step 0.62 -> 0.76 ms; thread-contiguous scan: +0.055 ms; coalesced wave-slice scan: +0.02 .. +0.1 ms against the rocprim
-  // launches in paired runs) — a single workgroup on one CU is not faster than four 5-us launches it replaces.  OFF.
-  int64_t hop_small_scans = 0;
-  // the hub walk's side queue created with the device's greatest priority (big eager launches only: hubf32.hip).  OFF: the
-  // isolated aggregate gains 1 % (13.75 -> 13.60 ms) but the products STEP nothing (75.46 vs 75.45 ms) and a partitioned step
-  // LOSES (dry 8-way share 14.3 -> 16.9 ms, 4-way 26.1 -> 29.3: profiles/r5_priority_ab.txt)
-  int64_t hub_priority = 0;
-  int64_t hub_pipe = 1;           // hub walk's consumer with its LDS reads software-pipelined (0 = round 4's: A/B, heavy configuration only)
-  int64_t softmax_sublanes = 0;   // edge softmax (gat.hip): lanes that share a (row, column), GPU build (0 = ggl_policy_softmax_sublanes)
-  int64_t hub_one_launch = 2;     // hub walk once per aggregate over the full width: 1 = always, 0 = once per column block, 2 = where the long rows lead the ids
-  // wide 16-bit-storage SpMM-sum / mean (ggl_spmm_*_x16): column blocks of this width (0 = one launch).  128 columns of 16 bits are
-  // the 256-byte slices the f32 launches gather at col_block = 64 (sweep: profiles/spmm16.txt, DESIGN.md "Mixed-precision aggregate")
-  int64_t col_block16 = 128;
+#define GGL_OPTION_FIELD(name, dflt) int64_t name = (dflt);
+  GGL_OPTIONS(GGL_OPTION_FIELD)
+#undef GGL_OPTION_FIELD
 };
 Options &options();
 

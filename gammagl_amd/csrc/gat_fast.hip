@@ -416,6 +416,10 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_src2_kernel(
 //     reach the weight lanes by a 16-value reduce-scatter over the row (row_ror:8, xor 4, quad_perm xor 2 / 1).
 //   * the row maximum of the logits is found by a first pass over (col, el) alone — 36 B per edge from a
 //     cache-resident panel — so the main walk needs no online rescaling.
+// One form per walk.  Measured against these and removed in ABI 11 (last present in 992473a): round 4's bodies
+// (operands in registers, scalar dots + a 16-value reduce-scatter with selects, ids fetched in the step that uses them), G in
+// LDS slots for the destination walk (no gain), the source walk built for 4 wavefronts per SIMD (spills, no faster) and a
+// second source-walk kernel with its gathers software-pipelined one step ahead (15.1 vs 15.1 ms per layer forward + backward).
 // =====================================================================================================
 constexpr int kShH = 8;  // heads (fixed: 16 lanes = 2 edges x 8 heads)
 
@@ -429,19 +433,6 @@ __device__ __forceinline__ double row_ror8_f64(double v) {   // lane ^ 8 of the 
   const int lo = __builtin_amdgcn_mov_dpp((int)(b & 0xffffffffll), 0x128, 0xF, 0xF, true);
   const int hi = __builtin_amdgcn_mov_dpp((int)(b >> 32), 0x128, 0xF, 0xF, true);
   return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned int)lo);
-}
-
-// v[k] (k = 0..15) summed over the 16 lanes of the row; lane l returns the total of v[l]
-__device__ __forceinline__ float reduce_scatter16(const float (&v)[16], int li) {
-  const bool b3 = li & 8, b2 = li & 4, b1 = li & 2, b0 = li & 1;
-  float a[8], b[4], c[2];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) a[k] = (b3 ? v[8 + k] : v[k]) + row_ror8(b3 ? v[k] : v[8 + k]);
-#pragma unroll
-  for (int k = 0; k < 4; ++k) b[k] = (b2 ? a[4 + k] : a[k]) + __shfl_xor(b2 ? a[k] : a[4 + k], 4, 64);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) c[k] = (b1 ? b[2 + k] : b[k]) + dpp_mov<0x4E>(b1 ? b[k] : b[2 + k]);
-  return (b0 ? c[1] : c[0]) + dpp_mov<0xB1>(b0 ? c[0] : c[1]);
 }
 
 // broadcast the 8 per-head weights of edge slot E (weight lanes 8E .. 8E+7) and accumulate w_h * x into acc[h]
@@ -496,21 +487,15 @@ template <typename L> __device__ __forceinline__ void sh_pairs_to_lds(const ShPa
     for (int j = 0; j < 2; ++j)
       lds[2 * c + j][threadIdx.x] = make_float4(P.p[c][2 * j].x, P.p[c][2 * j].y, P.p[c][2 * j + 1].x, P.p[c][2 * j + 1].y);
 }
-// the pair's 16 partial dots of this lane: v0[qp] = (head 2 qp, 2 qp + 1) against g0, v1 against g1
-template <bool LDS, typename L>
-__device__ __forceinline__ void sh_pair_dots(const ShPairs &P, L &lds, const float4 &g0, const float4 &g1, f2v (&v0)[4],
-                                             f2v (&v1)[4]) {
+// the pair's 16 partial dots of this lane: v0[qp] = (head 2 qp, 2 qp + 1) against g0, v1 against g1; pairs(c, pc) hands
+// out the four head pairs of column c (from registers: sh_pair_dots, or from the lane's LDS slots: sh_pair_dots_lds)
+template <typename PairsOf>
+__device__ __forceinline__ void sh_pair_dots_from(PairsOf pairs, const float4 &g0, const float4 &g1, f2v (&v0)[4], f2v (&v1)[4]) {
   const float ga[4] = {g0.x, g0.y, g0.z, g0.w}, gb[4] = {g1.x, g1.y, g1.z, g1.w};
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     f2v pc[4];
-    if constexpr (LDS) {
-      const float4 lo = lds[2 * c][threadIdx.x], hi = lds[2 * c + 1][threadIdx.x];
-      pc[0] = f2v{lo.x, lo.y}; pc[1] = f2v{lo.z, lo.w}; pc[2] = f2v{hi.x, hi.y}; pc[3] = f2v{hi.z, hi.w};
-    } else {
-#pragma unroll
-      for (int qp = 0; qp < 4; ++qp) pc[qp] = P.p[c][qp];
-    }
+    pairs(c, pc);
     const f2v sa = f2v{ga[c], ga[c]}, sb = f2v{gb[c], gb[c]};
 #pragma unroll
     for (int qp = 0; qp < 4; ++qp) {
@@ -518,6 +503,19 @@ __device__ __forceinline__ void sh_pair_dots(const ShPairs &P, L &lds, const flo
       v1[qp] = c == 0 ? pc[qp] * sb : __builtin_elementwise_fma(pc[qp], sb, v1[qp]);
     }
   }
+}
+__device__ __forceinline__ void sh_pair_dots(const ShPairs &P, const float4 &g0, const float4 &g1, f2v (&v0)[4], f2v (&v1)[4]) {
+  sh_pair_dots_from([&](int c, f2v (&pc)[4]) {
+#pragma unroll
+    for (int qp = 0; qp < 4; ++qp) pc[qp] = P.p[c][qp];
+  }, g0, g1, v0, v1);
+}
+template <typename L>
+__device__ __forceinline__ void sh_pair_dots_lds(L &lds, const float4 &g0, const float4 &g1, f2v (&v0)[4], f2v (&v1)[4]) {
+  sh_pair_dots_from([&](int c, f2v (&pc)[4]) {
+    const float4 lo = lds[2 * c][threadIdx.x], hi = lds[2 * c + 1][threadIdx.x];
+    pc[0] = f2v{lo.x, lo.y}; pc[1] = f2v{lo.z, lo.w}; pc[2] = f2v{hi.x, hi.y}; pc[3] = f2v{hi.z, hi.w};
+  }, g0, g1, v0, v1);
 }
 // reduce-scatter of the 16 partials over the row's 16 lanes; lane 8 e + h returns the total of (its slot-0 edge, head h).
 // Slot k of lane l holds head k ^ (l & 7) (sh_pairs_load's permutation) and lanes >= 8 hold the pair's edges swapped.
@@ -617,9 +615,9 @@ __device__ __forceinline__ void sh_block(const int32_t *__restrict__ col, int64_
 }
 
 // forward: A[i,h,:] = sum_p keep_p/(1-pd) exp(s_p - m) x[col[p],:] / (den + 1e-16), den[i,h] = sum_p exp(s_p - m)
-// PF (round 5, with gat_sh_bwd_src's ZLDS form: option gat_sh_zlds): the NEXT step's column ids are requested before this step's
-// gathers — a step then waits for one memory round trip instead of two dependent ones
-template <bool DROP, bool PF = false>
+// The NEXT step's column ids are requested before this step's gathers (round 5) — a step then waits for one memory round
+// trip instead of two dependent ones
+template <bool DROP>
 __global__ __launch_bounds__(kBlock) void gat_sh_fwd_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, const int32_t *__restrict__ row_order,
     const int32_t *__restrict__ long_rows, const int64_t *__restrict__ chunk_ptr, const float *__restrict__ el,
@@ -635,14 +633,10 @@ __global__ __launch_bounds__(kBlock) void gat_sh_fwd_kernel(
   for (int q = 0; q < kShH; ++q) acc[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   float den = 0.0f;
   ShBlock b, nb;
-  if (PF && (it.beg & ~(int64_t)3) < it.end) sh_block(col, it.beg & ~(int64_t)3, it.beg, it.end, nb);
+  if ((it.beg & ~(int64_t)3) < it.end) sh_block(col, it.beg & ~(int64_t)3, it.beg, it.end, nb);
   for (int64_t p0 = it.beg & ~(int64_t)3; p0 < it.end; p0 += 4) {
-    if (PF) {
-      b = nb;
-      if (p0 + 4 < it.end) sh_block(col, p0 + 4, it.beg, it.end, nb);
-    } else {
-      sh_block(col, p0, it.beg, it.end, b);
-    }
+    b = nb;
+    if (p0 + 4 < it.end) sh_block(col, p0 + 4, it.beg, it.end, nb);
     float4 xv[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) xv[u] = *reinterpret_cast<const float4 *>(x + (int64_t)b.c[u] * F + kk);   // (idle channel lanes re-read columns 0-3: kk = 0; their sums are never stored)
@@ -709,11 +703,10 @@ __global__ __launch_bounds__(kBlock) void gat_sh_fwd_final_kernel(const int32_t 
   }
 }
 
-// destination walk of the backward: ger[i,h] = sum_p de_p with <G_i[h,:], x_j> from the row's G in registers
-// GLDS (option gat_sh_glds, A/B): the row's G (8 heads x this lane's 4 columns, dot-product operands only) in per-lane LDS slots
-// like gat_sh_bwd_src's z_j
-// PK (round 6, option gat_sh_pk): the dots packed over head pairs and reduced without selects (sh_pair_dots / sh_pair_reduce)
-template <bool DROP, bool PF = false, bool GLDS = false, bool PK = false>
+// destination walk of the backward: ger[i,h] = sum_p de_p with <G_i[h,:], x_j> from the row's G in registers as head pairs:
+// the dots packed over head pairs and reduced without selects (sh_pair_dots / sh_pair_reduce, round 6), the next step's ids
+// requested ahead like the forward's
+template <bool DROP>
 __global__ __launch_bounds__(kBlock) void gat_sh_bwd_dst_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, const int32_t *__restrict__ row_order,
     const int32_t *__restrict__ long_rows, const int64_t *__restrict__ chunk_ptr, const float *__restrict__ el,
@@ -721,19 +714,8 @@ __global__ __launch_bounds__(kBlock) void gat_sh_bwd_dst_kernel(
     float *__restrict__ ger, float *__restrict__ pger, const int64_t *__restrict__ rng, const ShDims d) {
   GGL_SH_PROLOGUE();
   const int64_t F = d.F;
-  __shared__ float4 gs_lds[GLDS ? kShH : 1][GLDS ? kBlock : 1];
-  float4 g[(GLDS || PK) ? 1 : kShH];
   ShPairs GP;
-  if (PK) {
-    sh_pairs_load(GP, G + it.row * kShH * F + kk, F, li, act);
-    if constexpr (GLDS) sh_pairs_to_lds(GP, gs_lds);
-  } else {
-#pragma unroll
-    for (int q = 0; q < kShH; ++q) {
-      const float4 gq = act ? *reinterpret_cast<const float4 *>(G + (it.row * kShH + q) * F + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
-      if (GLDS) gs_lds[q][threadIdx.x] = gq; else g[(GLDS || PK) ? 0 : q] = gq;
-    }
-  }
+  sh_pairs_load(GP, G + it.row * kShH * F + kk, F, li, act);
   const float4 st = *reinterpret_cast<const float4 *>(stats + (it.row * kShH + h) * 4);  // {er, m, rinv, dot}
   const uint64_t seed = DROP ? (uint64_t)rng[0] : 0, offset = DROP ? (uint64_t)rng[1] : 0;
   // g_er[i,h] = sum_p l'_p alpha_p (da_p - s_i) is a sum of up to 10^5 cancelling terms; with the stored s_i = <G_i, A_i> and f32
@@ -743,14 +725,10 @@ __global__ __launch_bounds__(kBlock) void gat_sh_bwd_dst_kernel(
   // sum 1.5e-2 of a row's scale apart on 10^5-edge rows (profiles/r6_gat_fullsize_forms.txt).  stats.w is no longer read here.
   double sA = 0.0, sB = 0.0, sS = 0.0, sW = 0.0;
   ShBlock b, nb;
-  if (PF && (it.beg & ~(int64_t)3) < it.end) sh_block(col, it.beg & ~(int64_t)3, it.beg, it.end, nb);
+  if ((it.beg & ~(int64_t)3) < it.end) sh_block(col, it.beg & ~(int64_t)3, it.beg, it.end, nb);
   for (int64_t p0 = it.beg & ~(int64_t)3; p0 < it.end; p0 += 4) {
-    if (PF) {
-      b = nb;
-      if (p0 + 4 < it.end) sh_block(col, p0 + 4, it.beg, it.end, nb);
-    } else {
-      sh_block(col, p0, it.beg, it.end, b);
-    }
+    b = nb;
+    if (p0 + 4 < it.end) sh_block(col, p0 + 4, it.beg, it.end, nb);
     float4 xv[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) xv[u] = *reinterpret_cast<const float4 *>(x + (int64_t)b.c[u] * F + kk);   // (idle channel lanes re-read columns 0-3: kk = 0; their sums are never stored)
@@ -761,22 +739,9 @@ __global__ __launch_bounds__(kBlock) void gat_sh_bwd_dst_kernel(
     if (DROP) rw = drop_words4(p0 >> 2, kShH, h, offset, seed);
 #pragma unroll
     for (int pr = 0; pr < 2; ++pr) {  // pair of edges (2 pr, 2 pr + 1): 16 dots -> one per weight lane
-      float da;
-      if (GLDS) asm volatile("" ::: "memory");   // (re-read every step: hoisted, the slots would be registers again)
-      if (PK) {
-        f2v v0[4], v1[4];
-        sh_pair_dots<GLDS>(GP, gs_lds, sel4(e != 0, xv[2 * pr + 1], xv[2 * pr]), sel4(e != 0, xv[2 * pr], xv[2 * pr + 1]), v0, v1);
-        da = sh_pair_reduce(v0, v1);
-      } else {
-        float v[16];
-#pragma unroll
-        for (int q = 0; q < kShH; ++q) {
-          const float4 gq = GLDS ? gs_lds[q][threadIdx.x] : g[(GLDS || PK) ? 0 : q];
-          v[q] = dot4(gq, xv[2 * pr]);
-          v[8 + q] = dot4(gq, xv[2 * pr + 1]);
-        }
-        da = reduce_scatter16(v, li);
-      }
+      f2v v0[4], v1[4];
+      sh_pair_dots(GP, sel4(e != 0, xv[2 * pr + 1], xv[2 * pr]), sel4(e != 0, xv[2 * pr], xv[2 * pr + 1]), v0, v1);
+      float da = sh_pair_reduce(v0, v1);
       const float raw = (pr ? s1 : s0) + st.x;
       const float al = fexp(lrelu(raw, d.slope) - st.y) * st.z;
       if (DROP) da = (pick_word(rw, e + 2 * pr) >= d.drop_thresh) ? da * d.drop_scale : 0.0f;
@@ -801,15 +766,12 @@ __global__ __launch_bounds__(kBlock) void gat_sh_bwd_dst_kernel(
 
 // source walk of the backward (transposed plan): T[j,h,:] = sum_q alpha_q keep_q/(1-pd) gy[i_q,:] and
 // gel[j,h] = sum_q de_q, with <dA_ih, x_j> = <gy_i, z_jh>, z_j = the row's own transformed features (registers)
-// WAVES: wavefronts per SIMD the register allocator is asked to leave room for (1 = no request).  With dropout the kernel
-// needs 140 registers = 3 wavefronts per SIMD (without: 127 = 4); asked for 4 it fits 128 with 10 spilled values (44 bytes of
-// scratch).  Option `gat_sh_waves` (A/B, round 5): profiles/r5_gat_sh_waves.txt.
-// ZLDS (round 5, A/B: option gat_sh_zlds): the row's own transformed features z_j (8 heads x this lane's 4 columns = 32
-// registers that only feed the dot products) live in LDS instead — each lane reads back exactly the slot it wrote, so no barrier
-// is involved: LDS as a per-lane register file.  140 -> ~110 registers = 4 wavefronts per SIMD without spills; costs 16
-// ds_read_b128 per 4-edge step (the LDS pipe is otherwise idle here).
-template <bool DROP, int WAVES = 1, bool ZLDS = false, bool PK = false>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES, 8))) void gat_sh_bwd_src_kernel(
+// The row's own transformed features z_j (8 heads x this lane's 4 columns = 32 registers that only feed the dot products) live in
+// LDS as head pairs (round 5) — each lane reads back exactly the slot it wrote, so no barrier is involved: LDS as a per-lane
+// register file, 16 ds_read_b128 per 4-edge step (the LDS pipe is otherwise idle here).  The dots are packed over head pairs
+// (round 6, sh_pair_dots_lds / sh_pair_reduce): 125-128 registers = 4 wavefronts per SIMD without spills.
+template <bool DROP>
+__global__ __launch_bounds__(kBlock) void gat_sh_bwd_src_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col /* colT */, const int32_t *__restrict__ posT,
     const int32_t *__restrict__ row_order, const int32_t *__restrict__ long_rows,
     const int64_t *__restrict__ chunk_ptr, const float *__restrict__ el, const float *__restrict__ z,
@@ -817,53 +779,40 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES, 8
     float *__restrict__ pacc, float *__restrict__ pgel, const int64_t *__restrict__ rng, const ShDims d) {
   GGL_SH_PROLOGUE();
   const int64_t F = d.F;  // here: padded class width of gy / z rows
-  __shared__ float4 zs[ZLDS ? kShH : 1][ZLDS ? kBlock : 1];
-  float4 zr[(ZLDS || PK) ? 1 : kShH], acc[kShH];
-  ShPairs ZP;
-  if (PK) {
+  __shared__ float4 zs[kShH][kBlock];
+  float4 acc[kShH];
+  {
+    ShPairs ZP;
     sh_pairs_load(ZP, z + it.row * kShH * F + kk, F, li, act);
-    if constexpr (ZLDS) sh_pairs_to_lds(ZP, zs);
+    sh_pairs_to_lds(ZP, zs);
   }
 #pragma unroll
-  for (int q = 0; q < kShH; ++q) {
-    if (!PK) {
-      const float4 zq = act ? *reinterpret_cast<const float4 *>(z + (it.row * kShH + q) * F + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
-      if (ZLDS) zs[q][threadIdx.x] = zq; else zr[(ZLDS || PK) ? 0 : q] = zq;
-    }
-    acc[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  }
+  for (int q = 0; q < kShH; ++q) acc[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   const float el_j = el[it.row * kShH + h];
   const uint64_t seed = DROP ? (uint64_t)rng[0] : 0, offset = DROP ? (uint64_t)rng[1] : 0;
   double gl = 0.0;   // (round 6: the row's sum of signed logit-gradient terms in double, like the destination walk's)
-  // (ZLDS: the registers it frees also pay for the NEXT step's ids — requested before this step's gathers, so that a step
+  // (the registers the LDS slots free also pay for the NEXT step's ids — requested before this step's gathers, so that a step
   //  waits for one memory round trip, its gathers', instead of two dependent ones)
-  ShBlock b, fp, nb, nfp;  // fp: the block's FORWARD positions (dropout), fetched beside the column ids, not behind them
-  // (PK: a weight lane needs the forward positions of ITS two edges only, p0 + e and p0 + 2 + e: two dwords instead of the
-  //  block's four — 4 registers that keep the dropout form at 128 = 4 wavefronts per SIMD)
+  ShBlock b, nb;
+  // the FORWARD positions (dropout: the keep bit lives there), fetched beside the column ids, not behind them.  A weight lane
+  // needs those of ITS two edges only, p0 + e and p0 + 2 + e: two dwords instead of the block's four — 4 registers that keep
+  // the dropout form at 128 = 4 wavefronts per SIMD
   int32_t fq2[2] = {0, 0}, nfq2[2] = {0, 0};
   auto own_pos = [&](int64_t p0, int32_t (&o)[2]) {
     const int64_t a = p0 + e, c = p0 + 2 + e;
     o[0] = (a >= it.beg && a < it.end) ? posT[a] : 0;
     o[1] = (c >= it.beg && c < it.end) ? posT[c] : 0;
   };
-  if (ZLDS && (it.beg & ~(int64_t)3) < it.end) {
+  if ((it.beg & ~(int64_t)3) < it.end) {
     sh_block(col, it.beg & ~(int64_t)3, it.beg, it.end, nb);
-    if (DROP && !PK) sh_block(posT, it.beg & ~(int64_t)3, it.beg, it.end, nfp);
-    if (DROP && PK) own_pos(it.beg & ~(int64_t)3, nfq2);
+    if (DROP) own_pos(it.beg & ~(int64_t)3, nfq2);
   }
   for (int64_t p0 = it.beg & ~(int64_t)3; p0 < it.end; p0 += 4) {
-    if (ZLDS) {
-      b = nb;
-      if (DROP && !PK) fp = nfp;
-      if (DROP && PK) { fq2[0] = nfq2[0]; fq2[1] = nfq2[1]; }
-      if (p0 + 4 < it.end) {
-        sh_block(col, p0 + 4, it.beg, it.end, nb);
-        if (DROP && !PK) sh_block(posT, p0 + 4, it.beg, it.end, nfp);
-        if (DROP && PK) own_pos(p0 + 4, nfq2);
-      }
-    } else {
-      sh_block(col, p0, it.beg, it.end, b);
-      if (DROP) sh_block(posT, p0, it.beg, it.end, fp);
+    b = nb;
+    if (DROP) { fq2[0] = nfq2[0]; fq2[1] = nfq2[1]; }
+    if (p0 + 4 < it.end) {
+      sh_block(col, p0 + 4, it.beg, it.end, nb);
+      if (DROP) own_pos(p0 + 4, nfq2);
     }
     float4 gv[4];
 #pragma unroll
@@ -873,149 +822,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WAVES, 8
     const float4 st0 = *reinterpret_cast<const float4 *>(stats + ((int64_t)cA * kShH + h) * 4);
     const float4 st1 = *reinterpret_cast<const float4 *>(stats + ((int64_t)cB * kShH + h) * 4);
     float wk[2];
-    if (ZLDS) asm volatile("" ::: "memory");   // (the z slots are re-read every step: hoisted out of the loop they would be the 32 registers again)
-#pragma unroll
-    for (int pr = 0; pr < 2; ++pr) {
-      float da;
-      if (PK) {
-        f2v v0[4], v1[4];
-        sh_pair_dots<ZLDS>(ZP, zs, sel4(e != 0, gv[2 * pr + 1], gv[2 * pr]), sel4(e != 0, gv[2 * pr], gv[2 * pr + 1]), v0, v1);
-        if (ZLDS) asm volatile("" ::: "memory");
-        da = sh_pair_reduce(v0, v1);
-      } else {
-        float v[16];
-#pragma unroll
-        for (int q = 0; q < kShH; ++q) {
-          const float4 zq = ZLDS ? zs[q][threadIdx.x] : zr[(ZLDS || PK) ? 0 : q];
-          v[q] = dot4(zq, gv[2 * pr]);
-          v[8 + q] = dot4(zq, gv[2 * pr + 1]);
-        }
-        if (ZLDS) asm volatile("" ::: "memory");
-        da = reduce_scatter16(v, li);
-      }
-      const float4 st = pr ? st1 : st0;
-      const bool ok = pr ? okB : okA;
-      const float raw = el_j + st.x;
-      const float al = fexp(lrelu(raw, d.slope) - st.y) * st.z;
-      float alk = al;
-      if (DROP) {  // the keep bit lives at the FORWARD position of the edge
-        const int32_t fq = (PK && ZLDS) ? fq2[pr] : (pr ? (e ? fp.c[3] : fp.c[2]) : (e ? fp.c[1] : fp.c[0]));
-        const bool keep = ok && drop_word((int64_t)fq, kShH, h, offset, seed) >= d.drop_thresh;
-        alk = keep ? al * d.drop_scale : 0.0f;
-        da = keep ? da * d.drop_scale : 0.0f;
-      }
-      const float ds = al * (da - st.w);
-      const float dv = raw > 0.0f ? ds : ds * d.slope;
-      gl += (double)(ok ? dv : 0.0f);
-      wk[pr] = ok ? alk : 0.0f;
-    }
-    sh_accumulate<0>(wk[0], gv[0], acc);
-    sh_accumulate<1>(wk[0], gv[1], acc);
-    sh_accumulate<0>(wk[1], gv[2], acc);
-    sh_accumulate<1>(wk[1], gv[3], acc);
-  }
-  gl += row_ror8_f64(gl);
-  if (it.is_chunk) {
-    if (act) {
-#pragma unroll
-      for (int q = 0; q < kShH; ++q) *reinterpret_cast<float4 *>(pacc + (it.cid * kShH + q) * F + kk) = acc[q];
-    }
-    if (e == 0) pgel[it.cid * kShH + h] = (float)gl;
-    return;
-  }
-  if (act) {
-#pragma unroll
-    for (int q = 0; q < kShH; ++q) *reinterpret_cast<float4 *>(T + (it.row * kShH + q) * F + kk) = acc[q];
-  }
-  if (e == 0) gel[it.row * kShH + h] = (float)gl;
-}
-
-// PIPE (round 6, option gat_sh_pipe, A/B): the source walk above with its GATHERS software-pipelined — the gy rows and the stats panels of
-// step i + 1 are requested before step i's dots (their ids two steps ahead), so a wavefront's own arithmetic hides its own memory round trip
-// instead of relying on the 2-3 other wavefronts of the SIMD; costs ~24 more registers (the in-flight step's rows).  Packed pair dots, z_j pairs
-// in LDS slots (the PK + ZLDS form); same arithmetic in the same order: same bits.
-template <bool DROP>
-__global__ __launch_bounds__(kBlock) void gat_sh_bwd_src_pipe_kernel(
-    const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col /* colT */, const int32_t *__restrict__ posT,
-    const int32_t *__restrict__ row_order, const int32_t *__restrict__ long_rows,
-    const int64_t *__restrict__ chunk_ptr, const float *__restrict__ el, const float *__restrict__ z,
-    const float *__restrict__ gy, const float *__restrict__ stats, float *__restrict__ T, float *__restrict__ gel,
-    float *__restrict__ pacc, float *__restrict__ pgel, const int64_t *__restrict__ rng, const ShDims d) {
-  GGL_SH_PROLOGUE();
-  const int64_t F = d.F;
-  __shared__ float4 zs[kShH][kBlock];
-  float4 acc[kShH];
-  ShPairs ZP;
-  sh_pairs_load(ZP, z + it.row * kShH * F + kk, F, li, act);
-  sh_pairs_to_lds(ZP, zs);
-#pragma unroll
-  for (int q = 0; q < kShH; ++q) acc[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  const float el_j = el[it.row * kShH + h];
-  const uint64_t seed = DROP ? (uint64_t)rng[0] : 0, offset = DROP ? (uint64_t)rng[1] : 0;
-  double gl = 0.0;
-  const int64_t pfirst = it.beg & ~(int64_t)3;
-  if (pfirst >= it.end) {   // an empty row: zeros
-    if (!it.is_chunk) {
-      if (act) {
-#pragma unroll
-        for (int q = 0; q < kShH; ++q) *reinterpret_cast<float4 *>(T + (it.row * kShH + q) * F + kk) = acc[q];
-      }
-      if (e == 0) gel[it.row * kShH + h] = 0.0f;
-    } else {
-      if (act) {
-#pragma unroll
-        for (int q = 0; q < kShH; ++q) *reinterpret_cast<float4 *>(pacc + (it.cid * kShH + q) * F + kk) = acc[q];
-      }
-      if (e == 0) pgel[it.cid * kShH + h] = 0.0f;
-    }
-    return;
-  }
-  auto own_pos = [&](int64_t p0, int32_t (&o)[2]) {
-    const int64_t a = p0 + e, c = p0 + 2 + e;
-    o[0] = (a >= it.beg && a < it.end) ? posT[a] : 0;
-    o[1] = (c >= it.beg && c < it.end) ? posT[c] : 0;
-  };
-  // in flight: the rows / stats of the step about to be computed (N = "next"), and the ids of the step after it (nb)
-  ShBlock bN, nb;
-  int32_t fqN[2] = {0, 0}, nfq[2] = {0, 0};
-  float4 gvN[4], st0N, st1N;
-  auto request = [&](const ShBlock &b) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) gvN[u] = *reinterpret_cast<const float4 *>(gy + (int64_t)b.c[u] * F + kk);
-    const int32_t cA = e ? b.c[1] : b.c[0], cB = e ? b.c[3] : b.c[2];
-    st0N = *reinterpret_cast<const float4 *>(stats + ((int64_t)cA * kShH + h) * 4);
-    st1N = *reinterpret_cast<const float4 *>(stats + ((int64_t)cB * kShH + h) * 4);
-  };
-  sh_block(col, pfirst, it.beg, it.end, bN);
-  if (DROP) own_pos(pfirst, fqN);
-  request(bN);
-  if (pfirst + 4 < it.end) {
-    sh_block(col, pfirst + 4, it.beg, it.end, nb);
-    if (DROP) own_pos(pfirst + 4, nfq);
-  }
-  for (int64_t p0 = pfirst; p0 < it.end; p0 += 4) {
-    // this step's operands leave the in-flight set ...
-    const ShBlock b = bN;
-    const int32_t fq2[2] = {fqN[0], fqN[1]};
-    float4 gv[4] = {gvN[0], gvN[1], gvN[2], gvN[3]};
-    const float4 st0 = st0N, st1 = st1N;
-    // ... and the next step's are requested before this step's arithmetic
-    if (p0 + 4 < it.end) {
-      bN = nb;
-      if (DROP) { fqN[0] = nfq[0]; fqN[1] = nfq[1]; }
-      request(bN);
-      if (p0 + 8 < it.end) {
-        sh_block(col, p0 + 8, it.beg, it.end, nb);
-        if (DROP) own_pos(p0 + 8, nfq);
-      }
-    }
-    const bool okA = e ? b.ok[1] : b.ok[0], okB = e ? b.ok[3] : b.ok[2];
-    float wk[2];
-    asm volatile("" ::: "memory");
+    asm volatile("" ::: "memory");   // (the z slots are re-read every step: hoisted out of the loop they would be the 32 registers again)
 #pragma unroll
     for (int pr = 0; pr < 2; ++pr) {
       f2v v0[4], v1[4];
-      sh_pair_dots<true>(ZP, zs, sel4(e != 0, gv[2 * pr + 1], gv[2 * pr]), sel4(e != 0, gv[2 * pr], gv[2 * pr + 1]), v0, v1);
+      sh_pair_dots_lds(zs, sel4(e != 0, gv[2 * pr + 1], gv[2 * pr]), sel4(e != 0, gv[2 * pr], gv[2 * pr + 1]), v0, v1);
       asm volatile("" ::: "memory");
       float da = sh_pair_reduce(v0, v1);
       const float4 st = pr ? st1 : st0;
@@ -1023,7 +834,7 @@ __global__ __launch_bounds__(kBlock) void gat_sh_bwd_src_pipe_kernel(
       const float raw = el_j + st.x;
       const float al = fexp(lrelu(raw, d.slope) - st.y) * st.z;
       float alk = al;
-      if (DROP) {
+      if (DROP) {  // the keep bit lives at the FORWARD position of the edge
         const bool keep = ok && drop_word((int64_t)fq2[pr], kShH, h, offset, seed) >= d.drop_thresh;
         alk = keep ? al * d.drop_scale : 0.0f;
         da = keep ? da * d.drop_scale : 0.0f;
@@ -1262,15 +1073,8 @@ extern "C" int ggl_gat_sh_fwd(const ggl_segplan_t *plan, const int32_t *col, con
                (const float *)pmax, rowmax, plan->n_long);
     GGL_LAUNCH_CHECK();
   }
-  const bool pf = options().gat_sh_prefetch != 0;
-  if (d.drop_thresh && pf)
-    GGL_LAUNCH((gat_sh_fwd_kernel<true, true>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows, plan->chunk_ptr,
-               el, er, (const float *)rowmax, x, A, den, pacc, pden, (const int64_t *)rng_state, d);
-  else if (d.drop_thresh)
+  if (d.drop_thresh)
     GGL_LAUNCH((gat_sh_fwd_kernel<true>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows, plan->chunk_ptr,
-               el, er, (const float *)rowmax, x, A, den, pacc, pden, (const int64_t *)rng_state, d);
-  else if (pf)
-    GGL_LAUNCH((gat_sh_fwd_kernel<false, true>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows, plan->chunk_ptr,
                el, er, (const float *)rowmax, x, A, den, pacc, pden, (const int64_t *)rng_state, d);
   else
     GGL_LAUNCH((gat_sh_fwd_kernel<false>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows, plan->chunk_ptr,
@@ -1347,29 +1151,8 @@ extern "C" int ggl_gat_sh_bwd(const ggl_segplan_t *plan, const int32_t *col, con
     const int64_t grid = ceil_div((d.n_chunks + d.N) * 16, (int64_t)kBlock);
     GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "too many rows for one launch");
     const int32_t *order = options().row_order ? plan->row_order : nullptr;
-    const bool pf = options().gat_sh_prefetch != 0;
-    if (pf && options().gat_sh_pk != 0 && options().gat_sh_glds == 0) {   // round 6 default: packed pair dots, select-free reduce
-      if (d.drop_thresh)
-        GGL_LAUNCH((gat_sh_bwd_dst_kernel<true, true, false, true>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows,
-                   plan->chunk_ptr, el, x, G, stats, ger, pger, rng_used, d);
-      else
-        GGL_LAUNCH((gat_sh_bwd_dst_kernel<false, true, false, true>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows,
-                   plan->chunk_ptr, el, x, G, stats, ger, pger, rng_used, d);
-    } else if (pf && options().gat_sh_glds != 0) {
-      if (d.drop_thresh)
-        GGL_LAUNCH((gat_sh_bwd_dst_kernel<true, true, true>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows,
-                   plan->chunk_ptr, el, x, G, stats, ger, pger, rng_used, d);
-      else
-        GGL_LAUNCH((gat_sh_bwd_dst_kernel<false, true, true>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows,
-                   plan->chunk_ptr, el, x, G, stats, ger, pger, rng_used, d);
-    } else if (d.drop_thresh && pf)
-      GGL_LAUNCH((gat_sh_bwd_dst_kernel<true, true>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows,
-                 plan->chunk_ptr, el, x, G, stats, ger, pger, rng_used, d);
-    else if (d.drop_thresh)
+    if (d.drop_thresh)
       GGL_LAUNCH((gat_sh_bwd_dst_kernel<true>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows,
-                 plan->chunk_ptr, el, x, G, stats, ger, pger, rng_used, d);
-    else if (pf)
-      GGL_LAUNCH((gat_sh_bwd_dst_kernel<false, true>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows,
                  plan->chunk_ptr, el, x, G, stats, ger, pger, rng_used, d);
     else
       GGL_LAUNCH((gat_sh_bwd_dst_kernel<false>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows,
@@ -1395,41 +1178,8 @@ extern "C" int ggl_gat_sh_bwd(const ggl_segplan_t *plan, const int32_t *col, con
     const int64_t grid = ceil_div((d.n_chunks + d.N) * 16, (int64_t)kBlock);
     GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "too many rows for one launch");
     const int32_t *order = options().row_order ? planT->row_order : nullptr;
-    const bool pk = options().gat_sh_pk != 0 && options().gat_sh_zlds != 0;
-    if (options().gat_sh_pk != 0 && options().gat_sh_zlds == 0) {   // A/B: packed pair dots with the row's z_j pairs in REGISTERS (no LDS slots)
-      if (d.drop_thresh)
-        GGL_LAUNCH((gat_sh_bwd_src_kernel<true, 1, false, true>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows,
-                   planT->chunk_ptr, el, z, gy, stats, T, gel, pacc, pgel, rng_used, d);
-      else
-        GGL_LAUNCH((gat_sh_bwd_src_kernel<false, 1, false, true>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows,
-                   planT->chunk_ptr, el, z, gy, stats, T, gel, pacc, pgel, rng_used, d);
-    } else if (pk && options().gat_sh_pipe != 0) {    // A/B: gathers software-pipelined one step ahead
-      if (d.drop_thresh)
-        GGL_LAUNCH((gat_sh_bwd_src_pipe_kernel<true>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows,
-                   planT->chunk_ptr, el, z, gy, stats, T, gel, pacc, pgel, rng_used, d);
-      else
-        GGL_LAUNCH((gat_sh_bwd_src_pipe_kernel<false>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows,
-                   planT->chunk_ptr, el, z, gy, stats, T, gel, pacc, pgel, rng_used, d);
-    } else if (pk && d.drop_thresh && options().gat_sh_waves >= 4)   // (A/B: built for 4 wavefronts per SIMD — 128 registers + 12 spilled values)
-      GGL_LAUNCH((gat_sh_bwd_src_kernel<true, 4, true, true>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows,
-                 planT->chunk_ptr, el, z, gy, stats, T, gel, pacc, pgel, rng_used, d);
-    else if (pk && d.drop_thresh)
-      GGL_LAUNCH((gat_sh_bwd_src_kernel<true, 1, true, true>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows,
-                 planT->chunk_ptr, el, z, gy, stats, T, gel, pacc, pgel, rng_used, d);
-    else if (pk)
-      GGL_LAUNCH((gat_sh_bwd_src_kernel<false, 1, true, true>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows,
-                 planT->chunk_ptr, el, z, gy, stats, T, gel, pacc, pgel, rng_used, d);
-    else if (d.drop_thresh && options().gat_sh_zlds != 0)
-      GGL_LAUNCH((gat_sh_bwd_src_kernel<true, 1, true>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows,
-                 planT->chunk_ptr, el, z, gy, stats, T, gel, pacc, pgel, rng_used, d);
-    else if (d.drop_thresh && options().gat_sh_waves >= 4)
-      GGL_LAUNCH((gat_sh_bwd_src_kernel<true, 4>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows,
-                 planT->chunk_ptr, el, z, gy, stats, T, gel, pacc, pgel, rng_used, d);
-    else if (d.drop_thresh)
+    if (d.drop_thresh)
       GGL_LAUNCH((gat_sh_bwd_src_kernel<true>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows,
-                 planT->chunk_ptr, el, z, gy, stats, T, gel, pacc, pgel, rng_used, d);
-    else if (options().gat_sh_zlds != 0)
-      GGL_LAUNCH((gat_sh_bwd_src_kernel<false, 1, true>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows,
                  planT->chunk_ptr, el, z, gy, stats, T, gel, pacc, pgel, rng_used, d);
     else
       GGL_LAUNCH((gat_sh_bwd_src_kernel<false>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows,

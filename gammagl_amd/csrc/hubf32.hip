@@ -86,7 +86,7 @@ template <int PER> struct HfIds { int32_t row[PER], wi[PER]; };       // source 
 // four columns as one 8-byte load (VEC4) or four 2-byte loads, keeps the raw bits in the stage's registers (no ALU between
 // the gathers: the vmcnt counting below stays what it is) and widens them where it parks them, before the rounded multiply.
 // Tile, consumer and partial are the f32 ones: the same adds in the same order as on x.float().
-template <int MODE, bool VEC4, bool WPC, int PER, int LOG_LPE, bool F64 = false, bool PIPE = true, int X16 = 0>
+template <int MODE, bool VEC4, bool WPC, int PER, int LOG_LPE, bool F64 = false, int X16 = 0>
 __global__ __launch_bounds__(kHfBlock) void hub_rows_f32_kernel(const HubF32Args a) {
   static_assert(!F64 || hub_seg(MODE), "doubles: segment sums only (the SpMMs are f32 in the reference)");
   static_assert(!X16 || (!F64 && !WPC && !hub_seg(MODE) && !hub_heads(MODE)), "16-bit source rows: SpMM-sum / mean only");
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(kHfBlock) void hub_rows_f32_kernel(const HubF32Args
     if (lane < ncol && s < nst) {
       const int cnt = (int)((len - s * kHfStage) < kHfStage ? (len - s * kHfStage) : kHfStage);
       int e = 0;
-      if (PIPE && cnt == kHfStage) {
+      if (cnt == kHfStage) {
         // a full stage, software-pipelined (round 5): the NEXT eight ds_read_b32 are in flight while the current eight
         // dependent adds retire — LDS returns in order, so the wait before a group of adds is lgkmcnt(8), not (0).  The
         // add chain (4 cycles per dependent v_add_f32) is then the only thing on the critical path inside a stage; the
@@ -324,26 +324,19 @@ struct HubSide {
   // join-record sequence of one call must not interleave with another's (fork is shared, the FIFO order is the contract)
   std::mutex mu;
 };
-static HubSide *hub_side(bool capturing, bool high = false) {
-  static HubSide sides[16][4];
+static HubSide *hub_side(bool capturing) {
+  static HubSide sides[16][2];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  HubSide &s = sides[dev][(capturing ? 1 : 0) + (high ? 2 : 0)];
+  HubSide &s = sides[dev][capturing ? 1 : 0];
   static std::mutex create_mu;
   std::lock_guard<std::mutex> g(create_mu);
   if (!s.ok) {
-    // (a high-priority queue for the hub walk was measured and changes nothing: products step 74.99 vs 75.05 ms, bspmm
-    //  16 x 16 forward 17.39 vs 17.56 — profiles/r4_negative_results.txt)
-    // (high: the queue with the device's greatest priority — option hub_priority, for the ONE hub launch of a column-blocked
-    //  aggregate, whose workgroups are handed out over the whole aggregate in competition with the row walks')
-    int least = 0, greatest = 0;
-    bool good = true;
-    if (high) {
-      good = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&
-             hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, greatest) == hipSuccess;
-    } else {
-      good = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess;
-    }
+    // (a queue with the device's greatest priority for the hub walk was measured twice and bought nothing: products step
+    //  74.99 vs 75.05 ms, profiles/r4_negative_results.txt; round 5, big eager launches only: the isolated aggregate 13.75 ->
+    //  13.60 ms, the products step 75.46 vs 75.45 ms, a partitioned step LOSES — dry 8-way share 14.3 -> 16.9 ms,
+    //  profiles/r5_priority_ab.txt.  Removed in ABI 11; last present in 992473a.)
+    bool good = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess;
     good = good && hipEventCreateWithFlags(&s.fork, hipEventDisableTiming) == hipSuccess;
     for (int i = 0; good && i < kHubJoinRing; ++i) good = hipEventCreateWithFlags(&s.join[i], hipEventDisableTiming) == hipSuccess;
     if (!good) {      // nothing half-made stays behind (and the next call starts from scratch)
@@ -372,11 +365,7 @@ int hub_f32_launch(const HubF32Args &a, hipStream_t stream, bool beside, int *fo
   if (a.n_long <= 0 || a.K <= 0) return GGL_OK;
   hipStream_t s = stream;
   const bool capturing = beside && stream_is_capturing(stream);
-  // the greatest-priority queue (option hub_priority, off by default: common.hpp) only for big eager launches: a recorded
-  // arxiv-sized step (0.3 ms aggregates, replayed from a hipGraph) ran 3.1 -> 4.3 ms with it
-  const bool high = beside && options().hub_priority != 0 && !capturing &&
-                    a.avg_long_len * a.n_long >= ((int64_t)1 << 22);
-  HubSide *side = beside ? hub_side(capturing, high) : nullptr;
+  HubSide *side = beside ? hub_side(capturing) : nullptr;
   std::unique_lock<std::mutex> lock;
   int token = 0;
   if (side != nullptr) {
@@ -384,7 +373,7 @@ int hub_f32_launch(const HubF32Args &a, hipStream_t stream, bool beside, int *fo
     GGL_HIP_CHECK(hipEventRecord(side->fork, stream));
     GGL_HIP_CHECK(hipStreamWaitEvent(side->stream, side->fork, 0));
     s = side->stream;
-    token = 1 + side->next + (capturing ? kHubJoinRing : 0) + (high ? 2 * kHubJoinRing : 0);
+    token = 1 + side->next + (capturing ? kHubJoinRing : 0);
     side->next = (side->next + 1) % kHubJoinRing;
   }
   const bool narrow = a.K <= 16;                       // 16-column slabs, 4 lanes per element
@@ -401,8 +390,6 @@ int hub_f32_launch(const HubF32Args &a, hipStream_t stream, bool beside, int *fo
 #define GGL_HF2(M, W, V)                                                                          \
   do {                                                                                             \
     if (narrow) GGL_LAUNCH((hub_rows_f32_kernel<M, V, W, 2, 2>), grid, kHfBlock, s, a);            \
-    else if (heavy && options().hub_pipe == 0)  /* A/B: round 4's consumer (read 8, add 8, no overlap) */ \
-      GGL_LAUNCH((hub_rows_f32_kernel<M, V, W, 4, 4, false, false>), grid, kHfBlock, s, a);        \
     else if (heavy) GGL_LAUNCH((hub_rows_f32_kernel<M, V, W, 4, 4>), grid, kHfBlock, s, a);        \
     else GGL_LAUNCH((hub_rows_f32_kernel<M, V, W, 2, 4>), grid, kHfBlock, s, a);                   \
   } while (0)
@@ -418,9 +405,9 @@ int hub_f32_launch(const HubF32Args &a, hipStream_t stream, bool beside, int *fo
     }
 #define GGL_HF16_3(M, V, X)                                                                                  \
   do {                                                                                                        \
-    if (narrow) GGL_LAUNCH((hub_rows_f32_kernel<M, V, false, 2, 2, false, true, X>), grid, kHfBlock, s, a);   \
-    else if (heavy) GGL_LAUNCH((hub_rows_f32_kernel<M, V, false, 4, 4, false, true, X>), grid, kHfBlock, s, a); \
-    else GGL_LAUNCH((hub_rows_f32_kernel<M, V, false, 2, 4, false, true, X>), grid, kHfBlock, s, a);          \
+    if (narrow) GGL_LAUNCH((hub_rows_f32_kernel<M, V, false, 2, 2, false, X>), grid, kHfBlock, s, a);   \
+    else if (heavy) GGL_LAUNCH((hub_rows_f32_kernel<M, V, false, 4, 4, false, X>), grid, kHfBlock, s, a); \
+    else GGL_LAUNCH((hub_rows_f32_kernel<M, V, false, 2, 4, false, X>), grid, kHfBlock, s, a);          \
   } while (0)
 #define GGL_HF16_2(M, X)                                 \
   do {                                                   \
@@ -475,8 +462,7 @@ int hub_f32_launch(const HubF32Args &a, hipStream_t stream, bool beside, int *fo
 
 int hub_f32_join(hipStream_t stream, int token) {
   if (token <= 0) return GGL_OK;
-  const int which = (token - 1) / kHubJoinRing;          // bit 0: capturing caller, bit 1: high-priority queue
-  HubSide *side = hub_side((which & 1) != 0, (which & 2) != 0);
+  HubSide *side = hub_side((token - 1) / kHubJoinRing != 0);   // (the ring of the capturing callers' side stream)
   GGL_REQUIRE(side != nullptr, GGL_EHIP, "hub side stream is gone");
   GGL_HIP_CHECK(hipStreamWaitEvent(stream, side->join[(token - 1) % kHubJoinRing], 0));
   return GGL_OK;

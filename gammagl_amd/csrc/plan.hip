@@ -9,6 +9,7 @@
 // sync and never use atomics.
 #include "common.hpp"
 
+#include <cctype>
 #include <cstdarg>
 
 #ifndef GGL_EMULATE
@@ -37,41 +38,21 @@ static int64_t env_i64(const char *name, int64_t dflt) {
 
 int64_t max_grid_x() { return options().max_grid_x; }
 
+// "name" -> getenv("GGL_NAME"), or dflt
+static int64_t env_option(const char *name, int64_t dflt) {
+  char env[64] = "GGL_";
+  size_t n = 4;
+  for (; *name && n + 1 < sizeof(env); ++name) env[n++] = (char)toupper((unsigned char)*name);
+  env[n] = 0;
+  return env_i64(env, dflt);
+}
+
 Options &options() {
   static Options o = [] {
     Options t;
-    t.unroll = env_i64("GGL_UNROLL", t.unroll);
-    t.unroll_narrow = env_i64("GGL_UNROLL_NARROW", t.unroll_narrow);
-    t.unroll_narrow_max = env_i64("GGL_UNROLL_NARROW_MAX", t.unroll_narrow_max);
-    t.xcd_swizzle = env_i64("GGL_XCD_SWIZZLE", t.xcd_swizzle);
-    t.force_generic = env_i64("GGL_FORCE_GENERIC", t.force_generic);
-    t.ragged4 = env_i64("GGL_RAGGED4", t.ragged4);
-    t.col_block = env_i64("GGL_COL_BLOCK", t.col_block);
-    t.col_block16 = env_i64("GGL_COL_BLOCK16", t.col_block16);
-    t.col_block_min_edges = env_i64("GGL_COL_BLOCK_MIN_EDGES", t.col_block_min_edges);
-    t.col_block_min_degree = env_i64("GGL_COL_BLOCK_MIN_DEGREE", t.col_block_min_degree);
-    t.row_order = env_i64("GGL_ROW_ORDER", t.row_order);
-    t.max_grid_x = env_i64("GGL_MAX_GRID_X", t.max_grid_x);
-    t.exact_long_rows = env_i64("GGL_EXACT_LONG_ROWS", t.exact_long_rows);
-    t.exact_side_stream = env_i64("GGL_EXACT_SIDE_STREAM", t.exact_side_stream);
-    t.exact_long_max = env_i64("GGL_EXACT_LONG_MAX", t.exact_long_max);
-    t.hub_one_launch = env_i64("GGL_HUB_ONE_LAUNCH", t.hub_one_launch);
-    t.gat_sh_waves = env_i64("GGL_GAT_SH_WAVES", t.gat_sh_waves);
-    t.gat_sh_zlds = env_i64("GGL_GAT_SH_ZLDS", t.gat_sh_zlds);
-    t.gat_sh_pk = env_i64("GGL_GAT_SH_PK", t.gat_sh_pk);
-    t.gat_sh_pipe = env_i64("GGL_GAT_SH_PIPE", t.gat_sh_pipe);
-    t.gat_sh_prefetch = env_i64("GGL_GAT_SH_PREFETCH", t.gat_sh_prefetch);
-    t.gat_sh_glds = env_i64("GGL_GAT_SH_GLDS", t.gat_sh_glds);
-    t.hub_pipe = env_i64("GGL_HUB_PIPE", t.hub_pipe);
-    t.hub_priority = env_i64("GGL_HUB_PRIORITY", t.hub_priority);
-    t.hop_fused_scans = env_i64("GGL_HOP_FUSED_SCANS", t.hop_fused_scans);
-    t.hop_small_scans = env_i64("GGL_HOP_SMALL_SCANS", t.hop_small_scans);
-    t.maxbwd_arg32 = env_i64("GGL_MAXBWD_ARG32", t.maxbwd_arg32);
-    t.maxbwd_mask = env_i64("GGL_MAXBWD_MASK", t.maxbwd_mask);
-    t.maxbwd_mask_kmax = env_i64("GGL_MAXBWD_MASK_KMAX", t.maxbwd_mask_kmax);
-    t.maxbwd_mask_scatter = env_i64("GGL_MAXBWD_MASK_SCATTER", t.maxbwd_mask_scatter);
-    t.maxbwd_mask_wlane = env_i64("GGL_MAXBWD_MASK_WLANE", t.maxbwd_mask_wlane);
-    t.maxbwd_mask_cols = env_i64("GGL_MAXBWD_MASK_COLS", t.maxbwd_mask_cols);
+#define GGL_OPTION_ENV(name, dflt) t.name = env_option(#name, t.name);
+    GGL_OPTIONS(GGL_OPTION_ENV)
+#undef GGL_OPTION_ENV
     return t;
   }();
   return o;
@@ -296,81 +277,29 @@ extern "C" int ggl_device_info(int *cus_host, int *wave_host, char *arch_host, i
 
 extern "C" int ggl_set_option(const char *name, int64_t value) {
   Options &o = options();
-  if (!strcmp(name, "unroll")) o.unroll = value;
-  else if (!strcmp(name, "unroll_narrow")) o.unroll_narrow = value;
-  else if (!strcmp(name, "unroll_narrow_max")) o.unroll_narrow_max = value;
-  else if (!strcmp(name, "xcd_swizzle")) o.xcd_swizzle = value;
-  else if (!strcmp(name, "force_generic")) o.force_generic = value;
-  else if (!strcmp(name, "ragged4")) o.ragged4 = value;
-  else if (!strcmp(name, "ragged_max")) o.ragged_max = value;
-  else if (!strcmp(name, "col_block")) o.col_block = value;
-  else if (!strcmp(name, "col_block16")) o.col_block16 = value;
-  else if (!strcmp(name, "col_block_min_edges")) o.col_block_min_edges = value;
-  else if (!strcmp(name, "col_block_min_degree")) o.col_block_min_degree = value;
-  else if (!strcmp(name, "row_order")) o.row_order = value;
-  else if (!strcmp(name, "max_grid_x")) o.max_grid_x = value > 0 ? value : 1;
-  else if (!strcmp(name, "exact_long_rows")) o.exact_long_rows = value;
-  else if (!strcmp(name, "exact_side_stream")) o.exact_side_stream = value;
-  else if (!strcmp(name, "exact_long_max")) o.exact_long_max = value;
-  else if (!strcmp(name, "hub_one_launch")) o.hub_one_launch = value;
-  else if (!strcmp(name, "gat_sh_waves")) o.gat_sh_waves = value;
-  else if (!strcmp(name, "gat_sh_zlds")) o.gat_sh_zlds = value;
-  else if (!strcmp(name, "gat_sh_pk")) o.gat_sh_pk = value;
-  else if (!strcmp(name, "gat_sh_pipe")) o.gat_sh_pipe = value;
-  else if (!strcmp(name, "gat_sh_prefetch")) o.gat_sh_prefetch = value;
-  else if (!strcmp(name, "gat_sh_glds")) o.gat_sh_glds = value;
-  else if (!strcmp(name, "hub_pipe")) o.hub_pipe = value;
-  else if (!strcmp(name, "hub_priority")) o.hub_priority = value;
-  else if (!strcmp(name, "hop_fused_scans")) o.hop_fused_scans = value;
-  else if (!strcmp(name, "hop_small_scans")) o.hop_small_scans = value;
-  else if (!strcmp(name, "maxbwd_arg32")) o.maxbwd_arg32 = value;
-  else if (!strcmp(name, "maxbwd_mask")) o.maxbwd_mask = value;
-  else if (!strcmp(name, "maxbwd_mask_kmax")) o.maxbwd_mask_kmax = value;
-  else if (!strcmp(name, "maxbwd_mask_scatter")) o.maxbwd_mask_scatter = value;
-  else if (!strcmp(name, "maxbwd_mask_wlane")) o.maxbwd_mask_wlane = value;
-  else if (!strcmp(name, "maxbwd_mask_cols")) o.maxbwd_mask_cols = value;
-  else if (!strcmp(name, "softmax_sublanes")) o.softmax_sublanes = value;
-  else { set_error("unknown option %s", name); return GGL_EINVAL; }
-  return GGL_OK;
+  if (!strcmp(name, "max_grid_x") && value < 1) value = 1;
+#define GGL_OPTION_SET(opt, dflt) if (!strcmp(name, #opt)) { o.opt = value; return GGL_OK; }
+  GGL_OPTIONS(GGL_OPTION_SET)
+#undef GGL_OPTION_SET
+  set_error("unknown option %s", name);
+  return GGL_EINVAL;
 }
 
 extern "C" int64_t ggl_get_option(const char *name) {
   Options &o = options();
-  if (!strcmp(name, "unroll")) return o.unroll;
-  if (!strcmp(name, "unroll_narrow")) return o.unroll_narrow;
-  if (!strcmp(name, "unroll_narrow_max")) return o.unroll_narrow_max;
-  if (!strcmp(name, "xcd_swizzle")) return o.xcd_swizzle;
-  if (!strcmp(name, "force_generic")) return o.force_generic;
-  if (!strcmp(name, "ragged4")) return o.ragged4;
-  if (!strcmp(name, "ragged_max")) return o.ragged_max;
-  if (!strcmp(name, "col_block")) return o.col_block;
-  if (!strcmp(name, "col_block16")) return o.col_block16;
-  if (!strcmp(name, "col_block_min_edges")) return o.col_block_min_edges;
-  if (!strcmp(name, "col_block_min_degree")) return o.col_block_min_degree;
-  if (!strcmp(name, "row_order")) return o.row_order;
-  if (!strcmp(name, "max_grid_x")) return o.max_grid_x;
-  if (!strcmp(name, "exact_long_rows")) return o.exact_long_rows;
-  if (!strcmp(name, "exact_side_stream")) return o.exact_side_stream;
-  if (!strcmp(name, "exact_long_max")) return o.exact_long_max;
-  if (!strcmp(name, "hub_one_launch")) return o.hub_one_launch;
-  if (!strcmp(name, "gat_sh_waves")) return o.gat_sh_waves;
-  if (!strcmp(name, "gat_sh_zlds")) return o.gat_sh_zlds;
-  if (!strcmp(name, "gat_sh_pk")) return o.gat_sh_pk;
-  if (!strcmp(name, "gat_sh_pipe")) return o.gat_sh_pipe;
-  if (!strcmp(name, "gat_sh_prefetch")) return o.gat_sh_prefetch;
-  if (!strcmp(name, "gat_sh_glds")) return o.gat_sh_glds;
-  if (!strcmp(name, "hub_pipe")) return o.hub_pipe;
-  if (!strcmp(name, "hub_priority")) return o.hub_priority;
-  if (!strcmp(name, "hop_fused_scans")) return o.hop_fused_scans;
-  if (!strcmp(name, "hop_small_scans")) return o.hop_small_scans;
-  if (!strcmp(name, "maxbwd_arg32")) return o.maxbwd_arg32;
-  if (!strcmp(name, "maxbwd_mask")) return o.maxbwd_mask;
-  if (!strcmp(name, "maxbwd_mask_kmax")) return o.maxbwd_mask_kmax;
-  if (!strcmp(name, "maxbwd_mask_scatter")) return o.maxbwd_mask_scatter;
-  if (!strcmp(name, "maxbwd_mask_wlane")) return o.maxbwd_mask_wlane;
-  if (!strcmp(name, "maxbwd_mask_cols")) return o.maxbwd_mask_cols;
-  if (!strcmp(name, "softmax_sublanes")) return o.softmax_sublanes;
+#define GGL_OPTION_GET(opt, dflt) if (!strcmp(name, #opt)) return o.opt;
+  GGL_OPTIONS(GGL_OPTION_GET)
+#undef GGL_OPTION_GET
   return -1;
+}
+
+extern "C" const char *ggl_option_name(int i) {
+  static const char *const names[] = {
+#define GGL_OPTION_NAME(opt, dflt) #opt,
+      GGL_OPTIONS(GGL_OPTION_NAME)
+#undef GGL_OPTION_NAME
+  };
+  return (i >= 0 && i < (int)(sizeof(names) / sizeof(names[0]))) ? names[i] : NULL;
 }
 
 // ---- host policy, one copy (see the header) ----------------------------------------------------------------------------
@@ -601,21 +530,6 @@ extern "C" int ggl_plan_long_fill(const int64_t *rowptr, int64_t N, int64_t chun
              (const int64_t *)sl, (const int64_t *)sc, long_rows, chunk_ptr, n_long, totals[1]);
   GGL_LAUNCH_CHECK();
   GGL_HIP_CHECK(hipStreamSynchronize(s));
-  return GGL_OK;
-}
-
-// inv[perm[i]] = i: the inverse of a permutation of [0, n) (GraphPlan.tpos = the inverse of posT: forward sorted position
-// -> transposed sorted position, which ggl_spmm_max_mask scatters an edge's winner bits to)
-__global__ __launch_bounds__(kBlock) void invert_perm_kernel(const int32_t *__restrict__ perm, int64_t n, int32_t *__restrict__ inv) {
-  const int64_t stride = grid_threads();
-  for (int64_t i = thread_id(); i < n; i += stride) inv[perm[i]] = (int32_t)i;
-}
-
-extern "C" int ggl_invert_perm(const int32_t *perm, int64_t n, int32_t *inv, void *stream) {
-  GGL_REQUIRE(n >= 0 && n < ((int64_t)1 << 31) && ((perm && inv) || n == 0), GGL_EINVAL, "bad arguments");
-  if (n == 0) return GGL_OK;
-  GGL_LAUNCH((invert_perm_kernel), grid_for(n), kBlock, as_stream(stream), perm, n, inv);
-  GGL_LAUNCH_CHECK();
   return GGL_OK;
 }
 

@@ -39,8 +39,8 @@ enum Mode {
                        // instantiation — a run-time width switch inside the walk was measured and loses (the backend stops
                        // merging a lane's four witness loads: K = 256 forward + backward 68.0 -> 75.9 ms)
   MODE_MAXBWDM = 8     // MODE_MAXBWD reading ONE BIT per (edge, column) — "this edge's source is the row's witness" — from a
-                       // mask in transposed position order (ggl_spmm_max_mask builds it in destination order, where the
-                       // witness row is wave-uniform): K / 8 bytes per edge beside the 4K-byte gradient row instead of 8K
+                       // mask of per-edge records (ggl_spmm_max_mask builds it in destination order, where the witness row
+                       // is wave-uniform): K / 8 bytes per edge beside the 4K-byte gradient row instead of 8K
 };
 constexpr bool maxbwd_like(int mode) { return mode == MODE_MAXBWD || mode == MODE_MAXBWD32 || mode == MODE_MAXBWDM; }
 constexpr bool spmm_like(int mode) { return mode == MODE_SPMM || mode == MODE_SPMM_EPI; }
@@ -84,7 +84,8 @@ struct ReduceDims {
   int64_t epi_K, epi_col0;
   int64_t add_ld;          // row stride of epi_add
   int64_t mask_words;      // MODE_MAXBWDM: 32-bit words per edge record of the winner mask
-  int64_t mask_col0;       // ... and the first column of this launch inside the full row (column-block launches)
+  int64_t mask_col0;       // ... and the first column of this launch inside the full row: always 0 since ABI 11 (the masked walk's
+                           // column-block launches are gone); the field and its add stay so that the kernel's code is unchanged
 };
 
 template <typename S> struct RPtrs {
@@ -270,8 +271,9 @@ __device__ __forceinline__ void reduce_range(const RPtrs<typename TT<T>::S> &q, 
     } else {
       const int64_t c = (int64_t)q.col[p];
       xrow = c;
-      // the masked max backward looks its bits up by POSITION: its own, or (mask in forward order) the edge's forward
-      // position posT[p] — handed down in the aux_rowptr slot, which only the mean backward uses otherwise
+      // the masked max backward looks its bits up by POSITION: the edge's forward position posT[p] — handed down in the
+      // aux_rowptr slot, which only the mean backward uses otherwise (the hosts always pass it since ABI 11: the `: p` arm,
+      // records in transposed order, is never taken and stays only so that the kernel's code is unchanged)
       who = MODE == MODE_MAXBWDM ? (q.aux_rowptr ? (int64_t) reinterpret_cast<const int32_t *>(q.aux_rowptr)[p] : p) : c;
       wv = 1.0f;
       if (has_w) {
@@ -674,7 +676,7 @@ struct ReduceArgs {  // host-side bundle: everything one logical op needs
   // later); 2 = join the hub walk (if `hub_forked`) + long_final only
   int phase;
   int hub_forked;
-  int64_t mask_words, mask_col0;   // MODE_MAXBWDM
+  int64_t mask_words;   // MODE_MAXBWDM
 };
 
 static inline int pow2_ceil_log2(int64_t v) {
@@ -823,7 +825,7 @@ static int launch_typed(const ReduceArgs &a, hipStream_t stream) {
   d.epi_vec = (d.epi_K % 4 == 0) ? 4 : 1;
   d.add_ld = a.add_ld > 0 ? a.add_ld : a.K;
   d.mask_words = a.mask_words;
-  d.mask_col0 = a.mask_col0;
+  d.mask_col0 = 0;
   const int64_t kv = ceil_div(a.K, VEC);
   d.logL = pow2_ceil_log2(kv < kWave ? kv : kWave);
   if (d.logL > 6) d.logL = 6;
@@ -914,8 +916,7 @@ extern "C" int64_t ggl_spmm_col_blocks_plan(const ggl_segplan_t *plan, int64_t K
 
 template <int OP, int MODE>
 static int launch_f32_cols(const ReduceArgs &a0, hipStream_t stream) {
-  static_assert(OP != OP_MAX && (MODE == MODE_SPMM || MODE == MODE_SPMM_EPI || MODE == MODE_MAXBWDM),
-                "column blocks: sum / mean SpMM and the masked max backward (a sum) only");
+  static_assert(OP != OP_MAX && (MODE == MODE_SPMM || MODE == MODE_SPMM_EPI), "column blocks: sum / mean SpMM only");
   const int64_t bw = col_block_width(a0.E, a0.K, a0.N, a0.xcd_run_rows);
   if (bw <= 0 || a0.N <= 0) return launch_f32<OP, MODE>(a0, stream);
   // The hub rows are walked ONCE per aggregate, over the full width (round 5): one hub launch forked in front of the first
@@ -952,7 +953,6 @@ static int launch_f32_cols(const ReduceArgs &a0, hipStream_t stream) {
     }
     a.epi_K = a0.epi_K > 0 ? a0.epi_K : a0.K;
     a.epi_col0 = a0.epi_col0 + c0;
-    a.mask_col0 = a0.mask_col0 + c0;
     const int rc = launch_f32<OP, MODE>(a, stream);
     if (rc) return rc;
   }
@@ -1456,100 +1456,22 @@ extern "C" int ggl_spmm_max_bwd32(const ggl_segplan_t *planT, const int32_t *col
 // (dst, k).  Walked in source order (one output row per source, adds in ascending edge order: the reference's bits) every
 // edge used to look up its destination's witness row: 8K bytes of int64 beside the 4K-byte gradient row, 3x the sum's
 // traffic and 50 of the 68 ms of a K = 256 forward + backward.  The comparison only needs the witness row where it is
-// WAVE-UNIFORM — in destination order: max_mask_kernel walks the forward plan, a wavefront per row (chunks of hub rows as
+// WAVE-UNIFORM — in destination order: max_mask_seq_kernel walks the forward plan, a wavefront per row (chunks of hub rows as
 // in row_reduce_kernel), a lane per column holding that column's witness in a register; per edge one compare per 64
-// columns IS the ballot (v_cmp writes the 64-bit lane mask), and lanes 0 .. 2 NP - 1 store the edge's K bits at its
-// TRANSPOSED position (tpos: forward position -> transposed position, once per graph).  The transposed walk then streams
-// K / 8 bytes per edge in its own order.  Mask: word (t * ceil(K / 32) + k / 32), bit k % 32.
-template <int NP>
-__global__ __launch_bounds__(kBlock) void max_mask_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-                                                          const int32_t *__restrict__ tpos, const int64_t *__restrict__ argsrc,
-                                                          const int32_t *__restrict__ long_rows,
-                                                          const int64_t *__restrict__ chunk_ptr, uint32_t *__restrict__ mask,
-                                                          int64_t N, int64_t K, int64_t KW, int64_t chunk, int64_t n_long,
-                                                          int64_t n_chunks, int64_t chunk_blocks) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = threadIdx.x >> 6;
-  int64_t row, beg, end;
-  if (block_id() < chunk_blocks) {
-    const int64_t cid = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(block_id() * kWavesPerBlock + wave));
-    if (cid >= n_chunks) return;
-    int64_t lo = 0, hi = n_long - 1;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi + 1) >> 1;
-      if (chunk_ptr[mid] <= cid) lo = mid; else hi = mid - 1;
-    }
-    row = long_rows[lo];
-    beg = rowptr[row] + (cid - chunk_ptr[lo]) * chunk;
-    const int64_t rend = rowptr[row + 1];
-    end = beg + chunk < rend ? beg + chunk : rend;
-  } else {
-    row = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)((block_id() - chunk_blocks) * kWavesPerBlock + wave));
-    if (row >= N) return;
-    beg = rowptr[row];
-    end = rowptr[row + 1];
-    if (end - beg > chunk || end == beg) return;      // long rows: the chunk blocks above
-  }
-#ifdef GGL_EMULATE
-  if (lane != 0) return;
-  for (int64_t p = beg; p < end; ++p) {
-    const int64_t s = col[p], t = tpos[p];
-    for (int64_t wd = 0; wd < KW; ++wd) {
-      uint32_t bits = 0;
-      for (int b = 0; b < 32 && wd * 32 + b < K; ++b)
-        if (argsrc[row * K + wd * 32 + b] == s) bits |= 1u << b;
-      mask[t * KW + wd] = bits;
-    }
-  }
-#else
-  for (int64_t k0 = 0; k0 < K; k0 += (int64_t)kWave * NP) {
-    int32_t a[NP];
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const int64_t k = k0 + (int64_t)kWave * i + lane;
-      a[i] = k < K ? (int32_t)argsrc[row * K + k] : -1;     // (node ids are >= 0: a padding column never matches)
-    }
-    const int64_t w0 = k0 >> 5;
-    const bool stores = lane < 2 * NP && w0 + lane < KW;
-    const int half = lane & 1, plane = lane >> 1;
-    auto emit = [&](int32_t s, int64_t t) {
-      uint64_t b[NP];
-#pragma unroll
-      for (int i = 0; i < NP; ++i) b[i] = __ballot(a[i] == s);
-      uint64_t mine = b[0];
-#pragma unroll
-      for (int i = 1; i < NP; ++i) mine = plane == i ? b[i] : mine;
-      const uint32_t word = half ? (uint32_t)(mine >> 32) : (uint32_t)mine;
-      if (stores) mask[t * KW + w0 + lane] = word;
-    };
-    int64_t p = beg;
-    for (; p + 4 <= end; p += 4) {      // (unrolled by hand: the ballots are convergent operations, `#pragma unroll` declines)
-      int32_t s4[4];
-      int64_t t4[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) { s4[u] = col[p + u]; t4[u] = tpos[p + u]; }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) emit(s4[u], t4[u]);
-    }
-    for (; p < end; ++p) emit(col[p], tpos[p]);
-  }
-#endif
-}
-
-// The same comparison with the mask in FORWARD position order (tpos == NULL; round 5, second form).  Scattering 126 M
-// records of 8-32 bytes to transposed positions cost 6.4-7.8 ms on the products-sized graph whatever their width (every
-// one a partial-line write that ends in DRAM: profiles/r5_probe_hub_and_max_backward.txt) — more than the comparison itself.
-// Here the records of 32 consecutive forward positions are assembled ACROSS the wavefront's lanes — each ballot word is
-// selected into the lane that owns that piece of the 32-record block — and leave as one coalesced store per 32 edges;
-// the transposed walk then reads an edge's record at its forward position posT[p] (a random 8-32 byte READ beside its
-// 256-1024 byte gradient row).  Record = KWp words, KWp = ggl_spmm_max_mask_words(K): ceil(K / 32) rounded up to 1, 2, 4 or
-// a multiple of 8, so that a record is made of whole per-lane pieces.
+// columns IS the ballot (v_cmp writes the 64-bit lane mask).  The records of 32 consecutive forward positions are assembled
+// ACROSS the wavefront's lanes — each ballot word is written into the lane that owns that piece of the 32-record block — and
+// leave as one coalesced store per 32 edges; the transposed walk then reads an edge's record at its forward position posT[p]
+// (a random 8-32 byte READ beside its 256-1024 byte gradient row).  Record = KWp words, KWp = ggl_spmm_max_mask_words(K):
+// ceil(K / 32) rounded up to 1, 2, 4 or a multiple of 8, so that a record is made of whole per-lane pieces.
+// (Round 5's first form scattered every record to its TRANSPOSED position instead: 126 M partial-line writes of 8-32 bytes,
+//  6.4-7.8 ms on the products-sized graph whatever their width — profiles/r5_probe_hub_and_max_backward.txt — 41.7 vs 41.1 ms
+//  forward + backward at K = 256.  Removed in ABI 11; last present in 992473a.)
 // NW = words of a record this pass covers (8: two lanes x 4 words per edge; 4 / 2 / 1: one lane per edge).
 #ifndef GGL_EMULATE
 // lanes `lane` of r0..r3 := the wave-uniform words x0..x3 (v_writelane_b32, lane select in M0 so that the value may sit in
-// any SGPR: before gfx10 the two may not be different SGPRs).  This compiler exposes no writelane builtin; the select form
-// (compare on the lane id + v_cndmask per word + a v_mov per word to get the SGPR into a VGPR) costs 22 VALU instructions
-// per edge at K = 256 where this costs 12.  A/B: option maxbwd_mask_wlane.
+// any SGPR: before gfx10 the two may not be different SGPRs).  This compiler exposes no writelane builtin; a select form
+// (compare on the lane id + v_cndmask per word + a v_mov per word to get the SGPR into a VGPR) cost 22 VALU instructions
+// per edge at K = 256 where this costs 12: 44.4 vs 41.1 ms forward + backward.  Removed in ABI 11; last present in 992473a.
 __device__ __forceinline__ void put_lane4(int lane, uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t &r0, uint32_t &r1,
                                           uint32_t &r2, uint32_t &r3) {
   // M0 is a reserved register the compiler may hold a live value in (LDS-direct, movrel, sendmsg lowering) and that cannot be
@@ -1568,7 +1490,7 @@ __device__ __forceinline__ void put_lane2(int lane, uint32_t x0, uint32_t x1, ui
                : "s"(lane), "s"(x0), "s"(x1));
 }
 #endif
-template <int NP, int NW, bool WL = false>
+template <int NP, int NW>
 __global__ __launch_bounds__(kBlock) void max_mask_seq_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
                                                               const int64_t *__restrict__ argsrc,
                                                               const int32_t *__restrict__ long_rows,
@@ -1626,32 +1548,18 @@ __global__ __launch_bounds__(kBlock) void max_mask_seq_kernel(const int64_t *__r
         uint64_t b[NP];
 #pragma unroll
         for (int i = 0; i < NP; ++i) b[i] = __ballot(a[i] == s);
-        // the lane (NW = 8: the two lanes) that owns this edge's piece of the block takes the ballot words: a compare on the
-        // lane id + one v_cndmask per word (this compiler has no v_writelane builtin; the select is two instructions more)
-        if (WL && NW == 8) {
+        // the lane (NW = 8: the two lanes) that owns this edge's piece of the block takes the ballot words
+        if (NW == 8) {
           const uint64_t bA = b[0], bB = b[NP > 1 ? 1 : 0], bC = b[NP > 2 ? 2 : 0], bD = b[NP > 3 ? 3 : 0];
           put_lane4(2 * e, (uint32_t)bA, (uint32_t)(bA >> 32), (uint32_t)bB, (uint32_t)(bB >> 32), r0, r1, r2, r3);
           put_lane4(2 * e + 1, (uint32_t)bC, (uint32_t)(bC >> 32), (uint32_t)bD, (uint32_t)(bD >> 32), r0, r1, r2, r3);
-        } else if (WL && NW == 4) {
+        } else if (NW == 4) {
           const uint64_t bA = b[0], bB = b[NP > 1 ? 1 : 0];
           put_lane4(e, (uint32_t)bA, (uint32_t)(bA >> 32), (uint32_t)bB, (uint32_t)(bB >> 32), r0, r1, r2, r3);
-        } else if (WL && NW == 2) {
+        } else if (NW == 2) {
           put_lane2(e, (uint32_t)b[0], (uint32_t)(b[0] >> 32), r0, r1);
-        } else if (NW == 8) {
-          const bool m0 = lane == 2 * e, m1 = lane == 2 * e + 1;
-          const uint64_t bA = b[0], bB = b[NP > 1 ? 1 : 0], bC = b[NP > 2 ? 2 : 0], bD = b[NP > 3 ? 3 : 0];
-          r0 = m0 ? (uint32_t)bA : m1 ? (uint32_t)bC : r0;
-          r1 = m0 ? (uint32_t)(bA >> 32) : m1 ? (uint32_t)(bC >> 32) : r1;
-          r2 = m0 ? (uint32_t)bB : m1 ? (uint32_t)bD : r2;
-          r3 = m0 ? (uint32_t)(bB >> 32) : m1 ? (uint32_t)(bD >> 32) : r3;
         } else {
-          const bool m0 = lane == e;
-          r0 = m0 ? (uint32_t)b[0] : r0;
-          if (NW >= 2) r1 = m0 ? (uint32_t)(b[0] >> 32) : r1;
-          if (NW >= 4) {
-            r2 = m0 ? (uint32_t)b[NP > 1 ? 1 : 0] : r2;
-            r3 = m0 ? (uint32_t)(b[NP > 1 ? 1 : 0] >> 32) : r3;
-          }
+          r0 = lane == e ? (uint32_t)b[0] : r0;
         }
       };
       int64_t p = lo;
@@ -1677,15 +1585,13 @@ __global__ __launch_bounds__(kBlock) void max_mask_seq_kernel(const int64_t *__r
 #endif
 }
 
-// words per edge record: transposed-order mask (scatter form) ceil(K / 32); forward-order mask ggl_spmm_max_mask_words(K)
+// words per edge record of the winner mask
 static int64_t mask_words_seq(int64_t K) {
   const int64_t kw = (K + 31) / 32;
   return kw <= 1 ? 1 : kw <= 2 ? 2 : kw <= 4 ? 4 : ((kw + 7) / 8) * 8;
 }
-extern "C" int64_t ggl_spmm_max_mask_words(int64_t K, int forward_order) {
-  return forward_order ? mask_words_seq(K) : (K + 31) / 32;
-}
-extern "C" size_t ggl_spmm_max_mask_bytes(int64_t E, int64_t K) {     // (room for either form)
+extern "C" int64_t ggl_spmm_max_mask_words(int64_t K) { return mask_words_seq(K); }
+extern "C" size_t ggl_spmm_max_mask_bytes(int64_t E, int64_t K) {
   return (size_t)(E > 0 ? E : 0) * (size_t)mask_words_seq(K) * sizeof(uint32_t);
 }
 
@@ -1703,8 +1609,8 @@ extern "C" int ggl_policy_maxbwd_form(int64_t E, int64_t N_dst, int64_t K) {
   return o.maxbwd_arg32 != 0 ? 1 : 0;
 }
 
-extern "C" int ggl_spmm_max_mask(const ggl_segplan_t *planF, const int32_t *colF, const int32_t *tpos,
-                                 const int64_t *argsrc, int64_t K, uint32_t *mask, void *stream) {
+extern "C" int ggl_spmm_max_mask(const ggl_segplan_t *planF, const int32_t *colF, const int64_t *argsrc, int64_t K,
+                                 uint32_t *mask, void *stream) {
   GGL_REQUIRE(planF != nullptr && planF->rowptr != nullptr, GGL_EINVAL, "plan is NULL");
   const int64_t E = planF->E, N = planF->N;
   if (E <= 0 || K <= 0 || N <= 0) return GGL_OK;
@@ -1714,38 +1620,16 @@ extern "C" int ggl_spmm_max_mask(const ggl_segplan_t *planF, const int32_t *colF
   const int64_t chunk_blocks = planF->n_long > 0 ? ceil_div(planF->n_chunks, (int64_t)kWavesPerBlock) : 0;
   const int64_t grid = chunk_blocks + ceil_div(N, (int64_t)kWavesPerBlock);
   hipStream_t st = as_stream(stream);
-  if (tpos == nullptr) {      // forward-order records, assembled across lanes, one coalesced store per 32 edges
-    const int64_t KWp = mask_words_seq(K);
-    GGL_REQUIRE((reinterpret_cast<uintptr_t>(mask) & 15u) == 0, GGL_EINVAL, "mask must be 16-byte aligned");
-#ifdef GGL_EMULATE
-    constexpr bool kCanWl = false;
-#else
-    constexpr bool kCanWl = true;
-#endif
-    const bool wl = kCanWl && options().maxbwd_mask_wlane != 0;
+  const int64_t KWp = mask_words_seq(K);
+  GGL_REQUIRE((reinterpret_cast<uintptr_t>(mask) & 15u) == 0, GGL_EINVAL, "mask must be 16-byte aligned");
 #define GGL_MS(NP, NW)                                                                                              \
-  do {                                                                                                              \
-    if (wl) GGL_LAUNCH((max_mask_seq_kernel<NP, NW, kCanWl>), grid, kBlock, st, planF->rowptr, colF, argsrc, planF->long_rows, \
-                       planF->chunk_ptr, mask, N, K, KWp, planF->chunk, planF->n_long, planF->n_chunks, chunk_blocks);       \
-    else GGL_LAUNCH((max_mask_seq_kernel<NP, NW, false>), grid, kBlock, st, planF->rowptr, colF, argsrc, planF->long_rows,  \
-                    planF->chunk_ptr, mask, N, K, KWp, planF->chunk, planF->n_long, planF->n_chunks, chunk_blocks);          \
-  } while (0)
-    if (K <= 32) GGL_MS(1, 1);
-    else if (K <= 64) GGL_MS(1, 2);
-    else if (K <= 128) GGL_MS(2, 4);
-    else GGL_MS(4, 8);
+  GGL_LAUNCH((max_mask_seq_kernel<NP, NW>), grid, kBlock, st, planF->rowptr, colF, argsrc, planF->long_rows,        \
+             planF->chunk_ptr, mask, N, K, KWp, planF->chunk, planF->n_long, planF->n_chunks, chunk_blocks)
+  if (K <= 32) GGL_MS(1, 1);
+  else if (K <= 64) GGL_MS(1, 2);
+  else if (K <= 128) GGL_MS(2, 4);
+  else GGL_MS(4, 8);
 #undef GGL_MS
-    GGL_LAUNCH_CHECK();
-    return GGL_OK;
-  }
-  const int64_t KW = (K + 31) / 32;
-#define GGL_MM(NP)                                                                                                  \
-  GGL_LAUNCH((max_mask_kernel<NP>), grid, kBlock, st, planF->rowptr, colF, tpos, argsrc, planF->long_rows,         \
-             planF->chunk_ptr, mask, N, K, KW, planF->chunk, planF->n_long, planF->n_chunks, chunk_blocks)
-  if (K <= 64) GGL_MM(1);
-  else if (K <= 128) GGL_MM(2);
-  else GGL_MM(4);
-#undef GGL_MM
   GGL_LAUNCH_CHECK();
   return GGL_OK;
 }
@@ -1756,16 +1640,14 @@ extern "C" int ggl_spmm_max_bwd_mask(const ggl_segplan_t *planT, const int32_t *
   ReduceArgs a{};
   int rc = spmm_common(a, planT, colT, w, w_by_pos, g, K, gx, false);
   if (rc) return rc;
-  GGL_REQUIRE(mask || planT->E * K == 0, GGL_EINVAL, "mask is NULL");
+  GGL_REQUIRE((mask && mask_pos) || planT->E * K == 0, GGL_EINVAL, "mask or mask_pos is NULL");
   a.aux_arg = reinterpret_cast<const int64_t *>(mask);
-  // mask_pos = posT (the forward position of every transposed position): records in forward order; NULL: in transposed order
+  // mask_pos = posT (the forward position of every transposed position): the records are in forward order
   a.aux_rowptr = reinterpret_cast<const int64_t *>(mask_pos);
-  a.mask_words = mask_pos ? mask_words_seq(K) : (K + 31) / 32;
-  // ONE launch over the full width: the 64-column blocks that pay for the plain sum re-read every edge's mask record (and
-  // posT entry) once per block — measured on the products-sized graph at K = 256: the scattered-record walk 16.5 ms in one
-  // launch, 21.5 in four; with forward-order records (a random 32-byte read per edge and block) 32 ms
-  // (profiles/r5_max_backward.txt).  GGL_MAXBWD_MASK_COLS=1 takes the blocks (A/B).
-  if (options().maxbwd_mask_cols != 0) return launch_f32_cols<OP_SUM, MODE_MAXBWDM>(a, as_stream(stream));
+  a.mask_words = mask_words_seq(K);
+  // ONE launch over the full width: the 64-column blocks that pay for the plain sum re-read every edge's mask record (a
+  // random 32-byte read, and its posT entry) once per block — products-sized graph, K = 256, forward + backward: 46.8-54.6
+  // vs 41.1 ms (profiles/r5_max_backward.txt).  The column-blocked walk was removed in ABI 11; last present in 992473a.
   return launch_f32<OP_SUM, MODE_MAXBWDM>(a, as_stream(stream));
 }
 

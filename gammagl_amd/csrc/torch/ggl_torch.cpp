@@ -65,7 +65,7 @@ using torch::autograd::variable_list;
   X(ggl_sample_hop_workspace_bytes) X(ggl_sample_hop)                                                                \
   X(ggl_policy_chunk) X(ggl_policy_spmm_width) X(ggl_policy_head_channels) X(ggl_policy_mean_bwd_prescale)            \
   X(ggl_policy_gradw_sorted) X(ggl_policy_xcd_run_rows) X(ggl_policy_row_order)                                     \
-  X(ggl_spmm_max_mask_bytes) X(ggl_spmm_max_mask) X(ggl_spmm_max_bwd_mask) X(ggl_invert_perm) X(ggl_get_option)      \
+  X(ggl_spmm_max_mask_bytes) X(ggl_spmm_max_mask) X(ggl_spmm_max_bwd_mask) X(ggl_get_option)                         \
   X(ggl_spmm_max_bwd32) X(ggl_policy_maxbwd_form)                                                                   \
   X(ggl_segment_softmax_supported) X(ggl_segment_softmax_partial_bytes) X(ggl_segment_softmax_fwd) X(ggl_segment_softmax_bwd) \
   X(ggl_policy_softmax_sublanes) X(ggl_spmm_sum_x16) X(ggl_spmm_mean_x16) X(ggl_spmm_mean_bwd_x16)                    \
@@ -413,18 +413,6 @@ struct GraphPlan {
     inv.index_put_({pf.to(at::kLong)}, ar);
     posT = inv.index_select(0, pt.to(at::kLong)).contiguous();
   }
-  // forward sorted position -> transposed sorted position (int32 [E]; ops.py GraphPlan.tpos): where ggl_spmm_max_mask
-  // scatters an edge's winner bits for the max backward's transposed walk
-  Tensor tpos;
-  void need_tpos(const Tensor &index) {
-    need_posT(index);
-    std::lock_guard<std::mutex> g(mu);
-    if (tpos.defined()) return;
-    const Api &a = api_for(posT.device());
-    Tensor t = at::empty_like(posT);
-    check(a, a.ggl_invert_perm(posT.data_ptr<int32_t>(), E, t.data_ptr<int32_t>(), stream_of(posT.device())));
-    tpos = t;
-  }
 };
 
 static Cache<GraphPlan> &graph_cache() {
@@ -563,7 +551,7 @@ static Tensor spmm_fwd16(SpOp op, GraphPlan &gp, const SegPlan &p, const Tensor 
 
 static std::pair<Tensor, Tensor> spmm_fwd(SpOp op, GraphPlan &gp, const SegPlan &p, const Tensor &col, const Tensor &w,
                                           const Tensor &x, int64_t n_out, const Tensor &aux = Tensor(),
-                                          const Tensor &tpos = Tensor(), bool out_f32 = false) {
+                                          const Tensor &posT = Tensor(), bool out_f32 = false) {
   if (is_x16(x) && (op == SpOp::Sum || op == SpOp::Mean || op == SpOp::MeanBwd))
     return {spmm_fwd16(op, gp, p, col, w, x, n_out, aux, out_f32), Tensor()};
   const auto dev = x.device();
@@ -608,9 +596,9 @@ static std::pair<Tensor, Tensor> spmm_fwd(SpOp op, GraphPlan &gp, const SegPlan 
       break;
     case SpOp::MaxBwd: {
       // the form is the library's decision (ggl_policy_maxbwd_form: the winner mask only where its E x K/8-byte transient
-      // pays); `tpos` is defined iff the caller found the mask form chosen.  An allocation failure falls back to the int32 copy.
+      // pays); `posT` is defined iff the caller found the mask form chosen.  An allocation failure falls back to the int32 copy.
       Tensor mask;
-      if (tpos.defined()) {
+      if (posT.defined()) {
         try {
           mask = at::empty({static_cast<int64_t>(a.ggl_spmm_max_mask_bytes(p.E, K) / 4) + 4}, x.options().dtype(at::kInt));
         } catch (const c10::Error &) {
@@ -618,15 +606,13 @@ static std::pair<Tensor, Tensor> spmm_fwd(SpOp op, GraphPlan &gp, const SegPlan 
         }
       }
       if (mask.defined()) {
-        // a 1-bit winner mask built in destination order; records in forward order, read at posT[t] (ops.py _spmm_fwd) —
-        // `tpos` here IS posT unless the A/B knob maxbwd_mask_scatter asks for records scattered to transposed positions
-        const bool scatter = a.ggl_get_option("maxbwd_mask_scatter") != 0;
+        // a 1-bit winner mask built in destination order; records in forward order, read at posT[t] (ops.py _spmm_fwd)
         ggl_segplan_t fs = gp.fwd->c(Tensor());
-        check(a, a.ggl_spmm_max_mask(&fs, gp.col.data_ptr<int32_t>(), scatter ? tpos.data_ptr<int32_t>() : nullptr,
-                                     aux.data_ptr<int64_t>(), K, reinterpret_cast<uint32_t *>(mask.data_ptr<int32_t>()), st));
+        check(a, a.ggl_spmm_max_mask(&fs, gp.col.data_ptr<int32_t>(), aux.data_ptr<int64_t>(), K,
+                                     reinterpret_cast<uint32_t *>(mask.data_ptr<int32_t>()), st));
         check(a, a.ggl_spmm_max_bwd_mask(&cs, c, wp, by_pos, xp, reinterpret_cast<const uint32_t *>(mask.data_ptr<int32_t>()),
-                                         scatter ? nullptr : tpos.data_ptr<int32_t>(), K, op_, st));
-      } else if (tpos.defined() || a.ggl_get_option("maxbwd_arg32") != 0) {   // witnesses from a compact int32 copy (one [N, K] pass)
+                                         posT.data_ptr<int32_t>(), K, op_, st));
+      } else if (posT.defined() || a.ggl_get_option("maxbwd_arg32") != 0) {   // witnesses from a compact int32 copy (one [N, K] pass)
         Tensor aux32 = aux.to(at::kInt);
         check(a, a.ggl_spmm_max_bwd32(&cs, c, wp, by_pos, xp, aux32.data_ptr<int32_t>(), K, op_, st));
       } else {
@@ -877,19 +863,14 @@ static Tensor spmm_max_backward_kernel(const Tensor &index, const c10::optional<
   Tensor g = grad.contiguous(), w = opt_dense(weight);
   c10::OptionalDeviceGuard guard(g.device());
   auto gp = bwd_plan(index, g.size(0));
-  Tensor tpos;
+  Tensor posT;
   const int64_t Kw = g.dim() >= 2 ? g.numel() / std::max<int64_t>(g.size(0), 1) : 1;
   // (the inverse-permutation passes and the cached int32[E] only where the mask form is the one chosen for this K)
   if (api_for(g.device()).ggl_policy_maxbwd_form(gp->E, g.size(0), Kw) == 2) {
-    if (api_for(g.device()).ggl_get_option("maxbwd_mask_scatter") != 0) {
-      gp->need_tpos(index.contiguous());
-      tpos = gp->tpos;
-    } else {
-      gp->need_posT(index.contiguous());
-      tpos = gp->posT;
-    }
+    gp->need_posT(index.contiguous());
+    posT = gp->posT;
   }
-  return spmm_fwd(SpOp::MaxBwd, *gp, *gp->bwd, gp->colT, w, g, gp->N_src, arg.contiguous(), tpos).first;
+  return spmm_fwd(SpOp::MaxBwd, *gp, *gp->bwd, gp->colT, w, g, gp->N_src, arg.contiguous(), posT).first;
 }
 static std::tuple<Tensor, Tensor> spmm_max_arg_kernel(const Tensor &i, const c10::optional<Tensor> &w, const Tensor &x) {
   Tensor arg;

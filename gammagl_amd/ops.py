@@ -86,7 +86,7 @@ class SegPlan:
 class GraphPlan:
     """CSR (rows = destination) and, lazily, CSC (rows = source) plans of one edge_index."""
 
-    __slots__ = ("engine", "index", "N_dst", "N_src", "E", "fwd", "col", "_bwd", "_colT", "_posT", "_tpos", "_rowidx", "aux")
+    __slots__ = ("engine", "index", "N_dst", "N_src", "E", "fwd", "col", "_bwd", "_colT", "_posT", "_rowidx", "aux")
 
     def __init__(self, engine, index, n_dst, n_src):
         self.engine = engine
@@ -98,7 +98,7 @@ class GraphPlan:
         self.fwd = engine.seg_plan(index[1], self.N_dst)
         engine._check_range(index[0], self.N_src)
         self.col = engine.gather_i32(index[0], self.fwd.perm)
-        self._bwd = self._colT = self._posT = self._tpos = self._rowidx = None
+        self._bwd = self._colT = self._posT = self._rowidx = None
         self.aux = {}  # graph-constant tensors callers derive from this edge list (e.g. GCN edge norms)
         self._schedule()
 
@@ -133,7 +133,7 @@ class GraphPlan:
         # edge weights arrive in CSR order: the transposed walk reads them through `permute` (a COO-built plan's CSC side
         # carries the original edge id of every position in its own `perm` instead)
         gp._bwd.wperm = gp._posT
-        gp._rowidx = gp._tpos = None
+        gp._rowidx = None
         gp.aux = {}
         gp._schedule()
         return gp
@@ -204,17 +204,6 @@ class GraphPlan:
             inv[pf.long()] = ar
             self._posT = inv[pt.long()].contiguous()
         return self._posT
-
-    @property
-    def tpos(self):
-        """forward sorted position -> transposed sorted position (int32 [E]): the inverse of `posT` — where
-        ggl_spmm_max_mask scatters an edge's winner bits for the transposed walk of the max backward."""
-        if self._tpos is None:
-            posT = self.posT
-            self._tpos = torch.empty_like(posT)
-            eng = self.engine
-            eng._check(eng.lib.ggl_invert_perm(_ptr(posT), self.E, _ptr(self._tpos), eng._stream(posT.device)))
-        return self._tpos
 
 
 class RowsPlan:
@@ -899,13 +888,10 @@ class Engine:
                 # a 1-bit winner mask built in DESTINATION order (the witness row is wave-uniform there), read in the
                 # transposed walk's own order: K / 8 bytes per edge instead of 8K (include/ggl_mpops.h)
                 fs = gp.fwd.c_struct(None)
-                # records in forward order (coalesced writes; the walk reads record posT[t]) unless the A/B knob asks for
-                # the scatter to transposed positions (maxbwd_mask_scatter: streamed reads, slower writes)
-                scatter = int(L.ggl_get_option(b"maxbwd_mask_scatter")) != 0
-                self._check(L.ggl_spmm_max_mask(ctypes.byref(fs), _ptr(gp.col), _ptr(gp.tpos) if scatter else None, _ptr(aux), K,
-                                                _ptr(mask), st))
+                # records in forward order (coalesced writes); the walk reads record posT[t]
+                self._check(L.ggl_spmm_max_mask(ctypes.byref(fs), _ptr(gp.col), _ptr(aux), K, _ptr(mask), st))
                 self._check(L.ggl_spmm_max_bwd_mask(ctypes.byref(cs), _ptr(col), _ptr(w), w_by_pos, _ptr(x), _ptr(mask),
-                                                    None if scatter else _ptr(gp.posT), K, _ptr(out), st))
+                                                    _ptr(gp.posT), K, _ptr(out), st))
             elif form == 1:   # witnesses from a compact int32 copy (one [N, K] pass)
                 aux32 = aux.to(torch.int32)
                 self._check(L.ggl_spmm_max_bwd32(ctypes.byref(cs), _ptr(col), _ptr(w), w_by_pos, _ptr(x),

@@ -55,7 +55,13 @@ extern "C" {
 /* still 10: + ggl_spmm_{sum,mean,mean_bwd}_x16, ggl_spmm_col_blocks_x16, option col_block16 (the mixed-precision aggregate).
  *   Purely ADDITIVE symbols: no struct, no existing signature and no existing behaviour changed, so a caller built against 10
  *   keeps working and the number stays (hosts that want the new entry points look them up by name). */
-#define GGL_ABI_VERSION 10
+/* 11: the forms that lost their measurements are gone (DESIGN.md "Forms removed in ABI 11"; last present in 992473a):
+ *   ggl_spmm_max_mask loses `tpos` and ggl_spmm_max_mask_words loses `forward_order` (records are in forward position order,
+ *   always), ggl_spmm_max_bwd_mask REQUIRES mask_pos, - ggl_invert_perm; options gat_sh_{pk,pipe,glds,prefetch,zlds,waves},
+ *   hop_fused_scans, hop_small_scans, hub_priority, hub_pipe and maxbwd_mask_{scatter,wlane,cols} no longer exist (set answers
+ *   GGL_EINVAL, get -1); ggl_sample_hop_workspace_bytes shrinks; + ggl_option_name (the option table's enumerator); every
+ *   option reads GGL_<NAME> from the environment.  No struct change. */
+#define GGL_ABI_VERSION 11
 
 /* dtype codes (AT_DISPATCH_ALL_TYPES_AND2(Half, BFloat16), segment_sum_cpu.cpp:32-33) */
 enum {
@@ -319,23 +325,18 @@ int ggl_spmm_max_bwd32(const ggl_segplan_t *planT, const int32_t *colT, const fl
 /* The max backward through a WINNER MASK (round 5; same sums in the same order as ggl_spmm_max_bwd, spmm_max_cpu.cpp:88-93):
  *   ggl_spmm_max_mask  walks the FORWARD plan (rows = destinations, where argsrc's row is wave-uniform) and writes one
  *     record per edge, bit k = [argsrc[dst, k] == colF[p]] for the edge at forward position p:
- *       tpos == NULL (the hosts' default): records in FORWARD position order, ggl_spmm_max_mask_words(K, 1) words each
- *         (ceil(K/32) rounded up to 1, 2, 4 or a multiple of 8), written as coalesced 32-record blocks; the backward
- *         reads record posT[t] for transposed position t (pass mask_pos = posT, the hosts' GraphPlan.posT);
- *       tpos != NULL: records SCATTERED to transposed position tpos[p] (ggl_invert_perm of posT), ceil(K/32) words
- *         each; the backward streams them in its own order (mask_pos = NULL).  Measured slower (the scatter), kept as A/B.
- *     bit k of a record: word k/32, bit k%32.  mask: ggl_spmm_max_mask_bytes(E, K) bytes (room for either form), 16-byte
- *     aligned, every record fully overwritten;
- *   ggl_spmm_max_bwd_mask  is the transposed walk reading K/8 mask bytes per edge instead of 8K witness bytes. */
-int64_t ggl_spmm_max_mask_words(int64_t K, int forward_order);
+ *     records in FORWARD position order, ggl_spmm_max_mask_words(K) words each (ceil(K/32) rounded up to 1, 2, 4 or a
+ *     multiple of 8), written as coalesced 32-record blocks; bit k of a record: word k/32, bit k%32.
+ *     mask: ggl_spmm_max_mask_bytes(E, K) bytes, 16-byte aligned, every record fully overwritten;
+ *   ggl_spmm_max_bwd_mask  is the transposed walk reading K/8 mask bytes per edge instead of 8K witness bytes: record
+ *     mask_pos[t] for transposed position t — mask_pos = posT, the hosts' GraphPlan.posT, required where E * K > 0. */
+int64_t ggl_spmm_max_mask_words(int64_t K);
 size_t ggl_spmm_max_mask_bytes(int64_t E, int64_t K);
-int ggl_spmm_max_mask(const ggl_segplan_t *planF, const int32_t *colF, const int32_t *tpos, const int64_t *argsrc,
-                      int64_t K, uint32_t *mask, void *stream);
+int ggl_spmm_max_mask(const ggl_segplan_t *planF, const int32_t *colF, const int64_t *argsrc, int64_t K, uint32_t *mask,
+                      void *stream);
 int ggl_spmm_max_bwd_mask(const ggl_segplan_t *planT, const int32_t *colT, const float *w, int w_by_pos,
                           const float *g, const uint32_t *mask, const int32_t *mask_pos, int64_t K, float *gx,
                           void *stream);
-/* inv[perm[i]] = i for a permutation of [0, n), n < 2^31 */
-int ggl_invert_perm(const int32_t *perm, int64_t n, int32_t *inv, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * bspmm — multi-head SpMM, f32; supersedes bspmm_sum_cpu_{forward,backward}
@@ -577,11 +578,13 @@ int ggl_block_transpose(const int64_t *rowptr, const int32_t *col, int64_t N_dst
                         int64_t *rowptrT, int32_t *dstT, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Tuning knobs (process-wide; also read once from the environment: GGL_UNROLL, GGL_XCD_SWIZZLE,
- * GGL_FORCE_GENERIC, GGL_ROW_ORDER).  For A/B measurements only — results do not depend on them.
+ * Tuning knobs (process-wide; each is also read once from the environment, as GGL_ + its upper-cased name: GGL_UNROLL,
+ * GGL_ROW_ORDER, ...).  One table (GGL_OPTIONS, csrc/common.hpp) declares them all.  An unknown name: set answers
+ * GGL_EINVAL ("unknown option <name>"), get answers -1.  ggl_option_name(i) enumerates the names, NULL past the end.
  * ---------------------------------------------------------------------------------------------- */
 int ggl_set_option(const char *name, int64_t value);
 int64_t ggl_get_option(const char *name);
+const char *ggl_option_name(int i);
 
 /* ------------------------------------------------------------------------------------------------
  * Host policy, ONE copy (round 4).  Two hosts drive these kernels — gammagl_amd/ops.py (ctypes) and

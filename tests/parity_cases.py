@@ -2220,11 +2220,9 @@ def check_max_backward_forms(eng, dev, oracle, chunk=64):
                 one_piece = to_np(gp.bwd.counts() <= gp.bwd.chunk)          # (chunked transposed rows: within rounding)
                 for name, opts in (("int64 witnesses", {"maxbwd_mask": 0, "maxbwd_arg32": 0}),
                                    ("int32 witnesses", {"maxbwd_mask": 0, "maxbwd_arg32": 1}),
-                                   ("winner mask, forward order", {"maxbwd_mask": 1, "maxbwd_arg32": 0}),
-                                   ("winner mask, scattered", {"maxbwd_mask": 1, "maxbwd_arg32": 0, "maxbwd_mask_scatter": 1})):
+                                   ("winner mask, forward order", {"maxbwd_mask": 1, "maxbwd_arg32": 0})):
                     with option(eng, "maxbwd_mask", opts["maxbwd_mask"]), option(eng, "maxbwd_arg32", opts["maxbwd_arg32"]), \
-                            option(eng, "maxbwd_mask_kmax", 0), \
-                            option(eng, "maxbwd_mask_scatter", opts.get("maxbwd_mask_scatter", 0)):
+                            option(eng, "maxbwd_mask_kmax", 0):
                         for call in range(2):       # (second call: weights streamed from their sorted copy)
                             xt = to_t(xs, dev).requires_grad_(True)
                             eng.c_spmm_max(it, wt, xt).backward(to_t(go, dev))

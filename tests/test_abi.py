@@ -107,3 +107,79 @@ def test_maxbwd_form_policy_gates_the_winner_mask_on_its_footprint():
         assert form(400, 64, 602) == 2
     finally:
         lib.ggl_set_option(b"maxbwd_mask_kmax", old)
+
+
+
+# the options of the forms removed in ABI 11 (DESIGN.md "Forms removed in ABI 11")
+REMOVED_OPTIONS = ("gat_sh_pk", "gat_sh_pipe", "gat_sh_glds", "gat_sh_prefetch", "gat_sh_zlds", "gat_sh_waves",
+                   "hop_fused_scans", "hop_small_scans", "hub_priority", "hub_pipe", "maxbwd_mask_scatter",
+                   "maxbwd_mask_wlane", "maxbwd_mask_cols")
+
+
+def option_names(lib):
+    names = []
+    while True:
+        n = lib.ggl_option_name(len(names))
+        if n is None:
+            return names
+        names.append(n.decode())
+        assert len(names) < 1000, "ggl_option_name never answers NULL"
+
+
+def test_option_table_enumerates_unique_names():
+    from gammagl_amd import _lib
+
+    lib = _lib.bind(_lib.HOST_LIB_PATH)
+    names = option_names(lib)
+    assert names and all(names) and len(set(names)) == len(names), names
+    assert lib.ggl_option_name(-1) is None and lib.ggl_option_name(len(names) + 5) is None
+    for kept in ("exact_long_rows", "hub_one_launch", "col_block", "col_block16", "ragged4", "ragged_max", "row_order",
+                 "xcd_swizzle", "unroll", "force_generic", "max_grid_x", "maxbwd_arg32", "maxbwd_mask", "maxbwd_mask_kmax",
+                 "softmax_sublanes"):
+        assert kept in names, kept
+    assert not set(REMOVED_OPTIONS) & set(names)
+
+
+def test_every_option_round_trips_through_set_and_get():
+    from gammagl_amd import _lib
+
+    lib = _lib.bind(_lib.HOST_LIB_PATH)
+    for name in option_names(lib):
+        key = name.encode()
+        old = lib.ggl_get_option(key)
+        try:
+            assert lib.ggl_set_option(key, old) == 0 and lib.ggl_get_option(key) == old, name
+            assert lib.ggl_set_option(key, old + 1) == 0 and lib.ggl_get_option(key) == old + 1, name
+        finally:
+            assert lib.ggl_set_option(key, old) == 0
+        assert lib.ggl_get_option(key) == old, name
+    # the one special case: max_grid_x is clamped to >= 1 when set
+    old = lib.ggl_get_option(b"max_grid_x")
+    try:
+        assert lib.ggl_set_option(b"max_grid_x", 0) == 0 and lib.ggl_get_option(b"max_grid_x") == 1
+        assert lib.ggl_set_option(b"max_grid_x", -7) == 0 and lib.ggl_get_option(b"max_grid_x") == 1
+    finally:
+        lib.ggl_set_option(b"max_grid_x", old)
+
+
+@pytest.mark.parametrize("name", REMOVED_OPTIONS + ("no_such_option",))
+def test_removed_and_unknown_options_are_refused(name):
+    from gammagl_amd import _lib
+
+    lib = _lib.bind(_lib.HOST_LIB_PATH)
+    assert lib.ggl_set_option(name.encode(), 1) != 0
+    assert lib.ggl_last_error().decode() == f"unknown option {name}"
+    assert lib.ggl_get_option(name.encode()) == -1
+
+
+def test_every_option_reads_its_environment_variable():
+    """GGL_ + the upper-cased name, read once at first use: checked in a fresh process (ragged_max and softmax_sublanes had
+    no variable before the option table)."""
+    import sys
+
+    code = ("from gammagl_amd import _lib; lib = _lib.bind(_lib.HOST_LIB_PATH); "
+            "print(*[lib.ggl_get_option(n) for n in (b'ragged_max', b'softmax_sublanes', b'col_block16', b'row_order')])")
+    env = dict(os.environ, GGL_RAGGED_MAX="0", GGL_SOFTMAX_SUBLANES="4", GGL_COL_BLOCK16="64")   # (`-c` in cwd = REPO: the package imports from the tree)
+    env.pop("GGL_ROW_ORDER", None)
+    out = subprocess.run([sys.executable, "-c", code], env=env, cwd=REPO, capture_output=True, text=True, check=True).stdout
+    assert out.split() == ["0", "4", "64", "1"], out     # (row_order: not set, its default)

@@ -89,11 +89,11 @@ def test_gspmm_fuzz(oracle, prob):
 
 
 @settings(max_examples=40, deadline=None, suppress_health_check=list(HealthCheck))
-@given(problems(), st.sampled_from([0, 1]))
-def test_gspmm_max_backward_mask_fuzz(oracle, prob, scatter):
-    """the same cases with the max backward forced through the 1-bit winner mask (round 5), records in forward order / scattered"""
+@given(problems())
+def test_gspmm_max_backward_mask_fuzz(oracle, prob):
+    """the same cases with the max backward forced through the 1-bit winner mask (round 5), records in forward order"""
     eng = engine()
-    with pc.option(eng, "maxbwd_mask", 1), pc.option(eng, "maxbwd_mask_kmax", 0), pc.option(eng, "maxbwd_mask_scatter", scatter):
+    with pc.option(eng, "maxbwd_mask", 1), pc.option(eng, "maxbwd_mask_kmax", 0):
         run_gspmm_case(eng, DEV, oracle, prob)
 
 

@@ -778,13 +778,6 @@ def test_weight_dtype_guard(eng, dev):
 
 def test_static_shape_block_sampler(eng, dev, oracle):
     pc.check_block_sampler(eng, dev, oracle)
-    # ... and with count / flag + scan (+ clamp) fused into one launch each (single-pass chained scans; an A/B knob, off by
-    # default: same blocks, bit for bit — the checks compare against the dynamic sampler and the oracle)
-    with pc.option(eng, "hop_fused_scans", 1):
-        pc.check_block_sampler(eng, dev, oracle)
-    # round 6 (an A/B knob too, off: no faster): the scans of small hops as ONE single-workgroup launch each
-    with pc.option(eng, "hop_small_scans", 1):
-        pc.check_block_sampler(eng, dev, oracle)
 
 
 def test_minibatch_step_captures_into_one_hipgraph(eng, dev):
@@ -818,19 +811,6 @@ def test_minibatch_step_captures_into_one_hipgraph(eng, dev):
     assert bool((bs._first_pos == (1 << 62)).all()) and bs.overflow_count() == 0
     # eager step on the same trainer still works after capture (same code path, no graph)
     assert bool(torch.isfinite(tr.step(x, y, seeds)))
-
-
-def test_gat_headmean_walk_forms(eng, dev):
-    """The round-5 forms of the head-mean walks (z_j in LDS slots + ids requested a step ahead: options gat_sh_zlds /
-    gat_sh_prefetch, on by default) and the round-4 forms they replace: the same test either way."""
-    with pc.option(eng, "gat_sh_zlds", 0), pc.option(eng, "gat_sh_prefetch", 0):     # packed pair dots, z_j pairs in registers (A/B)
-        test_gat_headmean_layer_aggregate_then_transform(eng, dev)
-    with pc.option(eng, "gat_sh_pk", 0):     # round 5's dots + 16-value reduce-scatter with selects (round 6 default: packed pairs)
-        test_gat_headmean_layer_aggregate_then_transform(eng, dev)
-    with pc.option(eng, "gat_sh_pipe", 1):   # the source walk with its gathers software-pipelined one step ahead (A/B)
-        test_gat_headmean_layer_aggregate_then_transform(eng, dev)
-    with pc.option(eng, "gat_sh_pk", 0), pc.option(eng, "gat_sh_zlds", 0), pc.option(eng, "gat_sh_prefetch", 0):   # round 4's forms
-        test_gat_headmean_layer_aggregate_then_transform(eng, dev)
 
 
 def _rowscale_close(a, b, tol, what):
@@ -1049,8 +1029,6 @@ def test_max_backward_forms(eng, dev, oracle):
     also through folded 2-D grids."""
     pc.check_max_backward_forms(eng, dev, oracle)
     with pc.option(eng, "max_grid_x", 3):
-        pc.check_max_backward_forms(eng, dev, oracle)
-    with pc.option(eng, "maxbwd_mask_wlane", 0):        # the forward-order records assembled with selects (default: v_writelane)
         pc.check_max_backward_forms(eng, dev, oracle)
 
 

@@ -53,8 +53,8 @@ if "maxbwd" in what:
         torch.cuda.empty_cache()
 
 if "gat" in what:
-    # the head-mean output layer of config 3 (64 -> 8 x 41) forward + backward and the 2-layer GAT step, round-5 dots +
-    # select reduce-scatter (gat_sh_pk = 0) vs packed pair dots + select-free reduce (1), with and without attention dropout
+    # the head-mean output layer of config 3 (64 -> 8 x 41) forward + backward and the 2-layer GAT step, with and without
+    # attention dropout (the round-5 dots + select reduce-scatter this was first measured against were removed in ABI 11)
     import torch.nn.functional as Fn
     from gammagl_amd import layers
     n, e, _, _ = DATASETS["reddit"]
@@ -63,8 +63,7 @@ if "gat" in what:
     conv = layers.FusedGATConv(64, 41, heads=8, concat=False, dropout_rate=0.6).to(dev); conv.train()
     conv0 = layers.FusedGATConv(64, 41, heads=8, concat=False, dropout_rate=0.0).to(dev); conv0.train()
     xf = torch.randn(n, 602, device=dev); yl = torch.randint(0, 41, (n,), device=dev); tidx = torch.arange(0, n, 3, device=dev)
-    for pk, waves in ((0, 0), (1, 0), (1, 4), (0, 0), (1, 0), (1, 4)):
-        eng.set_option("gat_sh_pk", pk); eng.set_option("gat_sh_waves", waves)
+    for rep in range(2):
         f = ev(lambda: conv(x.detach(), ei, n)); fb = ev(lambda: conv(x, ei, n).sum().backward())
         fb0 = ev(lambda: conv0(x, ei, n).sum().backward())
         torch.manual_seed(0)
@@ -73,8 +72,7 @@ if "gat" in what:
         def step():
             net.train(); opt.zero_grad(set_to_none=True)
             Fn.cross_entropy(net(xf, ei, n)[tidx], yl[tidx]).backward(); opt.step()
-        print(f"gat_sh_pk={pk} gat_sh_waves={waves}: output layer fwd {f:.2f} ms, fwd+bwd dropout 0.6 {fb:.2f} ms, no dropout {fb0:.2f} ms; 2-layer GAT step {ev(step, 5):.2f} ms", flush=True)
-    eng.set_option("gat_sh_pk", 1); eng.set_option("gat_sh_waves", 0)
+        print(f"run {rep}: output layer fwd {f:.2f} ms, fwd+bwd dropout 0.6 {fb:.2f} ms, no dropout {fb0:.2f} ms; 2-layer GAT step {ev(step, 5):.2f} ms", flush=True)
     eng.clear_caches()
 
 if "planted" in what:
@@ -106,8 +104,8 @@ if "planted" in what:
     eng.clear_caches()
 
 if "gatfull" in what:
-    # full Reddit-sized graph, output layer 64 -> 8 x 41 (default init, no dropout): head-mean path with gat_sh_pk = 1 / 0 and the
-    # transform-first kernels, pairwise — which differences are the packed form's and which are two f32 evaluations' own
+    # full Reddit-sized graph, output layer 64 -> 8 x 41 (default init, no dropout): the head-mean path against the
+    # transform-first kernels — the difference between two f32 evaluations of the same layer
     from gammagl_amd import layers
     from oracle import parity
     n, e, _, _ = DATASETS["reddit"]
@@ -118,16 +116,16 @@ if "gatfull" in what:
     torch.manual_seed(0)
     fg = layers.FusedGATConv(64, 41, heads=8, concat=False).to(dev)
     res = {}
-    for name, fast, pk in (("headmean pk=1", True, 1), ("headmean pk=0", True, 0), ("transform-first", False, 1)):
-        eng.gat_fast = fast; eng.set_option("gat_sh_pk", pk)
+    for name, fast in (("headmean", True), ("transform-first", False)):
+        eng.gat_fast = fast
         for p_ in fg.parameters(): p_.grad = None
         xa = x.clone().requires_grad_(True)
         y = fg(xa, ei, n); y.backward(go)
         res[name] = [y.detach(), xa.grad, fg.w.grad.clone(), fg.att.grad.clone()]
-    eng.gat_fast = True; eng.set_option("gat_sh_pk", 1)
+    eng.gat_fast = True
     names = list(res)
-    for i in range(3):
-        for j in range(i + 1, 3):
+    for i in range(len(names)):
+        for j in range(i + 1, len(names)):
             line = f"{names[i]} vs {names[j]}:"
             for a, b, nm in zip(res[names[i]], res[names[j]], ("y", "gx", "gW", "gatt")):
                 a2, b2 = (t.reshape(t.shape[0], -1) if t.dim() > 1 else t.reshape(1, -1) for t in (a, b))
