@@ -579,7 +579,9 @@ def pmc_probe_gat(args, dev, eng):
 def run_gat(args, dev, rank, world, eng=None):
     """Config 3: 2-layer, 8-head GAT (602 -> 8 x 8 -> 41 classes, the last layer averages its heads; feature and
     attention dropout 0.6 — examples/gat/gat_trainer.py defaults) on the Reddit-sized graph, one full-graph
-    training step (fwd + bwd + Adam) through FusedGATConv = the fused edge-softmax + aggregate kernels."""
+    training step (fwd + bwd + Adam) through FusedGATConv = the fused edge-softmax + aggregate kernels.
+    args.amp (torch.bfloat16 / torch.float16; bench.py has no such flag: f32) runs the forward under torch.autocast — the
+    8 x 8 layer's panel is then stored in 16 bits (tools/gat16_bench.py)."""
     from .layers import GATModel
     from .synth import rmat_graph
 
@@ -601,12 +603,25 @@ def run_gat(args, dev, rank, world, eng=None):
     net = GATModel(f_in, C, n_cls, H, 0.6, 2, fused=True).to(dev)
     opt = torch.optim.Adam(net.parameters(), lr=0.005, weight_decay=5e-4)
 
+    amp = getattr(args, "amp", None)
+    scaler = torch.amp.GradScaler("cuda") if amp == torch.float16 else None
+
     def step():
         net.train()
         opt.zero_grad(set_to_none=True)
-        loss = F.cross_entropy(net(x, ei, n)[tidx], y[tidx])
-        loss.backward()
-        opt.step()
+        if amp is None:
+            loss = F.cross_entropy(net(x, ei, n)[tidx], y[tidx])
+        else:
+            with torch.autocast("cuda", dtype=amp):
+                out = net(x, ei, n)
+            loss = F.cross_entropy(out[tidx].float(), y[tidx])
+        if scaler is not None:
+            scaler.scale(loss).backward()
+            scaler.step(opt)
+            scaler.update()
+        else:
+            loss.backward()
+            opt.step()
         return loss
 
     for _ in range(args.warmup):
@@ -634,7 +649,7 @@ def run_gat(args, dev, rank, world, eng=None):
     out = {"metric": "edges aggregated/sec, 2-layer 8-head GAT training step, Reddit-sized graph (fused edge-softmax + aggregate)",
            "value": walks * E * args.steps / dt, "unit": "edges/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-           "dtype": "f32", "data": "synthetic", "rccl_ranks": 1,
+           "dtype": "f32" if amp is None else f"autocast({str(amp).replace('torch.', '')})", "data": "synthetic", "rccl_ranks": 1,
            "config": {"workload": f"reddit-gat: Reddit-sized R-MAT N={n}, E={E} directed incl. self-loops, GATModel({f_in} -> "
                                   f"{H}x{C} -> {n_cls}, heads averaged in the output layer), feature + attention dropout 0.6, "
                                   f"full-graph train step (fwd+bwd+Adam), {walks} edge walks/step",

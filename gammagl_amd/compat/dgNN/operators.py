@@ -44,7 +44,8 @@ __all__ = ["GATConvFuse"]
 
 def GATConvFuse(attn_row, attn_col, row_ptr, col_ind, col_ptr, row_ind, permute, negative_slope, in_feat, attn_drop=0.0):
     """Fused GAT aggregation over a caller-built CSR (see the module docstring).  Shapes: ``attn_row`` / ``attn_col``
-    [N, H], ``in_feat`` [N, H, C] f32; ``row_ptr`` [N + 1], ``col_ind`` [E], ``col_ptr`` [N + 1], ``row_ind`` [E],
+    [N, H] f32, ``in_feat`` [N, H, C] f32 — or stored as bf16 / f16 (an extension: a layer under autocast; f32 softmax and
+    sums, the result in ``in_feat``'s dtype); ``row_ptr`` [N + 1], ``col_ind`` [E], ``col_ptr`` [N + 1], ``row_ind`` [E],
     ``permute`` [E] int32 or int64.  Returns [N, H, C]."""
     if not (isinstance(in_feat, torch.Tensor) and in_feat.dim() == 3):
         raise RuntimeError("GATConvFuse: in_feat must be [num_nodes, heads, channels]")

@@ -46,9 +46,10 @@ namespace ggl {
 // Random word of (position p, head h): drop_word(p, h) above — a 15-instruction counter-based mix, so a draw per
 // edge is affordable in every walk (with Philox4x32-10 a draw per edge doubled the forward: 4.1 -> 9.4 ms, and the
 // walks were aligned to multiples of 4 to share one 4-word block; the alignment is kept for the 16-byte index loads).
-template <int VEC, bool DROP>
+// XT: how x is stored (float, or mxbf16_t / mxf16_t: 16-bit storage widened at the load; everything below is f32).
+template <typename XT, int VEC, bool DROP>
 __device__ __forceinline__ void gat_online(const int32_t *__restrict__ col, const float *__restrict__ el,
-                                           const float *__restrict__ x, float er_i, float slope, int64_t H,
+                                           const typename TT<XT>::S *__restrict__ x, float er_i, float slope, int64_t H,
                                            int64_t K, int64_t h, int64_t kk, int64_t beg, int64_t end,
                                            const GatDims &d, const int64_t *__restrict__ rng,
                                            float &m, float &den, float (&acc)[VEC]) {
@@ -75,7 +76,7 @@ __device__ __forceinline__ void gat_online(const int32_t *__restrict__ col, cons
   auto single = [&](int64_t q) {
     const int64_t c0 = col[q];
     float v0[VEC];
-    F32V<VEC>::load(x + c0 * K + kk, v0);
+    RowV<XT, VEC>::load(x + c0 * K + kk, v0);
     absorb(DROP ? drop_word(q, H, h, offset, seed) : 0u, lrelu(__fadd_rn(el[c0 * H + h], er_i), slope), v0);
   };
   int64_t p = beg;
@@ -90,7 +91,7 @@ __device__ __forceinline__ void gat_online(const int32_t *__restrict__ col, cons
 #pragma unroll
     for (int u = 0; u < 4; ++u) c[u] = col[p + u];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) F32V<VEC>::load(x + c[u] * K + kk, v[u]);
+    for (int u = 0; u < 4; ++u) RowV<XT, VEC>::load(x + c[u] * K + kk, v[u]);
 #pragma unroll
     for (int u = 0; u < 4; ++u) s[u] = lrelu(__fadd_rn(el[c[u] * H + h], er_i), slope);
 #pragma unroll
@@ -99,12 +100,13 @@ __device__ __forceinline__ void gat_online(const int32_t *__restrict__ col, cons
   for (; p < end; ++p) single(p);
 }
 
-template <int VEC, bool DROP>
+// OT: how out is stored (XT, or float beside 16-bit rows: a last layer's logits).  The hub-chunk partials are f32.
+template <typename XT, typename OT, int VEC, bool DROP>
 __global__ __launch_bounds__(kBlock) void gat_fwd_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const int32_t *__restrict__ row_order, const int32_t *__restrict__ long_rows,
     const int64_t *__restrict__ chunk_ptr, const float *__restrict__ el, const float *__restrict__ er,
-    const float *__restrict__ x, float *__restrict__ y, float *__restrict__ rowmax,
+    const typename TT<XT>::S *__restrict__ x, typename TT<OT>::S *__restrict__ y, float *__restrict__ rowmax,
     float *__restrict__ rowden, float *__restrict__ pacc, float *__restrict__ pm,
     float *__restrict__ pd, const int64_t *__restrict__ rng, const GatDims d) {
   const int lane = threadIdx.x & (kWave - 1);
@@ -126,7 +128,7 @@ __global__ __launch_bounds__(kBlock) void gat_fwd_kernel(
       const int64_t h = kk / d.C;
       const float er_i = er[row * H + h];
       float m, dsum, acc[VEC];
-      gat_online<VEC, DROP>(col, el, x, er_i, d.slope, H, K, h, kk, beg, end, d, rng, m, dsum, acc);
+      gat_online<XT, VEC, DROP>(col, el, x, er_i, d.slope, H, K, h, kk, beg, end, d, rng, m, dsum, acc);
       F32V<VEC>::store(pacc + cid * K + kk, acc);
       if (kk == h * d.C) {
         pm[cid * H + h] = m;
@@ -147,11 +149,11 @@ __global__ __launch_bounds__(kBlock) void gat_fwd_kernel(
     const int64_t h = kk / d.C;
     const float er_i = er[row * H + h];
     float m, dsum, acc[VEC];
-    gat_online<VEC, DROP>(col, el, x, er_i, d.slope, H, K, h, kk, beg, end, d, rng, m, dsum, acc);
+    gat_online<XT, VEC, DROP>(col, el, x, er_i, d.slope, H, K, h, kk, beg, end, d, rng, m, dsum, acc);
     const float inv = __fadd_rn(dsum, 1e-16f);  // softmax.py:35: exp / (sum + 1e-16)
 #pragma unroll
     for (int i = 0; i < VEC; ++i) acc[i] = __fdiv_rn(acc[i], inv);
-    F32V<VEC>::store(y + row * K + kk, acc);
+    RowV<OT, VEC>::store(y + row * K + kk, acc);  // the one rounding of a 16-bit out
     if (kk == h * d.C) {  // first lane of the head records the softmax statistics
       rowmax[row * H + h] = m;
       rowden[row * H + h] = dsum;
@@ -159,10 +161,11 @@ __global__ __launch_bounds__(kBlock) void gat_fwd_kernel(
   }
 }
 
-__global__ __launch_bounds__(kBlock) void gat_long_final_kernel(
+template <typename OT>
+__device__ __forceinline__ void gat_long_final_body(
     const int32_t *__restrict__ long_rows, const int64_t *__restrict__ chunk_ptr,
     const float *__restrict__ pacc, const float *__restrict__ pm, const float *__restrict__ pd,
-    float *__restrict__ y, float *__restrict__ rowmax, float *__restrict__ rowden, const GatDims d) {
+    typename TT<OT>::S *__restrict__ y, float *__restrict__ rowmax, float *__restrict__ rowden, const GatDims &d) {
   const int64_t j = block_id();
   if (j >= d.n_long) return;
   const int64_t row = long_rows[j];
@@ -178,12 +181,25 @@ __global__ __launch_bounds__(kBlock) void gat_long_final_kernel(
       den = __fadd_rn(den, __fmul_rn(pd[c * d.H + h], sc));
       acc = __fadd_rn(acc, __fmul_rn(pacc[c * d.K + k], sc));
     }
-    y[row * d.K + k] = __fdiv_rn(acc, __fadd_rn(den, 1e-16f));
+    y[row * d.K + k] = TT<OT>::store(__fdiv_rn(acc, __fadd_rn(den, 1e-16f)));
     if (k == h * d.C) {
       rowmax[row * d.H + h] = m;
       rowden[row * d.H + h] = den;
     }
   }
+}
+__global__ __launch_bounds__(kBlock) void gat_long_final_kernel(
+    const int32_t *__restrict__ long_rows, const int64_t *__restrict__ chunk_ptr,
+    const float *__restrict__ pacc, const float *__restrict__ pm, const float *__restrict__ pd,
+    float *__restrict__ y, float *__restrict__ rowmax, float *__restrict__ rowden, const GatDims d) {
+  gat_long_final_body<float>(long_rows, chunk_ptr, pacc, pm, pd, y, rowmax, rowden, d);
+}
+template <typename OT>  // the same merge of the same f32 partials; only the store rounds
+__global__ __launch_bounds__(kBlock) void gat_long_final16_kernel(
+    const int32_t *__restrict__ long_rows, const int64_t *__restrict__ chunk_ptr,
+    const float *__restrict__ pacc, const float *__restrict__ pm, const float *__restrict__ pd,
+    uint16_t *__restrict__ y, float *__restrict__ rowmax, float *__restrict__ rowden, const GatDims d) {
+  gat_long_final_body<OT>(long_rows, chunk_ptr, pacc, pm, pd, y, rowmax, rowden, d);
 }
 
 // Destination-major half of the backward in ONE walk of the forward plan.  A work item is a short row or
@@ -195,15 +211,20 @@ __global__ __launch_bounds__(kBlock) void gat_long_final_kernel(
 // CREG > 0: C is known at compile time and g_i[h,:] lives in registers; 0 = any C, g_i re-read (cached).
 // Replaces three launches (row dots, an edge-parallel alpha/de kernel, segment_sum(de) for ger: 0.3 + 5.7
 // + 2.7 ms on the Reddit-sized graph) with the same rounded operations in the same order.
-template <int VEC, int CREG>
+// XT: storage of x; GT: storage of g AND of the saved out (the forward's out type).  16-bit elements are widened at the
+// load; the dots run over the channels in ascending order whatever VEC is, so the bits do not depend on the load form.
+template <typename XT, typename GT, int VEC, int CREG>
 __global__ __launch_bounds__(kBlock) void gat_bwd_dst_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const int32_t *__restrict__ row_order, const int32_t *__restrict__ long_rows,
     const int64_t *__restrict__ chunk_ptr, const float *__restrict__ el, const float *__restrict__ er,
-    const float *__restrict__ x, const float *__restrict__ g, const float *__restrict__ out,
+    const typename TT<XT>::S *__restrict__ x, const typename TT<GT>::S *__restrict__ g,
+    const typename TT<GT>::S *__restrict__ out,
     const float *__restrict__ rowmax, const float *__restrict__ rowden, float *__restrict__ alpha,
     float *__restrict__ de, float *__restrict__ ger, float *__restrict__ pger,
     const int64_t *__restrict__ rng, const GatDims d) {
+  using XS = typename TT<XT>::S;
+  using GS = typename TT<GT>::S;
   const int64_t H = d.H, K = d.K;
   const int64_t C = CREG > 0 ? (int64_t)CREG : d.C;
   const uint64_t seed = d.drop_thresh ? (uint64_t)rng[0] : 0, offset = d.drop_thresh ? (uint64_t)rng[1] : 0;
@@ -231,24 +252,24 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_kernel(
     if (end - beg > d.chunk) return;  // long row: its chunks are separate items
   }
   for (int64_t h = li; h < H; h += LG) {
-    const float *__restrict__ gi = g + row * K + h * C;
-    const float *__restrict__ oi = out + row * K + h * C;
+    const GS *__restrict__ gi = g + row * K + h * C;
+    const GS *__restrict__ oi = out + row * K + h * C;
     float gr[CREG > 0 ? CREG : 1];
     float dot = 0.0f;
     if (CREG > 0) {
 #pragma unroll
       for (int c = 0; c < (CREG > 0 ? CREG : 1); ++c) {
-        gr[c] = gi[c];
-        dot = __fadd_rn(dot, __fmul_rn(gr[c], oi[c]));
+        gr[c] = TT<GT>::load(gi[c]);
+        dot = __fadd_rn(dot, __fmul_rn(gr[c], TT<GT>::load(oi[c])));
       }
     } else {
-      for (int64_t c = 0; c < C; ++c) dot = __fadd_rn(dot, __fmul_rn(gi[c], oi[c]));
+      for (int64_t c = 0; c < C; ++c) dot = __fadd_rn(dot, __fmul_rn(TT<GT>::load(gi[c]), TT<GT>::load(oi[c])));
     }
     const float er_i = er[row * H + h];
     const float m = rowmax[row * H + h];
     const float inv = __fadd_rn(rowden[row * H + h], 1e-16f);
     float gsum = 0.0f;
-    auto edge = [&](int64_t p, uint32_t word, float elv, const float *__restrict__ xj) {
+    auto edge = [&](int64_t p, uint32_t word, float elv, const XS *__restrict__ xj) {
       const float raw = __fadd_rn(elv, er_i);
       const float al = __fdiv_rn(GGL_EXPF(__fadd_rn(lrelu(raw, d.slope), -m)), inv);
       float da = 0.0f;
@@ -256,15 +277,15 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_kernel(
 #pragma unroll
         for (int c = 0; c < (CREG > 0 ? CREG : 1); c += VEC) {
           float xv[VEC];
-          F32V<VEC>::load(xj + c, xv);
+          RowV<XT, VEC>::load(xj + c, xv);
 #pragma unroll
           for (int q = 0; q < VEC; ++q) da = __fadd_rn(da, __fmul_rn(gr[(c + q) % (CREG > 0 ? CREG : 1)], xv[q]));
         }
       } else {
         for (int64_t c = 0; c < C; c += VEC) {
           float gv[VEC], xv[VEC];
-          F32V<VEC>::load(gi + c, gv);
-          F32V<VEC>::load(xj + c, xv);
+          RowV<GT, VEC>::load(gi + c, gv);
+          RowV<XT, VEC>::load(xj + c, xv);
 #pragma unroll
           for (int q = 0; q < VEC; ++q) da = __fadd_rn(da, __fmul_rn(gv[q], xv[q]));
         }
@@ -324,16 +345,37 @@ template <int LOGG> __device__ __forceinline__ float group_sum(float v) {
   return v;
 }
 
-template <int VEC, int LOGG, int HH>
+// 16-bit storage (XT / GT as in gat_bwd_dst_kernel) keeps the f32 form's ASSIGNMENT: four channels per lane (8-byte
+// loads of 16-bit rows), the same LOGG and HH for a head shape.  The butterfly's association depends on which
+// channels a lane holds, so this is what keeps alpha / de / ger equal, bit for bit, to the f32 kernel on the widened
+// rows; eight channels per lane would halve the loads and would have to give that equality up.  A 16-bit panel that
+// is not 8-byte aligned keeps the assignment too and reads its four channels one by one (d.vl = 0).
+template <typename T, int VEC, bool MAYBE>
+__device__ __forceinline__ void gat_wide_load(int vl, const typename TT<T>::S *__restrict__ p, float (&v)[VEC]) {
+  if constexpr (!MAYBE || VEC == 1) {
+    RowV<T, VEC>::load(p, v);
+  } else {
+    if (vl) {
+      RowV<T, VEC>::load(p, v);
+    } else {
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) v[i] = TT<T>::load(p[i]);
+    }
+  }
+}
+
+template <typename XT, typename GT, int VEC, int LOGG, int HH>
 __global__ __launch_bounds__(kBlock) void gat_bwd_dst_wide_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const int32_t *__restrict__ row_order, const int32_t *__restrict__ long_rows,
     const int64_t *__restrict__ chunk_ptr, const float *__restrict__ el, const float *__restrict__ er,
-    const float *__restrict__ x, const float *__restrict__ g, const float *__restrict__ out,
+    const typename TT<XT>::S *__restrict__ x, const typename TT<GT>::S *__restrict__ g,
+    const typename TT<GT>::S *__restrict__ out,
     const float *__restrict__ rowmax, const float *__restrict__ rowden, float *__restrict__ alpha,
     float *__restrict__ de, float *__restrict__ ger, float *__restrict__ pger,
     const int64_t *__restrict__ rng, const GatDims d) {
   constexpr int G = 1 << LOGG;
+  constexpr bool MB = gat_is16<XT>::value;  // only the 16-bit entry points can meet a panel aligned to less than VEC
   static_assert(G >= HH, "lane h finishes head h");
   const int64_t H = d.H, C = d.C, K = d.K;  // H <= HH: HH is the compile-time bound of the head loops
   const int64_t item = thread_id() >> LOGG;
@@ -367,8 +409,8 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_wide_kernel(
 #pragma unroll
     for (int q = 0; q < VEC; ++q) { gr[h][q] = 0.0f; ov[q] = 0.0f; }
     if (act && h < H) {
-      F32V<VEC>::load(g + row * K + h * C + c0, gr[h]);
-      F32V<VEC>::load(out + row * K + h * C + c0, ov);
+      gat_wide_load<GT, VEC, MB>(d.vl, g + row * K + h * C + c0, gr[h]);
+      gat_wide_load<GT, VEC, MB>(d.vl, out + row * K + h * C + c0, ov);
     }
     float t = 0.0f;
 #pragma unroll
@@ -425,8 +467,8 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_wide_kernel(
 #pragma unroll
       for (int q = 0; q < VEC; ++q) { x0[h][q] = 0.0f; x1[h][q] = 0.0f; }
       if (act && h < H) {
-        F32V<VEC>::load(x + j0 * K + h * C + c0, x0[h]);
-        F32V<VEC>::load(x + j1 * K + h * C + c0, x1[h]);
+        gat_wide_load<XT, VEC, MB>(d.vl, x + j0 * K + h * C + c0, x0[h]);
+        gat_wide_load<XT, VEC, MB>(d.vl, x + j1 * K + h * C + c0, x1[h]);
       }
     }
     one_edge(p, j0, x0);
@@ -439,7 +481,7 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_wide_kernel(
     for (int h = 0; h < HH; ++h) {
 #pragma unroll
       for (int q = 0; q < VEC; ++q) x0[h][q] = 0.0f;
-      if (act && h < H) F32V<VEC>::load(x + j0 * K + h * C + c0, x0[h]);
+      if (act && h < H) gat_wide_load<XT, VEC, MB>(d.vl, x + j0 * K + h * C + c0, x0[h]);
     }
     one_edge(p, j0, x0);
   }
@@ -470,10 +512,11 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_final_kernel(const int32_t
 // at.  Same lane layout as the forward; the first lane of each head also carries the gel sum.  Same
 // rounded operations in the same order as the bspmm + segment_sum pair this replaces (two walks, two
 // gathers of posT: 6.0 + 3.7 ms on the Reddit-sized graph), so the results are bit-identical to it.
-template <int VEC>
+// GT: storage of g (widened at the load); OT (kernel): storage of gx, rounded once at the store.
+template <typename GT, int VEC>
 __device__ __forceinline__ void gat_src_walk(const int32_t *__restrict__ colT, const int32_t *__restrict__ posT,
                                              const float *__restrict__ alpha, const float *__restrict__ de,
-                                             const float *__restrict__ g, int64_t H, int64_t K, int64_t h,
+                                             const typename TT<GT>::S *__restrict__ g, int64_t H, int64_t K, int64_t h,
                                              int64_t es, int64_t kk, bool lead, int64_t beg, int64_t end,
                                              float (&acc)[VEC], float &gl) {
 #pragma unroll
@@ -486,7 +529,7 @@ __device__ __forceinline__ void gat_src_walk(const int32_t *__restrict__ colT, c
 #pragma unroll
     for (int u = 0; u < 4; ++u) { r[u] = colT[q + u]; e[u] = posT[q + u]; }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) F32V<VEC>::load(g + r[u] * K + kk, v[u]);
+    for (int u = 0; u < 4; ++u) RowV<GT, VEC>::load(g + r[u] * K + kk, v[u]);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       a[u] = alpha[(e[u] * H + h) * es];
@@ -502,7 +545,7 @@ __device__ __forceinline__ void gat_src_walk(const int32_t *__restrict__ colT, c
   for (; q < end; ++q) {
     const int64_t r0 = colT[q], e0 = posT[q];
     float v0[VEC];
-    F32V<VEC>::load(g + r0 * K + kk, v0);
+    RowV<GT, VEC>::load(g + r0 * K + kk, v0);
     const float a0 = alpha[(e0 * H + h) * es];
 #pragma unroll
     for (int i = 0; i < VEC; ++i) acc[i] = __fadd_rn(acc[i], __fmul_rn(a0, v0[i]));
@@ -510,13 +553,13 @@ __device__ __forceinline__ void gat_src_walk(const int32_t *__restrict__ colT, c
   }
 }
 
-template <int VEC>
+template <typename GT, typename OT, int VEC>
 __global__ __launch_bounds__(kBlock) void gat_bwd_src_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colT, const int32_t *__restrict__ posT,
     const int32_t *__restrict__ row_order, const int32_t *__restrict__ long_rows,
     const int64_t *__restrict__ chunk_ptr, const float *__restrict__ alpha, const float *__restrict__ de,
-    const float *__restrict__ g, float *__restrict__ gx, float *__restrict__ gel, float *__restrict__ pacc,
-    float *__restrict__ pgel, const GatDims d) {
+    const typename TT<GT>::S *__restrict__ g, typename TT<OT>::S *__restrict__ gx, float *__restrict__ gel,
+    float *__restrict__ pacc, float *__restrict__ pgel, const GatDims d) {
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x >> 6;
   const int64_t H = d.H, K = d.K;
@@ -536,7 +579,7 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_src_kernel(
       const int64_t h = kk / d.C;
       const bool lead = (kk == h * d.C);
       float acc[VEC], gl;
-      gat_src_walk<VEC>(colT, posT, alpha, de, g, H, K, h, d.es, kk, lead, beg, end, acc, gl);
+      gat_src_walk<GT, VEC>(colT, posT, alpha, de, g, H, K, h, d.es, kk, lead, beg, end, acc, gl);
       F32V<VEC>::store(pacc + cid * K + kk, acc);
       if (lead) pgel[cid * H + h] = gl;
     }
@@ -554,17 +597,18 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_src_kernel(
     const int64_t h = kk / d.C;
     const bool lead = (kk == h * d.C);
     float acc[VEC], gl;
-    gat_src_walk<VEC>(colT, posT, alpha, de, g, H, K, h, d.es, kk, lead, beg, end, acc, gl);
-    F32V<VEC>::store(gx + row * K + kk, acc);
+    gat_src_walk<GT, VEC>(colT, posT, alpha, de, g, H, K, h, d.es, kk, lead, beg, end, acc, gl);
+    RowV<OT, VEC>::store(gx + row * K + kk, acc);
     if (lead) gel[row * H + h] = gl;
   }
 }
 
 // long source rows: partial sums combined in chunk order (deterministic)
-__global__ __launch_bounds__(kBlock) void gat_bwd_src_final_kernel(
+template <typename OT>
+__device__ __forceinline__ void gat_bwd_src_final_body(
     const int32_t *__restrict__ long_rows, const int64_t *__restrict__ chunk_ptr,
-    const float *__restrict__ pacc, const float *__restrict__ pgel, float *__restrict__ gx,
-    float *__restrict__ gel, const GatDims d) {
+    const float *__restrict__ pacc, const float *__restrict__ pgel, typename TT<OT>::S *__restrict__ gx,
+    float *__restrict__ gel, const GatDims &d) {
   const int64_t j = block_id();
   if (j >= d.n_long) return;
   const int64_t row = long_rows[j];
@@ -573,13 +617,26 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_src_final_kernel(
     float acc = 0.0f;
     if (k < d.K) {
       for (int64_t c = c0; c < c1; ++c) acc = __fadd_rn(acc, pacc[c * d.K + k]);
-      gx[row * d.K + k] = acc;
+      gx[row * d.K + k] = TT<OT>::store(acc);
     } else {
       const int64_t h = k - d.K;
       for (int64_t c = c0; c < c1; ++c) acc = __fadd_rn(acc, pgel[c * d.H + h]);
       gel[row * d.H + h] = acc;
     }
   }
+}
+__global__ __launch_bounds__(kBlock) void gat_bwd_src_final_kernel(
+    const int32_t *__restrict__ long_rows, const int64_t *__restrict__ chunk_ptr,
+    const float *__restrict__ pacc, const float *__restrict__ pgel, float *__restrict__ gx,
+    float *__restrict__ gel, const GatDims d) {
+  gat_bwd_src_final_body<float>(long_rows, chunk_ptr, pacc, pgel, gx, gel, d);
+}
+template <typename OT>
+__global__ __launch_bounds__(kBlock) void gat_bwd_src_final16_kernel(
+    const int32_t *__restrict__ long_rows, const int64_t *__restrict__ chunk_ptr,
+    const float *__restrict__ pacc, const float *__restrict__ pgel, uint16_t *__restrict__ gx,
+    float *__restrict__ gel, const GatDims d) {
+  gat_bwd_src_final_body<OT>(long_rows, chunk_ptr, pacc, pgel, gx, gel, d);
 }
 
 
@@ -593,10 +650,15 @@ extern "C" size_t ggl_gat_partial_bytes(int64_t n_chunks, int64_t H, int64_t C) 
 }
 
 
-extern "C" int ggl_gat_fused_fwd(const ggl_segplan_t *plan, const int32_t *col, const float *el,
-                                 const float *er, const float *x, float slope, int64_t H, int64_t C,
-                                 float p_drop, int64_t *rng_state, float *out, float *rowmax,
-                                 float *rowden, void *stream) {
+// The three launchers are written once for every storage: XT = x / gx, OT = out, GT = g and the saved out.  float
+// everywhere is the reference op (ggl_gat_fused_*); a 16-bit XT is ggl_gat_fused_*_x16.  Load forms: VEC = 4 where C % 4 == 0
+// and every vector-accessed pointer is aligned to 4 elements (16 bytes of f32, 8 of 16-bit), 16-bit rows also VEC = 8
+// (C % 8 == 0, 16 bytes), single elements otherwise.  No sum's order depends on VEC (the wide backward kernel keeps its
+// assignment, see there), so a 16-bit call computes the f32 call's bits on the widened rows whatever form it takes.
+template <typename XT, typename OT>
+static int gat_fwd_impl(const ggl_segplan_t *plan, const int32_t *col, const float *el, const float *er,
+                        const typename TT<XT>::S *x, float slope, int64_t H, int64_t C, float p_drop,
+                        int64_t *rng_state, typename TT<OT>::S *out, float *rowmax, float *rowden, void *stream) {
   GGL_REQUIRE(plan && plan->rowptr, GGL_EINVAL, "plan is NULL");
   GGL_REQUIRE(H > 0 && C > 0 && plan->chunk > 0, GGL_EINVAL, "H, C and chunk must be positive");
   const int64_t N = plan->N;
@@ -617,10 +679,13 @@ extern "C" int ggl_gat_fused_fwd(const ggl_segplan_t *plan, const int32_t *col, 
     pd = pm + plan->n_chunks * H;
     d.chunk_blocks = ceil_div(plan->n_chunks, kWavesPerBlock);
   }
-  const bool vec4 = (C % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15u) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(out) & 15u) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(pacc) & 15u) == 0) && !options().force_generic;
-  const int vec = vec4 ? 4 : 1;
+  auto vec_ok = [&](int v) {
+    return (C % v == 0) && gat_aligned<XT>(x, v) && gat_aligned<OT>(out, v) && gat_aligned<float>(pacc, v) &&
+           !options().force_generic;
+  };
+  const bool vec8 = gat_is16<XT>::value && vec_ok(8);
+  const bool vec4 = vec8 || vec_ok(4);
+  const int vec = vec8 ? 8 : (vec4 ? 4 : 1);
   d.logL = pow2_log2(ceil_div(d.K, vec));
   d.nblocks = ceil_div(N, (int64_t)kWavesPerBlock * (kWave >> d.logL));
   const int64_t grid = d.chunk_blocks + d.nblocks;
@@ -628,30 +693,45 @@ extern "C" int ggl_gat_fused_fwd(const ggl_segplan_t *plan, const int32_t *col, 
   const int32_t *order = options().row_order ? plan->row_order : nullptr;
   hipStream_t s = as_stream(stream);
 #define GGL_GAT_FWD(V, DR)                                                                              \
-  GGL_LAUNCH((gat_fwd_kernel<V, DR>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows,       \
+  GGL_LAUNCH((gat_fwd_kernel<XT, OT, V, DR>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows, \
              plan->chunk_ptr, el, er, x, out, rowmax, rowden, pacc, pm, pd, (const int64_t *)rng_state, d)
-  if (vec4 && d.drop_thresh) GGL_GAT_FWD(4, true);
+  if (vec == 8) {  // (16-bit rows only: the f32 op has no such instantiation)
+    if constexpr (gat_is16<XT>::value) {
+      if (d.drop_thresh) GGL_GAT_FWD(8, true);
+      else GGL_GAT_FWD(8, false);
+    }
+  } else if (vec4 && d.drop_thresh) GGL_GAT_FWD(4, true);
   else if (vec4) GGL_GAT_FWD(4, false);
   else if (d.drop_thresh) GGL_GAT_FWD(1, true);
   else GGL_GAT_FWD(1, false);
 #undef GGL_GAT_FWD
   GGL_LAUNCH_CHECK();
   if (plan->n_long > 0) {
-    GGL_LAUNCH((gat_long_final_kernel), plan->n_long, kBlock, s, plan->long_rows, plan->chunk_ptr,
-               (const float *)pacc, (const float *)pm, (const float *)pd, out, rowmax, rowden, d);
+    if constexpr (std::is_same<OT, float>::value)
+      GGL_LAUNCH((gat_long_final_kernel), plan->n_long, kBlock, s, plan->long_rows, plan->chunk_ptr,
+                 (const float *)pacc, (const float *)pm, (const float *)pd, out, rowmax, rowden, d);
+    else
+      GGL_LAUNCH((gat_long_final16_kernel<OT>), plan->n_long, kBlock, s, plan->long_rows, plan->chunk_ptr,
+                 (const float *)pacc, (const float *)pm, (const float *)pd, out, rowmax, rowden, d);
     GGL_LAUNCH_CHECK();
   }
   if (d.drop_thresh) return rng_advance(rng_state, stream);  // the next call draws a new mask
   return GGL_OK;
 }
 
-extern "C" int ggl_gat_fused_bwd_dst(const ggl_segplan_t *plan, const int32_t *col,
-                                     const int32_t *rowidx, const float *el, const float *er,
-                                     const float *x, const float *g, const float *out,
-                                     const float *rowmax, const float *rowden, float slope, int64_t H,
-                                     int64_t C, float p_drop, const int64_t *rng_used, float *alpha,
-                                     float *de, float *ger, float *dot_ws, void *stream) {
-  (void)rowidx; (void)dot_ws;  // needed by the first (edge-parallel) version; accepted, unused
+extern "C" int ggl_gat_fused_fwd(const ggl_segplan_t *plan, const int32_t *col, const float *el,
+                                 const float *er, const float *x, float slope, int64_t H, int64_t C,
+                                 float p_drop, int64_t *rng_state, float *out, float *rowmax,
+                                 float *rowden, void *stream) {
+  return gat_fwd_impl<float, float>(plan, col, el, er, x, slope, H, C, p_drop, rng_state, out, rowmax, rowden, stream);
+}
+
+template <typename XT, typename GT>
+static int gat_bwd_dst_impl(const ggl_segplan_t *plan, const int32_t *col, const float *el, const float *er,
+                            const typename TT<XT>::S *x, const typename TT<GT>::S *g,
+                            const typename TT<GT>::S *out, const float *rowmax, const float *rowden, float slope,
+                            int64_t H, int64_t C, float p_drop, const int64_t *rng_used, float *alpha, float *de,
+                            float *ger, void *stream) {
   GGL_REQUIRE(plan && plan->rowptr, GGL_EINVAL, "plan is NULL");
   GGL_REQUIRE(H > 0 && C > 0 && plan->chunk > 0, GGL_EINVAL, "H, C and chunk must be positive");
   const int64_t N = plan->N, E = plan->E;
@@ -676,20 +756,30 @@ extern "C" int ggl_gat_fused_bwd_dst(const ggl_segplan_t *plan, const int32_t *c
   GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "too many rows for one launch");
   const int32_t *order = options().row_order ? plan->row_order : nullptr;
   hipStream_t s = as_stream(stream);
-  const bool vec4 = (C % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15u) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(g) & 15u) == 0) && !options().force_generic;
+  constexpr bool x16 = gat_is16<XT>::value;
+  // (out is read by vectors in the wide kernel only; the f32 entry keeps its two tests, every torch allocation passes all)
+  auto vec_ok = [&](int v) {
+    return (C % v == 0) && gat_aligned<XT>(x, v) && gat_aligned<GT>(g, v) && (!x16 || gat_aligned<GT>(out, v)) &&
+           !options().force_generic;
+  };
+  const bool vec8 = x16 && vec_ok(8);
+  const bool vec4 = vec8 || vec_ok(4);
 #ifndef GGL_EMULATE
   // wide heads: lanes split the channels, shuffle-reduced dots (gat_bwd_dst_wide_kernel); needs a head count
   // the kernel is instantiated for and a head that fits one group (C <= 64 * vec)
   {
-    const int vec = vec4 ? 4 : 1;
+    // 16-bit rows: the assignment the f32 op takes on the widened (always 16-byte aligned) panel, i.e. by C alone;
+    // whether the four channels arrive in one load is d.vl
+    const bool wide4 = x16 ? ((C % 4 == 0) && !options().force_generic) : vec4;
+    d.vl = vec4 ? 1 : 0;
+    const int vec = wide4 ? 4 : 1;
     const bool h_ok = H <= 16;  // instantiated head-loop bounds: 1, 2, 4, 8, 16 (the next one >= H is used)
     if (C > 16 && h_ok && C <= 64 * vec && !options().force_generic) {
       int logg = pow2_log2(ceil_div(C, vec));
       if (logg < 4) logg = 4;  // >= 16 lanes: covers H <= 16 finishing lanes
       const int64_t wgrid = ceil_div(items << logg, (int64_t)kBlock);
 #define GGL_GAT_WIDE(V, LG, HH)                                                                          \
-  GGL_LAUNCH((gat_bwd_dst_wide_kernel<V, LG, HH>), wgrid, kBlock, s, plan->rowptr, col, order,            \
+  GGL_LAUNCH((gat_bwd_dst_wide_kernel<XT, GT, V, LG, HH>), wgrid, kBlock, s, plan->rowptr, col, order,    \
              plan->long_rows, plan->chunk_ptr, el, er, x, g, out, rowmax, rowden, alpha, de, ger, pger,   \
              rng_used, d)
 #define GGL_GAT_WIDE_H(V, LG)                                                                            \
@@ -700,7 +790,7 @@ extern "C" int ggl_gat_fused_bwd_dst(const ggl_segplan_t *plan, const int32_t *c
     else if (H <= 8) GGL_GAT_WIDE(V, LG, 8);                                                             \
     else GGL_GAT_WIDE(V, LG, 16);                                                                        \
   } while (0)
-      if (vec4) {
+      if (wide4) {
         if (logg == 4) GGL_GAT_WIDE_H(4, 4);
         else if (logg == 5) GGL_GAT_WIDE_H(4, 5);
         else GGL_GAT_WIDE_H(4, 6);
@@ -721,9 +811,15 @@ extern "C" int ggl_gat_fused_bwd_dst(const ggl_segplan_t *plan, const int32_t *c
   }
 #endif
 #define GGL_GAT_DST(V, CR)                                                                              \
-  GGL_LAUNCH((gat_bwd_dst_kernel<V, CR>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows,    \
+  GGL_LAUNCH((gat_bwd_dst_kernel<XT, GT, V, CR>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows, \
              plan->chunk_ptr, el, er, x, g, out, rowmax, rowden, alpha, de, ger, pger, rng_used, d)
-  if (vec4 && C == 8) GGL_GAT_DST(4, 8);
+  if (vec8) {  // (16-bit rows only)
+    if constexpr (x16) {
+      if (C == 8) GGL_GAT_DST(8, 8);
+      else if (C == 16) GGL_GAT_DST(8, 16);
+      else GGL_GAT_DST(8, 0);
+    }
+  } else if (vec4 && C == 8) GGL_GAT_DST(4, 8);
   else if (vec4 && C == 16) GGL_GAT_DST(4, 16);
   else if (vec4) GGL_GAT_DST(4, 0);
   else GGL_GAT_DST(1, 0);
@@ -737,12 +833,23 @@ extern "C" int ggl_gat_fused_bwd_dst(const ggl_segplan_t *plan, const int32_t *c
   return GGL_OK;
 }
 
+extern "C" int ggl_gat_fused_bwd_dst(const ggl_segplan_t *plan, const int32_t *col,
+                                     const int32_t *rowidx, const float *el, const float *er,
+                                     const float *x, const float *g, const float *out,
+                                     const float *rowmax, const float *rowden, float slope, int64_t H,
+                                     int64_t C, float p_drop, const int64_t *rng_used, float *alpha,
+                                     float *de, float *ger, float *dot_ws, void *stream) {
+  (void)rowidx; (void)dot_ws;  // needed by the first (edge-parallel) version; accepted, unused
+  return gat_bwd_dst_impl<float, float>(plan, col, el, er, x, g, out, rowmax, rowden, slope, H, C, p_drop, rng_used,
+                                        alpha, de, ger, stream);
+}
+
 // Source-major half of the backward (gat_bwd_src_kernel above).  planT->partial must hold
 // ggl_partial_bytes(GGL_F32, n_chunks, H*C + H, 0) bytes when the transposed plan has long rows.
-extern "C" int ggl_gat_fused_bwd_src(const ggl_segplan_t *planT, const int32_t *colT,
-                                     const int32_t *posT, const float *alpha, const float *de,
-                                     const float *g, int64_t H, int64_t C, float *gx, float *gel,
-                                     void *stream) {
+template <typename GT, typename OT>
+static int gat_bwd_src_impl(const ggl_segplan_t *planT, const int32_t *colT, const int32_t *posT, const float *alpha,
+                            const float *de, const typename TT<GT>::S *g, int64_t H, int64_t C,
+                            typename TT<OT>::S *gx, float *gel, void *stream) {
   GGL_REQUIRE(planT && planT->rowptr, GGL_EINVAL, "planT is NULL");
   GGL_REQUIRE(H > 0 && C > 0 && planT->chunk > 0, GGL_EINVAL, "H, C and chunk must be positive");
   const int64_t N = planT->N;
@@ -761,30 +868,96 @@ extern "C" int ggl_gat_fused_bwd_src(const ggl_segplan_t *planT, const int32_t *
     pgel = pacc + planT->n_chunks * d.K;
     d.chunk_blocks = ceil_div(planT->n_chunks, kWavesPerBlock);
   }
-  const bool vec4 = (C % 4 == 0) && ((reinterpret_cast<uintptr_t>(g) & 15u) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(gx) & 15u) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(pacc) & 15u) == 0) && !options().force_generic;
-  const int vec = vec4 ? 4 : 1;
+  auto vec_ok = [&](int v) {
+    return (C % v == 0) && gat_aligned<GT>(g, v) && gat_aligned<OT>(gx, v) && gat_aligned<float>(pacc, v) &&
+           !options().force_generic;
+  };
+  const bool vec8 = gat_is16<OT>::value && vec_ok(8);
+  const bool vec4 = vec8 || vec_ok(4);
+  const int vec = vec8 ? 8 : (vec4 ? 4 : 1);
   d.logL = pow2_log2(ceil_div(d.K, vec));
   d.nblocks = ceil_div(N, (int64_t)kWavesPerBlock * (kWave >> d.logL));
   const int64_t grid = d.chunk_blocks + d.nblocks;
   GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "too many rows for one launch");
   const int32_t *order = options().row_order ? planT->row_order : nullptr;
   hipStream_t s = as_stream(stream);
-  if (vec4)
-    GGL_LAUNCH((gat_bwd_src_kernel<4>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows,
-               planT->chunk_ptr, alpha, de, g, gx, gel, pacc, pgel, d);
-  else
-    GGL_LAUNCH((gat_bwd_src_kernel<1>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows,
-               planT->chunk_ptr, alpha, de, g, gx, gel, pacc, pgel, d);
+#define GGL_GAT_SRC(V)                                                                                          \
+  GGL_LAUNCH((gat_bwd_src_kernel<GT, OT, V>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows, \
+             planT->chunk_ptr, alpha, de, g, gx, gel, pacc, pgel, d)
+  if (vec == 8) {  // (16-bit gx only)
+    if constexpr (gat_is16<OT>::value) GGL_GAT_SRC(8);
+  } else if (vec4) GGL_GAT_SRC(4);
+  else GGL_GAT_SRC(1);
+#undef GGL_GAT_SRC
   GGL_LAUNCH_CHECK();
   if (planT->n_long > 0) {
-    GGL_LAUNCH((gat_bwd_src_final_kernel), planT->n_long, kBlock, s, planT->long_rows, planT->chunk_ptr,
-               (const float *)pacc, (const float *)pgel, gx, gel, d);
+    if constexpr (std::is_same<OT, float>::value)
+      GGL_LAUNCH((gat_bwd_src_final_kernel), planT->n_long, kBlock, s, planT->long_rows, planT->chunk_ptr,
+                 (const float *)pacc, (const float *)pgel, gx, gel, d);
+    else
+      GGL_LAUNCH((gat_bwd_src_final16_kernel<OT>), planT->n_long, kBlock, s, planT->long_rows, planT->chunk_ptr,
+                 (const float *)pacc, (const float *)pgel, gx, gel, d);
     GGL_LAUNCH_CHECK();
   }
   return GGL_OK;
 }
+
+extern "C" int ggl_gat_fused_bwd_src(const ggl_segplan_t *planT, const int32_t *colT,
+                                     const int32_t *posT, const float *alpha, const float *de,
+                                     const float *g, int64_t H, int64_t C, float *gx, float *gel,
+                                     void *stream) {
+  return gat_bwd_src_impl<float, float>(planT, colT, posT, alpha, de, g, H, C, gx, gel, stream);
+}
+
+// ---- 16-bit storage (an extension: the reference's GAT is f32 only).  Contract in include/ggl_mpops.h: the f32 entry
+// points above are F, these compute F's bits on the widened rows and round out / gx once.
+#define GGL_GAT16_PAIR(XD, OD, CALL)                                                       \
+  do {                                                                                     \
+    if ((XD) == GGL_BF16 && (OD) == GGL_BF16) { using XT = mxbf16_t; using OT = mxbf16_t; CALL; } \
+    if ((XD) == GGL_BF16 && (OD) == GGL_F32) { using XT = mxbf16_t; using OT = float; CALL; }     \
+    if ((XD) == GGL_F16 && (OD) == GGL_F16) { using XT = mxf16_t; using OT = mxf16_t; CALL; }     \
+    if ((XD) == GGL_F16 && (OD) == GGL_F32) { using XT = mxf16_t; using OT = float; CALL; }       \
+  } while (0)
+
+extern "C" int ggl_gat_fused_fwd_x16(const ggl_segplan_t *plan, const int32_t *col, const float *el, const float *er,
+                                     int x_dtype, const void *x, float slope, int64_t H, int64_t C, float p_drop,
+                                     int64_t *rng_state, int out_dtype, void *out, float *rowmax, float *rowden,
+                                     void *stream) {
+  GGL_GAT16_PAIR(x_dtype, out_dtype,
+                 return (gat_fwd_impl<XT, OT>(plan, col, el, er, static_cast<const uint16_t *>(x), slope, H, C, p_drop,
+                                              rng_state, static_cast<typename TT<OT>::S *>(out), rowmax, rowden,
+                                              stream)));
+  GGL_REQUIRE(false, GGL_EDTYPE, "gat_fused_fwd_x16: x must be bf16 / f16 and out x's dtype or f32 (got %d -> %d)",
+              x_dtype, out_dtype);
+}
+
+extern "C" int ggl_gat_fused_bwd_dst_x16(const ggl_segplan_t *plan, const int32_t *col, const float *el,
+                                         const float *er, int x_dtype, const void *x, int g_dtype, const void *g,
+                                         int out_dtype, const void *out, const float *rowmax, const float *rowden,
+                                         float slope, int64_t H, int64_t C, float p_drop, const int64_t *rng_used,
+                                         float *alpha, float *de, float *ger, void *stream) {
+  if (g_dtype == out_dtype)
+    GGL_GAT16_PAIR(x_dtype, out_dtype,
+                   return (gat_bwd_dst_impl<XT, OT>(plan, col, el, er, static_cast<const uint16_t *>(x),
+                                                    static_cast<const typename TT<OT>::S *>(g),
+                                                    static_cast<const typename TT<OT>::S *>(out), rowmax, rowden,
+                                                    slope, H, C, p_drop, rng_used, alpha, de, ger, stream)));
+  GGL_REQUIRE(false, GGL_EDTYPE,
+              "gat_fused_bwd_dst_x16: x must be bf16 / f16, out x's dtype or f32, g out's dtype (got x %d, g %d, out %d)",
+              x_dtype, g_dtype, out_dtype);
+}
+
+extern "C" int ggl_gat_fused_bwd_src_x16(const ggl_segplan_t *planT, const int32_t *colT, const int32_t *posT,
+                                         const float *alpha, const float *de, int g_dtype, const void *g, int64_t H,
+                                         int64_t C, int gx_dtype, void *gx, float *gel, void *stream) {
+  GGL_GAT16_PAIR(gx_dtype, g_dtype,  // XT = storage of gx, OT = storage of g
+                 return (gat_bwd_src_impl<OT, XT>(planT, colT, posT, alpha, de,
+                                                  static_cast<const typename TT<OT>::S *>(g), H, C,
+                                                  static_cast<uint16_t *>(gx), gel, stream)));
+  GGL_REQUIRE(false, GGL_EDTYPE, "gat_fused_bwd_src_x16: gx must be bf16 / f16 and g gx's dtype or f32 (got %d -> %d)",
+              g_dtype, gx_dtype);
+}
+#undef GGL_GAT16_PAIR
 
 // =====================================================================================================================
 // Edge softmax as an op of its own: ggl_segment_softmax_fwd / _bwd (gammagl/utils/softmax.py:29-35, the function every

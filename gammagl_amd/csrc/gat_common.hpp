@@ -20,6 +20,7 @@ struct GatDims {
   float drop_scale;      // Philox(p * H + h).x >= drop_thresh, kept alphas scaled by 1 / (1 - p)
   int64_t es;  // element stride of alpha / de: 1 = two [E,H] arrays, 2 = interleaved [E,H,2] (one 64-byte line per edge)
   int logL;
+  int vl;  // wide backward kernel on 16-bit rows: 1 = a lane's four channels are one aligned access, 0 = four single loads
 };
 
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.0f ? v : __fmul_rn(v, slope); }
@@ -61,17 +62,23 @@ __device__ __forceinline__ U4 drop_words4(int64_t b, int64_t H, int64_t h, uint6
             drop_word(4 * b + 2, H, h, offset, seed), drop_word(4 * b + 3, H, h, offset, seed)};
 }
 
-template <int VEC> struct F32V {
-  static __device__ __forceinline__ void load(const float *__restrict__ p, float (&v)[VEC]) {
+// A lane's VEC consecutive channels of a row whose elements are stored as T: float, or the 16-bit STORAGE types
+// mxbf16_t / mxf16_t (common.hpp), widened at the load (exact) and rounded once at the store.  One access of
+// VEC * sizeof(element) bytes, at most 16 (float x 8: two), so a pointer handed to VEC > 1 is aligned to that many
+// bytes (gat_aligned below); VEC = 1 reads single elements at any alignment.  The arithmetic between a load and a
+// store is f32 whatever T is.
+template <typename T, int VEC> struct RowV {
+  using S = typename TT<T>::S;
+  static __device__ __forceinline__ void load(const S *__restrict__ p, float (&v)[VEC]) {
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) v[i] = p[i];
+    for (int i = 0; i < VEC; ++i) v[i] = TT<T>::load(p[i]);
   }
-  static __device__ __forceinline__ void store(float *__restrict__ p, const float (&v)[VEC]) {
+  static __device__ __forceinline__ void store(S *__restrict__ p, const float (&v)[VEC]) {
 #pragma unroll
-    for (int i = 0; i < VEC; ++i) p[i] = v[i];
+    for (int i = 0; i < VEC; ++i) p[i] = TT<T>::store(v[i]);
   }
 };
-template <> struct F32V<4> {
+template <> struct RowV<float, 4> {
   static __device__ __forceinline__ void load(const float *__restrict__ p, float (&v)[4]) {
     const float4 t = *reinterpret_cast<const float4 *>(p);
     v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
@@ -82,6 +89,50 @@ template <> struct F32V<4> {
     *reinterpret_cast<float4 *>(p) = t;
   }
 };
+template <> struct RowV<float, 8> {  // f32 beside 16-bit rows of 8 (an f32 out / g, the hub-chunk partials): two float4
+  static __device__ __forceinline__ void load(const float *__restrict__ p, float (&v)[8]) {
+    const float4 a = reinterpret_cast<const float4 *>(p)[0], b = reinterpret_cast<const float4 *>(p)[1];
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  }
+  static __device__ __forceinline__ void store(float *__restrict__ p, const float (&v)[8]) {
+    float4 a, b;
+    a.x = v[0]; a.y = v[1]; a.z = v[2]; a.w = v[3]; b.x = v[4]; b.y = v[5]; b.z = v[6]; b.w = v[7];
+    reinterpret_cast<float4 *>(p)[0] = a;
+    reinterpret_cast<float4 *>(p)[1] = b;
+  }
+};
+// 16-bit rows: W 32-bit words = 2 W elements in one 8-byte (W = 2) or 16-byte (W = 4) access
+template <int W> struct alignas(4 * W) HWords { uint32_t w[W]; };
+template <typename T, int W> struct RowV16 {
+  static __device__ __forceinline__ void load(const uint16_t *__restrict__ p, float (&v)[2 * W]) {
+    const HWords<W> t = *reinterpret_cast<const HWords<W> *>(p);
+#pragma unroll
+    for (int i = 0; i < W; ++i) {  // little endian: the lower half-word is the lower channel
+      v[2 * i] = TT<T>::load((uint16_t)(t.w[i] & 0xffffu));
+      v[2 * i + 1] = TT<T>::load((uint16_t)(t.w[i] >> 16));
+    }
+  }
+  static __device__ __forceinline__ void store(uint16_t *__restrict__ p, const float (&v)[2 * W]) {
+    HWords<W> t;
+#pragma unroll
+    for (int i = 0; i < W; ++i) t.w[i] = (uint32_t)TT<T>::store(v[2 * i]) | ((uint32_t)TT<T>::store(v[2 * i + 1]) << 16);
+    *reinterpret_cast<HWords<W> *>(p) = t;
+  }
+};
+template <> struct RowV<mxbf16_t, 4> : RowV16<mxbf16_t, 2> {};
+template <> struct RowV<mxbf16_t, 8> : RowV16<mxbf16_t, 4> {};
+template <> struct RowV<mxf16_t, 4> : RowV16<mxf16_t, 2> {};
+template <> struct RowV<mxf16_t, 8> : RowV16<mxf16_t, 4> {};
+template <int VEC> using F32V = RowV<float, VEC>;
+
+// Can p be read / written VEC elements of T at a time?  (NULL: nothing is accessed through it.)
+template <typename T> static inline bool gat_aligned(const void *p, int vec) {
+  size_t bytes = sizeof(typename TT<T>::S) * (size_t)vec;
+  if (bytes > 16) bytes = 16;
+  return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0;
+}
+// is T one of the 16-bit storage tags (the rows of ggl_gat_fused_*_x16)?
+template <typename T> struct gat_is16 { static constexpr bool value = sizeof(typename TT<T>::S) == 2; };
 
 static inline int pow2_log2(int64_t v) {
   int l = 0;

@@ -60,6 +60,7 @@ using torch::autograd::variable_list;
   X(ggl_spmm_max) X(ggl_spmm_mean_bwd) X(ggl_spmm_max_bwd) X(ggl_bspmm_sum) X(ggl_bspmm_grad_w)                      \
   X(ggl_bspmm_grad_w_sorted_scratch_bytes) X(ggl_bspmm_grad_w_sorted)                                                \
   X(ggl_gat_partial_bytes) X(ggl_gat_fused_fwd) X(ggl_gat_fused_bwd_dst) X(ggl_gat_fused_bwd_src)                      \
+  X(ggl_gat_fused_fwd_x16) X(ggl_gat_fused_bwd_dst_x16) X(ggl_gat_fused_bwd_src_x16)                                    \
   X(ggl_gat_fast_supported) X(ggl_gat_fast_fwd) X(ggl_gat_fast_bwd) X(ggl_bias_act_fwd)                                \
   X(ggl_bias_act_bwd_workspace_bytes) X(ggl_bias_act_bwd) X(ggl_spmm_epi_ex) X(ggl_segment_epi)                        \
   X(ggl_sample_hop_workspace_bytes) X(ggl_sample_hop)                                                                \
@@ -933,23 +934,29 @@ static void reseed() {
   g_rng.clear();
 }
 
+// x may be STORED as f16 / bf16 (an extension: ggl_gat_fused_*_x16, the general kernels with f32 softmax and sums); el / er are f32
 static void gat_check(const Tensor &el, const Tensor &er, const Tensor &x) {
   same_device({&el, &er, &x});
-  f32("el", el); f32("er", er); f32("x", x);
+  f32("el", el); f32("er", er);
+  if (!is_x16(x)) f32("x", x);
   TORCH_CHECK(x.dim() == 3 && el.dim() == 2 && er.dim() == 2 && el.size(1) == x.size(1) && er.size(1) == x.size(1) &&
               el.size(0) == x.size(0), "gat_fused expects el [N_src, H], er [N_dst, H], x [N_src, H, C]");
 }
 
 // (out, rowmax, rowden, rng_used, fast): one launch (+ the hub-chunk combine inside the library)
 static std::tuple<Tensor, Tensor, Tensor, Tensor, bool> gat_forward(GraphPlan &gp, const Tensor &el_, const Tensor &er_,
-                                                                    const Tensor &x_, double slope, double p) {
+                                                                    const Tensor &x_, double slope, double p,
+                                                                    bool out_f32 = false) {
   const auto dev = x_.device();
   const Api &a = api_for(dev);
   Tensor el = el_.contiguous(), er = er_.contiguous(), x = x_.contiguous();
   TORCH_CHECK(er.size(0) == gp.N_dst && x.size(0) == gp.N_src, "gat_fused: er has ", er.size(0), " rows for ", gp.N_dst,
               " destinations, x ", x.size(0), " for ", gp.N_src, " sources");
   const int64_t N = gp.N_dst, H = x.size(1), C = x.size(2);
-  Tensor out = at::empty({N, H, C}, x.options()), rmax = at::empty({N, H}, x.options()), rden = at::empty({N, H}, x.options());
+  const bool x16 = is_x16(x);
+  TORCH_CHECK(!out_f32 || x16, "out_f32 is for f16 / bf16 rows (x is ", x.scalar_type(), ")");
+  Tensor out = at::empty({N, H, C}, out_f32 ? x.options().dtype(at::kFloat) : x.options());
+  Tensor rmax = at::empty({N, H}, el.options()), rden = at::empty({N, H}, el.options());
   Tensor part;
   if (gp.fwd->n_long > 0)
     part = at::empty({static_cast<int64_t>(a.ggl_gat_partial_bytes(gp.fwd->n_chunks, H, C)) + 16}, x.options().dtype(at::kByte));
@@ -960,10 +967,14 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor, bool> gat_forward(GraphPlan &g
     rng_used = rng.clone();   // the {seed, offset} this launch reads; the backward redraws the mask
   }
   static const bool want_fast = env_int("GGL_GAT_FAST", 1) != 0;
-  const bool fast = want_fast && a.ggl_gat_fast_supported(H, C) != 0;
+  const bool fast = !x16 && want_fast && a.ggl_gat_fast_supported(H, C) != 0;   // 16-bit rows: the general kernels
   void *st = stream_of(dev);
   int64_t *rp = rng.defined() ? rng.data_ptr<int64_t>() : nullptr;
-  if (fast)
+  if (x16)
+    check(a, a.ggl_gat_fused_fwd_x16(&cs, gp.col.data_ptr<int32_t>(), el.data_ptr<float>(), er.data_ptr<float>(), dtype_code(x),
+                                     x.data_ptr(), static_cast<float>(slope), H, C, static_cast<float>(p), rp, dtype_code(out),
+                                     out.data_ptr(), rmax.data_ptr<float>(), rden.data_ptr<float>(), st));
+  else if (fast)
     check(a, a.ggl_gat_fast_fwd(&cs, gp.col.data_ptr<int32_t>(), el.data_ptr<float>(), er.data_ptr<float>(),
                                 x.data_ptr<float>(), x.size(0), static_cast<float>(slope), H, C, static_cast<float>(p), rp,
                                 out.data_ptr<float>(), rmax.data_ptr<float>(), rden.data_ptr<float>(), st));
@@ -981,13 +992,17 @@ static std::tuple<Tensor, Tensor, Tensor> gat_backward(GraphPlan &gp, const Tens
                                                        const Tensor &rng_used, double slope, double p, bool fast) {
   const auto dev = x.device();
   const Api &a = api_for(dev);
-  Tensor g = g_.contiguous();
+  const bool x16 = is_x16(x);
+  TORCH_CHECK(!(x16 && fast), "gat_fused_backward: f16 / bf16 rows take the general kernels (fast must be false)");
+  // 16-bit rows: out is what the forward returned (x's dtype or f32) and the gradient is read in that dtype
+  Tensor g = x16 && g_.scalar_type() != out.scalar_type() ? g_.to(out.scalar_type()).contiguous() : g_.contiguous();
   const int64_t H = x.size(1), C = x.size(2);
   void *st = stream_of(dev);
   const SegPlan &fw = *gp.fwd, &bw = *gp.bwd;
-  Tensor ger = at::empty_like(er), gx = at::empty({gp.N_src, H, C}, x.options()), gel = at::empty({gp.N_src, H}, x.options());
-  // (the fast destination walk keeps four DOUBLE sums per chunk and head: 8 H floats' worth per chunk, include/ggl_mpops.h)
-  Tensor part_f = partial_for(a, fw, x, fast ? 8 * H : H, false), part_t = partial_for(a, bw, x, H * C + H, false);
+  Tensor ger = at::empty_like(er), gx = at::empty({gp.N_src, H, C}, x.options()), gel = at::empty({gp.N_src, H}, el.options());
+  // (the fast destination walk keeps four DOUBLE sums per chunk and head: 8 H floats' worth per chunk, include/ggl_mpops.h;
+  //  el is f32: the partials are, whatever x is stored as)
+  Tensor part_f = partial_for(a, fw, el, fast ? 8 * H : H, false), part_t = partial_for(a, bw, el, H * C + H, false);
   ggl_segplan_t cs = fw.c(part_f), csT = bw.c(part_t);
   const int64_t *ru = (p > 0 && rng_used.numel() == 2) ? rng_used.data_ptr<int64_t>() : nullptr;
   if (fast) {
@@ -1000,8 +1015,21 @@ static std::tuple<Tensor, Tensor, Tensor> gat_backward(GraphPlan &gp, const Tens
     return {gel, ger, gx};
   }
   // alpha and de interleaved [E, H, 2]: the source-side walk fetches both with one 64-byte line
-  Tensor ad = at::empty({std::max<int64_t>(gp.E, 1), H, 2}, x.options());
+  Tensor ad = at::empty({std::max<int64_t>(gp.E, 1), H, 2}, el.options());
   float *alpha = ad.data_ptr<float>(), *de = alpha + 1;
+  if (x16) {
+    TORCH_CHECK(out.scalar_type() == x.scalar_type() || out.scalar_type() == at::kFloat,
+                "gat_fused_backward: out must have x's dtype or Float (got ", out.scalar_type(), " for ", x.scalar_type(), ")");
+    Tensor oc = out.contiguous();
+    const int xc = dtype_code(x), gc = dtype_code(g);
+    check(a, a.ggl_gat_fused_bwd_dst_x16(&cs, gp.col.data_ptr<int32_t>(), el.data_ptr<float>(), er.data_ptr<float>(), xc,
+                                         x.data_ptr(), gc, g.data_ptr(), gc, oc.data_ptr(), rmax.data_ptr<float>(),
+                                         rden.data_ptr<float>(), static_cast<float>(slope), H, C, static_cast<float>(p), ru,
+                                         alpha, de, ger.data_ptr<float>(), st));
+    check(a, a.ggl_gat_fused_bwd_src_x16(&csT, colT.data_ptr<int32_t>(), posT.data_ptr<int32_t>(), alpha, de, gc, g.data_ptr(),
+                                         H, C, xc, gx.data_ptr(), gel.data_ptr<float>(), st));
+    return {gel, ger, gx};
+  }
   check(a, a.ggl_gat_fused_bwd_dst(&cs, gp.col.data_ptr<int32_t>(), nullptr, el.data_ptr<float>(), er.data_ptr<float>(),
                                    x.data_ptr<float>(), g.data_ptr<float>(), out.data_ptr<float>(), rmax.data_ptr<float>(),
                                    rden.data_ptr<float>(), static_cast<float>(slope), H, C, static_cast<float>(p), ru, alpha,
@@ -1025,6 +1053,18 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor, bool> gat_fused_forward_kernel
   c10::OptionalDeviceGuard guard(x.device());
   auto gp = gat_plan(index, num_nodes, x.size(0));
   return gat_forward(*gp, el, er, x, slope, p);
+}
+// gat_fused on f16 / bf16 rows with the choice of an f32 result (a last layer's logits); (out, rowmax, rowden, rng_used)
+static std::tuple<Tensor, Tensor, Tensor, Tensor> gat_x16_forward_kernel(const Tensor &index, const Tensor &el, const Tensor &er,
+                                                                         const Tensor &x, double slope, int64_t num_nodes,
+                                                                         double p, bool out_f32) {
+  gat_check(el, er, x);
+  TORCH_CHECK(is_x16(x), "gat_fused_x16 takes f16 / bf16 rows (x is ", x.scalar_type(), ")");
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout_rate must be in [0, 1)");
+  c10::OptionalDeviceGuard guard(x.device());
+  auto gp = gat_plan(index, num_nodes, x.size(0));
+  auto r = gat_forward(*gp, el, er, x, slope, p, out_f32);
+  return {std::get<0>(r), std::get<1>(r), std::get<2>(r), std::get<3>(r)};
 }
 static std::tuple<Tensor, Tensor, Tensor> gat_fused_backward_kernel(const Tensor &index, const Tensor &el, const Tensor &er,
                                                                     const Tensor &x, const Tensor &grad, const Tensor &out,
@@ -1619,6 +1659,42 @@ static Tensor gat_fused_autograd(const Tensor &index, const Tensor &el, const Te
   return GatFn::apply(index, el, er, x, slope, n, p);
 }
 
+// f16 / bf16 rows, out in x's dtype or f32: the backward is gat_fused_backward on the out this forward returned
+using GatX16FwdSig = std::tuple<Tensor, Tensor, Tensor, Tensor>(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
+                                                                double, int64_t, double, bool);
+struct GatX16Fn : public torch::autograd::Function<GatX16Fn> {
+  static Tensor forward(AutogradContext *ctx, const Tensor &index, const Tensor &el, const Tensor &er, const Tensor &x,
+                        double slope, int64_t n, double p, bool out_f32) {
+    at::AutoDispatchBelowADInplaceOrView below;
+    static auto op = op_handle<GatX16FwdSig>("ggl::gat_fused_x16_forward");
+    auto r = op.call(index, el, er, x, slope, n, p, out_f32);
+    ctx->save_for_backward({index, el, er, x, std::get<0>(r), std::get<1>(r), std::get<2>(r), std::get<3>(r)});
+    ctx->saved_data["slope"] = slope;
+    ctx->saved_data["n"] = n;
+    ctx->saved_data["p"] = p;
+    return std::get<0>(r);
+  }
+  static variable_list backward(AutogradContext *ctx, variable_list grads) {
+    auto s = ctx->get_saved_variables();
+    static auto op = op_handle<GatBwdSig>("ggl::gat_fused_backward");
+    auto r = op.call(s[0], s[1], s[2], s[3], grads[0], s[4], s[5], s[6], s[7], ctx->saved_data["slope"].toDouble(),
+                     ctx->saved_data["n"].toInt(), ctx->saved_data["p"].toDouble(), false);
+    return {Tensor(), std::get<0>(r), std::get<1>(r), std::get<2>(r), Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+static Tensor gat_fused_x16_autograd(const Tensor &index, const Tensor &el, const Tensor &er, const Tensor &x, double slope,
+                                     c10::optional<int64_t> num_nodes, double p, bool out_f32) {
+  gat_check(el, er, x);
+  TORCH_CHECK(is_x16(x), "gat_fused_x16 takes f16 / bf16 rows (x is ", x.scalar_type(), ")");
+  const int64_t n = num_nodes.has_value() ? *num_nodes : x.size(0), C = x.size(2);
+  const int64_t Cp = index.dim() == 2 ? api_for(x.device()).ggl_policy_head_channels(C, index.size(1), x.size(0)) : C;
+  if (Cp != C) {   // as gat_fused_autograd: the policy's zero pad
+    Tensor xp = at::constant_pad_nd(x, {0, Cp - C});
+    return GatX16Fn::apply(index, el, er, xp, slope, n, p, out_f32).slice(2, 0, C);
+  }
+  return GatX16Fn::apply(index, el, er, x, slope, n, p, out_f32);
+}
+
 using GatCsrFwdSig = std::tuple<Tensor, Tensor, Tensor, Tensor, bool>(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                                                                        const Tensor &, const Tensor &, const Tensor &,
                                                                        const Tensor &, double, double);
@@ -1823,9 +1899,20 @@ static std::tuple<Tensor, Tensor> bspmm_bwd_meta(const Tensor &, const Tensor &w
 
 static std::tuple<Tensor, Tensor, Tensor, Tensor, bool> gat_fwd_meta(const Tensor &, const Tensor &, const Tensor &er,
                                                                      const Tensor &x, double, int64_t n, double) {
-  auto o = x.options();
-  return {at::empty({n, x.size(1), x.size(2)}, o), at::empty({n, x.size(1)}, o), at::empty({n, x.size(1)}, o),
+  auto o = x.options(), f = er.options();   // the statistics are f32 whatever x is stored as
+  return {at::empty({n, x.size(1), x.size(2)}, o), at::empty({n, x.size(1)}, f), at::empty({n, x.size(1)}, f),
           at::empty({0}, o.dtype(at::kLong)), false};
+}
+static std::tuple<Tensor, Tensor, Tensor, Tensor> gat_x16_fwd_meta(const Tensor &, const Tensor &, const Tensor &er,
+                                                                   const Tensor &x, double, int64_t n, double, bool out_f32) {
+  auto o = out_f32 ? x.options().dtype(at::kFloat) : x.options(), f = er.options();
+  return {at::empty({n, x.size(1), x.size(2)}, o), at::empty({n, x.size(1)}, f), at::empty({n, x.size(1)}, f),
+          at::empty({0}, o.dtype(at::kLong))};
+}
+static Tensor gat_x16_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &x, double, c10::optional<int64_t> n,
+                           double, bool out_f32) {
+  return at::empty({n.has_value() ? *n : x.size(0), x.size(1), x.size(2)},
+                   out_f32 ? x.options().dtype(at::kFloat) : x.options());
 }
 static std::tuple<Tensor, Tensor, Tensor> gat_bwd_meta(const Tensor &, const Tensor &el, const Tensor &er, const Tensor &x,
                                                        const Tensor &, const Tensor &, const Tensor &, const Tensor &,
@@ -1839,8 +1926,8 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor, bool> gat_csr_fwd_meta(const T
                                                                          const Tensor &, const Tensor &, const Tensor &,
                                                                          const Tensor &, const Tensor &x, double, double) {
   const int64_t n = rp.size(0) - 1;
-  auto o = x.options();
-  return {at::empty({n, x.size(1), x.size(2)}, o), at::empty({n, x.size(1)}, o), at::empty({n, x.size(1)}, o),
+  auto o = x.options(), f = x.options().dtype(at::kFloat);
+  return {at::empty({n, x.size(1), x.size(2)}, o), at::empty({n, x.size(1)}, f), at::empty({n, x.size(1)}, f),
           at::empty({0}, o.dtype(at::kLong)), false};
 }
 static std::tuple<Tensor, Tensor, Tensor> gat_csr_bwd_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
@@ -1922,6 +2009,12 @@ TORCH_LIBRARY(ggl, m) {
   m.def("gat_fused_backward(Tensor index, Tensor el, Tensor er, Tensor x, Tensor grad, Tensor out, Tensor rowmax, "
         "Tensor rowden, Tensor rng_used, float negative_slope, int num_nodes, float dropout_rate, bool fast) -> "
         "(Tensor, Tensor, Tensor)");
+  // not in the reference: x stored as f16 / bf16 (the ops above take such rows too and return x's dtype); out_f32 keeps
+  // the f32 result
+  m.def("gat_fused_x16(Tensor index, Tensor el, Tensor er, Tensor x, float negative_slope=0.2, int? num_nodes=None, "
+        "float dropout_rate=0.0, bool out_f32=False) -> Tensor");
+  m.def("gat_fused_x16_forward(Tensor index, Tensor el, Tensor er, Tensor x, float negative_slope, int num_nodes, "
+        "float dropout_rate, bool out_f32) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("gat_fused_csr(Tensor row_ptr, Tensor col_ind, Tensor col_ptr, Tensor row_ind, Tensor permute, Tensor el, "
         "Tensor er, Tensor x, float negative_slope=0.2, float dropout_rate=0.0) -> Tensor");
   m.def("gat_fused_csr_forward(Tensor row_ptr, Tensor col_ind, Tensor col_ptr, Tensor row_ind, Tensor permute, Tensor el, "
@@ -1972,6 +2065,7 @@ TORCH_LIBRARY(ggl, m) {
     m.impl("bspmm_sum_backward", ggl_torch::bspmm_sum_backward_kernel);        \
     m.impl("gat_fused_forward", ggl_torch::gat_fused_forward_kernel);          \
     m.impl("gat_fused_backward", ggl_torch::gat_fused_backward_kernel);        \
+    m.impl("gat_fused_x16_forward", ggl_torch::gat_x16_forward_kernel);        \
     m.impl("gat_fused_csr_forward", ggl_torch::gat_csr_forward_kernel);        \
     m.impl("gat_fused_csr_backward", ggl_torch::gat_csr_backward_kernel);      \
     m.impl("bias_act_forward", ggl_torch::bias_act_forward_kernel);            \
@@ -1997,6 +2091,7 @@ TORCH_LIBRARY_IMPL(ggl, Autograd, m) {
   m.impl("spmm_sum_x16", ggl_torch::spmm_sum_x16_autograd);
   m.impl("spmm_mean_x16", ggl_torch::spmm_mean_x16_autograd);
   m.impl("gat_fused", ggl_torch::gat_fused_autograd);
+  m.impl("gat_fused_x16", ggl_torch::gat_fused_x16_autograd);
   m.impl("gat_fused_csr", ggl_torch::gat_fused_csr_autograd);
   m.impl("bias_act", ggl_torch::bias_act_autograd);
   m.impl("spmm_epi", ggl_torch::spmm_epi_autograd);
@@ -2026,6 +2121,8 @@ TORCH_LIBRARY_IMPL(ggl, Meta, m) {
   m.impl("bspmm_sum_backward", ggl_torch::bspmm_bwd_meta);
   m.impl("gat_fused", ggl_torch::gat_meta);
   m.impl("gat_fused_forward", ggl_torch::gat_fwd_meta);
+  m.impl("gat_fused_x16", ggl_torch::gat_x16_meta);
+  m.impl("gat_fused_x16_forward", ggl_torch::gat_x16_fwd_meta);
   m.impl("gat_fused_backward", ggl_torch::gat_bwd_meta);
   m.impl("gat_fused_csr", ggl_torch::gat_csr_meta);
   m.impl("gat_fused_csr_forward", ggl_torch::gat_csr_fwd_meta);

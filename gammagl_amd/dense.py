@@ -61,8 +61,11 @@ class _MatmulFn(torch.autograd.Function):
 
 
 def node_matmul(x, w):
-    """x @ w with the weight gradient as a slab-split sum (see _MatmulFn) where x is a contiguous [N, in] float matrix."""
-    if x.dim() == 2 and x.is_contiguous() and w.dim() == 2 and x.is_floating_point() and x.dtype == w.dtype:
+    """x @ w with the weight gradient as a slab-split sum (see _MatmulFn) where x is a contiguous [N, in] float matrix.
+    (Under torch.autocast the built-in matmul, as in Linear below: it casts its operands, returns the 16-bit panel and its
+    backward runs in the forward's dtype.)"""
+    if (x.dim() == 2 and x.is_contiguous() and w.dim() == 2 and x.is_floating_point() and x.dtype == w.dtype
+            and not torch.is_autocast_enabled(x.device.type)):
         return _MatmulFn.apply(x, w)
     return x @ w
 

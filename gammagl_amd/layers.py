@@ -379,7 +379,12 @@ class FusedGATConv(GATConv):
     CSR/CSC (`row_ptr`, `col_ind`, `col_ptr`, `row_ind`, `permute`) to skip its numpy preprocessing; here
     the destination-sorted plan is built on the device once per edge_index and cached, so those keywords are
     accepted and not needed.  Aggregates into edge_index[1] like GATConv (the reference's fused layer builds
-    its CSR on edge_index[0], which only coincides on symmetric graphs — SURVEY.md §8a row G)."""
+    its CSR on edge_index[0], which only coincides on symmetric graphs — SURVEY.md §8a row G).
+
+    Under torch.autocast the transformed [N, H, C] panel leaves the GEMM as bf16 / f16 and goes to the kernels as it is
+    (Engine.gat_fused on 16-bit rows: f32 softmax and sums, one rounding at the store); el / er are computed from it in f32
+    and the finish (reshape / head mean, bias) is torch's.  A head-averaging layer that takes the aggregate-first route
+    keeps it in f32: its input, the previous layer's bias + ELU, is f32."""
 
     def forward(self, x, edge_index, num_nodes=None, **kwargs):
         H, C = self.heads, self.out_channels
@@ -393,8 +398,9 @@ class FusedGATConv(GATConv):
                 and eng.gat_headmean_supported(H, x.shape[1], C)):
             # a head-averaging layer whose input row (F floats) is narrower than its H x C transformed row: aggregate
             # the input per head, transform afterwards (same math, 1408 B -> 256 B gathered per edge on the Reddit GAT)
-            y = eng.gat_headmean(edge_index, x, self.w, self.att, self.negative_slope, num_nodes=x.shape[0],
-                                 dropout_rate=self.dropout_rate, training=self.training)
+            with torch.autocast(x.device.type, enabled=False):   # f32 in, f32 GEMMs inside, f32 logits out
+                y = eng.gat_headmean(edge_index, x, self.w, self.att, self.negative_slope, num_nodes=x.shape[0],
+                                     dropout_rate=self.dropout_rate, training=self.training)
             # (bias_add: the bias gradient as the library's two-stage column sum instead of a torch reduce over [N, C])
             return eng.bias_add(y, self.bias) if self.bias is not None else y
         w = self.w
@@ -402,8 +408,9 @@ class FusedGATConv(GATConv):
         if pad:  # e.g. 41 classes per head: 44 channels inside the GEMM keep the kernels on 16-byte slices
             w = torch.nn.functional.pad(w.reshape(-1, H, C), (0, pad)).reshape(-1, H * (C + pad))
         x = node_matmul(x, w).reshape(-1, H, C + pad)
-        el = (x[:, :, :C] * self.att[:, :, :C]).sum(dim=-1)   # source term  a_src . x_j
-        er = (x[:, :, :C] * self.att[:, :, C:]).sum(dim=-1)   # destination term a_dst . x_i
+        xf = x[:, :, :C].float()                      # (x itself when it is f32) the logit terms are f32 whatever x is stored as
+        el = (xf * self.att[:, :, :C]).sum(dim=-1)    # source term  a_src . x_j
+        er = (xf * self.att[:, :, C:]).sum(dim=-1)    # destination term a_dst . x_i
         x = _engine(x).gat_fused(edge_index, el, er, x, self.negative_slope, num_nodes=num_nodes,
                                 dropout_rate=self.dropout_rate, training=self.training)
         return self._finish(x[:, :, :C] if pad else x)

@@ -1124,13 +1124,16 @@ class Engine:
                 return None, gw, gx
 
         class GATFused(torch.autograd.Function):
-            """edge-softmax + aggregate in one kernel (gat_conv.py:103-112 + softmax.py:29-35)."""
+            """edge-softmax + aggregate in one kernel (gat_conv.py:103-112 + softmax.py:29-35).  bf16 / f16 x (an
+            extension, ggl_gat_fused_*_x16): the general kernels on 16-bit rows, f32 softmax and sums, out in x's dtype
+            (or f32 with out_dtype); the backward reads x16 and the out RETURNED here, no f32 copy of either is kept."""
 
             @staticmethod
-            def forward(ctx, gp, el, er, x, slope, p_drop=0.0):
+            def forward(ctx, gp, el, er, x, slope, p_drop=0.0, out_dtype=None):
                 dev = x.device
                 N, H, C = gp.N_dst, int(x.shape[1]), int(x.shape[2])
-                out = torch.empty((N, H, C), dtype=torch.float32, device=dev)
+                x16 = x.dtype in _X16_DTYPES
+                out = torch.empty((N, H, C), dtype=(out_dtype or x.dtype) if x16 else torch.float32, device=dev)
                 rmax = torch.empty((N, H), dtype=torch.float32, device=dev)
                 rden = torch.empty((N, H), dtype=torch.float32, device=dev)
                 part = None
@@ -1142,8 +1145,13 @@ class Engine:
                 if p_drop > 0:
                     rng = eng._rng_state(dev)
                     rng_used = rng.clone()  # the {seed, offset} this launch reads; the backward redraws the mask
-                fast = bool(eng.gat_fast and eng.lib.ggl_gat_fast_supported(H, C))
-                if fast:
+                fast = bool(not x16 and eng.gat_fast and eng.lib.ggl_gat_fast_supported(H, C))
+                if x16:
+                    eng._check(eng.lib.ggl_gat_fused_fwd_x16(
+                        ctypes.byref(cs), _ptr(gp.col), _ptr(el), _ptr(er), _DTYPE_CODE[x.dtype], _ptr(x), float(slope),
+                        H, C, float(p_drop), _ptr(rng), _DTYPE_CODE[out.dtype], _ptr(out), _ptr(rmax), _ptr(rden),
+                        eng._stream(dev)))
+                elif fast:
                     eng._check(eng.lib.ggl_gat_fast_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(el), _ptr(er), _ptr(x),
                                                         int(x.shape[0]), float(slope), H, C, float(p_drop), _ptr(rng),
                                                         _ptr(out), _ptr(rmax), _ptr(rden), eng._stream(dev)))
@@ -1164,6 +1172,9 @@ class Engine:
                 dev = g.device
                 H, C = int(x.shape[1]), int(x.shape[2])
                 st = eng._stream(dev)
+                x16 = x.dtype in _X16_DTYPES
+                if x16 and g.dtype != out.dtype:
+                    g = g.to(out.dtype)
                 if ctx.fast:  # both walks recompute alpha / de from per-row constants: no [E, H, 2] buffer
                     bwd = gp.bwd
                     stats = torch.empty((gp.N_dst, H, 4), dtype=torch.float32, device=dev)
@@ -1178,26 +1189,38 @@ class Engine:
                         ctypes.byref(cs), _ptr(gp.col), ctypes.byref(csT), _ptr(gp.colT), _ptr(posT), _ptr(el),
                         _ptr(er), _ptr(x), _ptr(g), _ptr(out), _ptr(rmax), _ptr(rden), ctx.slope, H, C, ctx.p_drop,
                         _ptr(ctx.rng_used), _ptr(stats), _ptr(gx), _ptr(gel), _ptr(ger), st))
-                    return None, gel, ger, gx, None, None
+                    return None, gel, ger, gx, None, None, None
                 # alpha and de interleaved [E, H, 2]: the source-side walk fetches both with one 64-byte line
                 ad = torch.empty((max(gp.E, 1), H, 2), dtype=torch.float32, device=dev)
                 alpha, de = ad.data_ptr(), ad.data_ptr() + 4
                 ger = torch.empty_like(er)
                 part_f = eng._partial(gp.fwd, torch.float32, H, False, dev)  # must outlive the launch
                 cs = gp.fwd.c_struct(part_f)
-                eng._check(eng.lib.ggl_gat_fused_bwd_dst(
-                    ctypes.byref(cs), _ptr(gp.col), None, _ptr(el), _ptr(er), _ptr(x),
-                    _ptr(g), _ptr(out), _ptr(rmax), _ptr(rden), ctx.slope, H, C, ctx.p_drop,
-                    _ptr(ctx.rng_used), alpha, de, _ptr(ger), None, st))
+                xc, gc = _DTYPE_CODE.get(x.dtype), _DTYPE_CODE.get(g.dtype)
+                if x16:
+                    eng._check(eng.lib.ggl_gat_fused_bwd_dst_x16(
+                        ctypes.byref(cs), _ptr(gp.col), _ptr(el), _ptr(er), xc, _ptr(x), gc, _ptr(g), gc, _ptr(out),
+                        _ptr(rmax), _ptr(rden), ctx.slope, H, C, ctx.p_drop, _ptr(ctx.rng_used), alpha, de, _ptr(ger),
+                        st))
+                else:
+                    eng._check(eng.lib.ggl_gat_fused_bwd_dst(
+                        ctypes.byref(cs), _ptr(gp.col), None, _ptr(el), _ptr(er), _ptr(x),
+                        _ptr(g), _ptr(out), _ptr(rmax), _ptr(rden), ctx.slope, H, C, ctx.p_drop,
+                        _ptr(ctx.rng_used), alpha, de, _ptr(ger), None, st))
                 bwd = gp.bwd
-                gx = torch.empty((gp.N_src, H, C), dtype=torch.float32, device=dev)
+                gx = torch.empty((gp.N_src, H, C), dtype=x.dtype, device=dev)
                 gel = torch.empty((gp.N_src, H), dtype=torch.float32, device=dev)
                 part = eng._partial(bwd, torch.float32, H * C + H, False, dev)  # gx and gel partials of long rows
                 csT = bwd.c_struct(part)
-                eng._check(eng.lib.ggl_gat_fused_bwd_src(ctypes.byref(csT), _ptr(gp.colT), _ptr(gp.posT),
-                                                         alpha, de, _ptr(g), H, C,
-                                                         _ptr(gx), _ptr(gel), st))
-                return None, gel, ger, gx, None, None
+                if x16:
+                    eng._check(eng.lib.ggl_gat_fused_bwd_src_x16(ctypes.byref(csT), _ptr(gp.colT), _ptr(gp.posT),
+                                                                 alpha, de, gc, _ptr(g), H, C, xc, _ptr(gx), _ptr(gel),
+                                                                 st))
+                else:
+                    eng._check(eng.lib.ggl_gat_fused_bwd_src(ctypes.byref(csT), _ptr(gp.colT), _ptr(gp.posT),
+                                                             alpha, de, _ptr(g), H, C,
+                                                             _ptr(gx), _ptr(gel), st))
+                return None, gel, ger, gx, None, None, None
 
         class BiasAdd(torch.autograd.Function):
             """out = x + bias (bias broadcast over rows); d bias = column sums of the gradient."""
@@ -1625,12 +1648,17 @@ class Engine:
             return self.BSpMMSum.apply(gp, weight, xp.contiguous())[:, :, :C]
         return self.BSpMMSum.apply(gp, weight, x)
 
-    def gat_fused(self, index, el, er, x, negative_slope=0.2, num_nodes=None, dropout_rate=0.0, training=True):
+    def gat_fused(self, index, el, er, x, negative_slope=0.2, num_nodes=None, dropout_rate=0.0, training=True,
+                  out_dtype=None):
         """out[i,h,:] = sum_{j->i} dropout(softmax_i(LeakyReLU(el[j,h] + er[i,h]))) * x[j,h,:]
-        (dropout on the attention coefficients as gat_conv.py:104 / GATConvFuse(..., dropout_rate))."""
+        (dropout on the attention coefficients as gat_conv.py:104 / GATConvFuse(..., dropout_rate)).
+        x may be STORED as bf16 / f16 (an extension; el / er stay f32): the softmax and the sums are the f32 op's on the
+        widened rows, out is rounded once to x's dtype, or returned unrounded with out_dtype=torch.float32."""
         self._dev(index, el, er, x)
-        for n, t in (("el", el), ("er", er), ("x", x)):
+        for n, t in (("el", el), ("er", er)):
             self._check_f32(n, t)
+        self._check_f32_or_x16("x", x)
+        out_dtype = self._out_dtype(x, out_dtype)
         n = x.shape[0] if num_nodes is None else num_nodes
         gp = index if isinstance(index, GraphPlan) else self.graph_plan(index, n, x.shape[0])
         p = float(dropout_rate) if training else 0.0
@@ -1642,10 +1670,11 @@ class Engine:
             # e.g. 41 classes per head: one zero-padded copy of x ([N,H,44]) keeps every walk on 16-byte slices
             # (Reddit-sized, 8 x 41: forward 50 -> 20 ms); the pad channels aggregate to zero and are dropped
             xp = torch.nn.functional.pad(x, (0, Cp - C))
-            out = self.GATFused.apply(gp, el.contiguous(), er.contiguous(), xp.contiguous(), negative_slope, p)
+            out = self.GATFused.apply(gp, el.contiguous(), er.contiguous(), xp.contiguous(), negative_slope, p,
+                                      out_dtype)
             return out[:, :, :C]
         return self.GATFused.apply(gp, el.contiguous(), er.contiguous(), x.contiguous(),
-                                   negative_slope, p)
+                                   negative_slope, p, out_dtype)
 
     def _check_weight(self, weight, gp):
         """An edge-weight vector handed to a kernel as a raw pointer: f32 (spmm_sum_cpu.cpp:22 would raise

@@ -16,9 +16,11 @@ points (+ the fused GAT op and the fused epilogue) are dispatcher ops:
     torch.ops.gammagl_amd.bias_act(a, bias, relu, p_drop) -> Tensor
     torch.ops.gammagl_amd.spmm_sum_x16(index, weight, x, out_f32) -> Tensor   (not in the reference, see below)
     torch.ops.gammagl_amd.spmm_mean_x16(index, weight, x, out_f32) -> Tensor
+    torch.ops.gammagl_amd.gat_fused_x16(index, el, er, x, negative_slope, num_nodes, dropout_rate, out_f32) -> Tensor
 
 ``spmm_sum`` / ``spmm_mean`` also take ``x`` stored as bf16 / f16 (the reference is f32 only): the sums are made in f32 and
-rounded once to x's dtype.  ``spmm_*_x16(..., out_f32=True)`` returns those f32 sums unrounded.
+rounded once to x's dtype.  ``spmm_*_x16(..., out_f32=True)`` returns those f32 sums unrounded.  ``gat_fused`` does the
+same for its ``x`` (``el`` / ``er`` stay f32; softmax and sums in f32), ``gat_fused_x16`` adds the ``out_f32`` choice.
 
 Kernels are registered for ``CUDA`` / ``AutogradCUDA`` (= HIP on ROCm: libggl_mpops_hip.so) and for ``CPU`` /
 ``AutogradCPU`` (libggl_mpops_host.so, the host build of the same kernel sources) — the reference's ops dispatch
@@ -48,6 +50,8 @@ _SCHEMAS = {
     "bias_act": "(Tensor a, Tensor? bias, bool relu, float p_drop) -> Tensor",
     "spmm_sum_x16": "(Tensor index, Tensor? weight, Tensor x, bool out_f32=False) -> Tensor",
     "spmm_mean_x16": "(Tensor index, Tensor? weight, Tensor x, bool out_f32=False) -> Tensor",
+    "gat_fused_x16": "(Tensor index, Tensor el, Tensor er, Tensor x, float negative_slope=0.2, "
+                     "int? num_nodes=None, float dropout_rate=0.0, bool out_f32=False) -> Tensor",
 }
 
 _DEF = Library(NS, "DEF")
@@ -73,7 +77,16 @@ def _kernels(get_engine):
         "bias_act": lambda a, bias, relu, p_drop: get_engine().bias_act(a, bias, relu, p_drop, True),
         "spmm_sum_x16": lambda index, weight, x, out_f32=False: _x16(get_engine().c_spmm_sum, index, weight, x, out_f32),
         "spmm_mean_x16": lambda index, weight, x, out_f32=False: _x16(get_engine().c_spmm_mean, index, weight, x, out_f32),
+        "gat_fused_x16": lambda index, el, er, x, negative_slope=0.2, num_nodes=None, dropout_rate=0.0, out_f32=False:
+            _gat_x16(get_engine(), index, el, er, x, negative_slope, num_nodes, dropout_rate, out_f32),
     }
+
+
+def _gat_x16(eng, index, el, er, x, negative_slope, num_nodes, dropout_rate, out_f32):
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError(f"gat_fused_x16 takes f16 / bf16 rows (x is {x.dtype})")
+    return eng.gat_fused(index, el, er, x, negative_slope, num_nodes, dropout_rate, True,
+                         out_dtype=torch.float32 if out_f32 else None)
 
 
 def _x16(fn, index, weight, x, out_f32):
@@ -122,12 +135,16 @@ def _register_fakes():
         n = x.shape[0] if num_nodes is None else num_nodes
         return x.new_empty((n,) + tuple(x.shape[1:]))
 
+    def gat_x16(index, el, er, x, negative_slope=0.2, num_nodes=None, dropout_rate=0.0, out_f32=False):
+        n = x.shape[0] if num_nodes is None else num_nodes
+        return x.new_empty((n,) + tuple(x.shape[1:]), dtype=torch.float32 if out_f32 else x.dtype)
+
     for name, fn in (("segment_sum", seg), ("segment_mean", seg), ("segment_max", seg_max),
                      ("segment_softmax", lambda x, index, N: torch.empty_like(x)),
                      ("spmm_sum", like_x), ("spmm_mean", like_x), ("spmm_max", like_x),
                      ("bspmm_sum", like_x), ("gat_fused", gat),
                      ("bias_act", lambda a, bias, relu, p_drop: torch.empty_like(a)),
-                     ("spmm_sum_x16", like_x16), ("spmm_mean_x16", like_x16)):
+                     ("spmm_sum_x16", like_x16), ("spmm_mean_x16", like_x16), ("gat_fused_x16", gat_x16)):
         lib.impl(name, fn, "Meta")
     _IMPLS.append(lib)
 

@@ -61,6 +61,8 @@ extern "C" {
  *   hop_fused_scans, hop_small_scans, hub_priority, hub_pipe and maxbwd_mask_{scatter,wlane,cols} no longer exist (set answers
  *   GGL_EINVAL, get -1); ggl_sample_hop_workspace_bytes shrinks; + ggl_option_name (the option table's enumerator); every
  *   option reads GGL_<NAME> from the environment.  No struct change. */
+/* still 11: + ggl_gat_fused_{fwd,bwd_dst,bwd_src}_x16 (the fused GAT on bf16 / f16 rows).  Purely additive, as the _x16
+ *   aggregates were in 10. */
 #define GGL_ABI_VERSION 11
 
 /* dtype codes (AT_DISPATCH_ALL_TYPES_AND2(Half, BFloat16), segment_sum_cpu.cpp:32-33) */
@@ -461,6 +463,31 @@ int ggl_gat_fused_bwd_dst(const ggl_segplan_t *plan, const int32_t *col, const i
 int ggl_gat_fused_bwd_src(const ggl_segplan_t *planT, const int32_t *colT, const int32_t *posT,
                           const float *alpha, const float *de, const float *g, int64_t H,
                           int64_t C, float *gx, float *gel, void *stream);
+/* 16-bit STORAGE forms of the three walks above (an extension: the reference's GAT is f32 only; ABI still 11, the symbols are
+ * purely additive).  x [N_src,H,C] is GGL_BF16 or GGL_F16 (x_dtype); out is x_dtype or GGL_F32 (a last layer's logits); g has
+ * out's dtype (g_dtype == out_dtype) and `out` in the backward is the tensor the forward RETURNED (rounded, if it was rounded:
+ * no f32 copy is kept); gx has x's dtype.  Any other dtype pair returns GGL_EDTYPE.  el, er, rowmax, rowden, alpha, de, gel, ger
+ * and every hub-chunk partial stay f32: plan->partial is sized as for the f32 entry points (ggl_gat_partial_bytes,
+ * ggl_partial_bytes(GGL_F32, ...)).  x, g and out are widened at the load (exact), every operation in between is the f32 one
+ * of ggl_gat_fused_fwd / _bwd_dst / _bwd_src (call them F) in F's order, and out / gx are rounded ONCE, at the store:
+ *   forward   out(x16)          == F.out(x16 as f32) rounded to x_dtype      bit for bit
+ *             out(x16, GGL_F32) == F.out(x16 as f32)                         bit for bit
+ *             rowmax, rowden    == F's                                       bit for bit
+ *   backward  alpha, de, gel, ger == F_bwd(x16 as f32, g as f32, out as f32, rowmax, rowden)'s, gx == that gx rounded to x_dtype
+ * (F is NOT ggl_gat_fast_*, which is held to a tolerance.)  The attention-dropout word depends on (position, head, seed, offset)
+ * only, so with the same rng values the mask is F's.  A lane reads 16 bytes (8 channels) where C % 8 == 0 and the pointers
+ * are 16-byte aligned, 8 bytes where C % 4 == 0 and they are 8-byte aligned, single elements otherwise (a panel that starts one
+ * element into a buffer is fine); the bits do not depend on which. */
+int ggl_gat_fused_fwd_x16(const ggl_segplan_t *plan, const int32_t *col, const float *el, const float *er, int x_dtype,
+                          const void *x, float slope, int64_t H, int64_t C, float p_drop, int64_t *rng_state,
+                          int out_dtype, void *out, float *rowmax, float *rowden, void *stream);
+int ggl_gat_fused_bwd_dst_x16(const ggl_segplan_t *plan, const int32_t *col, const float *el, const float *er,
+                              int x_dtype, const void *x, int g_dtype, const void *g, int out_dtype, const void *out,
+                              const float *rowmax, const float *rowden, float slope, int64_t H, int64_t C, float p_drop,
+                              const int64_t *rng_used, float *alpha, float *de, float *ger, void *stream);
+int ggl_gat_fused_bwd_src_x16(const ggl_segplan_t *planT, const int32_t *colT, const int32_t *posT, const float *alpha,
+                              const float *de, int g_dtype, const void *g, int64_t H, int64_t C, int gx_dtype, void *gx,
+                              float *gel, void *stream);
 /* Fast path of the same op for heads of C = 4, 8, 16, 32 or 64 channels with H * C <= 256
  * (ggl_gat_fast_supported; e.g. the Reddit GAT's 8 x 8): same walks with ~5x fewer vector-ALU instructions
  * (v_exp_f32, one rescale per 4-8 edges, 16-byte index loads, 32-bit panel offsets, FMA) and a backward that

@@ -1,0 +1,179 @@
+"""The fused GAT on 16-bit rows (bf16 / f16 storage of x, g, out, gx; f32 softmax, sums and statistics; one rounding at the
+store: ggl_gat_fused_{fwd,bwd_dst,bwd_src}_x16) on the HOST library, CPU tensors, through the ctypes engine, the C++-registered
+``torch.ops.ggl`` and the Python-registered ``torch.ops.gammagl_amd``.  Every comparison is on the bits.
+Cases: tests/gat16_cases.py."""
+import ctypes
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+import torch
+
+import gat16_cases as gc
+import spmm16_cases as sc
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(HERE)
+DEV = torch.device("cpu")
+KINDS = gc.KINDS + ("rectangular",)
+
+
+@pytest.fixture(scope="module")
+def eng():
+    subprocess.check_call(["make", "-s", "-C", os.path.join(REPO, "gammagl_amd", "csrc"), "host", "torch"])
+    import gammagl_amd
+
+    return gammagl_amd.host_engine()
+
+
+@pytest.fixture(scope="module")
+def routes(eng):
+    return gc.make_routes(eng)
+
+
+def test_gat_fused_accepts_16_bit_rows(routes):
+    """Fails on the parent commit: gat_fused raised "expected scalar type Float" for bf16 / f16 x on every route."""
+    gc.check_accepts(routes, DEV)
+
+
+def test_still_refuses_what_it_refused(routes, eng):
+    gc.check_refusals(routes, eng, DEV)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_contract_bit_for_bit(routes, eng, kind):
+    """out, rowmax / rowden, alpha / de, gel, ger, gx against the general f32 op on the widened rows: every head shape of the
+    table, both dtypes, with and without attention dropout, 16-bit and f32 out, the C ABI and all three routes."""
+    n = gc.check_contract(routes, eng, DEV, kind)
+    assert n == len(gc.SHAPES) * len(gc.DTYPES) * 2
+
+
+def test_contract_on_a_plan_with_long_rows(eng):
+    gc.check_long_rows(eng, DEV)
+
+
+def test_sums_are_made_in_f32(routes):
+    gc.check_f32_accumulation(routes, DEV)
+
+
+def test_a_panel_one_element_into_its_buffer(eng):
+    gc.check_alignment(eng, DEV)
+
+
+def test_fusedgatconv_under_autocast_is_its_parts(eng):
+    gc.check_layer_parts(eng, DEV)
+
+
+def test_gat_model_under_autocast(eng):
+    gc.check_model_autocast(DEV)
+
+
+def test_gat_trainer_example_runs_with_amp_bf16():
+    """examples/gat_trainer_amd.py --gpu -1 --amp bf16: exits 0, the loss decreases, the accuracy beats chance (7 classes) by
+    the margin tests/test_spmm16_host.py asks of the GCN example."""
+    env = {k: v for k, v in os.environ.items() if k != "GGL_BENCH_EMUL"}
+    r = subprocess.run([sys.executable, os.path.join(REPO, "examples", "gat_trainer_amd.py"), "--gpu", "-1", "--n_epoch", "12",
+                        "--amp", "bf16"], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    losses = [float(m) for m in re.findall(r"train loss: ([0-9.]+)", r.stdout)]
+    assert len(losses) >= 2 and losses[-1] < losses[0], r.stdout[-1000:]
+    acc = float(re.search(r"Test acc:\s+([0-9.]+)", r.stdout).group(1))
+    assert acc > 1.0 / 7 + 0.1, r.stdout[-500:]
+
+
+def test_dispatcher_contracts(routes):
+    """schemas, Meta kernels and autograd registration of the ops that now take 16-bit rows and of gat_fused_x16; the forward /
+    backward ops on their own"""
+    from gammagl_amd import cpp_ops, torch_ops
+
+    g = torch.Generator().manual_seed(3)
+    ei = sc.make_index("uniform", 11, 60, g, DEV)
+    el, er, xf, go = gc.make_inputs(11, 11, 2, 8, g, DEV)
+    x, go = xf.bfloat16(), go.bfloat16()
+    utils = ("test_schema", "test_faketensor", "test_autograd_registration")
+    C = cpp_ops.load()
+    for ns in (C, torch_ops.ops):
+        torch.library.opcheck(ns.gat_fused.default, (ei, el, er, x, 0.2, 11, 0.0), test_utils=utils)
+        torch.library.opcheck(ns.gat_fused.default, (ei, el.clone().requires_grad_(True), er.clone().requires_grad_(True),
+                                                     x.clone().requires_grad_(True), 0.2, 11, 0.0), test_utils=utils)
+        for f32 in (False, True):
+            torch.library.opcheck(ns.gat_fused_x16.default, (ei, el, er, x.clone().requires_grad_(True), 0.2, 11, 0.0, f32),
+                                  test_utils=utils)
+        assert ns.gat_fused_x16(ei, el, er, x, 0.2, 11, 0.0, True).dtype == torch.float32
+        assert ns.gat_fused_x16(ei, el, er, x, 0.2, 11, 0.0, False).dtype == torch.bfloat16
+        with pytest.raises(RuntimeError):
+            ns.gat_fused_x16(ei, el, er, xf, 0.2, 11, 0.0, True)
+    two = ("test_schema", "test_faketensor")
+    torch.library.opcheck(C.gat_fused_forward.default, (ei, el, er, x, 0.2, 11, 0.0), test_utils=two)
+    torch.library.opcheck(C.gat_fused_x16_forward.default, (ei, el, er, x, 0.2, 11, 0.0, True), test_utils=two)
+    out, rmax, rden, rng_used, fast = C.gat_fused_forward(ei, el, er, x, 0.2, 11, 0.0)
+    assert out.dtype == torch.bfloat16 and rmax.dtype == rden.dtype == torch.float32 and not fast
+    torch.library.opcheck(C.gat_fused_backward.default, (ei, el, er, x, go, out, rmax, rden, rng_used, 0.2, 11, 0.0, False),
+                          test_utils=two)
+    ea, ra, xa = (t.clone().requires_grad_(True) for t in (el, er, x))
+    C.gat_fused(ei, ea, ra, xa, 0.2, 11, 0.0).backward(go)
+    gel, ger, gx = C.gat_fused_backward(ei, el, er, x, go, out, rmax, rden, rng_used, 0.2, 11, 0.0, False)
+    assert sc.same_bits(gel, ea.grad) and sc.same_bits(ger, ra.grad) and sc.same_bits(gx, xa.grad)
+    with pytest.raises(RuntimeError):
+        C.gat_fused_backward(ei, el, er, x, go, out, rmax, rden, rng_used, 0.2, 11, 0.0, True)     # no 16-bit fast path
+    # the caller's CSR (dgNN's GATConvFuse argument list) takes the 16-bit panel too, and gives the edge-list op's bits
+    from gammagl_amd.compat.dgNN.operators import GATConvFuse
+
+    order = torch.argsort(ei[1], stable=True)
+    src, dst = ei[0][order], ei[1][order]
+    row_ptr = torch.zeros(12, dtype=torch.int64)
+    row_ptr[1:] = torch.cumsum(torch.bincount(dst, minlength=11), 0)
+    t_order = torch.argsort(src, stable=True)
+    col_ptr = torch.zeros(12, dtype=torch.int64)
+    col_ptr[1:] = torch.cumsum(torch.bincount(src, minlength=11), 0)
+    csr = (row_ptr.int(), src.int(), col_ptr.int(), dst[t_order].int(), t_order.int())
+    got = GATConvFuse(er, el, *csr, 0.2, x, 0.0)
+    assert sc.same_bits(got, out)
+    torch.library.opcheck(C.gat_fused_csr.default, (*csr, el, er, x.clone().requires_grad_(True), 0.2, 0.0), test_utils=utils)
+
+
+def test_c_abi_surface(eng):
+    """the additive entry points: every wrong dtype pair is GGL_EDTYPE, and the ABI number stays"""
+    from gammagl_amd import _lib
+
+    assert _lib.ABI_VERSION == 11 and eng.lib.ggl_abi_version() == 11
+    g = torch.Generator().manual_seed(4)
+    ei = sc.make_index("uniform", 40, 300, g, DEV)
+    gp = eng.graph_plan(ei, 40)
+    H, C = 2, 8
+    el, er, xf, _ = gc.make_inputs(40, 40, H, C, g, DEV)
+    x = xf.bfloat16()
+    out, gbuf, gxbuf = (torch.zeros(40, H, C, dtype=torch.float64) for _ in range(3))    # roomy for every dtype tried
+    rmax, rden = torch.zeros(40, H), torch.zeros(40, H)
+    ad = torch.zeros(300, H, 2)
+    gel, ger = torch.zeros(40, H), torch.zeros(40, H)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    al, de = ad.data_ptr(), ad.data_ptr() + 4
+    cs, csT = gp.fwd.c_struct(None), gp.bwd.c_struct(None)
+    L = eng.lib
+    BF16, F16, F32, F64 = 6, 5, 7, 8
+
+    def fwd(xd, od):
+        return L.ggl_gat_fused_fwd_x16(ctypes.byref(cs), p(gp.col), p(el), p(er), xd, p(x), 0.2, H, C, 0.0, None, od, p(out),
+                                       p(rmax), p(rden), None)
+
+    def dst(xd, gd, od):
+        return L.ggl_gat_fused_bwd_dst_x16(ctypes.byref(cs), p(gp.col), p(el), p(er), xd, p(x), gd, p(gbuf), od, p(out), p(rmax),
+                                           p(rden), 0.2, H, C, 0.0, None, al, de, p(ger), None)
+
+    def src(gd, xd):
+        return L.ggl_gat_fused_bwd_src_x16(ctypes.byref(csT), p(gp.colT), p(gp.posT), al, de, gd, p(gbuf), H, C, xd, p(gxbuf),
+                                           p(gel), None)
+
+    assert _lib.GGL_EDTYPE == -3
+    for xd, od in ((F32, F32), (F32, BF16), (BF16, F16), (F16, BF16), (BF16, F64), (F64, F64), (F64, F32)):
+        assert fwd(xd, od) == _lib.GGL_EDTYPE, (xd, od)
+        assert dst(xd, od, od) == _lib.GGL_EDTYPE, (xd, od)
+        assert src(od, xd) == _lib.GGL_EDTYPE, (xd, od)
+    for xd, gd, od in ((BF16, F32, BF16), (BF16, BF16, F32), (F16, F32, F16), (BF16, F16, F16)):    # g follows out
+        assert dst(xd, gd, od) == _lib.GGL_EDTYPE, (xd, gd, od)
+    assert b"bf16 / f16" in L.ggl_last_error()
+    for xd, od in ((BF16, BF16), (BF16, F32), (F16, F16), (F16, F32)):
+        assert fwd(xd, od) == 0 and dst(xd, od, od) == 0 and src(od, xd) == 0, (xd, od)
