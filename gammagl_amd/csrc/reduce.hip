@@ -1260,31 +1260,11 @@ extern "C" int ggl_spmm_sum_ex(const ggl_segplan_t *plan, const int32_t *col, co
   return launch_f32_cols<OP_SUM, MODE_SPMM>(a, as_stream(stream));
 }
 
-// out = dropout(relu(A x + bias)) with the epilogue applied to each finished row in registers: what
-// ggl_spmm_sum followed by ggl_bias_act_fwd computes (same rounded operations, same dropout mask for the
-// same rng state), minus one write and one read of [N, K].
-extern "C" int ggl_spmm_sum_bias_act(const ggl_segplan_t *plan, const int32_t *col, const float *w,
-                                     int w_by_pos, const float *x, int64_t K, const float *bias, int relu,
-                                     float p_drop, int64_t *rng_state, float *out, void *stream) {
-  ReduceArgs a{};
-  int rc = spmm_common(a, plan, col, w, w_by_pos, x, K, out, false);
-  if (rc) return rc;
-  GGL_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, GGL_EINVAL, "p_drop must be in [0, 1)");
-  GGL_REQUIRE(p_drop == 0.0f || rng_state, GGL_EINVAL, "dropout needs an rng_state");
-  a.epi_bias = bias;
-  a.epi_rng = rng_state;
-  a.epi_relu = relu ? 1 : 0;
-  a.epi_thresh = p_drop > 0.0f ? (uint32_t)((double)p_drop * 4294967296.0) : 0u;
-  a.epi_scale = p_drop > 0.0f ? 1.0f / (1.0f - p_drop) : 1.0f;
-  rc = launch_f32_cols<OP_SUM, MODE_SPMM_EPI>(a, as_stream(stream));
-  if (rc) return rc;
-  if (a.epi_thresh && plan->N > 0 && K > 0) return rng_advance(rng_state, stream);
-  return GGL_OK;
-}
-
-// The general epilogue form behind ggl_spmm_sum_bias_act: sum or mean, strided x / out (a column block of a
-// wider matrix), accumulate (a second edge set added onto an existing partial result: the halo-source edges of
-// the multi-GPU path, whose epilogue therefore rides on the LAST block added), an extra per-row term
+// out = dropout(relu(reduce(A x) + add + bias)) with the epilogue applied to each finished row in registers: what
+// ggl_spmm_sum / ggl_spmm_mean followed by the adds and ggl_bias_act_fwd compute (same rounded operations, same
+// dropout mask for the same rng state), minus one write and one read of [N, K].  Sum or mean, strided x / out (a
+// column block of a wider matrix), accumulate (a second edge set added onto an existing partial result: the
+// halo-source edges of the multi-GPU path, whose epilogue therefore rides on the LAST block added), an extra per-row term
 // `add` (SAGEConv: mean + fc_self(x_dst) + bias -> act, sage_conv.py:100-108) and the dropout word of element
 // (row, epi_col0 + k) of an epi_K-wide row, so that column blocks assemble the mask of the full-width launch.
 // `bias` and `add` point at the block's first column.  advance_rng != 0 steps the rng state afterwards
@@ -1311,11 +1291,19 @@ extern "C" int ggl_spmm_epi_ex(const ggl_segplan_t *plan, const int32_t *col, co
   a.epi_thresh = p_drop > 0.0f ? (uint32_t)((double)p_drop * 4294967296.0) : 0u;
   a.epi_scale = p_drop > 0.0f ? 1.0f / (1.0f - p_drop) : 1.0f;
   a.epi_K = epi_K; a.epi_col0 = epi_col0;
-  rc = mean ? launch_f32_cols<OP_MEAN, MODE_SPMM_EPI>(a, as_stream(stream))
-            : launch_f32_cols<OP_SUM, MODE_SPMM_EPI>(a, as_stream(stream));
+  rc = !mean ? launch_f32_cols<OP_SUM, MODE_SPMM_EPI>(a, as_stream(stream))
+             : launch_f32_cols<OP_MEAN, MODE_SPMM_EPI>(a, as_stream(stream));
   if (rc) return rc;
   if (a.epi_thresh && advance_rng && plan->N > 0 && K > 0) return rng_advance(rng_state, stream);
   return GGL_OK;
+}
+
+// The first form of the above (sum, contiguous rows, bias only), kept for its callers: it forwards.
+extern "C" int ggl_spmm_sum_bias_act(const ggl_segplan_t *plan, const int32_t *col, const float *w,
+                                     int w_by_pos, const float *x, int64_t K, const float *bias, int relu,
+                                     float p_drop, int64_t *rng_state, float *out, void *stream) {
+  return ggl_spmm_epi_ex(plan, col, w, w_by_pos, x, 0, K, out, 0, 0, 0, nullptr, 0, bias, relu, p_drop, rng_state, 0, 0, 1,
+                         stream);
 }
 
 // segment_sum / segment_mean of f32 messages x[E, K] with the same epilogue on the finished row: the

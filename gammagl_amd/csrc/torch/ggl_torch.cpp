@@ -933,6 +933,24 @@ static void reseed() {
   std::lock_guard<std::mutex> g(g_rng_mu);
   g_rng.clear();
 }
+// One fused-dropout draw: `rng` is the device state the launch reads and then advances by one, `used` a clone of the
+// {seed, offset} it reads, which the op returns for its backward to redraw the mask.  At rate 0 nothing is drawn: rng is
+// undefined and `used` the EMPTY tensor that stands for "no dropout" wherever an op returns or takes a rng_used.
+struct Draw {
+  Tensor rng, used;
+  int64_t *ptr() const { return rng.defined() ? rng.data_ptr<int64_t>() : nullptr; }
+};
+static Draw draw(const c10::Device &dev, double p) {
+  if (p > 0) {
+    Tensor rng = rng_state(dev);
+    return {rng, rng.clone()};
+  }
+  return {Tensor(), at::empty({0}, at::TensorOptions().dtype(at::kLong).device(dev))};
+}
+// the {seed, offset} a backward hands its kernel: the forward's `used`, or NULL without dropout
+static const int64_t *used_ptr(double p, const Tensor &rng_used) {
+  return (p > 0 && rng_used.numel() == 2) ? rng_used.data_ptr<int64_t>() : nullptr;
+}
 
 // x may be STORED as f16 / bf16 (an extension: ggl_gat_fused_*_x16, the general kernels with f32 softmax and sums); el / er are f32
 static void gat_check(const Tensor &el, const Tensor &er, const Tensor &x) {
@@ -961,15 +979,11 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor, bool> gat_forward(GraphPlan &g
   if (gp.fwd->n_long > 0)
     part = at::empty({static_cast<int64_t>(a.ggl_gat_partial_bytes(gp.fwd->n_chunks, H, C)) + 16}, x.options().dtype(at::kByte));
   ggl_segplan_t cs = gp.fwd->c(part);
-  Tensor rng, rng_used;
-  if (p > 0) {
-    rng = rng_state(dev);
-    rng_used = rng.clone();   // the {seed, offset} this launch reads; the backward redraws the mask
-  }
+  const Draw d = draw(dev, p);
   static const bool want_fast = env_int("GGL_GAT_FAST", 1) != 0;
   const bool fast = !x16 && want_fast && a.ggl_gat_fast_supported(H, C) != 0;   // 16-bit rows: the general kernels
   void *st = stream_of(dev);
-  int64_t *rp = rng.defined() ? rng.data_ptr<int64_t>() : nullptr;
+  int64_t *rp = d.ptr();
   if (x16)
     check(a, a.ggl_gat_fused_fwd_x16(&cs, gp.col.data_ptr<int32_t>(), el.data_ptr<float>(), er.data_ptr<float>(), dtype_code(x),
                                      x.data_ptr(), static_cast<float>(slope), H, C, static_cast<float>(p), rp, dtype_code(out),
@@ -982,7 +996,7 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor, bool> gat_forward(GraphPlan &g
     check(a, a.ggl_gat_fused_fwd(&cs, gp.col.data_ptr<int32_t>(), el.data_ptr<float>(), er.data_ptr<float>(),
                                  x.data_ptr<float>(), static_cast<float>(slope), H, C, static_cast<float>(p), rp,
                                  out.data_ptr<float>(), rmax.data_ptr<float>(), rden.data_ptr<float>(), st));
-  return {out, rmax, rden, rng_used.defined() ? rng_used : at::empty({0}, x.options().dtype(at::kLong)), fast};
+  return {out, rmax, rden, d.used, fast};
 }
 
 // (gel, ger, gx): the destination walk and the source walk
@@ -1004,7 +1018,7 @@ static std::tuple<Tensor, Tensor, Tensor> gat_backward(GraphPlan &gp, const Tens
   //  el is f32: the partials are, whatever x is stored as)
   Tensor part_f = partial_for(a, fw, el, fast ? 8 * H : H, false), part_t = partial_for(a, bw, el, H * C + H, false);
   ggl_segplan_t cs = fw.c(part_f), csT = bw.c(part_t);
-  const int64_t *ru = (p > 0 && rng_used.numel() == 2) ? rng_used.data_ptr<int64_t>() : nullptr;
+  const int64_t *ru = used_ptr(p, rng_used);
   if (fast) {
     Tensor stats = at::empty({gp.N_dst, H, 4}, x.options());
     check(a, a.ggl_gat_fast_bwd(&cs, gp.col.data_ptr<int32_t>(), &csT, colT.data_ptr<int32_t>(),
@@ -1193,15 +1207,11 @@ static std::tuple<Tensor, Tensor> bias_act_forward_kernel(const Tensor &a_, cons
     b = b.contiguous().reshape({-1});
     TORCH_CHECK(b.numel() == K, "bias must hold one value per column");
   }
-  Tensor y = at::empty_like(a), rng, used = at::empty({0}, a.options().dtype(at::kLong));
-  if (p > 0) {
-    rng = rng_state(a.device());
-    used = rng.clone();
-  }
+  Tensor y = at::empty_like(a);
+  const Draw d = draw(a.device(), p);
   check(api, api.ggl_bias_act_fwd(a.data_ptr<float>(), b.defined() ? b.data_ptr<float>() : nullptr, N, K, relu ? 1 : 0,
-                                  static_cast<float>(p), rng.defined() ? rng.data_ptr<int64_t>() : nullptr,
-                                  y.data_ptr<float>(), stream_of(a.device())));
-  return {y, used};
+                                  static_cast<float>(p), d.ptr(), y.data_ptr<float>(), stream_of(a.device())));
+  return {y, d.used};
 }
 // (ga, gbias): the mask is rebuilt from y, the bias gradient reduced in the same pass (epilogue.hip)
 static std::tuple<Tensor, Tensor> bias_act_backward_kernel(const Tensor &g_, const Tensor &y, bool has_bias, bool relu, double p,
@@ -1215,9 +1225,8 @@ static std::tuple<Tensor, Tensor> bias_act_backward_kernel(const Tensor &g_, con
   const size_t wsb = api.ggl_bias_act_bwd_workspace_bytes(N, K);
   Tensor ws = at::empty({static_cast<int64_t>(std::max<size_t>(wsb, 4))}, g.options().dtype(at::kByte));
   check(api, api.ggl_bias_act_bwd(g.data_ptr<float>(), y.data_ptr<float>(), N, K, relu ? 1 : 0, static_cast<float>(p),
-                                  (p > 0 && rng_used.numel() == 2) ? rng_used.data_ptr<int64_t>() : nullptr,
-                                  ga.data_ptr<float>(), gb.defined() ? gb.data_ptr<float>() : nullptr, ws.data_ptr(), wsb,
-                                  stream_of(g.device())));
+                                  used_ptr(p, rng_used), ga.data_ptr<float>(), gb.defined() ? gb.data_ptr<float>() : nullptr,
+                                  ws.data_ptr(), wsb, stream_of(g.device())));
   return {ga, gb.defined() ? gb : at::empty({0}, g.options())};
 }
 
@@ -1246,17 +1255,14 @@ static std::tuple<Tensor, Tensor> spmm_epi_forward_kernel(const Tensor &index, c
   Tensor y = at::empty({s.gp->N_dst, K}, s.x.options());
   Tensor part = partial_for(a, p_, s.x, K, false);
   ggl_segplan_t cs = p_.c(part);
-  Tensor keep, rng, used = at::empty({0}, s.x.options().dtype(at::kLong));
+  Tensor keep;
   auto [wp, by_pos] = weights_for(a, *s.gp, p_, s.w, keep);
-  if (p > 0) {
-    rng = rng_state(x.device());
-    used = rng.clone();
-  }
+  const Draw d = draw(x.device(), p);
   check(a, a.ggl_spmm_epi_ex(&cs, s.gp->col.data_ptr<int32_t>(), wp, by_pos, s.x.data_ptr<float>(), K, K, y.data_ptr<float>(),
                              K, 0, mean ? 1 : 0, add.defined() ? add.data_ptr<float>() : nullptr, add.defined() ? K : 0,
                              bias.defined() ? bias.data_ptr<float>() : nullptr, relu ? 1 : 0, static_cast<float>(p),
-                             rng.defined() ? rng.data_ptr<int64_t>() : nullptr, 0, 0, 1, stream_of(x.device())));
-  return {y, used};
+                             d.ptr(), 0, 0, 1, stream_of(x.device())));
+  return {y, d.used};
 }
 
 // ---- spmm_rows: (A x + bias)[rows] on the restricted plan pair (include/ggl_mpops.h ggl_plan_rows_*; ops.py Engine.rows_plan) ----
@@ -1624,75 +1630,63 @@ using GatFwdSig = std::tuple<Tensor, Tensor, Tensor, Tensor, bool>(const Tensor 
 using GatBwdSig = std::tuple<Tensor, Tensor, Tensor>(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                                                      const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                                                      const Tensor &, double, int64_t, double, bool);
+// f16 / bf16 rows with the choice of an f32 result: the forward of gat_fused_x16, (out, rowmax, rowden, rng_used)
+using GatX16FwdSig = std::tuple<Tensor, Tensor, Tensor, Tensor>(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
+                                                                double, int64_t, double, bool);
+// gat_fused and (x16 = true) gat_fused_x16: the backward of both is gat_fused_backward on the out the forward returned,
+// 16-bit rows through the general kernels (fast = false)
 struct GatFn : public torch::autograd::Function<GatFn> {
   static Tensor forward(AutogradContext *ctx, const Tensor &index, const Tensor &el, const Tensor &er, const Tensor &x,
-                        double slope, int64_t n, double p) {
+                        double slope, int64_t n, double p, bool x16, bool out_f32) {
     at::AutoDispatchBelowADInplaceOrView below;
-    static auto op = op_handle<GatFwdSig>("ggl::gat_fused_forward");
-    auto r = op.call(index, el, er, x, slope, n, p);
-    ctx->save_for_backward({index, el, er, x, std::get<0>(r), std::get<1>(r), std::get<2>(r), std::get<3>(r)});
+    Tensor out, rmax, rden, used;
+    bool fast = false;
+    if (x16) {
+      static auto op = op_handle<GatX16FwdSig>("ggl::gat_fused_x16_forward");
+      std::tie(out, rmax, rden, used) = op.call(index, el, er, x, slope, n, p, out_f32);
+    } else {
+      static auto op = op_handle<GatFwdSig>("ggl::gat_fused_forward");
+      std::tie(out, rmax, rden, used, fast) = op.call(index, el, er, x, slope, n, p);
+    }
+    ctx->save_for_backward({index, el, er, x, out, rmax, rden, used});
     ctx->saved_data["slope"] = slope;
     ctx->saved_data["n"] = n;
     ctx->saved_data["p"] = p;
-    ctx->saved_data["fast"] = std::get<4>(r);
-    return std::get<0>(r);
+    ctx->saved_data["fast"] = fast;
+    return out;
   }
   static variable_list backward(AutogradContext *ctx, variable_list grads) {
     auto s = ctx->get_saved_variables();
     static auto op = op_handle<GatBwdSig>("ggl::gat_fused_backward");
     auto r = op.call(s[0], s[1], s[2], s[3], grads[0], s[4], s[5], s[6], s[7], ctx->saved_data["slope"].toDouble(),
                      ctx->saved_data["n"].toInt(), ctx->saved_data["p"].toDouble(), ctx->saved_data["fast"].toBool());
-    return {Tensor(), std::get<0>(r), std::get<1>(r), std::get<2>(r), Tensor(), Tensor(), Tensor()};
+    return {Tensor(), std::get<0>(r), std::get<1>(r), std::get<2>(r), Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
   }
 };
+// apply(x) on x zero-padded to the policy's head width (41 classes per head: one padded copy keeps every walk on 16-byte
+// slices, ops.py Engine.gat_fused), the pad channels — they aggregate to zero — sliced off again; pad and slice are ordinary
+// differentiable ops.  E < 0: no policy (the index is not an edge list), x as it is.
+template <typename Apply>
+static Tensor with_head_pad(const Tensor &x, int64_t E, Apply apply) {
+  const int64_t C = x.size(2), Cp = E < 0 ? C : api_for(x.device()).ggl_policy_head_channels(C, E, x.size(0));
+  if (Cp == C) return apply(x);
+  return apply(at::constant_pad_nd(x, {0, Cp - C})).slice(2, 0, C);
+}
+static Tensor gat_autograd(const Tensor &index, const Tensor &el, const Tensor &er, const Tensor &x, double slope,
+                           c10::optional<int64_t> num_nodes, double p, bool x16, bool out_f32) {
+  gat_check(el, er, x);
+  TORCH_CHECK(!x16 || is_x16(x), "gat_fused_x16 takes f16 / bf16 rows (x is ", x.scalar_type(), ")");
+  const int64_t n = num_nodes.has_value() ? *num_nodes : x.size(0);
+  return with_head_pad(x, index.dim() == 2 ? index.size(1) : -1,
+                       [&](const Tensor &xp) { return GatFn::apply(index, el, er, xp, slope, n, p, x16, out_f32); });
+}
 static Tensor gat_fused_autograd(const Tensor &index, const Tensor &el, const Tensor &er, const Tensor &x, double slope,
                                  c10::optional<int64_t> num_nodes, double p) {
-  gat_check(el, er, x);
-  const int64_t n = num_nodes.has_value() ? *num_nodes : x.size(0), C = x.size(2);
-  // 41 classes per head: one zero-padded copy keeps every walk on 16-byte slices (ops.py Engine.gat_fused); the pad
-  // channels aggregate to zero and are dropped — pad and slice are ordinary differentiable ops
-  const int64_t Cp = index.dim() == 2 ? api_for(x.device()).ggl_policy_head_channels(C, index.size(1), x.size(0)) : C;
-  if (Cp != C) {
-    Tensor xp = at::constant_pad_nd(x, {0, Cp - C});
-    return GatFn::apply(index, el, er, xp, slope, n, p).slice(2, 0, C);
-  }
-  return GatFn::apply(index, el, er, x, slope, n, p);
+  return gat_autograd(index, el, er, x, slope, num_nodes, p, false, false);
 }
-
-// f16 / bf16 rows, out in x's dtype or f32: the backward is gat_fused_backward on the out this forward returned
-using GatX16FwdSig = std::tuple<Tensor, Tensor, Tensor, Tensor>(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
-                                                                double, int64_t, double, bool);
-struct GatX16Fn : public torch::autograd::Function<GatX16Fn> {
-  static Tensor forward(AutogradContext *ctx, const Tensor &index, const Tensor &el, const Tensor &er, const Tensor &x,
-                        double slope, int64_t n, double p, bool out_f32) {
-    at::AutoDispatchBelowADInplaceOrView below;
-    static auto op = op_handle<GatX16FwdSig>("ggl::gat_fused_x16_forward");
-    auto r = op.call(index, el, er, x, slope, n, p, out_f32);
-    ctx->save_for_backward({index, el, er, x, std::get<0>(r), std::get<1>(r), std::get<2>(r), std::get<3>(r)});
-    ctx->saved_data["slope"] = slope;
-    ctx->saved_data["n"] = n;
-    ctx->saved_data["p"] = p;
-    return std::get<0>(r);
-  }
-  static variable_list backward(AutogradContext *ctx, variable_list grads) {
-    auto s = ctx->get_saved_variables();
-    static auto op = op_handle<GatBwdSig>("ggl::gat_fused_backward");
-    auto r = op.call(s[0], s[1], s[2], s[3], grads[0], s[4], s[5], s[6], s[7], ctx->saved_data["slope"].toDouble(),
-                     ctx->saved_data["n"].toInt(), ctx->saved_data["p"].toDouble(), false);
-    return {Tensor(), std::get<0>(r), std::get<1>(r), std::get<2>(r), Tensor(), Tensor(), Tensor(), Tensor()};
-  }
-};
 static Tensor gat_fused_x16_autograd(const Tensor &index, const Tensor &el, const Tensor &er, const Tensor &x, double slope,
                                      c10::optional<int64_t> num_nodes, double p, bool out_f32) {
-  gat_check(el, er, x);
-  TORCH_CHECK(is_x16(x), "gat_fused_x16 takes f16 / bf16 rows (x is ", x.scalar_type(), ")");
-  const int64_t n = num_nodes.has_value() ? *num_nodes : x.size(0), C = x.size(2);
-  const int64_t Cp = index.dim() == 2 ? api_for(x.device()).ggl_policy_head_channels(C, index.size(1), x.size(0)) : C;
-  if (Cp != C) {   // as gat_fused_autograd: the policy's zero pad
-    Tensor xp = at::constant_pad_nd(x, {0, Cp - C});
-    return GatX16Fn::apply(index, el, er, xp, slope, n, p, out_f32).slice(2, 0, C);
-  }
-  return GatX16Fn::apply(index, el, er, x, slope, n, p, out_f32);
+  return gat_autograd(index, el, er, x, slope, num_nodes, p, true, out_f32);
 }
 
 using GatCsrFwdSig = std::tuple<Tensor, Tensor, Tensor, Tensor, bool>(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
@@ -1725,17 +1719,30 @@ struct GatCsrFn : public torch::autograd::Function<GatCsrFn> {
 static Tensor gat_fused_csr_autograd(const Tensor &rp, const Tensor &ci, const Tensor &cp, const Tensor &ri, const Tensor &pm,
                                      const Tensor &el, const Tensor &er, const Tensor &x, double slope, double p) {
   gat_check(el, er, x);
-  const int64_t C = x.size(2);
-  const int64_t Cp = api_for(x.device()).ggl_policy_head_channels(C, ci.size(0), x.size(0));
-  if (Cp != C) {
-    Tensor xp = at::constant_pad_nd(x, {0, Cp - C});
-    return GatCsrFn::apply(rp, ci, cp, ri, pm, el, er, xp, slope, p).slice(2, 0, C);
-  }
-  return GatCsrFn::apply(rp, ci, cp, ri, pm, el, er, x, slope, p);
+  return with_head_pad(x, ci.size(0), [&](const Tensor &xp) { return GatCsrFn::apply(rp, ci, cp, ri, pm, el, er, xp, slope, p); });
 }
 
 using BiasFwdSig = std::tuple<Tensor, Tensor>(const Tensor &, const OptT_ &, bool, double);
 using BiasBwdSig = std::tuple<Tensor, Tensor>(const Tensor &, const Tensor &, bool, bool, double, const Tensor &);
+// a node's bias: whether there is one and its shape are kept at the forward; the backward's flat [K] gradient goes back in
+// that shape, or undefined without a bias
+static void save_bias(AutogradContext *ctx, const OptT_ &bias) {
+  const Tensor b = opt(bias);
+  ctx->saved_data["has_bias"] = b.defined();
+  ctx->saved_data["bias_shape"] = b.defined() ? b.sizes().vec() : std::vector<int64_t>{};
+}
+static bool has_bias(AutogradContext *ctx) { return ctx->saved_data["has_bias"].toBool(); }
+static Tensor bias_grad(AutogradContext *ctx, const Tensor &flat) {
+  return has_bias(ctx) ? flat.reshape(ctx->saved_data["bias_shape"].toIntVector()) : Tensor();
+}
+// (ga, gbias) back through dropout / ReLU / + bias of a node that saved "relu" and its bias (save_bias): y is the output
+// it returned, rng_used what its forward op returned (empty and p = 0 for a node without dropout)
+static std::tuple<Tensor, Tensor> epi_backward(AutogradContext *ctx, const Tensor &g, const Tensor &y, double p,
+                                               const Tensor &rng_used) {
+  static auto op = op_handle<BiasBwdSig>("ggl::bias_act_backward");
+  auto r = op.call(g, y, has_bias(ctx), ctx->saved_data["relu"].toBool(), p, rng_used);
+  return {std::get<0>(r), bias_grad(ctx, std::get<1>(r))};
+}
 struct BiasActFn : public torch::autograd::Function<BiasActFn> {
   static Tensor forward(AutogradContext *ctx, const Tensor &a, const OptT_ &bias, bool relu, double p) {
     at::AutoDispatchBelowADInplaceOrView below;
@@ -1744,17 +1751,13 @@ struct BiasActFn : public torch::autograd::Function<BiasActFn> {
     ctx->save_for_backward({std::get<0>(r), std::get<1>(r)});
     ctx->saved_data["relu"] = relu;
     ctx->saved_data["p"] = p;
-    ctx->saved_data["bias_shape"] = opt(bias).defined() ? opt(bias).sizes().vec() : std::vector<int64_t>{};
-    ctx->saved_data["has_bias"] = opt(bias).defined();
+    save_bias(ctx, bias);
     return std::get<0>(r);
   }
   static variable_list backward(AutogradContext *ctx, variable_list grads) {
     auto s = ctx->get_saved_variables();
-    static auto op = op_handle<BiasBwdSig>("ggl::bias_act_backward");
-    const bool hb = ctx->saved_data["has_bias"].toBool();
-    auto r = op.call(grads[0], s[0], hb, ctx->saved_data["relu"].toBool(), ctx->saved_data["p"].toDouble(), s[1]);
-    Tensor gb = hb ? std::get<1>(r).reshape(ctx->saved_data["bias_shape"].toIntVector()) : Tensor();
-    return {std::get<0>(r), gb, Tensor(), Tensor()};
+    auto [ga, gb] = epi_backward(ctx, grads[0], s[0], ctx->saved_data["p"].toDouble(), s[1]);
+    return {ga, gb, Tensor(), Tensor()};
   }
 };
 static Tensor bias_act_autograd(const Tensor &a, const OptT_ &bias, bool relu, double p) { return BiasActFn::apply(a, bias, relu, p); }
@@ -1771,21 +1774,16 @@ struct SpMMEpiFn : public torch::autograd::Function<SpMMEpiFn> {
     ctx->saved_data["relu"] = relu;
     ctx->saved_data["p"] = p;
     ctx->saved_data["has_add"] = opt(add).defined();
-    ctx->saved_data["has_bias"] = opt(bias).defined();
-    ctx->saved_data["bias_shape"] = opt(bias).defined() ? opt(bias).sizes().vec() : std::vector<int64_t>{};
+    save_bias(ctx, bias);
     return std::get<0>(r);
   }
   static variable_list backward(AutogradContext *ctx, variable_list grads) {
     auto s = ctx->get_saved_variables();
-    static auto bop = op_handle<BiasBwdSig>("ggl::bias_act_backward");
-    const bool hb = ctx->saved_data["has_bias"].toBool();
-    auto r = bop.call(grads[0], s[2], hb, ctx->saved_data["relu"].toBool(), ctx->saved_data["p"].toDouble(), s[3]);
-    Tensor ga = std::get<0>(r);
+    auto [ga, gb] = epi_backward(ctx, grads[0], s[2], ctx->saved_data["p"].toDouble(), s[3]);
     OptT_ w = s[1].defined() ? OptT_(s[1]) : OptT_();
     static auto sum_bwd = op_handle<SpSig>("ggl::spmm_sum_backward");
     static auto mean_bwd = op_handle<SpSig>("ggl::spmm_mean_backward");
     Tensor gx = ctx->saved_data["mean"].toBool() ? mean_bwd.call(s[0], w, ga) : sum_bwd.call(s[0], w, ga);
-    Tensor gb = hb ? std::get<1>(r).reshape(ctx->saved_data["bias_shape"].toIntVector()) : Tensor();
     return {Tensor(), Tensor(), gx, Tensor(), ctx->saved_data["has_add"].toBool() ? ga : Tensor(), gb, Tensor(), Tensor()};
   }
 };
@@ -1808,19 +1806,16 @@ struct SpMMRowsFn : public torch::autograd::Function<SpMMRowsFn> {
     Tensor y = op.call(index, weight, x, rows, bias);
     ctx->save_for_backward({index, opt(weight), rows});
     ctx->saved_data["n_src"] = x.size(0);
-    ctx->saved_data["has_bias"] = opt(bias).defined();
-    ctx->saved_data["bias_shape"] = opt(bias).defined() ? opt(bias).sizes().vec() : std::vector<int64_t>{};
+    save_bias(ctx, bias);
     return y;
   }
   static variable_list backward(AutogradContext *ctx, variable_list grads) {
     auto s = ctx->get_saved_variables();
     static auto op = op_handle<std::tuple<Tensor, Tensor>(const Tensor &, const OptT_ &, const Tensor &, const Tensor &, int64_t,
                                                           bool)>("ggl::spmm_rows_backward");
-    const bool hb = ctx->saved_data["has_bias"].toBool();
     OptT_ w = s[1].defined() ? OptT_(s[1]) : OptT_();
-    auto r = op.call(s[0], w, grads[0], s[2], ctx->saved_data["n_src"].toInt(), hb);
-    Tensor gb = hb ? std::get<1>(r).reshape(ctx->saved_data["bias_shape"].toIntVector()) : Tensor();
-    return {Tensor(), Tensor(), std::get<0>(r), Tensor(), gb};
+    auto r = op.call(s[0], w, grads[0], s[2], ctx->saved_data["n_src"].toInt(), has_bias(ctx));
+    return {Tensor(), Tensor(), std::get<0>(r), Tensor(), bias_grad(ctx, std::get<1>(r))};
   }
 };
 static Tensor spmm_rows_autograd(const Tensor &index, const OptT_ &weight, const Tensor &x, const Tensor &rows,
@@ -1843,16 +1838,12 @@ struct SegEpiFn : public torch::autograd::Function<SegEpiFn> {
     ctx->saved_data["mean"] = mean;
     ctx->saved_data["relu"] = relu;
     ctx->saved_data["has_add"] = opt(add).defined();
-    ctx->saved_data["has_bias"] = opt(bias).defined();
-    ctx->saved_data["bias_shape"] = opt(bias).defined() ? opt(bias).sizes().vec() : std::vector<int64_t>{};
+    save_bias(ctx, bias);
     return y;
   }
   static variable_list backward(AutogradContext *ctx, variable_list grads) {
     auto s = ctx->get_saved_variables();
-    static auto bop = op_handle<BiasBwdSig>("ggl::bias_act_backward");
-    const bool hb = ctx->saved_data["has_bias"].toBool();
-    auto r = bop.call(grads[0], s[1], hb, ctx->saved_data["relu"].toBool(), 0.0, at::empty({0}, s[0].options()));
-    Tensor ga = std::get<0>(r);
+    auto [ga, gb] = epi_backward(ctx, grads[0], s[1], 0.0, at::empty({0}, s[0].options()));
     auto shape = ctx->saved_data["x_shape"].toIntVector();
     Tensor gx;
     if (ctx->saved_data["mean"].toBool()) {
@@ -1862,7 +1853,6 @@ struct SegEpiFn : public torch::autograd::Function<SegEpiFn> {
       static auto op = op_handle<Tensor(const Tensor &, const Tensor &, c10::IntArrayRef)>("ggl::segment_sum_backward");
       gx = op.call(ga, s[0], shape);
     }
-    Tensor gb = hb ? std::get<1>(r).reshape(ctx->saved_data["bias_shape"].toIntVector()) : Tensor();
     return {gx, Tensor(), Tensor(), Tensor(), ctx->saved_data["has_add"].toBool() ? ga : Tensor(), gb, Tensor()};
   }
 };

@@ -35,7 +35,6 @@ import torch.nn.functional as F
 
 from . import engine as _default_engine
 from .dense import wgrad
-from .ops import _ptr
 
 HALO_CHUNKS = int(os.environ.get("GGL_HALO_CHUNKS", "0"))  # 0 = automatic (4 at K >= 256, 2 at K >= 128)
 DIST_EXACT = os.environ.get("GGL_DIST_EXACT", "1") == "1"   # 0: partitioned aggregates walk their hub rows chunk by chunk (A/B)
@@ -382,8 +381,7 @@ class _HaloAggregate(torch.autograd.Function):
         h = _HaloAggregate._pad4(h.contiguous())
         K = h.shape[1]
         dev = h.device
-        rng = eng._rng_state(dev) if (fused and p_drop > 0) else None
-        ctx.rng_used = rng.clone() if rng is not None else None
+        rng, rng_used = eng._draw(dev, p_drop if fused else 0.0)
         b = bias.contiguous().reshape(-1) if (fused and bias is not None) else None
         works = []
         if pre:      # the halo rows sit behind the local ones already: one "chunk", nothing on the wire
@@ -416,39 +414,21 @@ class _HaloAggregate(torch.autograd.Function):
         if out.shape[1] != ctx.k_orig:
             out = out[:, :ctx.k_orig].contiguous()
         if epi and not fused:
-            rng = eng._rng_state(dev) if p_drop > 0 else None
-            ctx.rng_used = rng.clone() if rng is not None else None
-            y = torch.empty_like(out)
-            bb = bias.contiguous().reshape(-1) if bias is not None else None
-            eng._check(eng.lib.ggl_bias_act_fwd(_ptr(out), _ptr(bb), out.shape[0], out.shape[1], int(relu),
-                                                float(p_drop), _ptr(rng), _ptr(y), eng._stream(out.device)))
-            out = y
-        ctx.pg, ctx.pre, ctx.epi = pg, pre, (epi, relu, p_drop, None if bias is None else bias.shape)
-        if epi:
-            ctx.save_for_backward(out)
+            rng, rng_used = eng._draw(dev, p_drop)
+            out = eng._epi_fwd(out, bias, relu, p_drop, rng)
+        ctx.pg, ctx.pre = pg, pre
+        ctx.epi = (relu, p_drop, rng_used, None if bias is None else bias.shape)   # Engine._epi_bwd's arguments after (g, y)
+        ctx.save_for_backward(out if epi else None)
         return out
 
     @staticmethod
     def backward(ctx, g):
         pg = ctx.pg
         eng = pg.eng
-        g = g.contiguous()
         dev = g.device
-        epi, relu, p_drop, bshape = ctx.epi
-        gb = None
-        if epi:  # through dropout / ReLU / + bias in one pass (mask redrawn from the saved rng state)
-            (y,) = ctx.saved_tensors
-            N, K0 = int(g.shape[0]), int(g.shape[1])
-            ga = torch.empty_like(g)
-            gb = torch.empty(K0, dtype=torch.float32, device=dev) if bshape is not None else None
-            wsb = eng.lib.ggl_bias_act_bwd_workspace_bytes(N, K0)
-            ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=dev)
-            eng._check(eng.lib.ggl_bias_act_bwd(_ptr(g), _ptr(y), N, K0, int(relu), float(p_drop),
-                                                _ptr(ctx.rng_used), _ptr(ga), _ptr(gb), _ptr(ws), wsb,
-                                                eng._stream(dev)))
-            g = ga
-            if gb is not None:
-                gb = gb.reshape(bshape)
+        (y,) = ctx.saved_tensors
+        # through dropout / ReLU / + bias in one pass (mask redrawn from the saved rng state); g itself without an epilogue
+        g, gb = eng._epi_bwd(g, y, *ctx.epi)
         if not ctx.needs_input_grad[0]:
             return None, None, gb, None, None, None
         g = _HaloAggregate._pad4(g)
@@ -502,8 +482,7 @@ class _ConstInputLayer(torch.autograd.Function):
         h = x_loc @ wp.t()
         out = torch.empty((nl, K), dtype=torch.float32, device=dev)
         epi = bias is not None or relu or p_drop > 0
-        rng = eng._rng_state(dev) if p_drop > 0 else None
-        ctx.rng_used = rng.clone() if rng is not None else None
+        rng, rng_used = eng._draw(dev, p_drop)
         b = bias.contiguous().reshape(-1) if bias is not None else None
         if pg.n_halo == 0:   # a rank without halo rows: the epilogue rides on the local walk
             eng.spmm_epi_into(pg.gp_loc.fwd, pg.gp_loc.col, pg.w_loc, h, out, bias=b, relu=relu, p_drop=p_drop, rng=rng,
@@ -517,7 +496,7 @@ class _ConstInputLayer(torch.autograd.Function):
             eng.spmm_epi_into(pg.gp_halo.fwd, pg.gp_halo.col, pg.w_halo, hh, out[:, c0:c1], accumulate=True, bias=b,
                               relu=relu, p_drop=p_drop, rng=rng, epi_K=K, col0=c0, advance_rng=(i == len(chunks) - 1))
         ctx.pg, ctx.n_out = pg, int(w.shape[0])
-        ctx.epi = (epi, bool(relu), float(p_drop), None if bias is None else bias.shape)
+        ctx.epi = (relu, p_drop, rng_used, None if bias is None else bias.shape)   # Engine._epi_bwd's arguments after (g, y)
         ctx.save_for_backward(x_cat, out if epi else None)
         return out
 
@@ -526,21 +505,8 @@ class _ConstInputLayer(torch.autograd.Function):
         pg = ctx.pg
         eng, nl = pg.eng, pg.n_local
         x_cat, y = ctx.saved_tensors
-        g = g.contiguous()
         dev = g.device
-        epi, relu, p_drop, bshape = ctx.epi
-        gb = None
-        if epi:
-            N, K0 = int(g.shape[0]), int(g.shape[1])
-            ga = torch.empty_like(g)
-            gb = torch.empty(K0, dtype=torch.float32, device=dev) if bshape is not None else None
-            wsb = eng.lib.ggl_bias_act_bwd_workspace_bytes(N, K0)
-            ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=dev)
-            eng._check(eng.lib.ggl_bias_act_bwd(_ptr(g), _ptr(y), N, K0, int(relu), float(p_drop), _ptr(ctx.rng_used),
-                                                _ptr(ga), _ptr(gb), _ptr(ws), wsb, eng._stream(dev)))
-            g = ga
-            if gb is not None:
-                gb = gb.reshape(bshape)
+        g, gb = eng._epi_bwd(g, y, *ctx.epi)
         gw = None
         if ctx.needs_input_grad[1]:
             K = int(g.shape[1])

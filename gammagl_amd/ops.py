@@ -641,17 +641,26 @@ class Engine:
                                                    self._stream(dev)))
         return out
 
-    def _partial(self, plan, dtype, K, with_arg, dev):
+    @staticmethod
+    def _hub_partial(plan, nbytes, dev):
+        """The partial buffer of the plan's long rows, `nbytes(n_chunks)` bytes + 16 of slack, or None for a plan
+        without long rows.  It must outlive the launch: keep the tensor in a local."""
         if plan.n_long == 0:
             return None
-        nb = self.lib.ggl_partial_bytes(_DTYPE_CODE[dtype], plan.n_chunks, K, 1 if with_arg else 0)
-        return torch.empty(nb + 16, dtype=torch.uint8, device=dev)
+        return torch.empty(nbytes(plan.n_chunks) + 16, dtype=torch.uint8, device=dev)
+
+    def _partial(self, plan, dtype, K, with_arg, dev):
+        return self._hub_partial(
+            plan, lambda n: self.lib.ggl_partial_bytes(_DTYPE_CODE[dtype], n, K, 1 if with_arg else 0), dev)
 
     def _softmax_partial(self, plan, K, dev):
-        if plan.n_long == 0:
-            return None
-        nb = self.lib.ggl_segment_softmax_partial_bytes(plan.n_chunks, K)
-        return torch.empty(nb + 16, dtype=torch.uint8, device=dev)
+        return self._hub_partial(plan, lambda n: self.lib.ggl_segment_softmax_partial_bytes(n, K), dev)
+
+    def _gat_partial(self, plan, H, C, dev):
+        return self._hub_partial(plan, lambda n: self.lib.ggl_gat_partial_bytes(n, H, C), dev)
+
+    def _gat_sh_partial(self, plan, width, dev):
+        return self._hub_partial(plan, lambda n: self.lib.ggl_gat_sh_partial_bytes(n, width), dev)
 
     def _softmax_width(self, x, plan):
         E = int(x.shape[0])
@@ -729,6 +738,20 @@ class Engine:
         self._check(self.lib.ggl_segment_max(code, _ptr(x), ctypes.byref(cs), K, _ptr(out), _ptr(arg),
                                              E, st))
         return out, arg
+
+    def _segment_bwd(self, g, ids, x_shape, rowptr=None):
+        """gx[e] = g[ids[e]] (segment_sum), divided by the segment's length with the plan's `rowptr` (segment_mean)."""
+        g = g.contiguous()
+        E, K = int(x_shape[0]), int(math.prod(x_shape[1:]))
+        gx = torch.empty(x_shape, dtype=g.dtype, device=g.device)
+        st = self._stream(g.device)
+        if rowptr is None:
+            self._check(self.lib.ggl_segment_sum_bwd(self._code(g), _ptr(g), _ptr(ids), E, K, _ptr(gx), st))
+        else:
+            if g.dtype not in _FLOAT_DTYPES:
+                raise RuntimeError("segment_mean backward needs a floating dtype")
+            self._check(self.lib.ggl_segment_mean_bwd(self._code(g), _ptr(g), _ptr(ids), _ptr(rowptr), E, K, _ptr(gx), st))
+        return gx
 
     @staticmethod
     def _row_stride(t, what):
@@ -983,13 +1006,7 @@ class Engine:
             @staticmethod
             def backward(ctx, g):
                 (ids,) = ctx.saved_tensors
-                g = g.contiguous()
-                E = ctx.x_shape[0]
-                K = int(math.prod(ctx.x_shape[1:]))
-                gin = torch.empty(ctx.x_shape, dtype=g.dtype, device=g.device)
-                eng._check(eng.lib.ggl_segment_sum_bwd(eng._code(g), _ptr(g), _ptr(ids), E, K,
-                                                       _ptr(gin), eng._stream(g.device)))
-                return gin, None, None
+                return eng._segment_bwd(g, ids, ctx.x_shape), None, None
 
         class SegmentMean(torch.autograd.Function):  # src/segment_mean.cpp:36-63
             @staticmethod
@@ -1003,15 +1020,7 @@ class Engine:
             @staticmethod
             def backward(ctx, g):
                 ids, rowptr = ctx.saved_tensors
-                g = g.contiguous()
-                if g.dtype not in _FLOAT_DTYPES:
-                    raise RuntimeError("segment_mean backward needs a floating dtype")
-                E = ctx.x_shape[0]
-                K = int(math.prod(ctx.x_shape[1:]))
-                gin = torch.empty(ctx.x_shape, dtype=g.dtype, device=g.device)
-                eng._check(eng.lib.ggl_segment_mean_bwd(eng._code(g), _ptr(g), _ptr(ids), _ptr(rowptr),
-                                                        E, K, _ptr(gin), eng._stream(g.device)))
-                return gin, None, None
+                return eng._segment_bwd(g, ids, ctx.x_shape, rowptr), None, None
 
         class SegmentMax(torch.autograd.Function):  # src/segment_max.cpp:37-61
             @staticmethod
@@ -1049,29 +1058,28 @@ class Engine:
                 (y,) = ctx.saved_tensors
                 return eng._softmax_bwd(y, g, ctx.plan), None
 
-        class SpMMSum(torch.autograd.Function):  # src/gspmm.cpp:26-80
-            @staticmethod
-            def forward(ctx, gp, w, x, out_dtype=None):
-                out, _ = eng._spmm_fwd("sum", gp.fwd, gp.col, w, x, gp.N_dst, out_dtype=out_dtype)
-                ctx.gp, ctx.w, ctx.x_dtype = gp, w, x.dtype
-                return out
+        def spmm_function(op):
+            """SpMMSum / SpMMMean (src/gspmm.cpp:26-80, 82-141): one body, the reduce as its parameter."""
 
-            @staticmethod
-            def backward(ctx, g):
-                gx = eng._spmm_bwd_x("sum", ctx.gp, ctx.w, g, ctx.x_dtype)
-                return None, None, gx, None  # weight is non-differentiable in the reference (gspmm.cpp:30)
+            class SpMM(torch.autograd.Function):
+                @staticmethod
+                def forward(ctx, gp, w, x, out_dtype=None):
+                    out, _ = eng._spmm_fwd(op, gp.fwd, gp.col, w, x, gp.N_dst, out_dtype=out_dtype)
+                    ctx.gp, ctx.w, ctx.x_dtype = gp, w, x.dtype
+                    return out
 
-        class SpMMMean(torch.autograd.Function):  # src/gspmm.cpp:82-141
-            @staticmethod
-            def forward(ctx, gp, w, x, out_dtype=None):
-                out, _ = eng._spmm_fwd("mean", gp.fwd, gp.col, w, x, gp.N_dst, out_dtype=out_dtype)
-                ctx.gp, ctx.w, ctx.x_dtype = gp, w, x.dtype
-                return out
+                @staticmethod
+                def backward(ctx, g):
+                    if op == "mean":   # the transposed walk divides by the destination row's length
+                        gx = eng._spmm_bwd_x("mean_bwd", ctx.gp, ctx.w, g, ctx.x_dtype, aux=ctx.gp.fwd.rowptr)
+                    else:
+                        gx = eng._spmm_bwd_x("sum", ctx.gp, ctx.w, g, ctx.x_dtype)
+                    return None, None, gx, None  # weight is non-differentiable in the reference (gspmm.cpp:30)
 
-            @staticmethod
-            def backward(ctx, g):
-                gx = eng._spmm_bwd_x("mean_bwd", ctx.gp, ctx.w, g, ctx.x_dtype, aux=ctx.gp.fwd.rowptr)
-                return None, None, gx, None
+            SpMM.__name__ = SpMM.__qualname__ = "SpMM" + op.capitalize()
+            return SpMM
+
+        SpMMSum, SpMMMean = spmm_function("sum"), spmm_function("mean")
 
         class SpMMMax(torch.autograd.Function):  # src/gspmm.cpp:143-202
             @staticmethod
@@ -1136,15 +1144,9 @@ class Engine:
                 out = torch.empty((N, H, C), dtype=(out_dtype or x.dtype) if x16 else torch.float32, device=dev)
                 rmax = torch.empty((N, H), dtype=torch.float32, device=dev)
                 rden = torch.empty((N, H), dtype=torch.float32, device=dev)
-                part = None
-                if gp.fwd.n_long > 0:
-                    part = torch.empty(eng.lib.ggl_gat_partial_bytes(gp.fwd.n_chunks, H, C) + 16,
-                                       dtype=torch.uint8, device=dev)
+                part = eng._gat_partial(gp.fwd, H, C, dev)
                 cs = gp.fwd.c_struct(part)
-                rng = rng_used = None
-                if p_drop > 0:
-                    rng = eng._rng_state(dev)
-                    rng_used = rng.clone()  # the {seed, offset} this launch reads; the backward redraws the mask
+                rng, rng_used = eng._draw(dev, p_drop)
                 fast = bool(not x16 and eng.gat_fast and eng.lib.ggl_gat_fast_supported(H, C))
                 if x16:
                     eng._check(eng.lib.ggl_gat_fused_fwd_x16(
@@ -1242,90 +1244,17 @@ class Engine:
             @staticmethod
             def forward(ctx, a, bias, relu, p_drop):
                 a = a.contiguous()
-                dev = a.device
-                N = int(a.shape[0])
-                K = a.numel() // N if N > 0 else int(math.prod(a.shape[1:]))
-                y = torch.empty_like(a)
-                rng = eng._rng_state(dev) if p_drop > 0 else None
-                rng_used = rng.clone() if rng is not None else None  # the {seed, offset} this launch reads
-                b = bias.contiguous().reshape(-1) if bias is not None else None
-                eng._check(eng.lib.ggl_bias_act_fwd(_ptr(a), _ptr(b), N, K, int(relu), float(p_drop),
-                                                    _ptr(rng), _ptr(y), eng._stream(dev)))
-                ctx.cfg = (N, K, int(relu), float(p_drop), None if bias is None else bias.shape)
-                ctx.rng_used = rng_used
+                rng, rng_used = eng._draw(a.device, p_drop)
+                y = eng._epi_fwd(a, bias, relu, p_drop, rng)
+                ctx.epi = (relu, p_drop, rng_used, None if bias is None else bias.shape)   # _epi_bwd's arguments after (g, y)
                 ctx.save_for_backward(y)
                 return y
 
             @staticmethod
             def backward(ctx, g):
                 (y,) = ctx.saved_tensors
-                N, K, relu, p_drop, bshape = ctx.cfg
-                g = g.contiguous()
-                dev = g.device
-                ga = torch.empty_like(g)
-                gb = torch.empty(K, dtype=torch.float32, device=dev) if bshape is not None else None
-                wsb = eng.lib.ggl_bias_act_bwd_workspace_bytes(N, K)
-                ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=dev)
-                eng._check(eng.lib.ggl_bias_act_bwd(_ptr(g), _ptr(y), N, K, relu, p_drop, _ptr(ctx.rng_used),
-                                                    _ptr(ga), _ptr(gb), _ptr(ws), wsb, eng._stream(dev)))
-                return ga, (gb.reshape(bshape) if gb is not None else None), None, None
-
-        class SpMMSumBiasAct(torch.autograd.Function):
-            """y = dropout(relu(A x + bias)) in ONE kernel: the epilogue is applied to each finished row of
-            the SpMM in registers (reduce.hip MODE_SPMM_EPI); backward = bias_act_bwd, transposed SpMM."""
-
-            @staticmethod
-            def forward(ctx, gp, w, x, bias, relu, p_drop):
-                dev = x.device
-                K = int(x.shape[1])
-                plan = gp.fwd
-                y = torch.empty((gp.N_dst, K), dtype=torch.float32, device=dev)
-                part = eng._partial(plan, torch.float32, K, False, dev)
-                ww, w_by_pos, wp = eng._weights(plan, w)
-                cs = plan.c_struct(part, wp)
-                rng = eng._rng_state(dev) if p_drop > 0 else None
-                ctx.rng_used = rng.clone() if rng is not None else None
-                b = bias.contiguous().reshape(-1) if bias is not None else None
-                eng._check(eng.lib.ggl_spmm_sum_bias_act(ctypes.byref(cs), _ptr(gp.col), _ptr(ww), w_by_pos,
-                                                         _ptr(x), K, _ptr(b), int(relu), float(p_drop),
-                                                         _ptr(rng), _ptr(y), eng._stream(dev)))
-                ctx.gp, ctx.w = gp, w
-                ctx.cfg = (int(gp.N_dst), K, int(relu), float(p_drop), None if bias is None else bias.shape)
-                ctx.save_for_backward(y)
-                return y
-
-            @staticmethod
-            def backward(ctx, g):
-                (y,) = ctx.saved_tensors
-                N, K, relu, p_drop, bshape = ctx.cfg
-                g = g.contiguous()
-                dev = g.device
-                ga = torch.empty_like(g)
-                gb = torch.empty(K, dtype=torch.float32, device=dev) if bshape is not None else None
-                wsb = eng.lib.ggl_bias_act_bwd_workspace_bytes(N, K)
-                ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=dev)
-                eng._check(eng.lib.ggl_bias_act_bwd(_ptr(g), _ptr(y), N, K, relu, p_drop, _ptr(ctx.rng_used),
-                                                    _ptr(ga), _ptr(gb), _ptr(ws), wsb, eng._stream(dev)))
-                gp = ctx.gp
-                gx = None
-                if ctx.needs_input_grad[2]:
-                    gx, _ = eng._spmm_fwd("sum", gp.bwd, gp.colT, ctx.w, ga, gp.N_src)
-                return None, None, gx, (gb.reshape(bshape) if gb is not None else None), None, None
-
-        def _epi_backward(ctx, g, y):
-            """Through dropout / ReLU / + bias / + add in one pass: returns (ga, gbias)."""
-            N, K, relu, p_drop, bshape = ctx.cfg
-            g = g.contiguous()
-            dev = g.device
-            if not (relu or p_drop > 0 or bshape is not None):
-                return g, None
-            ga = torch.empty_like(g)
-            gb = torch.empty(K, dtype=torch.float32, device=dev) if bshape is not None else None
-            wsb = eng.lib.ggl_bias_act_bwd_workspace_bytes(N, K)
-            ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=dev)
-            eng._check(eng.lib.ggl_bias_act_bwd(_ptr(g), _ptr(y), N, K, relu, p_drop, _ptr(ctx.rng_used),
-                                                _ptr(ga), _ptr(gb), _ptr(ws), wsb, eng._stream(dev)))
-            return ga, (gb.reshape(bshape) if gb is not None else None)
+                ga, gb = eng._epi_bwd(g, y, *ctx.epi)
+                return ga, gb, None, None
 
         class SpMMEpi(torch.autograd.Function):
             """y = dropout(relu(reduce(A x) + add + bias)), reduce = sum | mean, in ONE kernel (ggl_spmm_epi_ex):
@@ -1337,20 +1266,19 @@ class Engine:
                 dev = x.device
                 K = int(x.shape[1])
                 y = torch.empty((gp.N_dst, K), dtype=torch.float32, device=dev)
-                rng = eng._rng_state(dev) if p_drop > 0 else None
-                ctx.rng_used = rng.clone() if rng is not None else None
+                rng, rng_used = eng._draw(dev, p_drop)
                 b = bias.contiguous().reshape(-1) if bias is not None else None
                 a = add.contiguous() if add is not None else None
                 eng.spmm_epi_into(gp.fwd, gp.col, w, x, y, mean=mean, add=a, bias=b, relu=relu, p_drop=p_drop, rng=rng)
                 ctx.gp, ctx.w, ctx.mean, ctx.has_add = gp, w, bool(mean), add is not None
-                ctx.cfg = (int(gp.N_dst), K, int(relu), float(p_drop), None if bias is None else bias.shape)
+                ctx.epi = (relu, p_drop, rng_used, None if bias is None else bias.shape)
                 ctx.save_for_backward(y)
                 return y
 
             @staticmethod
             def backward(ctx, g):
                 (y,) = ctx.saved_tensors
-                ga, gb = _epi_backward(ctx, g, y)
+                ga, gb = eng._epi_bwd(g, y, *ctx.epi)
                 gp = ctx.gp
                 gx = None
                 if ctx.needs_input_grad[2]:
@@ -1378,25 +1306,18 @@ class Engine:
                 a = add.contiguous() if add is not None else None
                 eng._check(eng.lib.ggl_segment_epi(_ptr(x), ctypes.byref(cs), K, int(bool(mean)), _ptr(a), 0, _ptr(b),
                                                    int(bool(relu)), 0.0, None, _ptr(y), eng._stream(dev)))
-                ctx.mean, ctx.has_add, ctx.x_shape, ctx.rng_used = bool(mean), add is not None, x.shape, None
-                ctx.cfg = (int(plan.N), K, int(relu), 0.0, None if bias is None else bias.shape)
+                ctx.mean, ctx.has_add, ctx.x_shape = bool(mean), add is not None, x.shape
+                ctx.epi = (relu, 0.0, None, None if bias is None else bias.shape)
                 ctx.save_for_backward(y, ids, plan.rowptr)
                 return y
 
             @staticmethod
             def backward(ctx, g):
                 y, ids, rowptr = ctx.saved_tensors
-                ga, gb = _epi_backward(ctx, g, y)
+                ga, gb = eng._epi_bwd(g, y, *ctx.epi)
                 gx = None
                 if ctx.needs_input_grad[0]:
-                    E, K = int(ctx.x_shape[0]), int(ctx.x_shape[1])
-                    gx = torch.empty(ctx.x_shape, dtype=ga.dtype, device=ga.device)
-                    if ctx.mean:
-                        eng._check(eng.lib.ggl_segment_mean_bwd(eng._code(ga), _ptr(ga), _ptr(ids), _ptr(rowptr), E, K,
-                                                                _ptr(gx), eng._stream(ga.device)))
-                    else:
-                        eng._check(eng.lib.ggl_segment_sum_bwd(eng._code(ga), _ptr(ga), _ptr(ids), E, K, _ptr(gx),
-                                                               eng._stream(ga.device)))
+                    gx = eng._segment_bwd(ga, ids, ctx.x_shape, rowptr if ctx.mean else None)
                 return gx, None, None, None, (ga if ctx.has_add else None), gb, None
 
         class GATHeadMean(torch.autograd.Function):
@@ -1418,15 +1339,9 @@ class Engine:
                 rowmax = torch.empty((N, H), dtype=torch.float32, device=dev)
                 den = torch.empty((N, H), dtype=torch.float32, device=dev)
                 A = torch.empty((N, H, F), dtype=torch.float32, device=dev)
-                part = None
-                if gp.fwd.n_long > 0:
-                    part = torch.empty(eng.lib.ggl_gat_sh_partial_bytes(gp.fwd.n_chunks, F) + 16, dtype=torch.uint8,
-                                       device=dev)
+                part = eng._gat_sh_partial(gp.fwd, F, dev)
                 cs = gp.fwd.c_struct(part)
-                rng = rng_used = None
-                if p_drop > 0:
-                    rng = eng._rng_state(dev)
-                    rng_used = rng.clone()
+                rng, rng_used = eng._draw(dev, p_drop)
                 eng._check(eng.lib.ggl_gat_sh_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(el), _ptr(er), _ptr(x), F,
                                                   float(slope), float(p_drop), _ptr(rng), _ptr(rowmax), _ptr(A),
                                                   _ptr(den), eng._stream(dev)))
@@ -1462,13 +1377,7 @@ class Engine:
                 T = torch.empty((N, H, Cp), dtype=torch.float32, device=dev)
                 bwd = gp.bwd
                 # forward plan's partial: four doubles per hub chunk and head (the destination walk's row sums, round 6)
-                part_f = None
-                if gp.fwd.n_long > 0:
-                    part_f = torch.empty(eng.lib.ggl_gat_sh_partial_bytes(gp.fwd.n_chunks, 8) + 16, dtype=torch.uint8, device=dev)
-                part_t = None
-                if bwd.n_long > 0:
-                    part_t = torch.empty(eng.lib.ggl_gat_sh_partial_bytes(bwd.n_chunks, Cp) + 16, dtype=torch.uint8,
-                                         device=dev)
+                part_f, part_t = eng._gat_sh_partial(gp.fwd, 8, dev), eng._gat_sh_partial(bwd, Cp, dev)
                 cs, csT = gp.fwd.c_struct(part_f), bwd.c_struct(part_t)
                 posT = gp.posT if ctx.p_drop > 0 else None
                 eng._check(eng.lib.ggl_gat_sh_bwd(ctypes.byref(cs), _ptr(gp.col), ctypes.byref(csT), _ptr(gp.colT),
@@ -1502,15 +1411,15 @@ class Engine:
                 b = bias.contiguous().reshape(-1) if bias is not None else None
                 a = add.contiguous() if add is not None else None
                 eng.spmm_epi_into(blk.plan, blk.col, None, x, y, mean=True, add=a, bias=b, relu=relu)
-                ctx.blk, ctx.has_add, ctx.rng_used = blk, add is not None, None
-                ctx.cfg = (blk.n_dst_cap, K, int(relu), 0.0, None if bias is None else bias.shape)
+                ctx.blk, ctx.has_add = blk, add is not None
+                ctx.epi = (relu, 0.0, None, None if bias is None else bias.shape)
                 ctx.save_for_backward(y)
                 return y
 
             @staticmethod
             def backward(ctx, g):
                 (y,) = ctx.saved_tensors
-                ga, gb = _epi_backward(ctx, g, y)
+                ga, gb = eng._epi_bwd(g, y, *ctx.epi)
                 gx = None
                 if ctx.needs_input_grad[0]:
                     blk = ctx.blk
@@ -1558,7 +1467,6 @@ class Engine:
 
         self.SpMMRows = SpMMRows
         self.SpMMEpi, self.SegmentEpi = SpMMEpi, SegmentEpi
-        self.SpMMSumBiasAct = SpMMSumBiasAct
         self.BiasAct = BiasAct
         self.BiasAdd = BiasAdd
         self.SegmentSum, self.SegmentMean, self.SegmentMax = SegmentSum, SegmentMean, SegmentMax
@@ -1706,8 +1614,7 @@ class Engine:
         dev = self._dev(g)
         self._check_f32("g", g)
         g = g.contiguous()
-        N = int(g.shape[0])
-        K = g.numel() // N if N > 0 else int(math.prod(g.shape[1:]))
+        N, K = self._rows_cols(g)
         out = torch.empty(tuple(g.shape[1:]), dtype=torch.float32, device=dev)
         wsb = self.lib.ggl_colsum_workspace_bytes(N, K)
         ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=dev)
@@ -1726,6 +1633,47 @@ class Engine:
             st = torch.tensor([seed, 0], dtype=torch.int64, device=dev)
             self._rng[str(dev)] = st
         return st
+
+    def _draw(self, dev, p_drop):
+        """One fused-dropout draw on `dev`: (rng, rng_used) — the device state the launch reads and then advances by one,
+        and a clone of the {seed, offset} it reads, which the backward is handed to redraw the mask.  (None, None) at
+        rate 0: nothing is drawn and the state does not move."""
+        if not p_drop > 0:
+            return None, None
+        rng = self._rng_state(dev)
+        return rng, rng.clone()
+
+    @staticmethod
+    def _rows_cols(t):
+        """(N, K) of a row-major [N, ...] tensor walked as an [N, K] matrix."""
+        N = int(t.shape[0])
+        return N, (t.numel() // N if N > 0 else int(math.prod(t.shape[1:])))
+
+    def _epi_fwd(self, a, bias, relu, p_drop, rng):
+        """y = dropout(relu(a + bias)) of a contiguous f32 `a` in one kernel (ggl_bias_act_fwd); `rng` from _draw."""
+        N, K = self._rows_cols(a)
+        y = torch.empty_like(a)
+        b = bias.contiguous().reshape(-1) if bias is not None else None
+        self._check(self.lib.ggl_bias_act_fwd(_ptr(a), _ptr(b), N, K, int(relu), float(p_drop), _ptr(rng), _ptr(y),
+                                              self._stream(a.device)))
+        return y
+
+    def _epi_bwd(self, g, y, relu, p_drop, rng_used, bias_shape):
+        """Back through dropout / ReLU / + bias (/ + add) in one pass (ggl_bias_act_bwd): the mask is redrawn from
+        `rng_used` (the forward's _draw) and the ReLU read off the saved output `y`.  Returns (ga, gbias), gbias in
+        `bias_shape` or None without a bias; g itself when there is nothing to undo."""
+        g = g.contiguous()
+        if not (relu or p_drop > 0 or bias_shape is not None):
+            return g, None
+        dev = g.device
+        N, K = self._rows_cols(g)
+        ga = torch.empty_like(g)
+        gb = torch.empty(K, dtype=torch.float32, device=dev) if bias_shape is not None else None
+        wsb = self.lib.ggl_bias_act_bwd_workspace_bytes(N, K)
+        ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=dev)
+        self._check(self.lib.ggl_bias_act_bwd(_ptr(g), _ptr(y), N, K, int(relu), float(p_drop), _ptr(rng_used),
+                                              _ptr(ga), _ptr(gb), _ptr(ws), wsb, self._stream(dev)))
+        return ga, (gb.reshape(bias_shape) if gb is not None else None)
 
     def reseed(self, seed=None):
         """Forget the fused-dropout RNG state (the next use draws a new seed from torch's generator) — of this engine AND, for
@@ -1758,7 +1706,7 @@ class Engine:
             self._check_f32("bias", bias)
         p = float(p_drop) if training else 0.0
         if x.dim() == 2 and x.shape[1] % 4 == 0:
-            return self.SpMMSumBiasAct.apply(gp, weight, x.contiguous(), bias, bool(relu), p)
+            return self.SpMMEpi.apply(gp, weight, x.contiguous(), False, None, bias, bool(relu), p)
         return self.BiasAct.apply(self.SpMMSum.apply(gp, weight, x.contiguous()), bias, bool(relu), p)
 
     def spmm_epi(self, gp, weight, x, reduce="sum", add=None, bias=None, relu=False, p_drop=0.0, training=True):

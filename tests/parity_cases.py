@@ -1223,7 +1223,7 @@ def check_bias_act(eng, dev):
 
 
 def check_spmm_bias_act(eng, dev):
-    """SpMM with the layer epilogue applied in its store (ggl_spmm_sum_bias_act) == SpMM, then the epilogue
+    """SpMM with the layer epilogue applied in its store (Engine.spmm_bias_act: ggl_spmm_epi_ex) == SpMM, then the epilogue
     kernel, replayed on the same RNG state: values, dropout mask and every gradient bit for bit — short
     rows, chunked hub rows (epilogue in long_final_kernel), wave-per-row and narrow widths, K % 4 != 0."""
     g = torch.Generator(device="cpu").manual_seed(21)
@@ -1263,6 +1263,113 @@ def check_spmm_bias_act(eng, dev):
         assert torch.equal(eng.spmm_bias_act(gp, None, x, None, relu=True), torch.relu(eng.spmm(gp, None, x)))
         assert torch.equal(eng.spmm_bias_act(gp, None, x, None, relu=True, p_drop=0.9, training=False),
                            torch.relu(eng.spmm(gp, None, x)))
+    finally:
+        eng.chunk = old
+        eng.graph_cache.clear(); eng.seg_cache.clear()
+
+
+def check_spmm_bias_act_is_epi(eng, dev):
+    """Engine.spmm_bias_act IS Engine.spmm_epi(reduce="sum", add=None): on the shapes of check_spmm_bias_act and from the same
+    RNG state, output, x.grad and bias.grad are equal bit for bit (one autograd node and one C body serve both names)."""
+    g = torch.Generator(device="cpu").manual_seed(21)
+    old = eng.chunk
+    try:
+        for chunk in (0, 8):
+            eng.chunk = chunk
+            eng.graph_cache.clear(); eng.seg_cache.clear()
+            for (N, E, K) in ((40, 600, 8), (64, 900, 64), (50, 700, 256), (30, 300, 47), (5, 0, 4)):
+                ei = torch.randint(0, N, (2, E), generator=g)
+                if E:
+                    ei[1, : E // 3] = 3  # a hub row (chunked when chunk = 8)
+                ei = ei.to(dev)
+                w = torch.rand(E, generator=g).to(dev)
+                gp = eng.graph_plan(ei, N)
+                go = torch.randn(N, K, generator=g).to(dev)
+                for (relu, p) in ((False, 0.0), (True, 0.0), (True, 0.5), (False, 0.3)):
+                    xa = torch.randn(N, K, generator=g).to(dev).requires_grad_(True)
+                    ba = torch.randn(1, K, generator=g).to(dev).requires_grad_(True)
+                    xb, bb = xa.detach().clone().requires_grad_(True), ba.detach().clone().requires_grad_(True)
+                    st = eng._rng_state(dev).clone()
+                    ya = eng.spmm_bias_act(gp, w, xa, ba, relu, p)
+                    eng._rng_state(dev).copy_(st)
+                    yb = eng.spmm_epi(gp, w, xb, "sum", None, bb, relu, p)
+                    assert torch.equal(ya, yb), (chunk, N, E, K, relu, p)
+                    if N * K:
+                        ya.backward(go)
+                        yb.backward(go)
+                        assert torch.equal(xa.grad, xb.grad) and torch.equal(ba.grad, bb.grad), (chunk, N, E, K, relu, p)
+    finally:
+        eng.chunk = old
+        eng.graph_cache.clear(); eng.seg_cache.clear()
+
+
+def check_dropout_state_discipline(eng, dev):
+    """What Engine._draw promises, for every op that carries a fused dropout: a training forward at p > 0 reads the device
+    {seed, offset} state and advances the offset by exactly 1; the backward redraws the mask from the clone the forward
+    kept and moves nothing; p = 0 and training=False leave the state alone; and from a restored state the forward and
+    the backward reproduce the output and every gradient bit for bit.  N = 40, E = 600, a third of the edges on one hub
+    row, walked chunked (chunk = 8) and in one piece (chunk = 0).  The ops whose kernels the host build stubs out
+    (csrc/host/gpu_only_stubs.cpp: gat_headmean) are covered where the library has them."""
+    from gammagl_amd.dist import PartitionedGraph
+
+    N, E, p = 40, 600, 0.5
+    g = torch.Generator(device="cpu").manual_seed(33)
+    ei = torch.randint(0, N, (2, E), generator=g)
+    ei[1, : E // 3] = 3
+    ei = ei.to(dev)
+    w = torch.rand(E, generator=g).to(dev)
+
+    def rand(*shape):
+        return torch.randn(*shape, generator=g).to(dev)
+
+    x8, x6, b8, b6, add8 = rand(N, 8), rand(N, 6), rand(1, 8), rand(1, 6), rand(N, 8)
+    el, er, xg = rand(N, 2), rand(N, 2), rand(N, 2, 8)
+    xh, Wh, atth = rand(N, 16), rand(16, 8 * 4) * 0.3, rand(1, 8, 2 * 4) * 0.3
+
+    def offset():
+        return int(eng._rng_state(dev)[1])
+
+    def run(fn, inputs):
+        """fn on fresh leaves of `inputs`: (output, gradients, RNG offsets before / after the forward / after the backward)."""
+        leaves = [t.detach().clone().requires_grad_(True) for t in inputs]
+        o0 = offset()
+        y = fn(*leaves)
+        o1 = offset()
+        y.backward(torch.ones_like(y))
+        return y.detach(), [t.grad for t in leaves], (o0, o1, offset())
+
+    old = eng.chunk
+    try:
+        for chunk in (8, 0):
+            eng.chunk = chunk
+            eng.graph_cache.clear(); eng.seg_cache.clear()
+            gp = eng.graph_plan(ei, N)
+            pg = PartitionedGraph(ei, w, N, 0, 1, eng=eng)
+            pg.route = "ctypes"   # this engine's stream (torch.ops.ggl keeps a counter of its own, which Python cannot read)
+            cases = {
+                "bias_act": (lambda q, t: lambda a, b: eng.bias_act(a, b, True, q, t), (x8, b8)),
+                "spmm_bias_act": (lambda q, t: lambda x, b: eng.spmm_bias_act(gp, w, x, b, True, q, t), (x8, b8)),
+                "spmm_epi+add": (lambda q, t: lambda x, a, b: eng.spmm_epi(gp, w, x, "mean", a, b, True, q, t), (x8, add8, b8)),
+                "spmm_epi K=6": (lambda q, t: lambda x, b: eng.spmm_epi(gp, w, x, "sum", None, b, False, q, t), (x6, b6)),
+                "gat_fused": (lambda q, t: lambda a, b, x: eng.gat_fused(gp, a, b, x, 0.2, N, q, t), (el, er, xg)),
+                "aggregate": (lambda q, t: lambda h, b: pg.aggregate(h, b, True, q, t), (x8, b8)),
+            }
+            if eng.lib.ggl_gat_sh_supported(8, 16, 4):   # the GPU build; the host build's stub answers 0
+                cases["gat_headmean"] = (lambda q, t: lambda x, W, a: eng.gat_headmean(gp, x, W, a, 0.2, N, q, t), (xh, Wh, atth))
+            for name, (make, inputs) in cases.items():
+                what = (name, chunk)
+                st = eng._rng_state(dev).clone()
+                y1, g1, (o0, o1, o2) = run(make(p, True), inputs)
+                assert o1 == o0 + 1, (what, "the forward advances the offset by exactly 1", o0, o1)
+                assert o2 == o1, (what, "the backward does not move the state", o1, o2)
+                eng._rng_state(dev).copy_(st)
+                y2, g2, _ = run(make(p, True), inputs)
+                assert torch.equal(y1, y2), (what, "same state, same output")
+                assert all(torch.equal(a, b) for a, b in zip(g1, g2)), (what, "same state, same gradients")
+                for q, training in ((0.0, True), (p, False)):
+                    _, _, offs = run(make(q, training), inputs)
+                    assert offs[0] == offs[1] == offs[2], (what, "no dropout, no draw", q, training, offs)
+            pg.release()
     finally:
         eng.chunk = old
         eng.graph_cache.clear(); eng.seg_cache.clear()

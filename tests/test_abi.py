@@ -1,6 +1,7 @@
 """The drop-in boundary without a GPU: libggl_mpops_hip.so loads, exports every function
 include/ggl_mpops.h declares, reports the header's ABI version, and the ctypes prototypes in
-gammagl_amd/_lib.py have the declared number of parameters (no compute calls here)."""
+gammagl_amd/_lib.py have the declared number of parameters (no compute calls here, but for one entry point that only
+forwards: its direct call is the caller that keeps it honest)."""
 import ctypes
 import os
 import re
@@ -80,6 +81,38 @@ def test_host_library_is_a_product_artefact_with_the_same_surface():
     assert not [n for n in declared_functions() if not hasattr(lib, n)]
     # the capability queries of the GPU-only kernels answer "no" there (gpu_only_stubs.cpp)
     assert lib.ggl_gat_fast_supported(8, 8) == 0 and lib.ggl_gat_sh_supported(8, 64, 41) == 0
+
+
+def test_spmm_sum_bias_act_forwards_to_spmm_epi_ex():
+    """ggl_spmm_sum_bias_act stays in the header for its callers, but the engine launches ggl_spmm_epi_ex and the old entry
+    point forwards to it: called directly on the host library (N = 40, E = 600 with a hub row walked in one piece and in
+    chunks, K = 8, bias + ReLU, no dropout) it writes the bits of the general entry point, and those of the two-kernel form."""
+    import torch
+
+    from gammagl_amd import _lib
+    from gammagl_amd.ops import Engine, _ptr
+
+    eng = Engine(_lib.bind(_lib.HOST_LIB_PATH), require_cuda=False)
+    g = torch.Generator().manual_seed(7)
+    N, E, K = 40, 600, 8
+    ei = torch.randint(0, N, (2, E), generator=g)
+    ei[1, : E // 3] = 3
+    w, x, bias = torch.rand(E, generator=g), torch.randn(N, K, generator=g), torch.randn(K, generator=g)
+    for chunk in (0, 8):
+        eng.chunk = chunk
+        eng.graph_cache.clear()
+        gp = eng.graph_plan(ei, N)
+        part = eng._partial(gp.fwd, torch.float32, K, False, x.device)
+        ww, w_by_pos, wp = eng._weights(gp.fwd, w)
+        cs = gp.fwd.c_struct(part, wp)
+        st = eng._stream(x.device)
+        ya, yb = torch.full((N, K), float("nan")), torch.full((N, K), float("nan"))
+        assert eng.lib.ggl_spmm_sum_bias_act(ctypes.byref(cs), _ptr(gp.col), _ptr(ww), w_by_pos, _ptr(x), K, _ptr(bias), 1,
+                                             0.0, None, _ptr(ya), st) == 0, eng.lib.ggl_last_error()
+        assert eng.lib.ggl_spmm_epi_ex(ctypes.byref(cs), _ptr(gp.col), _ptr(ww), w_by_pos, _ptr(x), K, K, _ptr(yb), K, 0, 0,
+                                       None, 0, _ptr(bias), 1, 0.0, None, 0, 0, 1, st) == 0, eng.lib.ggl_last_error()
+        assert torch.equal(ya, yb), chunk
+        assert torch.equal(ya, torch.relu(eng.spmm(gp, w, x) + bias)), chunk
 
 
 def test_missing_library_is_an_import_error(monkeypatch, tmp_path):

@@ -95,6 +95,14 @@ def test_spmm_with_fused_epilogue(eng):
     pc.check_spmm_bias_act(eng, DEV)
 
 
+def test_spmm_bias_act_is_spmm_epi(eng):
+    pc.check_spmm_bias_act_is_epi(eng, DEV)
+
+
+def test_dropout_state_discipline(eng):
+    pc.check_dropout_state_discipline(eng, DEV)
+
+
 def test_random_vs_oracle(eng, oracle):
     pc.check_random_vs_oracle(eng, DEV, oracle)
 

@@ -140,6 +140,14 @@ def test_spmm_with_fused_epilogue(eng, dev):
     pc.check_spmm_bias_act(eng, dev)
 
 
+def test_spmm_bias_act_is_spmm_epi(eng, dev):
+    pc.check_spmm_bias_act_is_epi(eng, dev)
+
+
+def test_dropout_state_discipline(eng, dev):
+    pc.check_dropout_state_discipline(eng, dev)
+
+
 def test_plan_cache(eng, dev):
     pc.check_plan_cache(eng, dev)
 

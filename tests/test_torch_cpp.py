@@ -52,6 +52,14 @@ def test_reference_known_answers_and_oracle(cpp, golden, oracle):
     pc.check_edge_cases(cpp, dev, oracle)
 
 
+def test_registered_schemas_are_the_committed_ones(cpp):
+    """The operator surface under ggl:: — every name, argument, default and return — is tests/golden/ggl_schemas.txt,
+    character for character: a change of the library's inside (shared helpers, merged autograd nodes) must not move it."""
+    got = sorted(str(s) for s in torch._C._jit_get_all_schemas() if s.name.startswith("ggl::"))
+    want = open(os.path.join(HERE, "golden", "ggl_schemas.txt")).read().splitlines()
+    assert got == want, (sorted(set(got) - set(want)), sorted(set(want) - set(got)))
+
+
 def _pair(t):
     return t.clone().requires_grad_(True), t.clone().requires_grad_(True)
 
