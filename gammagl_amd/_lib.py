@@ -93,6 +93,8 @@ SIGNATURES = {
     "ggl_bspmm_grad_w": (c_int, [_V, _V, _V, c_int64, c_int64, c_int64, _V, _V]),
     "ggl_bspmm_grad_w_sorted_scratch_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
     "ggl_bspmm_grad_w_sorted": (c_int, [_P, _V, _V, _V, _V, c_int64, c_int64, _V, _V, _V]),
+    "ggl_spmm_grad_w_scratch_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int, c_int]),
+    "ggl_spmm_grad_w": (c_int, [_P, _V, _V, c_int, _V, c_int, _V, _V, c_int64, _V, _V, _V]),
     "ggl_colsum_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "ggl_colsum_f32": (c_int, [_V, c_int64, c_int64, _V, _V, c_size_t, _V]),
     "ggl_bias_act_fwd": (c_int, [_V, _V, c_int64, c_int64, c_int, c_float, _V, _V, _V]),

@@ -40,3 +40,11 @@ def load():
         torch.ops.load_library(LIB_PATH)
         _loaded = True
     return torch.ops.ggl
+
+
+def load_grad():
+    """``torch.ops.ggl_grad`` (the same library): ``spmm_grad_w(index, x, grad, mean)``, gspmm's gradient with respect to its
+    edge weights — the op the autograd formulas of spmm_sum / spmm_mean / spmm_*_x16 / spmm_epi call.  A namespace of its own:
+    the surface under ``ggl::`` is the reference's operators and their passes, pinned name by name."""
+    load()
+    return torch.ops.ggl_grad

@@ -59,6 +59,7 @@ using torch::autograd::variable_list;
   X(ggl_segment_sum_bwd) X(ggl_segment_mean_bwd) X(ggl_segment_max_bwd) X(ggl_spmm_sum) X(ggl_spmm_mean)             \
   X(ggl_spmm_max) X(ggl_spmm_mean_bwd) X(ggl_spmm_max_bwd) X(ggl_bspmm_sum) X(ggl_bspmm_grad_w)                      \
   X(ggl_bspmm_grad_w_sorted_scratch_bytes) X(ggl_bspmm_grad_w_sorted)                                                \
+  X(ggl_spmm_grad_w_scratch_bytes) X(ggl_spmm_grad_w)                                                                \
   X(ggl_gat_partial_bytes) X(ggl_gat_fused_fwd) X(ggl_gat_fused_bwd_dst) X(ggl_gat_fused_bwd_src)                      \
   X(ggl_gat_fused_fwd_x16) X(ggl_gat_fused_bwd_dst_x16) X(ggl_gat_fused_bwd_src_x16)                                    \
   X(ggl_gat_fast_supported) X(ggl_gat_fast_fwd) X(ggl_gat_fast_bwd) X(ggl_bias_act_fwd)                                \
@@ -878,6 +879,30 @@ static std::tuple<Tensor, Tensor> spmm_max_arg_kernel(const Tensor &i, const c10
   Tensor out = spmm_kernel(SpOp::Max, i, w, x, &arg);
   return {out, arg};
 }
+// gw[e] = sum_k x[src_e, k] * grad[dst_e, k] (mean: grad / the destination row's edge count first): gspmm's gradient with
+// respect to its edge weights, f32 [E] whatever x and grad are stored as (ggl_spmm_grad_w; an extension, gspmm.cpp:79)
+static Tensor spmm_grad_w_kernel(const Tensor &index, const Tensor &x_in, const Tensor &grad, bool mean) {
+  same_device({&index, &x_in, &grad});
+  Tensor x = x_in.contiguous(), g = grad.contiguous();
+  if (!is_x16(x)) f32("x", x);
+  if (!is_x16(g)) f32("grad", g);
+  TORCH_CHECK(x.dim() >= 1 && g.dim() >= 1 && width_of(x.sizes()) == width_of(g.sizes()),
+              "spmm_grad_w: x ", x.sizes(), " and grad ", g.sizes(), " differ in row width");
+  c10::OptionalDeviceGuard guard(g.device());
+  const Api &a = api_for(g.device());
+  auto gp = graph_plan(index, g.size(0), x.size(0));
+  const int64_t K = width_of(x.sizes());
+  if (gp->E == 0 || K == 0) return at::zeros({gp->E}, g.options().dtype(at::kFloat));
+  Tensor gw = at::empty({gp->E}, g.options().dtype(at::kFloat));   // every entry is written (through perm)
+  gp->need_rowidx(index);
+  const size_t sb = a.ggl_spmm_grad_w_scratch_bytes(gp->E, gp->N_dst, K, dtype_code(x), mean ? 1 : 0);
+  Tensor scratch = sb > 0 ? at::empty({static_cast<int64_t>(sb / 4)}, gw.options()) : Tensor();
+  ggl_segplan_t cs = gp->fwd->c(Tensor());
+  check(a, a.ggl_spmm_grad_w(&cs, gp->col.data_ptr<int32_t>(), gp->rowidx.data_ptr<int32_t>(), dtype_code(x), x.data_ptr(),
+                             dtype_code(g), g.data_ptr(), mean ? gp->fwd->rowptr.data_ptr<int64_t>() : nullptr, K,
+                             gw.data_ptr<float>(), scratch.defined() ? scratch.data_ptr() : nullptr, stream_of(g.device())));
+  return gw;
+}
 // (gw, gx): gx = the transposed walk; gw[e, h] = sum_c x[src, h, c] * g[dst, h, c]   (bspmm_sum_cpu.cpp:58-113)
 static std::tuple<Tensor, Tensor> bspmm_sum_backward_kernel(const Tensor &index, const Tensor &weight, const Tensor &x_in,
                                                             const Tensor &grad) {
@@ -1543,6 +1568,19 @@ struct SegmentSoftmaxFn : public torch::autograd::Function<SegmentSoftmaxFn> {
   }
 };
 
+// gspmm's sum / mean differentiate with respect to a weight that requires grad (an extension: gspmm.cpp:30 marks it
+// non-differentiable): such a node saves x as its LAST tensor, a constant weight saves what it always did.  grad_w answers
+// the weight's gradient from `saved` (x at `at` when it was kept, else none) in the weight's own shape.
+static void save_for_grad_w(AutogradContext *ctx, variable_list keep, const OptT &weight, const Tensor &x) {
+  if (opt(weight).defined() && opt(weight).requires_grad()) keep.push_back(x);
+  ctx->save_for_backward(keep);
+}
+static Tensor grad_w(const variable_list &saved, size_t at, const Tensor &g, bool mean) {
+  if (saved.size() <= at) return Tensor();
+  static auto op = op_handle<Tensor(const Tensor &, const Tensor &, const Tensor &, bool)>("ggl_grad::spmm_grad_w");
+  return op.call(saved[0], saved[at], g, mean).view(saved[1].sizes());
+}
+
 template <SpOp OP>
 struct SpMMFn : public torch::autograd::Function<SpMMFn<OP>> {
   static Tensor forward(AutogradContext *ctx, const Tensor &index, const OptT &weight, const Tensor &x) {
@@ -1555,7 +1593,7 @@ struct SpMMFn : public torch::autograd::Function<SpMMFn<OP>> {
       return std::get<0>(r);
     }
     static auto op = op_handle<SpSig>(OP == SpOp::Sum ? "ggl::spmm_sum" : "ggl::spmm_mean");
-    ctx->save_for_backward({index, opt(weight)});
+    save_for_grad_w(ctx, {index, opt(weight)}, weight, x);
     return op.call(index, weight, x);
   }
   static variable_list backward(AutogradContext *ctx, variable_list grads) {
@@ -1565,11 +1603,11 @@ struct SpMMFn : public torch::autograd::Function<SpMMFn<OP>> {
     if (OP == SpOp::Max) {
       static auto op = op_handle<Tensor(const Tensor &, const OptT &, const Tensor &, const Tensor &)>("ggl::spmm_max_backward");
       gx = op.call(saved[0], w, grads[0], saved[2]);
-    } else {
-      static auto op = op_handle<SpSig>(OP == SpOp::Sum ? "ggl::spmm_sum_backward" : "ggl::spmm_mean_backward");
-      gx = op.call(saved[0], w, grads[0]);
+      return {Tensor(), Tensor(), gx};
     }
-    return {Tensor(), Tensor(), gx};
+    static auto op = op_handle<SpSig>(OP == SpOp::Sum ? "ggl::spmm_sum_backward" : "ggl::spmm_mean_backward");
+    gx = op.call(saved[0], w, grads[0]);
+    return {Tensor(), grad_w(saved, 2, grads[0], OP == SpOp::Mean), gx};
   }
 };
 
@@ -1604,7 +1642,7 @@ struct SpMMX16Fn : public torch::autograd::Function<SpMMX16Fn<OP>> {
   static Tensor forward(AutogradContext *ctx, const Tensor &index, const OptT &weight, const Tensor &x, bool out_f32) {
     at::AutoDispatchBelowADInplaceOrView below;
     static auto op = op_handle<Sig16>(OP == SpOp::Sum ? "ggl::spmm_sum_x16" : "ggl::spmm_mean_x16");
-    ctx->save_for_backward({index, opt(weight)});
+    save_for_grad_w(ctx, {index, opt(weight)}, weight, x);
     ctx->saved_data["x_dtype"] = static_cast<int64_t>(x.scalar_type());
     return op.call(index, weight, x, out_f32);
   }
@@ -1614,7 +1652,7 @@ struct SpMMX16Fn : public torch::autograd::Function<SpMMX16Fn<OP>> {
     static auto op = op_handle<SpSig>(OP == SpOp::Sum ? "ggl::spmm_sum_backward" : "ggl::spmm_mean_backward");
     Tensor gx = op.call(saved[0], w, grads[0]);
     const auto xt = static_cast<at::ScalarType>(ctx->saved_data["x_dtype"].toInt());
-    return {Tensor(), Tensor(), gx.scalar_type() == xt ? gx : gx.to(xt), Tensor()};
+    return {Tensor(), grad_w(saved, 2, grads[0], OP == SpOp::Mean), gx.scalar_type() == xt ? gx : gx.to(xt), Tensor()};
   }
 };
 static Tensor spmm_sum_x16_autograd(const Tensor &i, const OptT &w, const Tensor &x, bool f) { return SpMMX16Fn<SpOp::Sum>::apply(i, w, x, f); }
@@ -1769,7 +1807,7 @@ struct SpMMEpiFn : public torch::autograd::Function<SpMMEpiFn> {
     at::AutoDispatchBelowADInplaceOrView below;
     static auto op = op_handle<EpiFwdSig>("ggl::spmm_epi_forward");
     auto r = op.call(index, weight, x, mean, add, bias, relu, p);
-    ctx->save_for_backward({index, opt(weight), std::get<0>(r), std::get<1>(r)});
+    save_for_grad_w(ctx, {index, opt(weight), std::get<0>(r), std::get<1>(r)}, weight, x);
     ctx->saved_data["mean"] = mean;
     ctx->saved_data["relu"] = relu;
     ctx->saved_data["p"] = p;
@@ -1783,8 +1821,11 @@ struct SpMMEpiFn : public torch::autograd::Function<SpMMEpiFn> {
     OptT_ w = s[1].defined() ? OptT_(s[1]) : OptT_();
     static auto sum_bwd = op_handle<SpSig>("ggl::spmm_sum_backward");
     static auto mean_bwd = op_handle<SpSig>("ggl::spmm_mean_backward");
-    Tensor gx = ctx->saved_data["mean"].toBool() ? mean_bwd.call(s[0], w, ga) : sum_bwd.call(s[0], w, ga);
-    return {Tensor(), Tensor(), gx, Tensor(), ctx->saved_data["has_add"].toBool() ? ga : Tensor(), gb, Tensor(), Tensor()};
+    const bool mean = ctx->saved_data["mean"].toBool();
+    Tensor gx = mean ? mean_bwd.call(s[0], w, ga) : sum_bwd.call(s[0], w, ga);
+    // the weight's gradient is the edge-dot of x with the PRE-ACTIVATION gradient
+    return {Tensor(), grad_w(s, 4, ga, mean), gx, Tensor(), ctx->saved_data["has_add"].toBool() ? ga : Tensor(), gb, Tensor(),
+            Tensor()};
   }
 };
 // one kernel for 16-byte rows; the reduce op followed by the adds and the epilogue pass otherwise (same values)
@@ -1871,6 +1912,9 @@ static std::tuple<Tensor, Tensor> seg_max_meta(const Tensor &x, const Tensor &, 
 static Tensor like_x_meta(const Tensor &, const OptT &, const Tensor &x) { return at::empty_like(x); }
 static Tensor x16_meta(const Tensor &, const OptT &, const Tensor &x, bool out_f32) {
   return out_f32 ? at::empty(x.sizes(), x.options().dtype(at::kFloat)) : at::empty_like(x);
+}
+static Tensor spmm_grad_w_meta(const Tensor &index, const Tensor &, const Tensor &g, bool) {
+  return at::empty({index.size(1)}, g.options().dtype(at::kFloat));
 }
 static std::tuple<Tensor, Tensor> spmm_max_arg_meta(const Tensor &, const OptT &, const Tensor &x) {
   return {at::empty_like(x), at::empty(x.sizes(), x.options().dtype(at::kLong))};
@@ -2128,3 +2172,13 @@ TORCH_LIBRARY_IMPL(ggl, Meta, m) {
   m.impl("spmm_rows_backward", ggl_torch::rows_bwd_meta);
   m.impl("segment_epi_forward", ggl_torch::seg_epi_meta);
 }
+
+// gspmm's weight gradient as a dispatcher op.  It lives in a namespace of its own: the operator surface under ggl:: is
+// pinned name by name (tests/golden/ggl_schemas.txt), and the autograd formulas of spmm_sum / spmm_mean / spmm_*_x16 /
+// spmm_epi above need an OP to call so that their backward traces under FakeTensor like the others.
+TORCH_LIBRARY(ggl_grad, m) {
+  m.def("spmm_grad_w(Tensor index, Tensor x, Tensor grad, bool mean) -> Tensor");
+}
+TORCH_LIBRARY_IMPL(ggl_grad, CPU, m) { m.impl("spmm_grad_w", ggl_torch::spmm_grad_w_kernel); }
+TORCH_LIBRARY_IMPL(ggl_grad, CUDA, m) { m.impl("spmm_grad_w", ggl_torch::spmm_grad_w_kernel); }
+TORCH_LIBRARY_IMPL(ggl_grad, Meta, m) { m.impl("spmm_grad_w", ggl_torch::spmm_grad_w_meta); }

@@ -109,11 +109,10 @@ class MessagePassing(nn.Module):
                    or x.dtype in (torch.bfloat16, torch.float16))
               and type(self).message is MessagePassing.message
               and type(self).aggregate is MessagePassing.aggregate
-              # gspmm treats the edge weight as a constant (gspmm.cpp:30); a weight that needs a gradient
-              # must stay on the message() route, which differentiates through the multiply — and so must a
-              # weight that is not one f32 value per edge (the message() route promotes / broadcasts it)
+              # a weight that is not one f32 value per edge stays on the message() route, which promotes /
+              # broadcasts it (a learnable one takes the SpMM: sum and mean differentiate with respect to it)
               and not (kwargs.get('edge_weight') is not None and
-                       (kwargs['edge_weight'].requires_grad or kwargs['edge_weight'].dtype != torch.float32
+                       (kwargs['edge_weight'].dtype != torch.float32
                         or kwargs['edge_weight'].numel() != edge_index.shape[1]))):
             # The default message() (gather * weight) + aggregate() pair IS an SpMM.  A big (full-graph) edge
             # list takes the fused rectangular kernel: no [E, K] message tensor (Reddit-sized SAGEConv layer:
@@ -198,12 +197,11 @@ class GCNConv(MessagePassing):
         bias = self.bias
         if pad and bias is not None:
             bias = torch.nn.functional.pad(bias, (0, pad))
-        if (weights.requires_grad or weights.dtype != torch.float32 or weights.dim() != 1
-                or weights.numel() != edge_index.shape[1]):
-            # a learnable edge weight: gspmm treats weights as constants (gspmm.cpp:30), so stay on the
-            # message() * weight -> unsorted_segment_sum route, which differentiates through the multiply; the
-            # same route takes weights that are not one f32 value per edge (a float64 edge_weight promotes the
-            # messages exactly as the reference's message() does, a mis-shaped one raises there as it does here)
+        if weights.dtype != torch.float32 or weights.dim() != 1 or weights.numel() != edge_index.shape[1]:
+            # weights that are not one f32 value per edge take the message() * weight -> unsorted_segment_sum route
+            # (a float64 edge_weight promotes the messages exactly as the reference's message() does, a mis-shaped
+            # one raises there as it does here); a learnable f32 one takes the aggregate below, which differentiates
+            # with respect to it
             out = self.aggregate(self.message(x, edge_index, weights), edge_index, num_nodes, 'sum')
             if out.dtype != torch.float32:   # promoted messages: the epilogue in torch, as the reference runs it
                 out = out + bias if bias is not None else out

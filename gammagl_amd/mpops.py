@@ -99,7 +99,15 @@ def gspmm(index, weight=None, x=None, reduce='sum'):
     An extension over the reference, which is f32 only: for 'sum' and 'mean', ``x`` may be STORED as bfloat16 / float16
     (what a preceding Linear produces under ``torch.autocast``).  Every product and add is then made in f32, in the f32
     op's order, and the result is rounded once to x's dtype: ``gspmm(i, w, x16) == gspmm(i, w, x16.float()).to(x16.dtype)``
-    bit for bit; the gradient w.r.t. x follows the same rule.  ``weight`` stays f32.  'max' and ``bspmm`` are f32 only."""
+    bit for bit; the gradient w.r.t. x follows the same rule.  ``weight`` stays f32.  'max' and ``bspmm`` are f32 only.
+
+    A second extension: 'sum' and 'mean' differentiate with respect to ``weight`` (the reference's extension returns no
+    weight gradient, gspmm.cpp:79).  ``weight.grad[e] = sum_k x[src_e, k] * g[dst_e, k]`` — for 'mean' with ``g`` divided
+    by the destination row's edge count first — in f32, k ascending, rounded multiply then rounded add, whatever ``x``
+    and ``g`` are stored as; no [E, K] tensor is formed.  A weight that does not require grad costs nothing new.  'max'
+    does not: its witnesses are source-node ids, so its weight stays a constant there.  A weight used twice on the same
+    graph is read from a sorted copy cached by its storage and version: change a learnable weight with in-place ops on the
+    tensor (an optimizer step does), not through ``weight.data``, which leaves the version and so the cached copy as they were."""
     _engine(x)._dev(index, weight, x)
     _ops = _ops_for(x)
     # weight=None: torch.py:332-333 builds ones([E]) f32; w * x == x exactly, so the kernels simply skip

@@ -990,6 +990,24 @@ class Engine:
         gx, _ = self._spmm_fwd(op, gp.bwd, gp.colT, w, g, gp.N_src, aux=aux)
         return gx if gx.dtype == x_dtype else gx.to(x_dtype)
 
+    def _spmm_grad_w(self, gp, x, g, mean):
+        """gw [E] of gspmm sum / mean (ggl_spmm_grad_w): gw[e] = sum_k x[src_e, k] * g[dst_e, k], g divided by
+        the destination row's edge count first for mean.  f32 [E] whatever x and g are stored as (f32 / bf16 / f16 each:
+        widened at the load, f32 products and adds in the serial order); along the destination-sorted forward plan."""
+        g = g.contiguous()
+        K = int(math.prod(x.shape[1:]))
+        if gp.E == 0 or K == 0:
+            return torch.zeros(gp.E, dtype=torch.float32, device=g.device)
+        gw = torch.empty(gp.E, dtype=torch.float32, device=g.device)     # every entry is written (through perm)
+        xc, gc = _DTYPE_CODE[x.dtype], _DTYPE_CODE[g.dtype]
+        sb = self.lib.ggl_spmm_grad_w_scratch_bytes(gp.E, gp.N_dst, K, xc, int(bool(mean)))
+        scratch = torch.empty(sb // 4, dtype=torch.float32, device=g.device) if sb else None
+        cs = gp.fwd.c_struct(None)
+        self._check(self.lib.ggl_spmm_grad_w(ctypes.byref(cs), _ptr(gp.col), _ptr(gp.rowidx), xc, _ptr(x), gc, _ptr(g),
+                                             _ptr(gp.fwd.rowptr) if mean else None, K, _ptr(gw), _ptr(scratch),
+                                             self._stream(g.device)))
+        return gw
+
     # ---- autograd Functions (closures over this engine) ---------------------------------------
     def _make_functions(self):
         eng = self
@@ -1059,22 +1077,30 @@ class Engine:
                 return eng._softmax_bwd(y, g, ctx.plan), None
 
         def spmm_function(op):
-            """SpMMSum / SpMMMean (src/gspmm.cpp:26-80, 82-141): one body, the reduce as its parameter."""
+            """SpMMSum / SpMMMean (src/gspmm.cpp:26-80, 82-141): one body, the reduce as its parameter.  An extension
+            over the reference (gspmm.cpp:30 marks the weight non-differentiable): a weight that requires grad gets its
+            gradient (Engine._spmm_grad_w); only then is x saved, a constant weight costs what it did."""
 
             class SpMM(torch.autograd.Function):
                 @staticmethod
                 def forward(ctx, gp, w, x, out_dtype=None):
                     out, _ = eng._spmm_fwd(op, gp.fwd, gp.col, w, x, gp.N_dst, out_dtype=out_dtype)
                     ctx.gp, ctx.w, ctx.x_dtype = gp, w, x.dtype
+                    if w is not None and ctx.needs_input_grad[1]:
+                        ctx.save_for_backward(x)
                     return out
 
                 @staticmethod
                 def backward(ctx, g):
-                    if op == "mean":   # the transposed walk divides by the destination row's length
-                        gx = eng._spmm_bwd_x("mean_bwd", ctx.gp, ctx.w, g, ctx.x_dtype, aux=ctx.gp.fwd.rowptr)
-                    else:
-                        gx = eng._spmm_bwd_x("sum", ctx.gp, ctx.w, g, ctx.x_dtype)
-                    return None, None, gx, None  # weight is non-differentiable in the reference (gspmm.cpp:30)
+                    gx = gw = None
+                    if ctx.needs_input_grad[2]:
+                        if op == "mean":   # the transposed walk divides by the destination row's length
+                            gx = eng._spmm_bwd_x("mean_bwd", ctx.gp, ctx.w, g, ctx.x_dtype, aux=ctx.gp.fwd.rowptr)
+                        else:
+                            gx = eng._spmm_bwd_x("sum", ctx.gp, ctx.w, g, ctx.x_dtype)
+                    if ctx.w is not None and ctx.needs_input_grad[1]:
+                        gw = eng._spmm_grad_w(ctx.gp, ctx.saved_tensors[0], g, op == "mean").view(ctx.w.shape)
+                    return None, gw, gx, None
 
             SpMM.__name__ = SpMM.__qualname__ = "SpMM" + op.capitalize()
             return SpMM
@@ -1272,21 +1298,25 @@ class Engine:
                 eng.spmm_epi_into(gp.fwd, gp.col, w, x, y, mean=mean, add=a, bias=b, relu=relu, p_drop=p_drop, rng=rng)
                 ctx.gp, ctx.w, ctx.mean, ctx.has_add = gp, w, bool(mean), add is not None
                 ctx.epi = (relu, p_drop, rng_used, None if bias is None else bias.shape)
-                ctx.save_for_backward(y)
+                # a learnable weight's gradient is the edge-dot of x with the pre-activation gradient: x is kept for it alone
+                ctx.want_gw = w is not None and ctx.needs_input_grad[1]
+                ctx.save_for_backward(y, *((x,) if ctx.want_gw else ()))
                 return y
 
             @staticmethod
             def backward(ctx, g):
-                (y,) = ctx.saved_tensors
+                y = ctx.saved_tensors[0]
                 ga, gb = eng._epi_bwd(g, y, *ctx.epi)
                 gp = ctx.gp
-                gx = None
+                gx = gw = None
                 if ctx.needs_input_grad[2]:
                     if ctx.mean:
                         gx, _ = eng._spmm_fwd("mean_bwd", gp.bwd, gp.colT, ctx.w, ga, gp.N_src, aux=gp.fwd.rowptr)
                     else:
                         gx, _ = eng._spmm_fwd("sum", gp.bwd, gp.colT, ctx.w, ga, gp.N_src)
-                return None, None, gx, None, (ga if ctx.has_add else None), gb, None, None
+                if ctx.want_gw:
+                    gw = eng._spmm_grad_w(gp, ctx.saved_tensors[1], ga, ctx.mean).view(ctx.w.shape)
+                return None, gw, gx, None, (ga if ctx.has_add else None), gb, None, None
 
         class SegmentEpi(torch.autograd.Function):
             """The same epilogue on segment_sum / segment_mean of f32 messages x[E, K] (ggl_segment_epi): the
@@ -1537,6 +1567,17 @@ class Engine:
         if x.dtype not in _X16_DTYPES or out_dtype != torch.float32:
             raise RuntimeError(f"out_dtype={out_dtype}: only torch.float32 from bf16 / f16 rows (x is {x.dtype})")
         return out_dtype
+
+    def spmm_grad_w(self, index, x, grad, mean=False):
+        """The weight gradient of c_spmm_sum / c_spmm_mean as an op of its own: f32 [E], gw[e] = sum_k x[src_e, k] *
+        grad[dst_e, k] (mean: grad divided by the destination row's edge count first); x and grad f32, bf16 or f16."""
+        self._dev(index, x, grad)
+        self._check_f32_or_x16("x", x)
+        self._check_f32_or_x16("grad", grad)
+        if math.prod(x.shape[1:]) != math.prod(grad.shape[1:]):
+            raise RuntimeError(f"spmm_grad_w: x {tuple(x.shape)} and grad {tuple(grad.shape)} differ in row width")
+        gp = self.graph_plan(index, grad.shape[0], x.shape[0])
+        return self._spmm_grad_w(gp, x.contiguous(), grad, mean)
 
     def c_spmm_max(self, index, weight, x):
         return self.SpMMMax.apply(*self._spmm_args(index, weight, x))

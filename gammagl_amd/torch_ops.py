@@ -17,10 +17,13 @@ points (+ the fused GAT op and the fused epilogue) are dispatcher ops:
     torch.ops.gammagl_amd.spmm_sum_x16(index, weight, x, out_f32) -> Tensor   (not in the reference, see below)
     torch.ops.gammagl_amd.spmm_mean_x16(index, weight, x, out_f32) -> Tensor
     torch.ops.gammagl_amd.gat_fused_x16(index, el, er, x, negative_slope, num_nodes, dropout_rate, out_f32) -> Tensor
+    torch.ops.gammagl_amd.spmm_grad_w(index, x, grad, mean) -> Tensor         (not in the reference, see below)
 
 ``spmm_sum`` / ``spmm_mean`` also take ``x`` stored as bf16 / f16 (the reference is f32 only): the sums are made in f32 and
 rounded once to x's dtype.  ``spmm_*_x16(..., out_f32=True)`` returns those f32 sums unrounded.  ``gat_fused`` does the
 same for its ``x`` (``el`` / ``er`` stay f32; softmax and sums in f32), ``gat_fused_x16`` adds the ``out_f32`` choice.
+``spmm_sum`` / ``spmm_mean`` differentiate with respect to ``weight`` too (the reference's extension does not):
+``spmm_grad_w`` is that gradient, ``gw[e] = sum_k x[src_e, k] * grad[dst_e, k]`` in f32 (``mean``: grad / edge count first).
 
 Kernels are registered for ``CUDA`` / ``AutogradCUDA`` (= HIP on ROCm: libggl_mpops_hip.so) and for ``CPU`` /
 ``AutogradCPU`` (libggl_mpops_host.so, the host build of the same kernel sources) — the reference's ops dispatch
@@ -52,6 +55,7 @@ _SCHEMAS = {
     "spmm_mean_x16": "(Tensor index, Tensor? weight, Tensor x, bool out_f32=False) -> Tensor",
     "gat_fused_x16": "(Tensor index, Tensor el, Tensor er, Tensor x, float negative_slope=0.2, "
                      "int? num_nodes=None, float dropout_rate=0.0, bool out_f32=False) -> Tensor",
+    "spmm_grad_w": "(Tensor index, Tensor x, Tensor grad, bool mean) -> Tensor",
 }
 
 _DEF = Library(NS, "DEF")
@@ -79,6 +83,7 @@ def _kernels(get_engine):
         "spmm_mean_x16": lambda index, weight, x, out_f32=False: _x16(get_engine().c_spmm_mean, index, weight, x, out_f32),
         "gat_fused_x16": lambda index, el, er, x, negative_slope=0.2, num_nodes=None, dropout_rate=0.0, out_f32=False:
             _gat_x16(get_engine(), index, el, er, x, negative_slope, num_nodes, dropout_rate, out_f32),
+        "spmm_grad_w": lambda index, x, grad, mean: get_engine().spmm_grad_w(index, x, grad, mean),
     }
 
 
@@ -144,7 +149,8 @@ def _register_fakes():
                      ("spmm_sum", like_x), ("spmm_mean", like_x), ("spmm_max", like_x),
                      ("bspmm_sum", like_x), ("gat_fused", gat),
                      ("bias_act", lambda a, bias, relu, p_drop: torch.empty_like(a)),
-                     ("spmm_sum_x16", like_x16), ("spmm_mean_x16", like_x16), ("gat_fused_x16", gat_x16)):
+                     ("spmm_sum_x16", like_x16), ("spmm_mean_x16", like_x16), ("gat_fused_x16", gat_x16),
+                     ("spmm_grad_w", lambda index, x, grad, mean: grad.new_empty((index.shape[1],), dtype=torch.float32))):
         lib.impl(name, fn, "Meta")
     _IMPLS.append(lib)
 

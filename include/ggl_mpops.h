@@ -63,6 +63,8 @@ extern "C" {
  *   option reads GGL_<NAME> from the environment.  No struct change. */
 /* still 11: + ggl_gat_fused_{fwd,bwd_dst,bwd_src}_x16 (the fused GAT on bf16 / f16 rows).  Purely additive, as the _x16
  *   aggregates were in 10. */
+/* still 11: + ggl_spmm_grad_w, ggl_spmm_grad_w_scratch_bytes (gspmm's sum / mean gradient with respect to the edge weights, on
+ *   f32 / bf16 / f16 rows).  Purely additive again. */
 #define GGL_ABI_VERSION 11
 
 /* dtype codes (AT_DISPATCH_ALL_TYPES_AND2(Half, BFloat16), segment_sum_cpu.cpp:32-33) */
@@ -359,6 +361,27 @@ int ggl_bspmm_grad_w(const int64_t *index /* [2,E] int64 */, const float *x, con
 size_t ggl_bspmm_grad_w_sorted_scratch_bytes(int64_t E, int64_t N, int64_t H, int64_t C);
 int ggl_bspmm_grad_w_sorted(const ggl_segplan_t *plan, const int32_t *col, const int32_t *rowidx, const float *x,
                             const float *g, int64_t H, int64_t C, float *gw, float *scratch, void *stream);
+/* gspmm's gradient with respect to its edge weights (an extension: gspmm.cpp:79 returns none), sum and mean; max has none
+ * (its witnesses are source-node ids: with duplicate edges "the winner's weight" is ambiguous).  Along the destination-
+ * sorted FORWARD plan, as above:
+ *     gw[e] = sum_k x[src_e, k] * g'[dst_e, k]        k ascending, rounded multiply then rounded add, never contracted
+ *   sum  (mean_rowptr == NULL): g' = g
+ *   mean (mean_rowptr = the forward plan's rowptr): g'[r, :] = g[r, :] / count(r), count(r) = the row's edge count as f32
+ *        and the division the rounded f32 one — (g / count) * w, ggl_spmm_mean_bwd's order.  It is made once per row,
+ *        into an f32 [N_dst, K] panel in the scratch.
+ * x [N_src, K] and g [N_dst, K] are each GGL_F32, GGL_BF16 or GGL_F16, independently (g is f32 under 16-bit rows when the
+ * forward returned f32).  A 16-bit element is widened at the load (exact); products and adds are the f32 ones in the f32
+ * order and gw [E] is f32, never rounded:  gw(x16, g16) == gw(widen(x16), widen(g16)), and for f32 x and g the sum form
+ * == ggl_bspmm_grad_w_sorted(H = 1, C = K) (it runs those kernels), bit for bit, for every K.  gw is in the caller's edge
+ * order (through plan->perm; NULL = already sorted).  16-bit operands take the LDS-staged kernel for K % 8 == 0 and
+ * 16-byte aligned panels, f32 ones for K % 4 == 0; the rest, and the host build, walk one edge per thread.
+ * scratch: ggl_spmm_grad_w_scratch_bytes(E, N_dst, K, x_dtype, mean != 0) bytes, 16-byte aligned (0 -> may be NULL): the
+ * carried chain of launches over column blocks (options col_block / col_block16 by x's dtype, under the col_block_min_*
+ * thresholds), then the mean panel. */
+size_t ggl_spmm_grad_w_scratch_bytes(int64_t E, int64_t N_dst, int64_t K, int x_dtype, int mean);
+int ggl_spmm_grad_w(const ggl_segplan_t *plan, const int32_t *col, const int32_t *rowidx, int x_dtype, const void *x,
+                    int g_dtype, const void *g, const int64_t *mean_rowptr, int64_t K, float *gw, void *scratch,
+                    void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Column sums of a row-major [N,K] f32 matrix: out[k] = sum_r g[r,k] — the gradient of the
