@@ -345,7 +345,7 @@ extern "C" int ggl_bspmm_grad_w(const int64_t *index, const float *x, const floa
   // lane-to-lane ripple costs more than the strided loads it saves — 1 x 256: 103 -> 171 ms — so wider heads
   // stay on the thread-per-item kernel; a butterfly would be faster still, 57 ms, but not bit-exact)
   if (C > 16 && C <= 64 && C % 4 == 0 &&
-      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g)) & 15u) == 0 && !options().force_generic) {
+      aligned16(x) && aligned16(g) && !options().force_generic) {
     int logg = 2;
     while (logg < 4 && ((int64_t)4 << logg) < C) ++logg;  // lanes per item: next power of two >= C / 4, 4..16
     const int64_t groups = ceil_div(E * H, (int64_t)kGradWPerGroup);

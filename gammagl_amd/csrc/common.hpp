@@ -154,7 +154,6 @@ __device__ __forceinline__ U4 philox4x32_10(uint64_t index, uint64_t offset, uin
 
 int rng_advance(int64_t *rng_state, void *stream);  // offset += 1 on the stream (epilogue.hip)
 
-#ifndef GGL_EMULATE
 // hubf32.hip: the long rows of an f32 sum in serial order, one partial row each (see the file's header)
 struct HubF32Args {
   const float *x;
@@ -175,12 +174,47 @@ struct HubF32Args {
   int x16;                  // 0, or GGL_BF16 / GGL_F16: x holds 16-bit elements (x_ld / K in elements), widened before the multiply;
                             // tile, consumer and partial stay f32 (SpMM modes without heads only)
 };
+#ifndef GGL_EMULATE   // (GPU build only: the host build walks every row in one piece)
 int hub_f32_launch(const HubF32Args &a, hipStream_t stream, bool beside, int *forked);   // *forked: 0 or the join token
 int hub_f32_join(hipStream_t stream, int token);
 #endif
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// ---- host-side recipes every entry point shares (plain C++: the host build compiles them too) ----------------------
+// Dropout probability -> keep where the element's random word >= thresh (P(drop) = thresh / 2^32), kept values times scale
+static inline void dropout_params(float p_drop, uint32_t *thresh, float *scale) {
+  *thresh = p_drop > 0.0f ? (uint32_t)((double)p_drop * 4294967296.0) : 0u;
+  *scale = p_drop > 0.0f ? 1.0f / (1.0f - p_drop) : 1.0f;
+}
+
+// What a launcher reads off a plan before it walks it.  n_chunks is 0 and partial NULL for a plan without long rows;
+// how the partial buffer is carved up (pm = pacc + n_chunks * K, ...) belongs to the kernel and stays with the caller.
+struct WalkPlan {
+  int64_t N, E, chunk, n_long, n_chunks;
+  const int32_t *order;   // the plan's length-sorted row order, or NULL (option row_order = 0)
+  float *partial;
+};
+// The entry points word their rejections differently and the words are part of the ABI: null_text / chunk_text are the
+// caller's, `which` ("plan", "transposed plan") names the plan in the workspace error.
+static inline int walk_plan(const ggl_segplan_t *plan, const char *which, const char *null_text, const char *chunk_text,
+                            WalkPlan &p) {
+  GGL_REQUIRE(plan && plan->rowptr, GGL_EINVAL, "%s", null_text);
+  GGL_REQUIRE(plan->chunk > 0, GGL_EINVAL, "%s", chunk_text);
+  p.N = plan->N; p.E = plan->E; p.chunk = plan->chunk;
+  p.n_long = plan->n_long > 0 ? plan->n_long : 0;
+  p.n_chunks = p.n_long > 0 ? plan->n_chunks : 0;
+  p.order = options().row_order ? plan->row_order : nullptr;
+  p.partial = nullptr;
+  if (p.n_long > 0) {
+    GGL_REQUIRE(plan->long_rows && plan->chunk_ptr && plan->partial, GGL_EWORKSPACE,
+                "%s has long rows but long_rows/chunk_ptr/partial is NULL", which);
+    p.partial = static_cast<float *>(plan->partial);
+  }
+  return GGL_OK;
+}
 
 // ---- dtype semantics: "accumulate in the storage dtype" (segment_sum_cpu.cpp:56) ---------------
 // S = storage type in memory, A = register type.  add() rounds to storage precision after every

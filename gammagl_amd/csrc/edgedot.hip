@@ -367,7 +367,7 @@ extern "C" int ggl_bspmm_grad_w_sorted(const ggl_segplan_t *plan, const int32_t 
   GGL_REQUIRE(col && rowidx && x && g && gw, GGL_EINVAL, "NULL pointer");
   const int64_t total = E * H;
   hipStream_t s = as_stream(stream);
-  const bool vec = (C % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g)) & 15u) == 0 &&
+  const bool vec = (C % 4 == 0) && aligned16(x) && aligned16(g) &&
                    !options().force_generic;
 #ifndef GGL_EMULATE
   if (vec) {
@@ -436,7 +436,7 @@ static int gradw16_launch(const ggl_segplan_t *plan, const int32_t *col, const i
                           const void *g, int64_t K, float *gw, float *carry, hipStream_t s) {
   const int64_t E = plan->E;
 #ifndef GGL_EMULATE
-  const bool vec = (K % 8 == 0) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g)) & 15u) == 0 &&
+  const bool vec = (K % 8 == 0) && aligned16(x) && aligned16(g) &&
                    !options().force_generic;
   if (vec) {
     // this kernel walks in units of 8 columns and its tail template covers (width % 32) / 8 units: a block width that is

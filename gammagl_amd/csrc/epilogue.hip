@@ -233,11 +233,11 @@ extern "C" int ggl_bias_act_fwd(const float *a, const float *bias, int64_t N, in
   GGL_REQUIRE(a && y, GGL_EINVAL, "NULL pointer");
   GGL_REQUIRE(p_drop == 0.0f || rng_state, GGL_EINVAL, "dropout needs an rng_state");
   // keep when r >= thresh, r uniform on [0, 2^32): P(drop) = thresh / 2^32
-  const uint32_t thresh = p_drop > 0.0f ? (uint32_t)((double)p_drop * 4294967296.0) : 0u;
-  const float scale = p_drop > 0.0f ? 1.0f / (1.0f - p_drop) : 1.0f;
+  uint32_t thresh;
+  float scale;
+  dropout_params(p_drop, &thresh, &scale);
   hipStream_t s = as_stream(stream);
-  const bool vec4 = (K % 4 == 0) && ((reinterpret_cast<uintptr_t>(a) & 15u) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(y) & 15u) == 0);
+  const bool vec4 = (K % 4 == 0) && aligned16(a) && aligned16(y);
   int kp, groups;
   int64_t grid, rpb;
   geometry(N, K, vec4, &kp, &groups, &grid, &rpb);
@@ -281,17 +281,16 @@ extern "C" int ggl_bias_act_bwd(const float *g, const float *y, int64_t N, int64
   // 1.10 -> 1.87 ms on [2.45 M, 256] — is only paid where it is needed: dropout without ReLU.
   const bool redraw = p_drop > 0.0f && rng_used != nullptr && !relu;
   const int masked = relu ? 1 : (redraw ? 3 : (p_drop > 0.0f ? 2 : 0));
-  const uint32_t thresh = p_drop > 0.0f ? (uint32_t)((double)p_drop * 4294967296.0) : 0u;
+  uint32_t thresh;
+  float scale;
+  dropout_params(p_drop, &thresh, &scale);
   GGL_REQUIRE(!masked || masked == 3 || y || N == 0, GGL_EINVAL, "y is needed to rebuild the ReLU/dropout mask");
   GGL_REQUIRE(!gbias || (workspace && workspace_bytes >= ggl_bias_act_bwd_workspace_bytes(N, K)),
               GGL_EWORKSPACE, "bias_act_bwd workspace too small");
-  const bool vec4 = (K % 4 == 0) && ((reinterpret_cast<uintptr_t>(g) & 15u) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(ga) & 15u) == 0) &&
-                    (!masked || masked == 3 || (reinterpret_cast<uintptr_t>(y) & 15u) == 0);
+  const bool vec4 = (K % 4 == 0) && aligned16(g) && aligned16(ga) && (!masked || masked == 3 || aligned16(y));
   int kp, groups;
   int64_t blocks, rpb;
   geometry(N, K, vec4, &kp, &groups, &blocks, &rpb);
-  const float scale = p_drop > 0.0f ? 1.0f / (1.0f - p_drop) : 1.0f;
   hipStream_t s = as_stream(stream);
   float *partial = gbias ? static_cast<float *>(workspace) : nullptr;
 #define GGL_BAB(V, M)                                                                                    \
@@ -317,7 +316,7 @@ extern "C" int ggl_bias_grad_rows(const float *g, const int64_t *rows, int64_t R
   GGL_REQUIRE(R >= 0 && N >= 0 && R <= N && K > 0 && K % 4 == 0, GGL_EINVAL,
               "bias_grad_rows needs R <= N rows of a multiple of 4 columns");
   GGL_REQUIRE(gbias && ((g && rows) || R == 0), GGL_EINVAL, "NULL pointer");
-  GGL_REQUIRE((reinterpret_cast<uintptr_t>(g) & 15u) == 0, GGL_EINVAL, "g must be 16-byte aligned");
+  GGL_REQUIRE(aligned16(g), GGL_EINVAL, "g must be 16-byte aligned");
   GGL_REQUIRE(workspace && workspace_bytes >= ggl_bias_act_bwd_workspace_bytes(N, K), GGL_EWORKSPACE,
               "bias_grad_rows workspace too small (ggl_bias_act_bwd_workspace_bytes(N, K))");
   int kp, groups;

@@ -659,25 +659,22 @@ template <typename XT, typename OT>
 static int gat_fwd_impl(const ggl_segplan_t *plan, const int32_t *col, const float *el, const float *er,
                         const typename TT<XT>::S *x, float slope, int64_t H, int64_t C, float p_drop,
                         int64_t *rng_state, typename TT<OT>::S *out, float *rowmax, float *rowden, void *stream) {
-  GGL_REQUIRE(plan && plan->rowptr, GGL_EINVAL, "plan is NULL");
-  GGL_REQUIRE(H > 0 && C > 0 && plan->chunk > 0, GGL_EINVAL, "H, C and chunk must be positive");
-  const int64_t N = plan->N;
+  WalkPlan p;
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", "H, C and chunk must be positive", p)) return rc;
+  GGL_REQUIRE(H > 0 && C > 0, GGL_EINVAL, "H, C and chunk must be positive");
+  const int64_t N = p.N;
   if (N == 0) return GGL_OK;
   GGL_REQUIRE(er && out && rowmax && rowden, GGL_EINVAL, "NULL pointer");
-  GGL_REQUIRE((col && el && x) || plan->E == 0, GGL_EINVAL, "NULL pointer");
+  GGL_REQUIRE((col && el && x) || p.E == 0, GGL_EINVAL, "NULL pointer");
   GatDims d{};
-  d.slope = slope; d.N = N; d.H = H; d.C = C; d.K = H * C; d.E = plan->E;
-  d.chunk = plan->chunk; d.n_long = plan->n_long; d.n_chunks = plan->n_chunks;
-  int rcd = set_dropout(d, p_drop, rng_state);
-  if (rcd) return rcd;
-  float *pacc = nullptr, *pm = nullptr, *pd = nullptr;
-  if (plan->n_long > 0) {
-    GGL_REQUIRE(plan->long_rows && plan->chunk_ptr && plan->partial, GGL_EWORKSPACE,
-                "plan has long rows but long_rows/chunk_ptr/partial is NULL");
-    pacc = static_cast<float *>(plan->partial);
-    pm = pacc + plan->n_chunks * d.K;
-    pd = pm + plan->n_chunks * H;
-    d.chunk_blocks = ceil_div(plan->n_chunks, kWavesPerBlock);
+  d.slope = slope; d.N = N; d.H = H; d.C = C; d.K = H * C; d.E = p.E;
+  d.chunk = p.chunk; d.n_long = p.n_long; d.n_chunks = p.n_chunks;
+  if (int rc = set_dropout(d, p_drop, rng_state)) return rc;
+  float *pacc = p.partial, *pm = nullptr, *pd = nullptr;
+  if (p.n_long > 0) {
+    pm = pacc + p.n_chunks * d.K;
+    pd = pm + p.n_chunks * H;
+    d.chunk_blocks = ceil_div(p.n_chunks, kWavesPerBlock);
   }
   auto vec_ok = [&](int v) {
     return (C % v == 0) && gat_aligned<XT>(x, v) && gat_aligned<OT>(out, v) && gat_aligned<float>(pacc, v) &&
@@ -690,10 +687,9 @@ static int gat_fwd_impl(const ggl_segplan_t *plan, const int32_t *col, const flo
   d.nblocks = ceil_div(N, (int64_t)kWavesPerBlock * (kWave >> d.logL));
   const int64_t grid = d.chunk_blocks + d.nblocks;
   GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "too many rows for one launch");
-  const int32_t *order = options().row_order ? plan->row_order : nullptr;
   hipStream_t s = as_stream(stream);
 #define GGL_GAT_FWD(V, DR)                                                                              \
-  GGL_LAUNCH((gat_fwd_kernel<XT, OT, V, DR>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows, \
+  GGL_LAUNCH((gat_fwd_kernel<XT, OT, V, DR>), grid, kBlock, s, plan->rowptr, col, p.order, plan->long_rows, \
              plan->chunk_ptr, el, er, x, out, rowmax, rowden, pacc, pm, pd, (const int64_t *)rng_state, d)
   if (vec == 8) {  // (16-bit rows only: the f32 op has no such instantiation)
     if constexpr (gat_is16<XT>::value) {
@@ -732,29 +728,24 @@ static int gat_bwd_dst_impl(const ggl_segplan_t *plan, const int32_t *col, const
                             const typename TT<GT>::S *out, const float *rowmax, const float *rowden, float slope,
                             int64_t H, int64_t C, float p_drop, const int64_t *rng_used, float *alpha, float *de,
                             float *ger, void *stream) {
-  GGL_REQUIRE(plan && plan->rowptr, GGL_EINVAL, "plan is NULL");
-  GGL_REQUIRE(H > 0 && C > 0 && plan->chunk > 0, GGL_EINVAL, "H, C and chunk must be positive");
-  const int64_t N = plan->N, E = plan->E;
+  WalkPlan p;
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", "H, C and chunk must be positive", p)) return rc;
+  GGL_REQUIRE(H > 0 && C > 0, GGL_EINVAL, "H, C and chunk must be positive");
+  const int64_t N = p.N, E = p.E;
   if (N == 0) return GGL_OK;
   GGL_REQUIRE(er && g && out && rowmax && rowden && ger, GGL_EINVAL, "NULL pointer");
   GGL_REQUIRE((col && el && x && alpha && de) || E == 0, GGL_EINVAL, "NULL pointer");
   GatDims d{};
   d.slope = slope; d.N = N; d.H = H; d.C = C; d.K = H * C; d.E = E;
   d.es = (de == alpha + 1) ? 2 : 1;  // de == alpha + 1: one interleaved [E,H,2] buffer
-  d.chunk = plan->chunk; d.n_long = plan->n_long; d.n_chunks = plan->n_long > 0 ? plan->n_chunks : 0;
-  int rcd = set_dropout(d, p_drop, rng_used);
-  if (rcd) return rcd;
-  float *pger = nullptr;
-  if (plan->n_long > 0) {
-    GGL_REQUIRE(plan->long_rows && plan->chunk_ptr && plan->partial, GGL_EWORKSPACE,
-                "plan has long rows but long_rows/chunk_ptr/partial is NULL");
-    pger = static_cast<float *>(plan->partial);
-  }
+  d.chunk = p.chunk; d.n_long = p.n_long; d.n_chunks = p.n_chunks;
+  if (int rc = set_dropout(d, p_drop, rng_used)) return rc;
+  float *pger = p.partial;
   d.logL = pow2_log2(H);  // lanes per work item: the next power of two >= H, at most 64
   const int64_t items = d.n_chunks + N;
   const int64_t grid = ceil_div(items << d.logL, (int64_t)kBlock);
   GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "too many rows for one launch");
-  const int32_t *order = options().row_order ? plan->row_order : nullptr;
+  const int32_t *order = p.order;
   hipStream_t s = as_stream(stream);
   constexpr bool x16 = gat_is16<XT>::value;
   // (out is read by vectors in the wide kernel only; the f32 entry keeps its two tests, every torch allocation passes all)
@@ -850,23 +841,21 @@ template <typename GT, typename OT>
 static int gat_bwd_src_impl(const ggl_segplan_t *planT, const int32_t *colT, const int32_t *posT, const float *alpha,
                             const float *de, const typename TT<GT>::S *g, int64_t H, int64_t C,
                             typename TT<OT>::S *gx, float *gel, void *stream) {
-  GGL_REQUIRE(planT && planT->rowptr, GGL_EINVAL, "planT is NULL");
-  GGL_REQUIRE(H > 0 && C > 0 && planT->chunk > 0, GGL_EINVAL, "H, C and chunk must be positive");
-  const int64_t N = planT->N;
+  WalkPlan p;
+  if (int rc = walk_plan(planT, "transposed plan", "planT is NULL", "H, C and chunk must be positive", p)) return rc;
+  GGL_REQUIRE(H > 0 && C > 0, GGL_EINVAL, "H, C and chunk must be positive");
+  const int64_t N = p.N;
   if (N == 0) return GGL_OK;
   GGL_REQUIRE(gx && gel, GGL_EINVAL, "NULL pointer");
-  GGL_REQUIRE((colT && posT && alpha && de && g) || planT->E == 0, GGL_EINVAL, "NULL pointer");
+  GGL_REQUIRE((colT && posT && alpha && de && g) || p.E == 0, GGL_EINVAL, "NULL pointer");
   GatDims d{};
-  d.N = N; d.H = H; d.C = C; d.K = H * C; d.E = planT->E;
+  d.N = N; d.H = H; d.C = C; d.K = H * C; d.E = p.E;
   d.es = (de == alpha + 1) ? 2 : 1;
-  d.chunk = planT->chunk; d.n_long = planT->n_long; d.n_chunks = planT->n_chunks;
-  float *pacc = nullptr, *pgel = nullptr;
-  if (planT->n_long > 0) {
-    GGL_REQUIRE(planT->long_rows && planT->chunk_ptr && planT->partial, GGL_EWORKSPACE,
-                "transposed plan has long rows but long_rows/chunk_ptr/partial is NULL");
-    pacc = static_cast<float *>(planT->partial);
-    pgel = pacc + planT->n_chunks * d.K;
-    d.chunk_blocks = ceil_div(planT->n_chunks, kWavesPerBlock);
+  d.chunk = p.chunk; d.n_long = p.n_long; d.n_chunks = p.n_chunks;
+  float *pacc = p.partial, *pgel = nullptr;
+  if (p.n_long > 0) {
+    pgel = pacc + p.n_chunks * d.K;
+    d.chunk_blocks = ceil_div(p.n_chunks, kWavesPerBlock);
   }
   auto vec_ok = [&](int v) {
     return (C % v == 0) && gat_aligned<GT>(g, v) && gat_aligned<OT>(gx, v) && gat_aligned<float>(pacc, v) &&
@@ -879,10 +868,9 @@ static int gat_bwd_src_impl(const ggl_segplan_t *planT, const int32_t *colT, con
   d.nblocks = ceil_div(N, (int64_t)kWavesPerBlock * (kWave >> d.logL));
   const int64_t grid = d.chunk_blocks + d.nblocks;
   GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "too many rows for one launch");
-  const int32_t *order = options().row_order ? planT->row_order : nullptr;
   hipStream_t s = as_stream(stream);
 #define GGL_GAT_SRC(V)                                                                                          \
-  GGL_LAUNCH((gat_bwd_src_kernel<GT, OT, V>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows, \
+  GGL_LAUNCH((gat_bwd_src_kernel<GT, OT, V>), grid, kBlock, s, planT->rowptr, colT, posT, p.order, planT->long_rows, \
              planT->chunk_ptr, alpha, de, g, gx, gel, pacc, pgel, d)
   if (vec == 8) {  // (16-bit gx only)
     if constexpr (gat_is16<OT>::value) GGL_GAT_SRC(8);
@@ -1357,20 +1345,17 @@ static inline int ssm_logs(const ggl_segplan_t *plan, int64_t K) {
 #endif
 }
 
-static inline int ssm_setup(const ggl_segplan_t *plan, int64_t K, SsmDims &d, double *&part, int &logs) {
-  GGL_REQUIRE(plan && plan->rowptr, GGL_EINVAL, "plan is NULL");
+static inline int ssm_setup(const ggl_segplan_t *plan, int64_t K, SsmDims &d, double *&part, const int32_t *&order,
+                            int &logs) {
+  WalkPlan p;
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", "chunk must be positive", p)) return rc;
   GGL_REQUIRE(ggl_segment_softmax_supported(K), GGL_EINVAL, "segment_softmax: K = %lld is outside [1, 64]", (long long)K);
-  GGL_REQUIRE(plan->chunk > 0, GGL_EINVAL, "chunk must be positive");
-  d.N = plan->N; d.K = K;
-  d.n_long = plan->n_long > 0 ? plan->n_long : 0;
-  d.n_chunks = d.n_long > 0 ? plan->n_chunks : 0;
-  d.chunk = d.n_long > 0 ? plan->chunk : INT64_MAX;  // no long-row table: every row in one piece
-  part = nullptr;
-  if (d.n_long > 0) {
-    GGL_REQUIRE(plan->long_rows && plan->chunk_ptr && plan->partial, GGL_EWORKSPACE,
-                "plan has long rows but long_rows/chunk_ptr/partial is NULL");
-    part = reinterpret_cast<double *>((reinterpret_cast<uintptr_t>(plan->partial) + 7u) & ~(uintptr_t)7u);
-  }
+  d.N = p.N; d.K = K;
+  d.n_long = p.n_long;
+  d.n_chunks = p.n_chunks;
+  d.chunk = d.n_long > 0 ? p.chunk : INT64_MAX;  // no long-row table: every row in one piece
+  order = p.order;
+  part = p.partial ? reinterpret_cast<double *>((reinterpret_cast<uintptr_t>(p.partial) + 7u) & ~(uintptr_t)7u) : nullptr;
   logs = ssm_logs(plan, K);
   GGL_REQUIRE(ceil_div(((d.n_chunks + d.N) * K) << logs, kBlock) < ((int64_t)1 << 31), GGL_EINVAL,
               "too many rows for one launch");
@@ -1408,12 +1393,11 @@ extern "C" size_t ggl_segment_softmax_partial_bytes(int64_t n_chunks, int64_t K)
 extern "C" int ggl_segment_softmax_fwd(const float *x, const ggl_segplan_t *plan, int64_t K, float *y, void *stream) {
   SsmDims d{};
   double *part = nullptr;
+  const int32_t *order = nullptr;
   int logs = 0;
-  const int rc = ssm_setup(plan, K, d, part, logs);
-  if (rc) return rc;
+  if (int rc = ssm_setup(plan, K, d, part, order, logs)) return rc;
   if (plan->E == 0 || d.N == 0) return GGL_OK;
   GGL_REQUIRE(x && y, GGL_EINVAL, "NULL pointer");
-  const int32_t *order = options().row_order ? plan->row_order : nullptr;
   double *rowp = part ? part + d.n_chunks * K * 4 : nullptr;  // the long rows' merged statistics
   hipStream_t s = as_stream(stream);
   if (d.n_chunks > 0) {
@@ -1434,12 +1418,11 @@ extern "C" int ggl_segment_softmax_bwd(const float *y, const float *g, const ggl
                                        void *stream) {
   SsmDims d{};
   double *part = nullptr;
+  const int32_t *order = nullptr;
   int logs = 0;
-  const int rc = ssm_setup(plan, K, d, part, logs);
-  if (rc) return rc;
+  if (int rc = ssm_setup(plan, K, d, part, order, logs)) return rc;
   if (plan->E == 0 || d.N == 0) return GGL_OK;
   GGL_REQUIRE(y && g && gx, GGL_EINVAL, "NULL pointer");
-  const int32_t *order = options().row_order ? plan->row_order : nullptr;
   double *rowp = part ? part + d.n_chunks * K * 4 : nullptr;
   hipStream_t s = as_stream(stream);
   if (d.n_chunks > 0) {

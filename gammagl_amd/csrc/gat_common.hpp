@@ -146,11 +146,11 @@ static inline int64_t gat_grid_for(int64_t n) {
   return b < 1 ? 1 : b;
 }
 
-static inline int set_dropout(GatDims &d, float p_drop, const int64_t *rng) {
+// D: GatDims, or the shared-row path's ShDims (gat_fast.hip)
+template <typename D> static inline int set_dropout(D &d, float p_drop, const int64_t *rng) {
   GGL_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, GGL_EINVAL, "p_drop must be in [0, 1)");
   GGL_REQUIRE(p_drop == 0.0f || rng, GGL_EINVAL, "attention dropout needs an rng_state");
-  d.drop_thresh = p_drop > 0.0f ? (uint32_t)((double)p_drop * 4294967296.0) : 0u;
-  d.drop_scale = p_drop > 0.0f ? 1.0f / (1.0f - p_drop) : 1.0f;
+  dropout_params(p_drop, &d.drop_thresh, &d.drop_scale);
   return GGL_OK;
 }
 

@@ -880,7 +880,6 @@ static int gat_fast_c4(int64_t H, int64_t C) {
 
 extern "C" int ggl_gat_fast_supported(int64_t H, int64_t C) { return gat_fast_c4(H, C) ? 1 : 0; }
 
-static inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // dispatch KERN<C4, DROP, OFF32> over the supported head widths
 #define GGL_GAT2_DISPATCH(KERN, c4, drop, off32, ...)                                                  \
   do {                                                                                                 \
@@ -898,39 +897,53 @@ static inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) 
   case C4 * 4 + 2: GGL_LAUNCH((KERN<C4, true, false>), grid, kBlock, s, __VA_ARGS__); break;           \
   case C4 * 4 + 3: GGL_LAUNCH((KERN<C4, true, true>), grid, kBlock, s, __VA_ARGS__); break;
 
+// the hub chunks' partials combined behind a destination / source walk of either backward (nothing for a plan without long rows)
+static int bwd_dst_final4(const ggl_segplan_t *plan, const float *pger, float *ger, int64_t H, hipStream_t s) {
+  if (plan->n_long <= 0) return GGL_OK;
+  GGL_LAUNCH((gat_bwd_dst_final4_kernel), gat_grid_for(plan->n_long * H), kBlock, s, plan->long_rows, plan->chunk_ptr,
+             reinterpret_cast<const double *>(pger), ger, plan->n_long, H);
+  GGL_LAUNCH_CHECK();
+  return GGL_OK;
+}
+static int bwd_src_final(const ggl_segplan_t *planT, const float *pacc, const float *pgel, float *gx, float *gel,
+                         const GatDims &d, hipStream_t s) {
+  if (planT->n_long <= 0) return GGL_OK;
+  GGL_LAUNCH((gat_bwd_src_final_kernel), planT->n_long, kBlock, s, planT->long_rows, planT->chunk_ptr, pacc, pgel, gx, gel, d);
+  GGL_LAUNCH_CHECK();
+  return GGL_OK;
+}
+
+static const char kFastShape[] = "head shape not supported by the fast GAT path";
+
 extern "C" int ggl_gat_fast_fwd(const ggl_segplan_t *plan, const int32_t *col, const float *el,
                                 const float *er, const float *x, int64_t N_src, float slope, int64_t H,
                                 int64_t C, float p_drop, int64_t *rng_state, float *out, float *rowmax,
                                 float *rowden, void *stream) {
-  GGL_REQUIRE(plan && plan->rowptr, GGL_EINVAL, "plan is NULL");
+  WalkPlan p;
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", kFastShape, p)) return rc;
   const int c4 = gat_fast_c4(H, C);
-  GGL_REQUIRE(c4 > 0 && plan->chunk > 0, GGL_EINVAL, "head shape not supported by the fast GAT path");
-  const int64_t N = plan->N;
+  GGL_REQUIRE(c4 > 0, GGL_EINVAL, "%s", kFastShape);
+  const int64_t N = p.N;
   if (N == 0) return GGL_OK;
   GGL_REQUIRE(er && out && rowmax && rowden, GGL_EINVAL, "NULL pointer");
-  GGL_REQUIRE((col && el && x) || plan->E == 0, GGL_EINVAL, "NULL pointer");
+  GGL_REQUIRE((col && el && x) || p.E == 0, GGL_EINVAL, "NULL pointer");
   GatDims d{};
-  d.slope = slope; d.N = N; d.H = H; d.C = C; d.K = H * C; d.E = plan->E;
-  d.chunk = plan->chunk; d.n_long = plan->n_long; d.n_chunks = plan->n_long > 0 ? plan->n_chunks : 0;
-  int rcd = set_dropout(d, p_drop, rng_state);
-  if (rcd) return rcd;
-  float *pacc = nullptr, *pm = nullptr, *pd = nullptr;
-  if (plan->n_long > 0) {
-    GGL_REQUIRE(plan->long_rows && plan->chunk_ptr && plan->partial, GGL_EWORKSPACE,
-                "plan has long rows but long_rows/chunk_ptr/partial is NULL");
-    pacc = static_cast<float *>(plan->partial);
-    pm = pacc + plan->n_chunks * d.K;
-    pd = pm + plan->n_chunks * H;
+  d.slope = slope; d.N = N; d.H = H; d.C = C; d.K = H * C; d.E = p.E;
+  d.chunk = p.chunk; d.n_long = p.n_long; d.n_chunks = p.n_chunks;
+  if (int rc = set_dropout(d, p_drop, rng_state)) return rc;
+  float *pacc = p.partial, *pm = nullptr, *pd = nullptr;
+  if (p.n_long > 0) {
+    pm = pacc + p.n_chunks * d.K;
+    pd = pm + p.n_chunks * H;
   }
-  GGL_REQUIRE(al16(x) && al16(out) && al16(pacc) && al16(col), GGL_EINVAL, "fast GAT path needs 16-byte aligned buffers");
+  GGL_REQUIRE(aligned16(x) && aligned16(out) && aligned16(pacc) && aligned16(col), GGL_EINVAL, "fast GAT path needs 16-byte aligned buffers");
   d.logL = pow2_log2(H * c4);
   const int64_t items = d.n_chunks + N;
   const int64_t grid = ceil_div(items << d.logL, (int64_t)kBlock);
   GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "too many rows for one launch");
-  const int32_t *order = options().row_order ? plan->row_order : nullptr;
   const bool off32 = N_src > 0 && N_src * d.K * 4 < ((int64_t)1 << 32);
   hipStream_t s = as_stream(stream);
-  GGL_GAT2_DISPATCH(gat_fwd2_kernel, c4, d.drop_thresh != 0, off32, plan->rowptr, col, order, plan->long_rows,
+  GGL_GAT2_DISPATCH(gat_fwd2_kernel, c4, d.drop_thresh != 0, off32, plan->rowptr, col, p.order, plan->long_rows,
                     plan->chunk_ptr, el, er, x, out, rowmax, rowden, pacc, pm, pd, (const int64_t *)rng_state, d);
   GGL_LAUNCH_CHECK();
   if (plan->n_long > 0) {
@@ -950,69 +963,49 @@ extern "C" int ggl_gat_fast_bwd(const ggl_segplan_t *plan, const int32_t *col, c
                                 const float *rowden, float slope, int64_t H, int64_t C, float p_drop,
                                 const int64_t *rng_used, float *stats, float *gx, float *gel, float *ger,
                                 void *stream) {
-  GGL_REQUIRE(plan && plan->rowptr && planT && planT->rowptr, GGL_EINVAL, "plan is NULL");
+  WalkPlan p, pT;
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", kFastShape, p)) return rc;
+  if (int rc = walk_plan(planT, "transposed plan", "plan is NULL", kFastShape, pT)) return rc;
   const int c4 = gat_fast_c4(H, C);
-  GGL_REQUIRE(c4 > 0 && plan->chunk > 0 && planT->chunk > 0, GGL_EINVAL, "head shape not supported by the fast GAT path");
-  const int64_t N = plan->N, NT = planT->N, E = plan->E;
-  GGL_REQUIRE(planT->E == E, GGL_EINVAL, "forward and transposed plans disagree");
+  GGL_REQUIRE(c4 > 0, GGL_EINVAL, "%s", kFastShape);
+  const int64_t N = p.N, NT = pT.N, E = p.E;
+  GGL_REQUIRE(pT.E == E, GGL_EINVAL, "forward and transposed plans disagree");
   hipStream_t s = as_stream(stream);
   GatDims d{};
   d.slope = slope; d.H = H; d.C = C; d.K = H * C; d.E = E;
-  int rcd = set_dropout(d, p_drop, rng_used);
-  if (rcd) return rcd;
+  if (int rc = set_dropout(d, p_drop, rng_used)) return rc;
   GGL_REQUIRE(p_drop == 0.0f || posT || E == 0, GGL_EINVAL, "attention dropout needs posT");
   d.logL = pow2_log2(H * c4);
   const bool off32 = (N > NT ? N : NT) * d.K * 4 < ((int64_t)1 << 32);
   if (N > 0) {  // destination walk
     GGL_REQUIRE(er && g && out && rowmax && rowden && ger && stats, GGL_EINVAL, "NULL pointer");
     GGL_REQUIRE((col && el && x) || E == 0, GGL_EINVAL, "NULL pointer");
-    d.N = N; d.chunk = plan->chunk; d.n_long = plan->n_long; d.n_chunks = plan->n_long > 0 ? plan->n_chunks : 0;
-    float *pger = nullptr;
-    if (plan->n_long > 0) {
-      GGL_REQUIRE(plan->long_rows && plan->chunk_ptr && plan->partial, GGL_EWORKSPACE,
-                  "plan has long rows but long_rows/chunk_ptr/partial is NULL");
-      pger = static_cast<float *>(plan->partial);
-    }
-    GGL_REQUIRE(al16(x) && al16(g) && al16(out) && al16(stats) && al16(col), GGL_EINVAL,
+    d.N = N; d.chunk = p.chunk; d.n_long = p.n_long; d.n_chunks = p.n_chunks;
+    float *pger = p.partial;
+    GGL_REQUIRE(aligned16(x) && aligned16(g) && aligned16(out) && aligned16(stats) && aligned16(col), GGL_EINVAL,
                 "fast GAT path needs 16-byte aligned buffers");
     const int64_t grid = ceil_div((d.n_chunks + N) << d.logL, (int64_t)kBlock);
     GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "too many rows for one launch");
-    const int32_t *order = options().row_order ? plan->row_order : nullptr;
-    GGL_GAT2_DISPATCH(gat_bwd_dst2_kernel, c4, d.drop_thresh != 0, off32, plan->rowptr, col, order,
+    GGL_GAT2_DISPATCH(gat_bwd_dst2_kernel, c4, d.drop_thresh != 0, off32, plan->rowptr, col, p.order,
                       plan->long_rows, plan->chunk_ptr, el, er, x, g, out, rowmax, rowden, stats, ger, pger,
                       rng_used, d);
     GGL_LAUNCH_CHECK();
-    if (plan->n_long > 0) {
-      GGL_LAUNCH((gat_bwd_dst_final4_kernel), gat_grid_for(plan->n_long * H), kBlock, s, plan->long_rows,
-                 plan->chunk_ptr, reinterpret_cast<const double *>(pger), ger, plan->n_long, H);
-      GGL_LAUNCH_CHECK();
-    }
+    if (int rc = bwd_dst_final4(plan, pger, ger, H, s)) return rc;
   }
   if (NT > 0) {  // source walk
     GGL_REQUIRE(gx && gel && el && x, GGL_EINVAL, "NULL pointer");
     GGL_REQUIRE((colT && g && stats) || E == 0, GGL_EINVAL, "NULL pointer");
-    d.N = NT; d.chunk = planT->chunk; d.n_long = planT->n_long; d.n_chunks = planT->n_long > 0 ? planT->n_chunks : 0;
-    float *pacc = nullptr, *pgel = nullptr;
-    if (planT->n_long > 0) {
-      GGL_REQUIRE(planT->long_rows && planT->chunk_ptr && planT->partial, GGL_EWORKSPACE,
-                  "transposed plan has long rows but long_rows/chunk_ptr/partial is NULL");
-      pacc = static_cast<float *>(planT->partial);
-      pgel = pacc + planT->n_chunks * d.K;
-    }
-    GGL_REQUIRE(al16(x) && al16(g) && al16(gx) && al16(pacc) && al16(colT), GGL_EINVAL,
+    d.N = NT; d.chunk = pT.chunk; d.n_long = pT.n_long; d.n_chunks = pT.n_chunks;
+    float *pacc = pT.partial, *pgel = pT.n_long > 0 ? pacc + pT.n_chunks * d.K : nullptr;
+    GGL_REQUIRE(aligned16(x) && aligned16(g) && aligned16(gx) && aligned16(pacc) && aligned16(colT), GGL_EINVAL,
                 "fast GAT path needs 16-byte aligned buffers");
     const int64_t grid = ceil_div((d.n_chunks + NT) << d.logL, (int64_t)kBlock);
     GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "too many rows for one launch");
-    const int32_t *order = options().row_order ? planT->row_order : nullptr;
-    GGL_GAT2_DISPATCH(gat_bwd_src2_kernel, c4, d.drop_thresh != 0, off32, planT->rowptr, colT, posT, order,
+    GGL_GAT2_DISPATCH(gat_bwd_src2_kernel, c4, d.drop_thresh != 0, off32, planT->rowptr, colT, posT, pT.order,
                       planT->long_rows, planT->chunk_ptr, el, x, g, (const float *)stats, gx, gel, pacc, pgel,
                       rng_used, d);
     GGL_LAUNCH_CHECK();
-    if (planT->n_long > 0) {
-      GGL_LAUNCH((gat_bwd_src_final_kernel), planT->n_long, kBlock, s, planT->long_rows, planT->chunk_ptr,
-                 (const float *)pacc, (const float *)pgel, gx, gel, d);
-      GGL_LAUNCH_CHECK();
-    }
+    if (int rc = bwd_src_final(planT, pacc, pgel, gx, gel, d, s)) return rc;
   }
   return GGL_OK;
 }
@@ -1029,42 +1022,34 @@ extern "C" size_t ggl_gat_sh_partial_bytes(int64_t n_chunks, int64_t F) {
   return (size_t)n_chunks * (size_t)(8 * F + 16) * sizeof(float) + 64;
 }
 
-static int sh_dims(ShDims &d, const ggl_segplan_t *plan, int64_t F, float slope, float p_drop, const int64_t *rng) {
-  GGL_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, GGL_EINVAL, "p_drop must be in [0, 1)");
-  GGL_REQUIRE(p_drop == 0.0f || rng, GGL_EINVAL, "attention dropout needs an rng_state");
-  d.slope = slope; d.N = plan->N; d.F = F; d.E = plan->E;
-  d.chunk = plan->chunk; d.n_long = plan->n_long; d.n_chunks = plan->n_long > 0 ? plan->n_chunks : 0;
-  d.drop_thresh = p_drop > 0.0f ? (uint32_t)((double)p_drop * 4294967296.0) : 0u;
-  d.drop_scale = p_drop > 0.0f ? 1.0f / (1.0f - p_drop) : 1.0f;
-  if (plan->n_long > 0)
-    GGL_REQUIRE(plan->long_rows && plan->chunk_ptr && plan->partial, GGL_EWORKSPACE,
-                "plan has long rows but long_rows/chunk_ptr/partial is NULL");
-  return GGL_OK;
+static int sh_dims(ShDims &d, const WalkPlan &p, int64_t F, float slope, float p_drop, const int64_t *rng) {
+  d.slope = slope; d.N = p.N; d.F = F; d.E = p.E;
+  d.chunk = p.chunk; d.n_long = p.n_long; d.n_chunks = p.n_chunks;
+  return set_dropout(d, p_drop, rng);
 }
 
 // A[N,8,F] = sum_j alpha_ijh x[j,:] (normalised), den[N,8], rowmax[N,8]; x[N_src,F], el[N_src,8], er[N,8]
 extern "C" int ggl_gat_sh_fwd(const ggl_segplan_t *plan, const int32_t *col, const float *el, const float *er,
                               const float *x, int64_t F, float slope, float p_drop, int64_t *rng_state,
                               float *rowmax, float *A, float *den, void *stream) {
-  GGL_REQUIRE(plan && plan->rowptr && plan->chunk > 0, GGL_EINVAL, "plan is NULL");
+  WalkPlan p;
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", "plan is NULL", p)) return rc;
   GGL_REQUIRE(ggl_gat_sh_supported(8, F, 1), GGL_EINVAL, "row width not supported by the shared-row GAT path");
-  if (plan->N == 0) return GGL_OK;
+  if (p.N == 0) return GGL_OK;
   GGL_REQUIRE(er && rowmax && A && den, GGL_EINVAL, "NULL pointer");
-  GGL_REQUIRE((col && el && x) || plan->E == 0, GGL_EINVAL, "NULL pointer");
+  GGL_REQUIRE((col && el && x) || p.E == 0, GGL_EINVAL, "NULL pointer");
   ShDims d{};
-  int rc = sh_dims(d, plan, F, slope, p_drop, rng_state);
-  if (rc) return rc;
-  float *pacc = nullptr, *pden = nullptr, *pmax = nullptr;
-  if (plan->n_long > 0) {
-    pacc = static_cast<float *>(plan->partial);
-    pden = pacc + plan->n_chunks * 8 * F;
-    pmax = pden + plan->n_chunks * 8;
+  if (int rc = sh_dims(d, p, F, slope, p_drop, rng_state)) return rc;
+  float *pacc = p.partial, *pden = nullptr, *pmax = nullptr;
+  if (p.n_long > 0) {
+    pden = pacc + p.n_chunks * 8 * F;
+    pmax = pden + p.n_chunks * 8;
   }
-  GGL_REQUIRE(al16(x) && al16(A) && al16(pacc) && al16(col), GGL_EINVAL, "shared-row GAT path needs 16-byte aligned buffers");
+  GGL_REQUIRE(aligned16(x) && aligned16(A) && aligned16(pacc) && aligned16(col), GGL_EINVAL, "shared-row GAT path needs 16-byte aligned buffers");
   hipStream_t s = as_stream(stream);
   const int64_t grid = ceil_div((d.n_chunks + d.N) * 16, (int64_t)kBlock);
   GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "too many rows for one launch");
-  const int32_t *order = options().row_order ? plan->row_order : nullptr;
+  const int32_t *order = p.order;
   GGL_LAUNCH((gat_sh_rowmax_kernel), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows, plan->chunk_ptr, el,
              er, rowmax, pmax, d);
   GGL_LAUNCH_CHECK();
@@ -1073,12 +1058,12 @@ extern "C" int ggl_gat_sh_fwd(const ggl_segplan_t *plan, const int32_t *col, con
                (const float *)pmax, rowmax, plan->n_long);
     GGL_LAUNCH_CHECK();
   }
-  if (d.drop_thresh)
-    GGL_LAUNCH((gat_sh_fwd_kernel<true>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows, plan->chunk_ptr,
-               el, er, (const float *)rowmax, x, A, den, pacc, pden, (const int64_t *)rng_state, d);
-  else
-    GGL_LAUNCH((gat_sh_fwd_kernel<false>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows, plan->chunk_ptr,
-               el, er, (const float *)rowmax, x, A, den, pacc, pden, (const int64_t *)rng_state, d);
+#define GGL_SH_FWD(DR)                                                                                                 \
+  GGL_LAUNCH((gat_sh_fwd_kernel<DR>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows, plan->chunk_ptr, el, \
+             er, (const float *)rowmax, x, A, den, pacc, pden, (const int64_t *)rng_state, d)
+  if (d.drop_thresh) GGL_SH_FWD(true);
+  else GGL_SH_FWD(false);
+#undef GGL_SH_FWD
   GGL_LAUNCH_CHECK();
   if (plan->n_long > 0) {
     GGL_LAUNCH((gat_sh_fwd_final_kernel), plan->n_long, kBlock, s, plan->long_rows, plan->chunk_ptr, (const float *)pacc,
@@ -1121,7 +1106,7 @@ extern "C" int ggl_gat_sh_stats(const float *er, const float *rowmax, const floa
   GGL_REQUIRE(N >= 0 && F > 0 && F % 4 == 0, GGL_EINVAL, "ggl_gat_sh_stats: F must be a positive multiple of 4");
   if (N == 0) return GGL_OK;
   GGL_REQUIRE(er && rowmax && den && G && A && stats, GGL_EINVAL, "NULL pointer");
-  GGL_REQUIRE(al16(G) && al16(A) && al16(stats), GGL_EINVAL, "ggl_gat_sh_stats needs 16-byte aligned buffers");
+  GGL_REQUIRE(aligned16(G) && aligned16(A) && aligned16(stats), GGL_EINVAL, "ggl_gat_sh_stats needs 16-byte aligned buffers");
   const int64_t NH = N * kShH;
   int64_t grid = ceil_div(NH * 16, (int64_t)kBlock);
   if (grid > 65536) grid = 65536;
@@ -1135,63 +1120,49 @@ extern "C" int ggl_gat_sh_bwd(const ggl_segplan_t *plan, const int32_t *col, con
                               const float *G, const float *stats, const float *z, const float *gy, int64_t Cp,
                               float slope, float p_drop, const int64_t *rng_used, float *ger, float *T, float *gel,
                               void *stream) {
-  GGL_REQUIRE(plan && plan->rowptr && planT && planT->rowptr && plan->chunk > 0 && planT->chunk > 0, GGL_EINVAL, "plan is NULL");
+  WalkPlan p, pT;   // (this entry names both plans "plan" in its errors)
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", "plan is NULL", p)) return rc;
+  if (int rc = walk_plan(planT, "plan", "plan is NULL", "plan is NULL", pT)) return rc;
   GGL_REQUIRE(ggl_gat_sh_supported(8, F, Cp) && Cp % 4 == 0, GGL_EINVAL, "shape not supported by the shared-row GAT path");
-  GGL_REQUIRE(planT->E == plan->E, GGL_EINVAL, "forward and transposed plans disagree");
-  GGL_REQUIRE(p_drop == 0.0f || posT || plan->E == 0, GGL_EINVAL, "attention dropout needs posT");
+  GGL_REQUIRE(pT.E == p.E, GGL_EINVAL, "forward and transposed plans disagree");
+  GGL_REQUIRE(p_drop == 0.0f || posT || p.E == 0, GGL_EINVAL, "attention dropout needs posT");
   hipStream_t s = as_stream(stream);
-  if (plan->N > 0) {
+  if (p.N > 0) {
     GGL_REQUIRE(ger && G && stats && el && x, GGL_EINVAL, "NULL pointer");
     ShDims d{};
-    int rc = sh_dims(d, plan, F, slope, p_drop, rng_used);
-    if (rc) return rc;
+    if (int rc = sh_dims(d, p, F, slope, p_drop, rng_used)) return rc;
     // (forward plan's partial: FOUR doubles per chunk and head since round 6 = 256 bytes per chunk: ggl_gat_sh_partial_bytes(n_chunks, 8))
-    float *pger = plan->n_long > 0 ? static_cast<float *>(plan->partial) : nullptr;
-    GGL_REQUIRE(al16(x) && al16(G) && al16(stats) && al16(col) && al16(pger), GGL_EINVAL, "shared-row GAT path needs 16-byte aligned buffers");
+    float *pger = p.partial;
+    GGL_REQUIRE(aligned16(x) && aligned16(G) && aligned16(stats) && aligned16(col) && aligned16(pger), GGL_EINVAL, "shared-row GAT path needs 16-byte aligned buffers");
     const int64_t grid = ceil_div((d.n_chunks + d.N) * 16, (int64_t)kBlock);
     GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "too many rows for one launch");
-    const int32_t *order = options().row_order ? plan->row_order : nullptr;
-    if (d.drop_thresh)
-      GGL_LAUNCH((gat_sh_bwd_dst_kernel<true>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows,
-                 plan->chunk_ptr, el, x, G, stats, ger, pger, rng_used, d);
-    else
-      GGL_LAUNCH((gat_sh_bwd_dst_kernel<false>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows,
-                 plan->chunk_ptr, el, x, G, stats, ger, pger, rng_used, d);
+#define GGL_SH_DST(DR)                                                                                     \
+  GGL_LAUNCH((gat_sh_bwd_dst_kernel<DR>), grid, kBlock, s, plan->rowptr, col, p.order, plan->long_rows,    \
+             plan->chunk_ptr, el, x, G, stats, ger, pger, rng_used, d)
+    if (d.drop_thresh) GGL_SH_DST(true);
+    else GGL_SH_DST(false);
+#undef GGL_SH_DST
     GGL_LAUNCH_CHECK();
-    if (plan->n_long > 0) {
-      GGL_LAUNCH((gat_bwd_dst_final4_kernel), gat_grid_for(plan->n_long * 8), kBlock, s, plan->long_rows, plan->chunk_ptr,
-                 reinterpret_cast<const double *>(pger), ger, plan->n_long, (int64_t)8);
-      GGL_LAUNCH_CHECK();
-    }
+    if (int rc = bwd_dst_final4(plan, pger, ger, 8, s)) return rc;
   }
-  if (planT->N > 0) {
+  if (pT.N > 0) {
     GGL_REQUIRE(T && gel && z && gy && stats && el, GGL_EINVAL, "NULL pointer");
     ShDims d{};
-    int rc = sh_dims(d, planT, Cp, slope, p_drop, rng_used);
-    if (rc) return rc;
-    float *pacc = nullptr, *pgel = nullptr;
-    if (planT->n_long > 0) {
-      pacc = static_cast<float *>(planT->partial);
-      pgel = pacc + planT->n_chunks * 8 * Cp;
-    }
-    GGL_REQUIRE(al16(z) && al16(gy) && al16(T) && al16(pacc) && al16(colT), GGL_EINVAL, "shared-row GAT path needs 16-byte aligned buffers");
+    if (int rc = sh_dims(d, pT, Cp, slope, p_drop, rng_used)) return rc;
+    float *pacc = pT.partial, *pgel = pT.n_long > 0 ? pacc + pT.n_chunks * 8 * Cp : nullptr;
+    GGL_REQUIRE(aligned16(z) && aligned16(gy) && aligned16(T) && aligned16(pacc) && aligned16(colT), GGL_EINVAL, "shared-row GAT path needs 16-byte aligned buffers");
     const int64_t grid = ceil_div((d.n_chunks + d.N) * 16, (int64_t)kBlock);
     GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "too many rows for one launch");
-    const int32_t *order = options().row_order ? planT->row_order : nullptr;
-    if (d.drop_thresh)
-      GGL_LAUNCH((gat_sh_bwd_src_kernel<true>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows,
-                 planT->chunk_ptr, el, z, gy, stats, T, gel, pacc, pgel, rng_used, d);
-    else
-      GGL_LAUNCH((gat_sh_bwd_src_kernel<false>), grid, kBlock, s, planT->rowptr, colT, posT, order, planT->long_rows,
-                 planT->chunk_ptr, el, z, gy, stats, T, gel, pacc, pgel, rng_used, d);
+#define GGL_SH_SRC(DR)                                                                                            \
+  GGL_LAUNCH((gat_sh_bwd_src_kernel<DR>), grid, kBlock, s, planT->rowptr, colT, posT, pT.order, planT->long_rows, \
+             planT->chunk_ptr, el, z, gy, stats, T, gel, pacc, pgel, rng_used, d)
+    if (d.drop_thresh) GGL_SH_SRC(true);
+    else GGL_SH_SRC(false);
+#undef GGL_SH_SRC
     GGL_LAUNCH_CHECK();
-    if (planT->n_long > 0) {
-      GatDims gd{};
-      gd.H = 8; gd.K = 8 * Cp; gd.n_long = planT->n_long;
-      GGL_LAUNCH((gat_bwd_src_final_kernel), planT->n_long, kBlock, s, planT->long_rows, planT->chunk_ptr,
-                 (const float *)pacc, (const float *)pgel, T, gel, gd);
-      GGL_LAUNCH_CHECK();
-    }
+    GatDims gd{};
+    gd.H = 8; gd.K = 8 * Cp; gd.n_long = planT->n_long;
+    if (int rc = bwd_src_final(planT, pacc, pgel, T, gel, gd, s)) return rc;
   }
   return GGL_OK;
 }

@@ -203,7 +203,7 @@ extern "C" int ggl_segment_hub16(int dtype, int mean, const void *x, const ggl_s
   const int64_t slabs = ceil_div(K, (int64_t)kHubCols);
   const int64_t grid = plan->n_long * slabs;
   hipStream_t s = as_stream(stream);
-  const bool v16 = K % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15u) == 0;
+  const bool v16 = K % 8 == 0 && aligned16(x);
 #define GGL_HUB16(T, V)                                                                                          \
   GGL_LAUNCH((hub_rows16_kernel<T, V>), grid, kHubBlock, s, static_cast<const uint16_t *>(x), plan->perm, plan->rowptr, \
              plan->long_rows, plan->long_order, plan->n_long, K, slabs, mean ? 1 : 0, static_cast<uint16_t *>(out))

@@ -789,7 +789,7 @@ __global__ __launch_bounds__(kBlock) void calib_stream_kernel(const float4 *__re
 extern "C" int ggl_calib_stream(const float *src, float *dst, int64_t n_vec4, int mode, void *stream) {
   GGL_REQUIRE(n_vec4 >= 0 && (mode == 0 || mode == 1), GGL_EINVAL, "bad arguments");
   if (n_vec4 == 0) return GGL_OK;
-  GGL_REQUIRE(src && dst && (reinterpret_cast<uintptr_t>(src) & 15u) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0,
+  GGL_REQUIRE(src && dst && aligned16(src) && aligned16(dst),
               GGL_EINVAL, "src / dst must be 16-byte aligned");
   int64_t g = ceil_div(n_vec4, (int64_t)kBlock * 4);
   if (g > 256 * 8) g = 256 * 8;        // 256 CUs x 8 blocks of 4 wavefronts (full occupancy), grid-stride for the rest
@@ -806,7 +806,7 @@ extern "C" int ggl_gather_rows_f32_ex(const float *src, int64_t src_ld, const in
   if (n == 0 || K == 0) return GGL_OK;
   GGL_REQUIRE(src && idx && out, GGL_EINVAL, "NULL pointer");
   const bool vec4 = K % 4 == 0 && src_ld % 4 == 0 && out_ld % 4 == 0 &&
-                    (reinterpret_cast<uintptr_t>(src) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
+                    aligned16(src) && aligned16(out);
   // enough blocks in flight to cover the random-row latency (a pure gather: 32 blocks per CU)
   int64_t g = ceil_div(n * (vec4 ? K / 4 : K), kBlock);
   if (g > 256 * 32) g = 256 * 32;

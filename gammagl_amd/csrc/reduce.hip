@@ -710,7 +710,6 @@ template <typename T, int OP, int MODE> static bool exact_long_applies(const Red
 #endif
 }
 
-#ifndef GGL_EMULATE
 template <typename T, int MODE> static HubF32Args hub_args_of(const ReduceArgs &a, int64_t x_ld) {
   HubF32Args h{};
   constexpr int kWords = std::is_same<T, double>::value ? 2 : 1;   // doubles travel as pairs of 4-byte words (hubf32.hip)
@@ -733,7 +732,6 @@ template <typename T, int MODE> static HubF32Args hub_args_of(const ReduceArgs &
   h.avg_long_len = a.n_chunks * a.chunk / (a.n_long > 0 ? a.n_long : 1);   // (chunks are full but the last of a row)
   return h;
 }
-#endif
 
 template <typename T, int VEC, int OP, int MODE, int IDX, bool RAG = false>
 static int launch_idx(const ReduceArgs &a_in, ReduceDims d, hipStream_t stream) {
@@ -851,8 +849,6 @@ static int launch_typed(const ReduceArgs &a, hipStream_t stream) {
   }
 }
 
-static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 template <int OP, int MODE>
 static int launch_f32(const ReduceArgs &a, hipStream_t stream) {
   constexpr bool kStatic = (seg_like(MODE) || spmm_like(MODE) || MODE == MODE_MAXBWDM);
@@ -914,78 +910,86 @@ extern "C" int64_t ggl_spmm_col_blocks_plan(const ggl_segplan_t *plan, int64_t K
   return bw > 0 ? (K + bw - 1) / bw : 1;
 }
 
-template <int OP, int MODE>
-static int launch_f32_cols(const ReduceArgs &a0, hipStream_t stream) {
-  static_assert(OP != OP_MAX && (MODE == MODE_SPMM || MODE == MODE_SPMM_EPI), "column blocks: sum / mean SpMM only");
-  const int64_t bw = col_block_width(a0.E, a0.K, a0.N, a0.xcd_run_rows);
-  if (bw <= 0 || a0.N <= 0) return launch_f32<OP, MODE>(a0, stream);
-  // The hub rows are walked ONCE per aggregate, over the full width (round 5): one hub launch forked in front of the first
-  // column block, every slab of every hub row an independent workgroup — the K / 64 add chains of the longest row run
-  // side by side instead of one per column-block launch, each of which used to end 0.2-0.5 ms after its row walk — joined
-  // before ONE long_final over the full width.  The partial buffer holds n_chunks >= n_long full-width rows.
-  bool one_hub = false;
+// The column-block loop of every wide aggregate.  bw: block width in columns; xsz / osz: bytes per element of x / out;
+// per_block(a, c0): whatever else moves with the block's first column; launch(a): one block, or (phase 2) the join and the
+// long_final over the full width.
+// one_hub: the hub rows are walked ONCE per aggregate, over the full width (round 5): one hub launch (args: hub(x_ld)) forked
+// in front of the first column block, every slab of every hub row an independent workgroup — the K / 64 add chains of the
+// longest row run side by side instead of one per column-block launch, each of which used to end 0.2-0.5 ms after its row
+// walk — joined before ONE long_final over the full width.  The partial buffer holds n_chunks >= n_long full-width rows.
+template <typename Hub, typename PerBlock, typename Launch>
+static int launch_col_blocks(const ReduceArgs &a0, int64_t bw, size_t xsz, size_t osz, bool one_hub, Hub hub,
+                             PerBlock per_block, Launch launch, hipStream_t stream) {
   int forked = 0;
 #ifndef GGL_EMULATE
-  // hub_one_launch: 1 = always, 0 = never (a hub launch per block), 2 = where the plan says its long rows lead the id range
-  // (xcd_run_rows < 0: a degree-sorted node order).  Measured, K = 256, products-sized graph (r5_hub_alone.txt): random order
-  // 13.6 ms per block-wise aggregate vs 13.8-14.0 in one launch; degree order 14.3 vs 14.1.
-  const int64_t ohl = options().hub_one_launch;
-  if ((ohl == 1 || (ohl == 2 && a0.xcd_run_rows < 0)) && exact_long_applies<float, OP, MODE>(a0)) {
+  if (one_hub) {
     GGL_REQUIRE(a0.partial != nullptr, GGL_EWORKSPACE, "plan has long rows but no partial buffer");
-    const HubF32Args h = hub_args_of<float, MODE>(a0, a0.x_ld > 0 ? a0.x_ld : a0.K);
-    const int rc = hub_f32_launch(h, stream, options().exact_side_stream != 0, &forked);
+    const int rc = hub_f32_launch(hub(a0.x_ld > 0 ? a0.x_ld : a0.K), stream, options().exact_side_stream != 0, &forked);
     if (rc) return rc;
-    one_hub = true;
   }
 #endif
   for (int64_t c0 = 0; c0 < a0.K; c0 += bw) {
     ReduceArgs a = a0;
     a.phase = one_hub ? 1 : 0;
     a.K = (a0.K - c0) < bw ? (a0.K - c0) : bw;
-    a.x = static_cast<const float *>(a0.x) + c0;
-    a.out = static_cast<float *>(a0.out) + c0;
+    a.x = static_cast<const char *>(a0.x) + (size_t)c0 * xsz;
+    a.out = static_cast<char *>(a0.out) + (size_t)c0 * osz;
     a.x_ld = a0.x_ld > 0 ? a0.x_ld : a0.K;
     a.out_ld = a0.out_ld > 0 ? a0.out_ld : a0.K;
-    if (a0.epi_bias) a.epi_bias = a0.epi_bias + c0;
-    if (a0.epi_add) {
-      a.epi_add = a0.epi_add + c0;
-      a.add_ld = a0.add_ld > 0 ? a0.add_ld : a0.K;
-    }
-    a.epi_K = a0.epi_K > 0 ? a0.epi_K : a0.K;
-    a.epi_col0 = a0.epi_col0 + c0;
-    const int rc = launch_f32<OP, MODE>(a, stream);
+    per_block(a, c0);
+    const int rc = launch(a);
     if (rc) return rc;
   }
   if (one_hub) {
     ReduceArgs a = a0;
     a.phase = 2;
     a.hub_forked = forked;
-    return launch_f32<OP, MODE>(a, stream);
+    return launch(a);
   }
   return GGL_OK;
+}
+// hub_one_launch: 1 = always, 0 = never (a hub launch per block), 2 = where the plan says its long rows lead the id range
+// (xcd_run_rows < 0: a degree-sorted node order).  Measured, K = 256, products-sized graph (r5_hub_alone.txt): random order
+// 13.6 ms per block-wise aggregate vs 13.8-14.0 in one launch; degree order 14.3 vs 14.1.  `exact`: exact_long_applies of
+// the launch (never on the host build).
+static bool hub_once(const ReduceArgs &a0, bool exact) {
+  const int64_t ohl = options().hub_one_launch;
+  return (ohl == 1 || (ohl == 2 && a0.xcd_run_rows < 0)) && exact;
+}
+
+template <int OP, int MODE>
+static int launch_f32_cols(const ReduceArgs &a0, hipStream_t stream) {
+  static_assert(OP != OP_MAX && (MODE == MODE_SPMM || MODE == MODE_SPMM_EPI), "column blocks: sum / mean SpMM only");
+  const int64_t bw = col_block_width(a0.E, a0.K, a0.N, a0.xcd_run_rows);
+  if (bw <= 0 || a0.N <= 0) return launch_f32<OP, MODE>(a0, stream);
+  return launch_col_blocks(
+      a0, bw, sizeof(float), sizeof(float), hub_once(a0, exact_long_applies<float, OP, MODE>(a0)),
+      [&](int64_t x_ld) { return hub_args_of<float, MODE>(a0, x_ld); },
+      [&](ReduceArgs &a, int64_t c0) {   // the epilogue's operands follow the block; its dropout word stays the full-width one
+        if (a0.epi_bias) a.epi_bias = a0.epi_bias + c0;
+        if (a0.epi_add) {
+          a.epi_add = a0.epi_add + c0;
+          a.add_ld = a0.add_ld > 0 ? a0.add_ld : a0.K;
+        }
+        a.epi_K = a0.epi_K > 0 ? a0.epi_K : a0.K;
+        a.epi_col0 = a0.epi_col0 + c0;
+      },
+      [&](const ReduceArgs &a) { return launch_f32<OP, MODE>(a, stream); }, stream);
 }
 
 // bspmm over the same 64-column blocks where a block lies INSIDE one head (the block width divides C): the kernels compute a
 // column's head as k / C with k counted from the block's first column, so the weight pointer moves to the block's head and
 // everything else is the strided launch above.  Products-sized graph, forward: 1 x 256 16.0 -> 14.8 ms.  Blocks of several
 // narrow heads were measured too and LOSE (16 x 16: 17.4 -> 18.2 ms, 32 x 8: 19.1 -> 22.7 — every block launch fetches the
-// edge's whole [H] weight row for the few heads it uses): those shapes stay one launch.
+// edge's whole [H] weight row for the few heads it uses): those shapes stay one launch.  (A hub launch per block.)
 static int launch_bspmm_cols(const ReduceArgs &a0, hipStream_t stream) {
   int64_t bw = col_block_width(a0.E, a0.K, a0.N);
   if (bw > 0 && a0.C % bw != 0) bw = 0;
   if (bw <= 0 || a0.N <= 0 || !a0.w) return launch_f32<OP_SUM, MODE_BSPMM>(a0, stream);
-  for (int64_t c0 = 0; c0 < a0.K; c0 += bw) {
-    ReduceArgs a = a0;
-    a.K = (a0.K - c0) < bw ? (a0.K - c0) : bw;
-    a.x = static_cast<const float *>(a0.x) + c0;
-    a.out = static_cast<float *>(a0.out) + c0;
-    a.x_ld = a0.x_ld > 0 ? a0.x_ld : a0.K;
-    a.out_ld = a0.out_ld > 0 ? a0.out_ld : a0.K;
-    a.w = a0.w + c0 / a0.C;          // [., H] rows: the block's first head (H stays the row stride)
-    const int rc = launch_f32<OP_SUM, MODE_BSPMM>(a, stream);
-    if (rc) return rc;
-  }
-  return GGL_OK;
+  return launch_col_blocks(
+      a0, bw, sizeof(float), sizeof(float), false, [](int64_t) { return HubF32Args{}; },
+      [&](ReduceArgs &a, int64_t c0) { a.w = a0.w + c0 / a0.C; },   // [., H] rows: the block's first head (H stays the row stride)
+      [&](const ReduceArgs &a) { return launch_f32<OP_SUM, MODE_BSPMM>(a, stream); }, stream);
 }
 
 // 16-byte vector path usable: K a multiple of the vector width and every base pointer 16-byte aligned
@@ -1083,44 +1087,18 @@ template <int OP>
 static int launch_x16_cols(int xd, int od, const ReduceArgs &a0, hipStream_t stream) {
   const int64_t bw = col_block_width16(a0.E, a0.K, a0.N);
   if (bw <= 0 || a0.N <= 0) return launch_x16<OP, MODE_SPMM>(xd, od, a0, stream);
-  // (the hub launch, its side stream and the join are the f32 path's: launch_f32_cols)
-  bool one_hub = false;
-  int forked = 0;
-#ifndef GGL_EMULATE
-  const int64_t ohl = options().hub_one_launch;
-  if ((ohl == 1 || (ohl == 2 && a0.xcd_run_rows < 0)) && exact_long_applies<mxbf16_t, OP, MODE_SPMM>(a0)) {
-    GGL_REQUIRE(a0.partial != nullptr, GGL_EWORKSPACE, "plan has long rows but no partial buffer");
-    const int64_t ld = a0.x_ld > 0 ? a0.x_ld : a0.K;
-    const HubF32Args h = xd == GGL_BF16 ? hub_args_of<mxbf16_t, MODE_SPMM>(a0, ld) : hub_args_of<mxf16_t, MODE_SPMM>(a0, ld);
-    const int rc = hub_f32_launch(h, stream, options().exact_side_stream != 0, &forked);
-    if (rc) return rc;
-    one_hub = true;
-  }
-#endif
-  const size_t osz = dtype_size(od);
-  for (int64_t c0 = 0; c0 < a0.K; c0 += bw) {
-    ReduceArgs a = a0;
-    a.phase = one_hub ? 1 : 0;
-    a.K = (a0.K - c0) < bw ? (a0.K - c0) : bw;
-    a.x = static_cast<const uint16_t *>(a0.x) + c0;
-    a.out = static_cast<char *>(a0.out) + (size_t)c0 * osz;
-    a.x_ld = a0.x_ld > 0 ? a0.x_ld : a0.K;
-    a.out_ld = a0.out_ld > 0 ? a0.out_ld : a0.K;
-    const int rc = launch_x16<OP, MODE_SPMM>(xd, od, a, stream);
-    if (rc) return rc;
-  }
-  if (one_hub) {
-    ReduceArgs a = a0;
-    a.phase = 2;
-    a.hub_forked = forked;
-    return launch_x16<OP, MODE_SPMM>(xd, od, a, stream);
-  }
-  return GGL_OK;
+  // (the conditions of the exact walk are the same for both 16-bit types; the hub args are made per type)
+  return launch_col_blocks(
+      a0, bw, sizeof(uint16_t), dtype_size(od), hub_once(a0, exact_long_applies<mxbf16_t, OP, MODE_SPMM>(a0)),
+      [&](int64_t x_ld) {
+        return xd == GGL_BF16 ? hub_args_of<mxbf16_t, MODE_SPMM>(a0, x_ld) : hub_args_of<mxf16_t, MODE_SPMM>(a0, x_ld);
+      },
+      [](ReduceArgs &, int64_t) {}, [&](const ReduceArgs &a) { return launch_x16<OP, MODE_SPMM>(xd, od, a, stream); }, stream);
 }
 
 static int fill_plan(ReduceArgs &a, const ggl_segplan_t *plan, int dtype, int64_t K, bool with_arg) {
-  GGL_REQUIRE(plan != nullptr && plan->rowptr != nullptr, GGL_EINVAL, "plan / rowptr is NULL");
-  GGL_REQUIRE(plan->chunk > 0, GGL_EINVAL, "plan->chunk must be > 0");
+  WalkPlan p;   // (the checks; launch_idx has its own row-order rule and the kernels take the plan's raw counts)
+  if (int rc = walk_plan(plan, "plan", "plan / rowptr is NULL", "plan->chunk must be > 0", p)) return rc;
   GGL_REQUIRE(K >= 0 && plan->N >= 0 && plan->E >= 0, GGL_EINVAL, "negative size");
   a.rowptr = plan->rowptr;
   a.perm = plan->perm;
@@ -1138,14 +1116,10 @@ static int fill_plan(ReduceArgs &a, const ggl_segplan_t *plan, int dtype, int64_
   a.n_chunks = plan->n_chunks;
   a.partial = plan->partial;
   a.partial_arg = nullptr;
-  if (plan->n_long > 0) {
-    GGL_REQUIRE(plan->long_rows && plan->chunk_ptr && plan->partial, GGL_EWORKSPACE,
-                "plan has long rows but long_rows/chunk_ptr/partial is NULL");
-    if (with_arg) {
-      size_t off = (size_t)plan->n_chunks * (size_t)K * dtype_size(dtype);
-      off = (off + 15) & ~(size_t)15;
-      a.partial_arg = reinterpret_cast<int64_t *>(static_cast<char *>(plan->partial) + off);
-    }
+  if (plan->n_long > 0 && with_arg) {
+    size_t off = (size_t)plan->n_chunks * (size_t)K * dtype_size(dtype);
+    off = (off + 15) & ~(size_t)15;
+    a.partial_arg = reinterpret_cast<int64_t *>(static_cast<char *>(plan->partial) + off);
   }
   return GGL_OK;
 }
@@ -1165,13 +1139,7 @@ extern "C" size_t ggl_partial_bytes(int dtype, int64_t n_chunks, int64_t K, int 
 // ---- segment ops ---------------------------------------------------------------------------------
 extern "C" int ggl_segment_sum(int dtype, const void *x, const ggl_segplan_t *plan, int64_t K,
                                void *out, void *stream) {
-  ReduceArgs a{};
-  int rc = fill_plan(a, plan, dtype, K, false);
-  if (rc) return rc;
-  GGL_REQUIRE((x || plan->E * K == 0) && (out || plan->N * K == 0), GGL_EINVAL, "x/out is NULL");
-  a.x = x;
-  a.out = out;
-  return launch_seg<OP_SUM>(dtype, a, as_stream(stream));
+  return ggl_segment_sum_ex(dtype, x, 0, plan, K, out, 0, 0, stream);
 }
 
 // Strided / accumulating form: x rows x_ld elements apart, out rows out_ld apart (both >= K; 0 = K), and
@@ -1228,7 +1196,7 @@ extern "C" int ggl_segment_max(int dtype, const void *x, const ggl_segplan_t *pl
 
 // ---- gspmm ---------------------------------------------------------------------------------------
 static int spmm_common(ReduceArgs &a, const ggl_segplan_t *plan, const int32_t *col, const float *w,
-                       int w_by_pos, const float *x, int64_t K, float *out, bool with_arg) {
+                       int w_by_pos, const void *x, int64_t K, void *out, bool with_arg) {
   int rc = fill_plan(a, plan, GGL_F32, K, with_arg);
   if (rc) return rc;
   GGL_REQUIRE(col || plan->E == 0, GGL_EINVAL, "col is NULL");
@@ -1243,10 +1211,7 @@ static int spmm_common(ReduceArgs &a, const ggl_segplan_t *plan, const int32_t *
 
 extern "C" int ggl_spmm_sum(const ggl_segplan_t *plan, const int32_t *col, const float *w,
                             int w_by_pos, const float *x, int64_t K, float *out, void *stream) {
-  ReduceArgs a{};
-  int rc = spmm_common(a, plan, col, w, w_by_pos, x, K, out, false);
-  if (rc) return rc;
-  return launch_f32_cols<OP_SUM, MODE_SPMM>(a, as_stream(stream));
+  return ggl_spmm_sum_ex(plan, col, w, w_by_pos, x, 0, K, out, 0, 0, stream);
 }
 
 extern "C" int ggl_spmm_sum_ex(const ggl_segplan_t *plan, const int32_t *col, const float *w, int w_by_pos,
@@ -1258,6 +1223,19 @@ extern "C" int ggl_spmm_sum_ex(const ggl_segplan_t *plan, const int32_t *col, co
   GGL_REQUIRE((x_ld == 0 || x_ld >= K) && (out_ld == 0 || out_ld >= K), GGL_EINVAL, "row stride < K");
   a.x_ld = x_ld; a.out_ld = out_ld; a.accumulate = accumulate ? 1 : 0;
   return launch_f32_cols<OP_SUM, MODE_SPMM>(a, as_stream(stream));
+}
+
+// the epilogue both fused entries below apply (each checks its own row strides first)
+static int fill_epilogue(ReduceArgs &a, const float *add, int64_t add_ld, const float *bias, int relu, float p_drop,
+                         int64_t *rng_state) {
+  GGL_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, GGL_EINVAL, "p_drop must be in [0, 1)");
+  GGL_REQUIRE(p_drop == 0.0f || rng_state, GGL_EINVAL, "dropout needs an rng_state");
+  a.epi_bias = bias;
+  a.epi_add = add; a.add_ld = add_ld;
+  a.epi_rng = rng_state;
+  a.epi_relu = relu ? 1 : 0;
+  dropout_params(p_drop, &a.epi_thresh, &a.epi_scale);
+  return GGL_OK;
 }
 
 // out = dropout(relu(reduce(A x) + add + bias)) with the epilogue applied to each finished row in registers: what
@@ -1280,16 +1258,10 @@ extern "C" int ggl_spmm_epi_ex(const ggl_segplan_t *plan, const int32_t *col, co
   GGL_REQUIRE((x_ld == 0 || x_ld >= K) && (out_ld == 0 || out_ld >= K) && (add_ld == 0 || add_ld >= K),
               GGL_EINVAL, "row stride < K");
   GGL_REQUIRE(!(mean && accumulate), GGL_EINVAL, "mean cannot accumulate onto a partial result");
-  GGL_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, GGL_EINVAL, "p_drop must be in [0, 1)");
-  GGL_REQUIRE(p_drop == 0.0f || rng_state, GGL_EINVAL, "dropout needs an rng_state");
+  rc = fill_epilogue(a, add, add_ld, bias, relu, p_drop, rng_state);
+  if (rc) return rc;
   GGL_REQUIRE(epi_col0 >= 0 && (epi_K == 0 || epi_col0 + K <= epi_K), GGL_EINVAL, "column block outside the row");
   a.x_ld = x_ld; a.out_ld = out_ld; a.accumulate = accumulate ? 1 : 0;
-  a.epi_bias = bias;
-  a.epi_add = add; a.add_ld = add_ld;
-  a.epi_rng = rng_state;
-  a.epi_relu = relu ? 1 : 0;
-  a.epi_thresh = p_drop > 0.0f ? (uint32_t)((double)p_drop * 4294967296.0) : 0u;
-  a.epi_scale = p_drop > 0.0f ? 1.0f / (1.0f - p_drop) : 1.0f;
   a.epi_K = epi_K; a.epi_col0 = epi_col0;
   rc = !mean ? launch_f32_cols<OP_SUM, MODE_SPMM_EPI>(a, as_stream(stream))
              : launch_f32_cols<OP_MEAN, MODE_SPMM_EPI>(a, as_stream(stream));
@@ -1317,16 +1289,10 @@ extern "C" int ggl_segment_epi(const float *x, const ggl_segplan_t *plan, int64_
   if (rc) return rc;
   GGL_REQUIRE((x || plan->E * K == 0) && (out || plan->N * K == 0), GGL_EINVAL, "x/out is NULL");
   GGL_REQUIRE(add_ld == 0 || add_ld >= K, GGL_EINVAL, "row stride < K");
-  GGL_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, GGL_EINVAL, "p_drop must be in [0, 1)");
-  GGL_REQUIRE(p_drop == 0.0f || rng_state, GGL_EINVAL, "dropout needs an rng_state");
+  rc = fill_epilogue(a, add, add_ld, bias, relu, p_drop, rng_state);
+  if (rc) return rc;
   a.x = x;
   a.out = out;
-  a.epi_bias = bias;
-  a.epi_add = add; a.add_ld = add_ld;
-  a.epi_rng = rng_state;
-  a.epi_relu = relu ? 1 : 0;
-  a.epi_thresh = p_drop > 0.0f ? (uint32_t)((double)p_drop * 4294967296.0) : 0u;
-  a.epi_scale = p_drop > 0.0f ? 1.0f / (1.0f - p_drop) : 1.0f;
   rc = mean ? launch_f32<OP_MEAN, MODE_SEG_EPI>(a, as_stream(stream))
             : launch_f32<OP_SUM, MODE_SEG_EPI>(a, as_stream(stream));
   if (rc) return rc;
@@ -1372,16 +1338,9 @@ static int spmm16_common(ReduceArgs &a, const ggl_segplan_t *plan, const int32_t
     set_error("x16: x must be f16 or bf16 and out the same or f32 (got dtype codes %d -> %d)", x_dtype, out_dtype);
     return GGL_EDTYPE;
   }
-  int rc = fill_plan(a, plan, GGL_F32, K, false);     // (chunk / hub partials are f32: ggl_partial_bytes(GGL_F32, ...))
+  int rc = spmm_common(a, plan, col, w, w_by_pos, x, K, out, false);   // (chunk / hub partials are f32, as the f32 op's)
   if (rc) return rc;
-  GGL_REQUIRE(col || plan->E == 0, GGL_EINVAL, "col is NULL");
-  GGL_REQUIRE((x || plan->E * K == 0) && (out || plan->N * K == 0), GGL_EINVAL, "x/out is NULL");
   GGL_REQUIRE((x_ld == 0 || x_ld >= K) && (out_ld == 0 || out_ld >= K), GGL_EINVAL, "row stride < K");
-  a.x = x;
-  a.col = col;
-  a.w = w;
-  a.w_by_pos = w_by_pos;
-  a.out = out;
   a.x_ld = x_ld;
   a.out_ld = out_ld;
   return GGL_OK;
@@ -1417,26 +1376,28 @@ extern "C" int ggl_spmm_mean_bwd_x16(const ggl_segplan_t *planT, const int32_t *
   return launch_x16<OP_SUM, MODE_MEANBWD>(g_dtype, gx_dtype, a, as_stream(stream));
 }
 
-extern "C" int ggl_spmm_max_bwd(const ggl_segplan_t *planT, const int32_t *colT, const float *w,
-                                int w_by_pos, const float *g, const int64_t *argsrc, int64_t K,
-                                float *gx, void *stream) {
+// the witnesses as the forward wrote them (int64), or a compact int32 copy of them
+static int spmm_max_bwd(const ggl_segplan_t *planT, const int32_t *colT, const float *w, int w_by_pos, const float *g,
+                        const void *argsrc, bool arg32, int64_t K, float *gx, void *stream) {
   ReduceArgs a{};
   int rc = spmm_common(a, planT, colT, w, w_by_pos, g, K, gx, false);
   if (rc) return rc;
-  GGL_REQUIRE(argsrc || planT->E * K == 0, GGL_EINVAL, "argsrc is NULL");
-  a.aux_arg = argsrc;
-  return launch_f32<OP_SUM, MODE_MAXBWD>(a, as_stream(stream));
+  GGL_REQUIRE(argsrc || planT->E * K == 0, GGL_EINVAL, "%s", arg32 ? "argsrc32 is NULL" : "argsrc is NULL");
+  a.aux_arg = static_cast<const int64_t *>(argsrc);
+  return !arg32 ? launch_f32<OP_SUM, MODE_MAXBWD>(a, as_stream(stream))
+                : launch_f32<OP_SUM, MODE_MAXBWD32>(a, as_stream(stream));
+}
+
+extern "C" int ggl_spmm_max_bwd(const ggl_segplan_t *planT, const int32_t *colT, const float *w,
+                                int w_by_pos, const float *g, const int64_t *argsrc, int64_t K,
+                                float *gx, void *stream) {
+  return spmm_max_bwd(planT, colT, w, w_by_pos, g, argsrc, false, K, gx, stream);
 }
 
 extern "C" int ggl_spmm_max_bwd32(const ggl_segplan_t *planT, const int32_t *colT, const float *w,
                                   int w_by_pos, const float *g, const int32_t *argsrc32, int64_t K,
                                   float *gx, void *stream) {
-  ReduceArgs a{};
-  int rc = spmm_common(a, planT, colT, w, w_by_pos, g, K, gx, false);
-  if (rc) return rc;
-  GGL_REQUIRE(argsrc32 || planT->E * K == 0, GGL_EINVAL, "argsrc32 is NULL");
-  a.aux_arg = reinterpret_cast<const int64_t *>(argsrc32);
-  return launch_f32<OP_SUM, MODE_MAXBWD32>(a, as_stream(stream));
+  return spmm_max_bwd(planT, colT, w, w_by_pos, g, argsrc32, true, K, gx, stream);
 }
 
 // ---- gspmm(max) backward through a winner mask (round 5) --------------------------------------------------------------
@@ -1609,7 +1570,7 @@ extern "C" int ggl_spmm_max_mask(const ggl_segplan_t *planF, const int32_t *colF
   const int64_t grid = chunk_blocks + ceil_div(N, (int64_t)kWavesPerBlock);
   hipStream_t st = as_stream(stream);
   const int64_t KWp = mask_words_seq(K);
-  GGL_REQUIRE((reinterpret_cast<uintptr_t>(mask) & 15u) == 0, GGL_EINVAL, "mask must be 16-byte aligned");
+  GGL_REQUIRE(aligned16(mask), GGL_EINVAL, "mask must be 16-byte aligned");
 #define GGL_MS(NP, NW)                                                                                              \
   GGL_LAUNCH((max_mask_seq_kernel<NP, NW>), grid, kBlock, st, planF->rowptr, colF, argsrc, planF->long_rows,        \
              planF->chunk_ptr, mask, N, K, KWp, planF->chunk, planF->n_long, planF->n_chunks, chunk_blocks)

@@ -442,7 +442,7 @@ def check_exact_long_rows(eng, dev, oracle, chunk=64):
                 assert_same(to_np(eng.c_segment_sum(xt, it, N)), oracle.segment_sum(x, ids_k, N), f"exact f64 seg sum K{K} sorted={sort}")
                 assert_same(to_np(eng.c_segment_mean(xt, it, N)), oracle.segment_mean(x, ids_k, N), f"exact f64 seg mean K{K} sorted={sort}")
         # ---- gspmm sum / mean, forward and transposed backward; weights absent / first sight / sorted copy
-        for K in (4, 48, 64, 100, 256):
+        for K in (4, 48, 64, 100, 256, 264):
             index = np.stack([rng.integers(0, N, size=E), hub_ids()]).astype(np.int64)
             index[0, E - 1500:] = 11                      # a source hub: long rows in the transposed plan too
             o = rng.permutation(E)
@@ -463,8 +463,9 @@ def check_exact_long_rows(eng, dev, oracle, chunk=64):
             assert_same(to_np(eng.c_spmm_mean(it, wt, to_t(x, dev))), oracle.spmm_mean_fwd(index, w, x)[0], f"exact spmm mean K{K}")
             ones = np.ones(E, np.float32)
             assert_same(to_np(eng.c_spmm_sum(it, None, to_t(x, dev))), oracle.spmm_sum_fwd(index, ones, x), f"exact spmm sum no weights K{K}")
-            # the 64-column block launches (forced: the graph is far below the automatic threshold)
-            if K % 64 == 0 and K >= 128:
+            # the 64-column block launches (forced: the graph is far below the automatic threshold); K = 264: wider than one
+            # pass of a lane group and no multiple of the block, i.e. four full blocks and an 8-column remainder block
+            if K >= 128 and (K % 64 == 0 or K > 256):
                 with option(eng, "col_block_min_edges", 0), option(eng, "col_block_min_degree", 0):
                     assert int(eng.lib.ggl_spmm_col_blocks(E, K, N)) > 1
                     # hub_one_launch = 1 (round 5): ONE hub launch over the full width in front of the first block + one
@@ -493,6 +494,25 @@ def check_exact_long_rows(eng, dev, oracle, chunk=64):
                                 first_acc = got_acc
                             else:
                                 assert_same(got_acc, first_acc, f"accumulate K{K}: one hub launch vs one per block")
+                    # the whole epilogue under column blocks (add + bias + ReLU + dropout) against the one-launch call from
+                    # the same RNG state: element (row, col) draws the word of the full-width row in every block
+                    addm = rng.standard_normal((N, K)).astype(np.float32)
+
+                    def epi():
+                        out = torch.empty(N, K, device=dev)
+                        st = torch.tensor([1234, 5], dtype=torch.int64, device=dev)
+                        eng.spmm_epi_into(gp.fwd, gp.col, wt, to_t(x, dev), out, add=to_t(addm, dev), bias=to_t(bb, dev),
+                                          relu=True, p_drop=0.5, rng=st, advance_rng=False)
+                        return to_np(out)
+
+                    with option(eng, "col_block", 0):
+                        assert int(eng.lib.ggl_spmm_col_blocks(E, K, N)) == 1
+                        one_launch = epi()
+                    kept = np.count_nonzero(one_launch) / one_launch.size       # ReLU and p = 0.5 both zero elements
+                    assert 0.1 < kept < 0.4, kept
+                    for one in (1, 0):
+                        with option(eng, "hub_one_launch", one):
+                            assert_same(epi(), one_launch, f"spmm epi add + bias + relu + dropout K{K} column blocks one_hub={one}")
             # strided + accumulate: a column block of a wider matrix, a second edge set added onto a result
             if K >= 48 and K % 16 == 0:
                 wide = to_t(np.concatenate([x, x[:, :16]], axis=1), dev)
@@ -548,6 +568,52 @@ def check_exact_long_rows(eng, dev, oracle, chunk=64):
             assert_same(capped, chunked, "exact_long_max below the longest row = the chunked walk")
         else:
             assert_same(capped, exact, "host build: one piece either way")
+    finally:
+        eng.chunk = old
+        eng.clear_caches()
+
+
+def check_forwarding_entry_points(eng, dev, chunk=64):
+    """ggl_segment_sum IS ggl_segment_sum_ex(x_ld = 0, out_ld = 0, accumulate = 0) and ggl_spmm_sum IS ggl_spmm_sum_ex with the
+    same zeros: called through the C ABI on one plan with long rows, the forwarding name gives the callee's bits."""
+    import ctypes
+
+    from gammagl_amd.ops import _ptr
+
+    old = eng.chunk
+    eng.chunk = chunk
+    eng.clear_caches()
+    try:
+        rng = np.random.default_rng(23)
+        N, E, K = 50, 5000, 48
+        ids = rng.integers(0, N, size=E).astype(np.int64)
+        ids[:2900], ids[2900:3924] = 7, 0
+        rng.shuffle(ids)
+        index = to_t(np.stack([rng.integers(0, N, size=E), ids]).astype(np.int64), dev)
+        st = eng._stream(index.device)
+        # segment sum of [E, K] messages
+        msg = to_t((rng.standard_normal((E, K)) * 3).astype(np.float32), dev)
+        sp = eng.seg_plan(index[1].contiguous(), N)
+        assert sp.n_long >= 2
+        part = eng._partial(sp, torch.float32, K, False, index.device)
+        cs = sp.c_struct(part)
+        a, b = torch.full((N, K), np.nan, device=dev), torch.full((N, K), np.nan, device=dev)
+        eng._check(eng.lib.ggl_segment_sum(eng._code(msg), _ptr(msg), ctypes.byref(cs), K, _ptr(a), st))
+        eng._check(eng.lib.ggl_segment_sum_ex(eng._code(msg), _ptr(msg), 0, ctypes.byref(cs), K, _ptr(b), 0, 0, st))
+        assert_same(to_np(a), to_np(b), "ggl_segment_sum vs ggl_segment_sum_ex")
+        # gspmm sum, weights through the plan's permutation
+        gp = eng.graph_plan(index, N)
+        assert gp.fwd.n_long >= 2
+        x = to_t(rng.standard_normal((N, K)).astype(np.float32), dev)
+        w = to_t(rng.standard_normal(E).astype(np.float32), dev)
+        part = eng._partial(gp.fwd, torch.float32, K, False, index.device)
+        wv, w_by_pos, wp = eng._weights(gp.fwd, w)
+        cs = gp.fwd.c_struct(part, wp)
+        a, b = torch.full((N, K), np.nan, device=dev), torch.full((N, K), np.nan, device=dev)
+        eng._check(eng.lib.ggl_spmm_sum(ctypes.byref(cs), _ptr(gp.col), _ptr(wv), w_by_pos, _ptr(x), K, _ptr(a), st))
+        eng._check(eng.lib.ggl_spmm_sum_ex(ctypes.byref(cs), _ptr(gp.col), _ptr(wv), w_by_pos, _ptr(x), 0, K, _ptr(b), 0, 0, st))
+        assert_same(to_np(a), to_np(b), "ggl_spmm_sum vs ggl_spmm_sum_ex")
+        assert not np.isnan(to_np(a)).any()
     finally:
         eng.chunk = old
         eng.clear_caches()

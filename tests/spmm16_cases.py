@@ -11,6 +11,8 @@ The contract (include/ggl_mpops.h), with F = the SAME route on the upcast rows:
     x16.grad                 == (F's gradient on g.float()).to(x16.dtype)
 Every comparison is torch.equal on the integer view of the bits: no tolerance anywhere.
 """
+import ctypes
+
 import pytest
 import torch
 
@@ -129,6 +131,40 @@ def check_long_rows(eng, dev, widths=(7, 8, 64, 264), chunk=64, N=300, E=20_000,
                     for reduce in ("sum", "mean"):
                         check_contract_case(route, index, ww, x.to(dt), g.to(dt), reduce, "explicit plan")
         return gp
+    finally:
+        eng.chunk = old
+
+
+def check_column_blocks(eng, dev, K=256, chunk=64, N=50, E=5000, seed=11):
+    """ggl_spmm_{sum,mean}_x16 in column blocks (col_block16 = 128, thresholds lowered: two blocks of a 256-wide row) on a
+    plan with long rows, the hub rows walked once per aggregate (hub_one_launch = 1) and once per block (0), out in x's dtype
+    and in f32: the bits of the one-launch call (col_block16 = 0)."""
+    from parity_cases import option
+
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    index = make_index("power", N, E, gen, dev)
+    index[0, E - 1500:] = 11
+    w = torch.rand(E, generator=gen, device=dev)
+    x = torch.randn(N, K, generator=gen, device=dev)
+    old = eng.chunk
+    eng.chunk = chunk
+    try:
+        gp = eng.graph_plan(index, N)
+        assert gp.fwd.n_long >= 2 and gp.fwd.chunk == chunk
+        blocks = lambda: int(eng.lib.ggl_spmm_col_blocks_x16(ctypes.byref(gp.fwd.c_struct(None)), K))  # noqa: E731
+        with option(eng, "col_block_min_edges", 0), option(eng, "col_block_min_degree", 0):
+            for dt in DTYPES:
+                for reduce in ("sum", "mean"):
+                    for od in (None, torch.float32):
+                        with option(eng, "col_block16", 0):
+                            assert blocks() == 1
+                            want = eng.spmm(gp, w, x.to(dt), reduce, out_dtype=od)
+                        for one in (1, 0):
+                            with option(eng, "col_block16", 128), option(eng, "hub_one_launch", one):
+                                assert blocks() == 2
+                                got = eng.spmm(gp, w, x.to(dt), reduce, out_dtype=od)
+                            assert same_bits(got, want), (dt, reduce, od, one)
+                assert same_bits(want, eng.spmm(gp, w, x.to(dt).float(), "mean"))   # (the last `want`: mean, f32 output)
     finally:
         eng.chunk = old
 

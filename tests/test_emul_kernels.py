@@ -115,6 +115,10 @@ def test_long_rows_in_the_reference_order(eng, oracle):
     pc.check_exact_long_rows(eng, DEV, oracle)
 
 
+def test_forwarding_entry_points_give_the_callees_bits(eng):
+    pc.check_forwarding_entry_points(eng, DEV)
+
+
 def test_host_build_walks_every_summing_row_in_one_piece(eng, oracle):
     """CPU tensors (the reference dispatches on x.is_cpu() too): no row of any summing mode is chunked, so f64 sums —
     which the GPU's serial hub kernel does not cover — and the backward walks are the reference's bits as well."""

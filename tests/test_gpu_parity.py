@@ -85,6 +85,10 @@ def test_long_rows_in_the_reference_order(eng, dev, oracle):
         pc.check_exact_long_rows(eng, dev, oracle)
 
 
+def test_forwarding_entry_points_give_the_callees_bits(eng, dev):
+    pc.check_forwarding_entry_points(eng, dev)
+
+
 def test_gat_fused_random(eng, dev, oracle):
     pc.check_gat_random(eng, dev, oracle)
 

@@ -52,6 +52,10 @@ def test_contract_on_a_plan_with_long_rows_gpu(eng, dev):
     assert gp.bwd.n_long > 0, "the transposed plan is meant to have long rows as well"
 
 
+def test_column_blocks_give_the_one_launch_bits_gpu(eng, dev):
+    sc.check_column_blocks(eng, dev)
+
+
 def test_sums_are_made_in_f32_gpu(routes, dev):
     sc.check_f32_accumulation(routes, dev)
 

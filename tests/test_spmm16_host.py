@@ -50,6 +50,10 @@ def test_contract_on_a_plan_with_long_rows(eng):
     sc.check_long_rows(eng, DEV)
 
 
+def test_column_blocks_give_the_one_launch_bits(eng):
+    sc.check_column_blocks(eng, DEV)
+
+
 def test_sums_are_made_in_f32(routes):
     sc.check_f32_accumulation(routes, DEV)
 
