@@ -10,6 +10,8 @@ import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB_PATH = os.path.join(_HERE, "lib", "libggl_mpops_hip.so")
 HOST_LIB_PATH = os.path.join(_HERE, "lib", "libggl_mpops_host.so")
@@ -28,6 +30,20 @@ class SegPlanC(ctypes.Structure):
         ("long_order", c_void_p),
         ("max_len", c_int64),
     ]
+
+
+# enum ggl_dtype (include/ggl_mpops.h)
+_DTYPE_CODE = {
+    torch.uint8: 0, torch.int8: 1, torch.int16: 2, torch.int32: 3, torch.int64: 4,
+    torch.float16: 5, torch.bfloat16: 6, torch.float32: 7, torch.float64: 8,
+}
+_FLOAT_DTYPES = (torch.float16, torch.bfloat16, torch.float32, torch.float64)
+# gspmm sum / mean also take rows STORED in these (f32 arithmetic, one rounding at the store: ggl_spmm_*_x16)
+_X16_DTYPES = (torch.float16, torch.bfloat16)
+
+
+def _ptr(t):
+    return None if t is None else c_void_p(t.data_ptr())
 
 
 _P = POINTER(SegPlanC)

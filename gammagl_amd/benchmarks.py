@@ -364,7 +364,7 @@ def pmc_probe_gcn(args, dev, eng):
     # ... and the hub walk beside them runs once per launch — or ONCE per aggregate where the plan's long rows lead the id
     # range (a degree-sorted order; option hub_one_launch, round 5)
     ohl = int(eng.lib.ggl_get_option(b"hub_one_launch"))
-    one_hub = launches > 1 and (ohl == 1 or (ohl == 2 and bool(getattr(gp.fwd, "hub_first", False))))
+    one_hub = launches > 1 and (ohl == 1 or (ohl == 2 and gp.fwd.hub_first))
     hub = 5 * (1 if one_hub else launches)
     print(f"pmc-probe: E={gp.E} rows_in={rows} K={args.hidden} launches/aggregate={launches} ms/aggregate={ms:.3f} "
           f"aggregates=5 dispatches={5 * launches},{hub}", flush=True)
@@ -532,7 +532,7 @@ def run_gcn(args, dev, rank, world, eng=None):
             entry = {"relabel": other, "ms_per_step": dt_b / args.steps * 1e3,
                      "value": tr.net.agg_per_step * pg.e_global * args.steps / dt_b,
                      "ms_per_aggregate_K%d" % K: ms_b, "setup_s": round(t2, 2), "E": pg.e_global,
-                     "xcd_run_rows": int(getattr(gp_b.fwd, "xcd_run", 0) or 0)}
+                     "xcd_run_rows": gp_b.fwd.xcd_run}
             if "clusters" in stats2:
                 entry["clusters"] = stats2["clusters"]
             orderings.append(entry)

@@ -178,7 +178,7 @@ struct SegPlan {
   uint64_t uid = 0;
   Tensor rowptr, perm, long_rows, chunk_ptr, long_order;
   // the row hand-out order is a scheduling aid worth ~100 us of sorting: computed when the plan is launched a SECOND
-  // time, so a plan used once (a fresh edge list per mini-batch) never pays for it (ops.py SegPlan.c_struct)
+  // time, so a plan used once (a fresh edge list per mini-batch) never pays for it (plans.py SegPlan.c_struct)
   mutable Tensor row_order;
   mutable std::mutex order_mu;
   mutable int uses = 0;
@@ -271,7 +271,7 @@ static std::shared_ptr<SegPlan> build_plan(const Tensor &ids_in, int64_t N) {
   return p;
 }
 
-// LRU keyed on the identity + version of a tensor; an entry dies with the tensor's storage (ops.py _PlanCache)
+// LRU keyed on the identity + version of a tensor; an entry dies with the tensor's storage (plans.py _PlanCache)
 struct TensorKey {
   const void *storage = nullptr;
   int64_t offset = 0, numel = 0, version = 0, a = 0, b = 0;
@@ -371,7 +371,7 @@ struct GraphPlan {
   std::mutex mu;
   Cache<SortedW> weights{8};
 
-  // share of the (sampled) edges whose endpoints lie within N / 64 ids of each other (ops.py GraphPlan.locality)
+  // share of the (sampled) edges whose endpoints lie within N / 64 ids of each other (plans.py GraphPlan.locality)
   double locality() const {
     const int64_t N = std::max(N_dst, N_src);
     if (E == 0 || N_dst != N_src) return 0.0;
@@ -381,7 +381,7 @@ struct GraphPlan {
     Tensor near = (col.index_select(0, pos).to(at::kLong) - rows).abs() < std::max<int64_t>(N / 64, 4096);
     return near.to(at::kFloat).mean().item<double>();
   }
-  void schedule() {   // XCD runs where the node order carries locality (ops.py GraphPlan._schedule)
+  void schedule() {   // XCD runs where the node order carries locality (plans.py GraphPlan._schedule)
     const Api &a = api_for(fwd->rowptr.device());
     const bool need = a.ggl_policy_xcd_run_rows(E, 1.0) > 0 || a.ggl_policy_xcd_run_rows(E, 0.0) > 0;
     const int64_t run = a.ggl_policy_xcd_run_rows(E, need ? locality() : 0.0);   // (locality() is one host read)
@@ -402,7 +402,7 @@ struct GraphPlan {
     if (rowidx.defined()) return;
     rowidx = gather_i32(api_for(index.device()), index.select(0, 1), fwd->perm);
   }
-  // transposed sorted position -> forward sorted position (int32 [E]; ops.py GraphPlan.posT)
+  // transposed sorted position -> forward sorted position (int32 [E]; plans.py GraphPlan.posT)
   Tensor posT;
   void need_posT(const Tensor &index) {
     need_bwd(index);

@@ -675,7 +675,7 @@ class DistGCNTrainer:
         except (RuntimeError, TypeError):
             self.opt = torch.optim.Adam(self.net.parameters(), lr=lr, weight_decay=l2_coef)
         self.graph = None
-        from .ops import _PlanCache
+        from .plans import _PlanCache
 
         # train lists already checked for the restricted output layer (sorted, unique int64); an entry dies with its storage
         self._rows_ok = _PlanCache(cap=16)

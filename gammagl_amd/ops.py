@@ -1,16 +1,8 @@
-"""Host side of the MI355X message-passing backend: plans, plan caches and autograd glue over the
-C ABI (include/ggl_mpops.h).
+"""Host side of the MI355X message-passing backend: the ``Engine`` — the ops over the C ABI (include/ggl_mpops.h), their
+argument checks, plan builders and plan caches.  PyTorch is plumbing here (device memory, streams, autograd graph).
 
-This is the part of the reference that lives in ``gammagl/mpops/torch_ext/src/*.cpp`` — the seven
-``torch::autograd::Function``s and their device dispatch (src/segment_sum.cpp:35-54,
-src/segment_mean.cpp:36-63, src/segment_max.cpp:37-61, src/gspmm.cpp:26-260) — restated for a
-backend whose kernels work on a destination-sorted plan instead of atomics:
-
-* ``SegPlan``   : perm / rowptr / long-row lists for one id vector (built once, cached by the
-                  identity + version counter of the id tensor's storage; no per-call host sync).
-* ``GraphPlan`` : the pair of SegPlans (by destination, by source) for one ``edge_index`` plus the
-                  int32 column arrays — CSR for the forward SpMM, CSC for its backward.
-* ``Engine``    : the ops.  PyTorch is plumbing here (device memory, streams, autograd graph).
+The plans it builds and caches (``SegPlan``, ``GraphPlan``, ``RowsPlan``) live in ``plans.py``, the autograd formulas its
+methods apply in ``autograd.py``, the dtype codes and the ctypes binding in ``_lib.py``.
 
 ``Engine`` takes the ctypes library as a constructor argument; the product singleton
 (``gammagl_amd.engine()``) is always built on the HIP library and refuses non-GPU tensors.
@@ -18,289 +10,15 @@ backend whose kernels work on a destination-sorted plan instead of atomics:
 import ctypes
 import math
 import os
-from collections import OrderedDict
 
 import torch
-from torch.autograd.function import once_differentiable
 from torch.multiprocessing.reductions import StorageWeakRef
 
-from . import _lib
-from ._lib import SegPlanC
-
-_DTYPE_CODE = {
-    torch.uint8: 0, torch.int8: 1, torch.int16: 2, torch.int32: 3, torch.int64: 4,
-    torch.float16: 5, torch.bfloat16: 6, torch.float32: 7, torch.float64: 8,
-}
-_FLOAT_DTYPES = (torch.float16, torch.bfloat16, torch.float32, torch.float64)
-# gspmm sum / mean also take rows STORED in these (f32 arithmetic, one rounding at the store: ggl_spmm_*_x16)
-_X16_DTYPES = (torch.float16, torch.bfloat16)
+from . import _lib, autograd
+from ._lib import _DTYPE_CODE, _FLOAT_DTYPES, _X16_DTYPES, _ptr
+from .plans import GraphPlan, RowsPlan, SegPlan, _PlanCache
 
 DEFAULT_CHUNK = int(os.environ.get("GGL_LONG_ROW", "0"))  # 0 = automatic, see Engine.auto_chunk
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-class SegPlan:
-    """Destination-sorted view of one id vector (struct ggl_segplan + the tensors that own it)."""
-
-    __slots__ = ("N", "E", "rowptr", "perm", "is_sorted", "max_len", "chunk", "long_rows",
-                 "chunk_ptr", "n_long", "n_chunks", "device", "row_order", "uid", "xcd_run", "order_fn", "uses", "wperm", "long_order", "hub_first")
-
-    def c_struct(self, partial=None, perm_override=None, unsplit=False, skip_long=False):
-        """`unsplit`: present the plan without its long-row table, every row walked in one piece.
-        `skip_long`: withhold the long-row table but keep the threshold — rows longer than `chunk` are left out
-        of the launch (ggl_segment_hub16 fills them in)."""
-        perm = self.perm if perm_override is None else perm_override
-        n_long = 0 if (unsplit or skip_long) else self.n_long
-        lo = getattr(self, "long_order", None)
-        fn = getattr(self, "order_fn", None)
-        if fn is not None:
-            # the row hand-out order is a scheduling aid worth ~100 us of sorting: a plan that is used ONCE (a fresh
-            # edge list per mini-batch) never pays for it, a plan that comes back gets it on its second launch
-            self.uses = getattr(self, "uses", 0) + 1
-            # never while a hipGraph is being recorded: the argsort would be allocated in the capture pool and only
-            # FILLED on replay, and an eager launch of this plan before the first replay would read garbage row ids
-            if self.uses >= 2 and not (self.rowptr.is_cuda and torch.cuda.is_current_stream_capturing()):
-                self.order_fn = None
-                self.row_order = fn(self.counts())
-        return SegPlanC(
-            rowptr=self.rowptr.data_ptr(), perm=(perm.data_ptr() if perm is not None else None),
-            long_rows=(self.long_rows.data_ptr() if n_long else None),
-            chunk_ptr=(self.chunk_ptr.data_ptr() if n_long else None),
-            n_long=n_long, n_chunks=(self.n_chunks if n_long else 0),
-            chunk=((1 << 62) if unsplit else self.chunk),
-            partial=(partial.data_ptr() if partial is not None else None), N=self.N, E=self.E,
-            row_order=(self.row_order.data_ptr() if self.row_order is not None else None),
-            # > 0: XCD runs (a node order with locality); -1: no runs, but the long rows LEAD the id range (a degree-sorted
-            # order): the hub walk of a column-blocked aggregate then runs once over the full width (include/ggl_mpops.h)
-            xcd_run_rows=(int(getattr(self, "xcd_run", 0) or 0) or (-1 if (n_long and getattr(self, "hub_first", False)) else 0)),
-            long_order=(lo.data_ptr() if (n_long and lo is not None) else None),
-            max_len=int(getattr(self, "max_len", 0) or 0))
-
-    def counts(self):
-        return self.rowptr[1:] - self.rowptr[:-1]
-
-
-class GraphPlan:
-    """CSR (rows = destination) and, lazily, CSC (rows = source) plans of one edge_index."""
-
-    __slots__ = ("engine", "index", "N_dst", "N_src", "E", "fwd", "col", "_bwd", "_colT", "_posT", "_rowidx", "aux")
-
-    def __init__(self, engine, index, n_dst, n_src):
-        self.engine = engine
-        self.index = index
-        self.N_dst, self.N_src = int(n_dst), int(n_src)
-        self.E = int(index.shape[1])
-        # shared with the segment-op cache: degree(dst) / unsorted_segment_*(.., edge_index[1], N)
-        # on the same edge list reuse this very plan (and vice versa)
-        self.fwd = engine.seg_plan(index[1], self.N_dst)
-        engine._check_range(index[0], self.N_src)
-        self.col = engine.gather_i32(index[0], self.fwd.perm)
-        self._bwd = self._colT = self._posT = self._rowidx = None
-        self.aux = {}  # graph-constant tensors callers derive from this edge list (e.g. GCN edge norms)
-        self._schedule()
-
-    @classmethod
-    def from_csr(cls, engine, row_ptr, col_ind, col_ptr, row_ind, permute, n_rows, n_cols):
-        """A GraphPlan from structures the caller already holds, no sort: the CSR of the aggregating rows
-        (`row_ptr` [n_rows + 1], `col_ind` [E]: the nodes each row gathers from), its transpose (`col_ptr` [n_cols + 1],
-        `row_ind` [E]) and `permute` [E] = the CSR position of every CSC entry — the five tensors FusedGATConv takes as
-        keyword arguments (fusedgat_conv.py:95-100) and otherwise rebuilds on the host in every forward (:102-117)."""
-        gp = cls.__new__(cls)
-        gp.engine, gp.index = engine, None
-        gp.N_dst, gp.N_src, gp.E = int(n_rows), int(n_cols), int(col_ind.shape[0])
-        for nm, t, n in (("row_ptr", row_ptr, gp.N_dst + 1), ("col_ptr", col_ptr, gp.N_src + 1), ("col_ind", col_ind, gp.E),
-                         ("row_ind", row_ind, gp.E), ("permute", permute, gp.E)):
-            if t.dim() != 1 or int(t.shape[0]) != n or t.dtype not in (torch.int32, torch.int64):
-                raise RuntimeError(f"{nm} must be a 1-D int32 / int64 tensor of {n} elements, got {tuple(t.shape)} {t.dtype}")
-        engine._dev(row_ptr, col_ind, col_ptr, row_ind, permute)
-        engine._check_range(col_ind, gp.N_src)
-        engine._check_range(row_ind, gp.N_dst)
-        engine._check_range(permute, max(gp.E, 1))
-        for nm, ptr in (("row_ptr", row_ptr), ("col_ptr", col_ptr)):   # one-off (per plan) host reads
-            if int(ptr[0]) != 0 or int(ptr[-1]) != gp.E or (ptr.numel() > 1 and bool((ptr[1:] < ptr[:-1]).any())):
-                raise RuntimeError(f"{nm} must rise from 0 to the number of edges ({gp.E})")
-        def own_i32(t):   # the plan keeps ITS OWN int32 copy: a later in-place edit of the caller's tensor cannot reach it
-            return t.to(torch.int32).contiguous() if t.dtype != torch.int32 else t.clone().contiguous()
-
-        gp.fwd = engine.plan_from_rowptr(row_ptr.clone() if row_ptr.dtype == torch.int64 else row_ptr, gp.E)
-        gp.col = own_i32(col_ind)
-        gp._bwd = engine.plan_from_rowptr(col_ptr.clone() if col_ptr.dtype == torch.int64 else col_ptr, gp.E)
-        gp._colT = own_i32(row_ind)
-        gp._posT = own_i32(permute)
-        # edge weights arrive in CSR order: the transposed walk reads them through `permute` (a COO-built plan's CSC side
-        # carries the original edge id of every position in its own `perm` instead)
-        gp._bwd.wperm = gp._posT
-        gp._rowidx = None
-        gp.aux = {}
-        gp._schedule()
-        return gp
-
-    def locality(self, samples=1 << 16):
-        """Share of the edges (a strided sample) whose two endpoints lie within N / 64 ids of each other: ~3 % for
-        randomly labelled nodes, 30-40 % for degree-sorted power-law graphs (hub-to-hub edges), 70 %+ when the order
-        comes from a clustering (partition.cluster_order) or from the data itself.  One host read."""
-        E, N = self.E, max(self.N_dst, self.N_src)
-        if E == 0 or self.N_dst != self.N_src:
-            return 0.0
-        S = min(int(samples), E)
-        pos = torch.arange(S, device=self.col.device, dtype=torch.int64) * (E // S)
-        rows = torch.searchsorted(self.fwd.rowptr, pos, right=True) - 1
-        near = (self.col[pos].long() - rows).abs() < max(N // 64, 4096)
-        return float(near.float().mean())
-
-    def _schedule(self):
-        """Scheduling hint for the row kernels (results identical either way): on a graph whose node order carries
-        locality every XCD gets RUNS of consecutive row slots (SegPlan.xcd_run -> ggl_segplan.xcd_run_rows), so that a
-        neighbourhood's source rows are fetched into ONE private L2 instead of all eight — measured on the
-        products-sized planted-community graph in cluster order: K = 256 aggregate 13.4 -> 10.9 ms, K = 64
-        3.31 -> 2.62 ms; on randomly labelled or degree-sorted R-MAT the same mapping LOSES 7-8 % (nothing to keep,
-        and runs of heavy rows unbalance the XCDs), hence the test (profiles/r3_xcd_run_swizzle.txt)."""
-        eng = self.engine
-        run = int(eng.xcd_run_rows)
-        if run < 0:       # automatic: the library's rule on this plan's locality (locality() is one host read)
-            need = int(eng.lib.ggl_policy_xcd_run_rows(self.E, 1.0)) > 0 or int(eng.lib.ggl_policy_xcd_run_rows(self.E, 0.0)) > 0
-            run = int(eng.lib.ggl_policy_xcd_run_rows(self.E, self.locality() if need else 0.0))
-        self.fwd.xcd_run = run
-        if self._bwd is not None:
-            self._bwd.xcd_run = run
-
-    @property
-    def rowidx(self):
-        """destination node of every sorted position (int32 [E]): the row each element of the forward walk belongs
-        to, for walks that run flat over positions instead of row by row (ggl_bspmm_grad_w_sorted)."""
-        if self._rowidx is None:
-            if self.index is not None:
-                self._rowidx = self.engine.gather_i32(self.index[1], self.fwd.perm)
-            else:
-                self._rowidx = torch.repeat_interleave(
-                    torch.arange(self.N_dst, device=self.fwd.rowptr.device, dtype=torch.int32), self.fwd.counts())
-        return self._rowidx
-
-    @property
-    def bwd(self):
-        if self._bwd is None:
-            self._bwd = self.engine.seg_plan(self.index[0], self.N_src)
-            self._colT = self.engine.gather_i32(self.index[1], self._bwd.perm)
-            self._bwd.xcd_run = int(getattr(self.fwd, "xcd_run", 0) or 0)
-        return self._bwd
-
-    @property
-    def colT(self):
-        self.bwd  # noqa: B018
-        return self._colT
-
-    @property
-    def posT(self):
-        """transposed sorted position -> forward sorted position (int32 [E])."""
-        if self._posT is None:
-            E, dev = self.E, self.index.device
-            ar = torch.arange(E, device=dev, dtype=torch.int32)
-            pf = self.fwd.perm if self.fwd.perm is not None else ar
-            pt = self.bwd.perm if self.bwd.perm is not None else ar
-            inv = torch.empty(E, device=dev, dtype=torch.int32)
-            inv[pf.long()] = ar
-            self._posT = inv[pt.long()].contiguous()
-        return self._posT
-
-
-class RowsPlan:
-    """A GraphPlan cut down to a sorted list of destination rows (Engine.rows_plan): `fwd` R x N_src and `bwd` N_src x R
-    SegPlans with their column arrays and the edge weights in sorted order.  `w_ref`: the weight tensor's storage (an
-    entry whose weights died is a miss: the address may have been handed to another tensor)."""
-
-    __slots__ = ("R", "N_dst", "N_src", "rows", "fwd", "col", "w_fwd", "bwd", "colT", "w_bwd", "w_ref")
-
-
-class _PlanCache:
-    """LRU keyed on the identity of the id tensor's storage + its version counter, bounded by entry count AND
-    by the bytes its plans hold (a products-sized GraphPlan is ~2.5 GB of HBM: a caller that builds a fresh
-    edge_index every epoch must not accumulate 16 of them).  An entry dies with its id tensor's storage.
-
-    Identity + version cannot see a mutation made behind autograd's back (`.data`, numpy-shared memory): set
-    GGL_VERIFY_PLANS=1 to keep a (first, last, sum) checksum of the ids with every plan and verify it on each
-    hit (one device reduction + a host read per call: a debugging aid, off by default)."""
-
-    def __init__(self, cap=16, max_bytes=None):
-        self.cap = cap
-        self.max_bytes = int(float(os.environ.get("GGL_PLAN_CACHE_GB", "48")) * 2**30) if max_bytes is None else max_bytes
-        self.d = OrderedDict()
-        self.bytes = 0
-        self.verify = os.environ.get("GGL_VERIFY_PLANS", "0") == "1"
-
-    @staticmethod
-    def key(t, extra):
-        st = t.untyped_storage()
-        return (st._cdata, t.storage_offset(), tuple(t.shape), tuple(t.stride()), t._version,
-                t.dtype, str(t.device)) + tuple(extra)
-
-    @staticmethod
-    def _checksum(t):
-        if t.numel() == 0:
-            return (0, 0, 0)
-        f = t.reshape(-1)
-        return (int(f[0]), int(f[-1]), int(f.sum()))
-
-    @staticmethod
-    def _nbytes(val):
-        """HBM held by a cached value (SegPlan / GraphPlan / tensor), for the byte bound."""
-        if isinstance(val, SegPlan):   # the common miss (a fresh id tensor per mini-batch): no generic walk
-            own = sum(t.untyped_storage().nbytes() for t in (val.rowptr, val.perm, val.long_rows, val.chunk_ptr)
-                      if t is not None)
-            return own + 4 * val.N        # (+ the row order it gets if it is launched again)
-        seen, total = set(), 0
-
-        def visit(o, depth=0):
-            nonlocal total
-            if isinstance(o, torch.Tensor):
-                k = o.untyped_storage()._cdata
-                if k not in seen:
-                    seen.add(k)
-                    total += o.untyped_storage().nbytes()
-            elif depth < 3 and hasattr(o, "__slots__"):
-                for a in o.__slots__:
-                    if a not in ("engine", "index"):      # (the caller's own edge_index is not ours to count)
-                        visit(getattr(o, a, None), depth + 1)
-            elif depth < 3 and isinstance(o, dict):
-                for v in o.values():
-                    visit(v, depth + 1)
-
-        visit(val)
-        return total
-
-    def get(self, t, extra):
-        k = self.key(t, extra)
-        hit = self.d.get(k)
-        if hit is not None:
-            ref, val, nb, chk = hit
-            if not ref.expired():
-                if chk is not None and chk != self._checksum(t):
-                    raise RuntimeError("gammagl_amd: an id tensor was modified in place behind its version counter "
-                                       "(.data / shared memory) after its plan was cached; call "
-                                       "Engine.clear_caches() after such edits")
-                self.d.move_to_end(k)
-                return val
-            self.bytes -= nb
-            del self.d[k]
-        return None
-
-    def put(self, t, extra, val):
-        k = self.key(t, extra)
-        old = self.d.pop(k, None)
-        if old is not None:
-            self.bytes -= old[2]
-        nb = self._nbytes(val)
-        self.d[k] = (StorageWeakRef(t.untyped_storage()), val, nb, self._checksum(t) if self.verify else None)
-        self.bytes += nb
-        while len(self.d) > 1 and (len(self.d) > self.cap or self.bytes > self.max_bytes):
-            _, (_, _, onb, _) = self.d.popitem(last=False)
-            self.bytes -= onb
-
-    def clear(self):
-        self.d.clear()
-        self.bytes = 0
 
 
 class Engine:
@@ -328,7 +46,6 @@ class Engine:
         self.row_order_window, self.row_order_heavy = int(win.value), int(heavy.value)   # see _row_order (0 = global sort)
         self.xcd_run_rows = -1   # -1 = per graph (ggl_policy_xcd_run_rows on the plan's locality), >= 0 forces it
         self.gradw_sorted = True    # bspmm weight gradient along the sorted plan with LDS-staged strips (A/B switch)
-        self._make_functions()
 
     def clear_caches(self):
         """Drop every cached plan, sorted-weight copy and graph-constant (e.g. GCN norms).  Plans are keyed on
@@ -409,38 +126,38 @@ class Engine:
             ids = ids.to(torch.int64)
         E, N = int(ids.shape[0]), int(N)
         chunk = int(chunk or self.chunk or self.auto_chunk(E))
-        st = self._stream(dev)
-        p = SegPlan()
-        p.N, p.E, p.chunk, p.device = N, E, chunk, dev
-        p.rowptr = torch.empty(N + 1, dtype=torch.int64, device=dev)
+        rowptr = torch.empty(N + 1, dtype=torch.int64, device=dev)
         perm = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
         wsb = self.lib.ggl_plan_workspace_bytes(E, N)
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
         is_sorted, max_len = ctypes.c_int32(0), ctypes.c_int64(0)
-        self._check(self.lib.ggl_plan_build(_ptr(ids), E, N, _ptr(perm), _ptr(p.rowptr), _ptr(ws),
-                                            wsb, st, ctypes.byref(is_sorted), ctypes.byref(max_len)))
-        p.is_sorted, p.max_len = bool(is_sorted.value), int(max_len.value)
-        p.perm = None if p.is_sorted else perm[:E]
-        p.n_long = p.n_chunks = 0
-        p.long_rows = p.chunk_ptr = p.long_order = None
-        if p.max_len > chunk:
-            lwb = self.lib.ggl_plan_long_workspace_bytes(N)
+        self._check(self.lib.ggl_plan_build(_ptr(ids), E, N, _ptr(perm), _ptr(rowptr), _ptr(ws),
+                                            wsb, self._stream(dev), ctypes.byref(is_sorted), ctypes.byref(max_len)))
+        p = self._finish_plan(SegPlan(N, E, rowptr, chunk, max_len.value, dev, perm=None if is_sorted.value else perm[:E],
+                                      is_sorted=bool(is_sorted.value)))
+        # do the long rows lead the id range (degree-sorted node order)?  One more host read, at plan build only.
+        p.hub_first = bool(p.n_long >= 8 and int(p.long_rows[-1]) < 4 * p.n_long)
+        return p
+
+    def _finish_plan(self, p):
+        """What every plan this engine builds gets after its rowptr: the long-row table (rows of more than `chunk`
+        elements) with its `long_order`, the deferred row-order hook, and its number."""
+        if p.max_len > p.chunk:
+            dev, st = p.device, self._stream(p.device)
+            lwb = self.lib.ggl_plan_long_workspace_bytes(p.N)
             lws = torch.empty(lwb, dtype=torch.uint8, device=dev)
             nl, nc = ctypes.c_int64(0), ctypes.c_int64(0)
-            self._check(self.lib.ggl_plan_long_count(_ptr(p.rowptr), N, chunk, _ptr(lws), lwb, st,
+            self._check(self.lib.ggl_plan_long_count(_ptr(p.rowptr), p.N, p.chunk, _ptr(lws), lwb, st,
                                                      ctypes.byref(nl), ctypes.byref(nc)))
             p.n_long, p.n_chunks = int(nl.value), int(nc.value)
             p.long_rows = torch.empty(p.n_long, dtype=torch.int32, device=dev)
             p.chunk_ptr = torch.empty(p.n_long + 1, dtype=torch.int64, device=dev)
-            self._check(self.lib.ggl_plan_long_fill(_ptr(p.rowptr), N, chunk, p.n_long,
-                                                    _ptr(p.long_rows), _ptr(p.chunk_ptr), _ptr(lws),
-                                                    lwb, st))
+            self._check(self.lib.ggl_plan_long_fill(_ptr(p.rowptr), p.N, p.chunk, p.n_long,
+                                                    _ptr(p.long_rows), _ptr(p.chunk_ptr), _ptr(lws), lwb, st))
             p.long_order = self._long_order(p)
-            # do the long rows lead the id range (degree-sorted node order)?  One more host read, at plan build only.
-            p.hub_first = bool(p.n_long >= 8 and int(p.long_rows[-1]) < 4 * p.n_long)
         # scheduling aid: rows by descending length inside id windows, see _row_order / ggl_segplan.row_order —
         # computed when the plan is launched a second time (SegPlan.c_struct)
-        p.row_order, p.uses, p.order_fn = None, 0, (self._row_order if N > 1 else None)
+        p.order_fn = self._row_order if p.N > 1 else None
         self.stats["plans_built"] += 1
         p.uid = self.stats["plans_built"]
         return p
@@ -477,30 +194,12 @@ class Engine:
         list): no sort, and no host sync when the caller knows ``max_len`` (e.g. the fan-out).  ``chunk``: the
         long-row threshold of the plan these rows were cut from (rows_plan), instead of the policy's for this E."""
         dev = self._dev(rowptr)
-        p = SegPlan()
-        p.N, p.E, p.chunk, p.device = int(rowptr.shape[0]) - 1, int(E), int(chunk or self.chunk or self.auto_chunk(E)), dev
-        p.rowptr = rowptr.contiguous().to(torch.int64)
-        p.perm, p.is_sorted = None, True
-        p.max_len = int(max_len) if max_len is not None else (int(p.counts().max()) if p.N > 0 else 0)
-        p.n_long = p.n_chunks = 0
-        p.long_rows = p.chunk_ptr = p.long_order = None
-        if p.max_len > p.chunk:
-            st = self._stream(dev)
-            lwb = self.lib.ggl_plan_long_workspace_bytes(p.N)
-            lws = torch.empty(lwb, dtype=torch.uint8, device=dev)
-            nl, nc = ctypes.c_int64(0), ctypes.c_int64(0)
-            self._check(self.lib.ggl_plan_long_count(_ptr(p.rowptr), p.N, p.chunk, _ptr(lws), lwb, st,
-                                                     ctypes.byref(nl), ctypes.byref(nc)))
-            p.n_long, p.n_chunks = int(nl.value), int(nc.value)
-            p.long_rows = torch.empty(p.n_long, dtype=torch.int32, device=dev)
-            p.chunk_ptr = torch.empty(p.n_long + 1, dtype=torch.int64, device=dev)
-            self._check(self.lib.ggl_plan_long_fill(_ptr(p.rowptr), p.N, p.chunk, p.n_long,
-                                                    _ptr(p.long_rows), _ptr(p.chunk_ptr), _ptr(lws), lwb, st))
-            p.long_order = self._long_order(p)
-        p.row_order, p.uses, p.order_fn = None, 0, (self._row_order if p.N > 1 else None)
-        self.stats["plans_built"] += 1
-        p.uid = self.stats["plans_built"]
-        return p
+        N = int(rowptr.shape[0]) - 1
+        rowptr = rowptr.contiguous().to(torch.int64)
+        if max_len is None:
+            max_len = int((rowptr[1:] - rowptr[:-1]).max()) if N > 0 else 0
+        # (hub_first stays unset: it would cost a host read, and this builder is sync-free when the caller knows max_len)
+        return self._finish_plan(SegPlan(N, E, rowptr, chunk or self.chunk or self.auto_chunk(E), max_len, dev))
 
     def adopt_plan(self, ids, N, plan):
         """Register a plan built elsewhere (e.g. straight from a sampler's CSR block) for the id tensor
@@ -591,7 +290,7 @@ class Engine:
         E_r = int(n.value)
         rp.col = torch.empty(E_r, dtype=torch.int32, device=dev)
         rp.w_fwd = torch.empty(E_r, dtype=torch.float32, device=dev) if w is not None else None
-        wperm = gp.fwd.perm if gp.fwd.perm is not None else getattr(gp.fwd, "wperm", None)
+        wperm = gp.fwd.perm if gp.fwd.perm is not None else gp.fwd.wperm
         self._check(L.ggl_plan_rows_fwd_fill(_ptr(gp.fwd.rowptr), _ptr(gp.col), _ptr(w), _ptr(wperm), _ptr(rows), R,
                                              _ptr(rowptr_r), E_r, _ptr(rp.col), _ptr(rp.w_fwd), st))
         rp.fwd = self.plan_from_rowptr(rowptr_r, E_r, chunk=gp.fwd.chunk)   # the full plan's threshold: the same rows are long
@@ -604,7 +303,7 @@ class Engine:
             raise RuntimeError(f"restricted plans disagree: {E_r} forward elements, {int(n.value)} transposed")
         rp.colT = torch.empty(E_r, dtype=torch.int32, device=dev)
         rp.w_bwd = torch.empty(E_r, dtype=torch.float32, device=dev) if w is not None else None
-        wpermT = bwd.perm if bwd.perm is not None else getattr(bwd, "wperm", None)
+        wpermT = bwd.perm if bwd.perm is not None else bwd.wperm
         self._check(L.ggl_plan_rows_bwd_fill(_ptr(colT), _ptr(w), _ptr(wpermT), E, _ptr(rank), _ptr(pos), _ptr(rp.colT),
                                              _ptr(rp.w_bwd), st))
         rp.bwd = self.plan_from_rowptr(rowptrT_r, E_r, chunk=bwd.chunk)
@@ -630,7 +329,7 @@ class Engine:
             self._check_f32("bias", bias)
             if bias.numel() != x.shape[1]:
                 raise RuntimeError("bias must hold one value per column")
-        return self.SpMMRows.apply(gp, weight, x.contiguous(), rows, bias)
+        return autograd.SpMMRows.apply(self, gp, weight, x.contiguous(), rows, bias)
 
     def gather_i32(self, src_i64, perm):
         dev = src_i64.device
@@ -932,7 +631,7 @@ class Engine:
         permutation, or, on the CSC side of a CSR-built plan, through `wperm` (GraphPlan.from_csr)."""
         if perm_override is not None or w is None:
             return w, 0, perm_override
-        wp = plan.perm if plan.perm is not None else getattr(plan, "wperm", None)
+        wp = plan.perm if plan.perm is not None else plan.wperm
         if wp is None:
             return w, 0, None
         w, by_pos = self._sorted_weights(plan, w, wp)
@@ -983,11 +682,14 @@ class Engine:
         if t.dtype != torch.float32 and t.dtype not in _X16_DTYPES:
             raise RuntimeError(f"expected scalar type Float (or Half / BFloat16 storage) but found {t.dtype} for {name}")
 
-    def _spmm_bwd_x(self, op, gp, w, g, x_dtype, aux=None):
-        """gx of sum / mean in x's dtype: the transposed walk on g as it arrives.  An f32 g for 16-bit rows (the forward
-        returned f32: out_dtype) is walked in f32 and rounded once."""
+    def _spmm_bwd_x(self, gp, w, g, x_dtype, mean):
+        """gx of sum / mean in x's dtype: the transposed walk on g as it arrives (mean: it divides by the destination
+        row's length).  An f32 g for 16-bit rows (the forward returned f32: out_dtype) is walked in f32 and rounded once."""
         g = g.contiguous()
-        gx, _ = self._spmm_fwd(op, gp.bwd, gp.colT, w, g, gp.N_src, aux=aux)
+        if mean:
+            gx, _ = self._spmm_fwd("mean_bwd", gp.bwd, gp.colT, w, g, gp.N_src, aux=gp.fwd.rowptr)
+        else:
+            gx, _ = self._spmm_fwd("sum", gp.bwd, gp.colT, w, g, gp.N_src)
         return gx if gx.dtype == x_dtype else gx.to(x_dtype)
 
     def _spmm_grad_w(self, gp, x, g, mean):
@@ -1008,502 +710,6 @@ class Engine:
                                              self._stream(g.device)))
         return gw
 
-    # ---- autograd Functions (closures over this engine) ---------------------------------------
-    def _make_functions(self):
-        eng = self
-
-        class SegmentSum(torch.autograd.Function):  # src/segment_sum.cpp:35-54
-            @staticmethod
-            def forward(ctx, x, ids, N):
-                plan = eng.seg_plan(ids, N)
-                out, _ = eng._segment_fwd("sum", x, plan)
-                ctx.save_for_backward(ids)
-                ctx.x_shape = x.shape
-                return out
-
-            @staticmethod
-            def backward(ctx, g):
-                (ids,) = ctx.saved_tensors
-                return eng._segment_bwd(g, ids, ctx.x_shape), None, None
-
-        class SegmentMean(torch.autograd.Function):  # src/segment_mean.cpp:36-63
-            @staticmethod
-            def forward(ctx, x, ids, N):
-                plan = eng.seg_plan(ids, N)
-                out, _ = eng._segment_fwd("mean", x, plan)
-                ctx.save_for_backward(ids, plan.rowptr)
-                ctx.x_shape = x.shape
-                return out
-
-            @staticmethod
-            def backward(ctx, g):
-                ids, rowptr = ctx.saved_tensors
-                return eng._segment_bwd(g, ids, ctx.x_shape, rowptr), None, None
-
-        class SegmentMax(torch.autograd.Function):  # src/segment_max.cpp:37-61
-            @staticmethod
-            def forward(ctx, x, ids, N):
-                plan = eng.seg_plan(ids, N)
-                out, arg = eng._segment_fwd("max", x, plan)
-                ctx.save_for_backward(arg)
-                ctx.x_shape = x.shape
-                ctx.mark_non_differentiable(arg)
-                return out, arg
-
-            @staticmethod
-            def backward(ctx, g, _garg):
-                (arg,) = ctx.saved_tensors
-                g = g.contiguous()
-                E = ctx.x_shape[0]
-                K = int(math.prod(ctx.x_shape[1:]))
-                gin = torch.empty(ctx.x_shape, dtype=g.dtype, device=g.device)
-                eng._check(eng.lib.ggl_segment_max_bwd(eng._code(g), _ptr(g), _ptr(arg), E,
-                                                       int(arg.shape[0]), K, _ptr(gin),
-                                                       eng._stream(g.device)))
-                return gin, None, None
-
-        class SegmentSoftmax(torch.autograd.Function):  # utils/softmax.py:29-35 as one op each way
-            @staticmethod
-            def forward(ctx, x, plan):
-                y = eng._softmax_fwd(x, plan)
-                ctx.save_for_backward(y)
-                ctx.plan = plan
-                return y
-
-            @staticmethod
-            @once_differentiable
-            def backward(ctx, g):
-                (y,) = ctx.saved_tensors
-                return eng._softmax_bwd(y, g, ctx.plan), None
-
-        def spmm_function(op):
-            """SpMMSum / SpMMMean (src/gspmm.cpp:26-80, 82-141): one body, the reduce as its parameter.  An extension
-            over the reference (gspmm.cpp:30 marks the weight non-differentiable): a weight that requires grad gets its
-            gradient (Engine._spmm_grad_w); only then is x saved, a constant weight costs what it did."""
-
-            class SpMM(torch.autograd.Function):
-                @staticmethod
-                def forward(ctx, gp, w, x, out_dtype=None):
-                    out, _ = eng._spmm_fwd(op, gp.fwd, gp.col, w, x, gp.N_dst, out_dtype=out_dtype)
-                    ctx.gp, ctx.w, ctx.x_dtype = gp, w, x.dtype
-                    if w is not None and ctx.needs_input_grad[1]:
-                        ctx.save_for_backward(x)
-                    return out
-
-                @staticmethod
-                def backward(ctx, g):
-                    gx = gw = None
-                    if ctx.needs_input_grad[2]:
-                        if op == "mean":   # the transposed walk divides by the destination row's length
-                            gx = eng._spmm_bwd_x("mean_bwd", ctx.gp, ctx.w, g, ctx.x_dtype, aux=ctx.gp.fwd.rowptr)
-                        else:
-                            gx = eng._spmm_bwd_x("sum", ctx.gp, ctx.w, g, ctx.x_dtype)
-                    if ctx.w is not None and ctx.needs_input_grad[1]:
-                        gw = eng._spmm_grad_w(ctx.gp, ctx.saved_tensors[0], g, op == "mean").view(ctx.w.shape)
-                    return None, gw, gx, None
-
-            SpMM.__name__ = SpMM.__qualname__ = "SpMM" + op.capitalize()
-            return SpMM
-
-        SpMMSum, SpMMMean = spmm_function("sum"), spmm_function("mean")
-
-        class SpMMMax(torch.autograd.Function):  # src/gspmm.cpp:143-202
-            @staticmethod
-            def forward(ctx, gp, w, x):
-                out, arg = eng._spmm_fwd("max", gp.fwd, gp.col, w, x, gp.N_dst)
-                ctx.gp, ctx.w = gp, w
-                ctx.save_for_backward(arg)
-                return out
-
-            @staticmethod
-            def backward(ctx, g):
-                gp = ctx.gp
-                (arg,) = ctx.saved_tensors
-                gx, _ = eng._spmm_fwd("max_bwd", gp.bwd, gp.colT, ctx.w, g.contiguous(), gp.N_src,
-                                      aux=arg, gp=gp)
-                return None, None, gx
-
-        class BSpMMSum(torch.autograd.Function):  # src/gspmm.cpp:204-260
-            @staticmethod
-            def forward(ctx, gp, w, x):
-                out = eng._bspmm_fwd(gp.fwd, gp.col, w, x, gp.N_dst)
-                ctx.gp = gp
-                ctx.save_for_backward(w, x)
-                return out
-
-            @staticmethod
-            def backward(ctx, g):
-                gp = ctx.gp
-                w, x = ctx.saved_tensors
-                g = g.contiguous()
-                gx = eng._bspmm_fwd(gp.bwd, gp.colT, w, g, gp.N_src)
-                H, C = int(x.shape[1]), int(x.shape[2])
-                gw = torch.empty_like(w)
-                # a plan built from the caller's CSR has no COO edge list to walk (gp.index is None): it always takes the
-                # sorted route, whose plain kernel covers any channel count
-                if gp.index is None or (eng.gradw_sorted and eng.lib.ggl_policy_gradw_sorted(H, C)):
-                    # along the destination-sorted forward plan, strips staged through LDS (edgedot.hip): the g rows
-                    # of a batch are a handful of rows, only x[src] is a random gather — and a coalesced one
-                    sb = eng.lib.ggl_bspmm_grad_w_sorted_scratch_bytes(gp.E, gp.N_dst, H, C)
-                    scratch = torch.empty(sb // 4, dtype=torch.float32, device=g.device) if sb else None
-                    cs = gp.fwd.c_struct(None)
-                    eng._check(eng.lib.ggl_bspmm_grad_w_sorted(ctypes.byref(cs), _ptr(gp.col), _ptr(gp.rowidx), _ptr(x),
-                                                               _ptr(g), H, C, _ptr(gw), _ptr(scratch),
-                                                               eng._stream(g.device)))
-                else:
-                    eng._check(eng.lib.ggl_bspmm_grad_w(_ptr(gp.index), _ptr(x), _ptr(g), gp.E, H, C,
-                                                        _ptr(gw), eng._stream(g.device)))
-                # the reference returns grad_weight although it marked weight non-differentiable
-                # (gspmm.cpp:208,259; SURVEY §8a A8): w.grad is populated there, and here.
-                return None, gw, gx
-
-        class GATFused(torch.autograd.Function):
-            """edge-softmax + aggregate in one kernel (gat_conv.py:103-112 + softmax.py:29-35).  bf16 / f16 x (an
-            extension, ggl_gat_fused_*_x16): the general kernels on 16-bit rows, f32 softmax and sums, out in x's dtype
-            (or f32 with out_dtype); the backward reads x16 and the out RETURNED here, no f32 copy of either is kept."""
-
-            @staticmethod
-            def forward(ctx, gp, el, er, x, slope, p_drop=0.0, out_dtype=None):
-                dev = x.device
-                N, H, C = gp.N_dst, int(x.shape[1]), int(x.shape[2])
-                x16 = x.dtype in _X16_DTYPES
-                out = torch.empty((N, H, C), dtype=(out_dtype or x.dtype) if x16 else torch.float32, device=dev)
-                rmax = torch.empty((N, H), dtype=torch.float32, device=dev)
-                rden = torch.empty((N, H), dtype=torch.float32, device=dev)
-                part = eng._gat_partial(gp.fwd, H, C, dev)
-                cs = gp.fwd.c_struct(part)
-                rng, rng_used = eng._draw(dev, p_drop)
-                fast = bool(not x16 and eng.gat_fast and eng.lib.ggl_gat_fast_supported(H, C))
-                if x16:
-                    eng._check(eng.lib.ggl_gat_fused_fwd_x16(
-                        ctypes.byref(cs), _ptr(gp.col), _ptr(el), _ptr(er), _DTYPE_CODE[x.dtype], _ptr(x), float(slope),
-                        H, C, float(p_drop), _ptr(rng), _DTYPE_CODE[out.dtype], _ptr(out), _ptr(rmax), _ptr(rden),
-                        eng._stream(dev)))
-                elif fast:
-                    eng._check(eng.lib.ggl_gat_fast_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(el), _ptr(er), _ptr(x),
-                                                        int(x.shape[0]), float(slope), H, C, float(p_drop), _ptr(rng),
-                                                        _ptr(out), _ptr(rmax), _ptr(rden), eng._stream(dev)))
-                else:
-                    eng._check(eng.lib.ggl_gat_fused_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(el), _ptr(er),
-                                                         _ptr(x), float(slope), H, C, float(p_drop), _ptr(rng),
-                                                         _ptr(out), _ptr(rmax), _ptr(rden), eng._stream(dev)))
-                ctx.fast = fast
-                ctx.gp, ctx.slope, ctx.p_drop, ctx.rng_used = gp, float(slope), float(p_drop), rng_used
-                ctx.save_for_backward(el, er, x, out, rmax, rden)
-                return out
-
-            @staticmethod
-            def backward(ctx, g):
-                gp = ctx.gp
-                el, er, x, out, rmax, rden = ctx.saved_tensors
-                g = g.contiguous()
-                dev = g.device
-                H, C = int(x.shape[1]), int(x.shape[2])
-                st = eng._stream(dev)
-                x16 = x.dtype in _X16_DTYPES
-                if x16 and g.dtype != out.dtype:
-                    g = g.to(out.dtype)
-                if ctx.fast:  # both walks recompute alpha / de from per-row constants: no [E, H, 2] buffer
-                    bwd = gp.bwd
-                    stats = torch.empty((gp.N_dst, H, 4), dtype=torch.float32, device=dev)
-                    ger = torch.empty_like(er)
-                    gx = torch.empty((gp.N_src, H, C), dtype=torch.float32, device=dev)
-                    gel = torch.empty((gp.N_src, H), dtype=torch.float32, device=dev)
-                    part_f = eng._partial(gp.fwd, torch.float32, 8 * H, False, dev)   # four double sums per chunk and head
-                    part_t = eng._partial(bwd, torch.float32, H * C + H, False, dev)
-                    cs, csT = gp.fwd.c_struct(part_f), bwd.c_struct(part_t)
-                    posT = gp.posT if ctx.p_drop > 0 else None
-                    eng._check(eng.lib.ggl_gat_fast_bwd(
-                        ctypes.byref(cs), _ptr(gp.col), ctypes.byref(csT), _ptr(gp.colT), _ptr(posT), _ptr(el),
-                        _ptr(er), _ptr(x), _ptr(g), _ptr(out), _ptr(rmax), _ptr(rden), ctx.slope, H, C, ctx.p_drop,
-                        _ptr(ctx.rng_used), _ptr(stats), _ptr(gx), _ptr(gel), _ptr(ger), st))
-                    return None, gel, ger, gx, None, None, None
-                # alpha and de interleaved [E, H, 2]: the source-side walk fetches both with one 64-byte line
-                ad = torch.empty((max(gp.E, 1), H, 2), dtype=torch.float32, device=dev)
-                alpha, de = ad.data_ptr(), ad.data_ptr() + 4
-                ger = torch.empty_like(er)
-                part_f = eng._partial(gp.fwd, torch.float32, H, False, dev)  # must outlive the launch
-                cs = gp.fwd.c_struct(part_f)
-                xc, gc = _DTYPE_CODE.get(x.dtype), _DTYPE_CODE.get(g.dtype)
-                if x16:
-                    eng._check(eng.lib.ggl_gat_fused_bwd_dst_x16(
-                        ctypes.byref(cs), _ptr(gp.col), _ptr(el), _ptr(er), xc, _ptr(x), gc, _ptr(g), gc, _ptr(out),
-                        _ptr(rmax), _ptr(rden), ctx.slope, H, C, ctx.p_drop, _ptr(ctx.rng_used), alpha, de, _ptr(ger),
-                        st))
-                else:
-                    eng._check(eng.lib.ggl_gat_fused_bwd_dst(
-                        ctypes.byref(cs), _ptr(gp.col), None, _ptr(el), _ptr(er), _ptr(x),
-                        _ptr(g), _ptr(out), _ptr(rmax), _ptr(rden), ctx.slope, H, C, ctx.p_drop,
-                        _ptr(ctx.rng_used), alpha, de, _ptr(ger), None, st))
-                bwd = gp.bwd
-                gx = torch.empty((gp.N_src, H, C), dtype=x.dtype, device=dev)
-                gel = torch.empty((gp.N_src, H), dtype=torch.float32, device=dev)
-                part = eng._partial(bwd, torch.float32, H * C + H, False, dev)  # gx and gel partials of long rows
-                csT = bwd.c_struct(part)
-                if x16:
-                    eng._check(eng.lib.ggl_gat_fused_bwd_src_x16(ctypes.byref(csT), _ptr(gp.colT), _ptr(gp.posT),
-                                                                 alpha, de, gc, _ptr(g), H, C, xc, _ptr(gx), _ptr(gel),
-                                                                 st))
-                else:
-                    eng._check(eng.lib.ggl_gat_fused_bwd_src(ctypes.byref(csT), _ptr(gp.colT), _ptr(gp.posT),
-                                                             alpha, de, _ptr(g), H, C,
-                                                             _ptr(gx), _ptr(gel), st))
-                return None, gel, ger, gx, None, None, None
-
-        class BiasAdd(torch.autograd.Function):
-            """out = x + bias (bias broadcast over rows); d bias = column sums of the gradient."""
-
-            @staticmethod
-            def forward(ctx, x, bias):
-                ctx.bias_shape = bias.shape
-                return x + bias
-
-            @staticmethod
-            def backward(ctx, g):
-                gb = eng.colsum(g.reshape(g.shape[0], -1)).reshape(ctx.bias_shape)
-                return g, gb
-
-        class BiasAct(torch.autograd.Function):
-            """y = dropout(relu(a + bias)) in one kernel; backward rebuilds the mask from y and reduces
-            the bias gradient in the same pass (csrc/epilogue.hip)."""
-
-            @staticmethod
-            def forward(ctx, a, bias, relu, p_drop):
-                a = a.contiguous()
-                rng, rng_used = eng._draw(a.device, p_drop)
-                y = eng._epi_fwd(a, bias, relu, p_drop, rng)
-                ctx.epi = (relu, p_drop, rng_used, None if bias is None else bias.shape)   # _epi_bwd's arguments after (g, y)
-                ctx.save_for_backward(y)
-                return y
-
-            @staticmethod
-            def backward(ctx, g):
-                (y,) = ctx.saved_tensors
-                ga, gb = eng._epi_bwd(g, y, *ctx.epi)
-                return ga, gb, None, None
-
-        class SpMMEpi(torch.autograd.Function):
-            """y = dropout(relu(reduce(A x) + add + bias)), reduce = sum | mean, in ONE kernel (ggl_spmm_epi_ex):
-            GCNConv's "+ bias" (gcn_conv.py:105-106) and SAGEConv's "mean + fc_self(x_dst) + bias -> act"
-            (sage_conv.py:100-108) applied to each finished row in registers."""
-
-            @staticmethod
-            def forward(ctx, gp, w, x, mean, add, bias, relu, p_drop):
-                dev = x.device
-                K = int(x.shape[1])
-                y = torch.empty((gp.N_dst, K), dtype=torch.float32, device=dev)
-                rng, rng_used = eng._draw(dev, p_drop)
-                b = bias.contiguous().reshape(-1) if bias is not None else None
-                a = add.contiguous() if add is not None else None
-                eng.spmm_epi_into(gp.fwd, gp.col, w, x, y, mean=mean, add=a, bias=b, relu=relu, p_drop=p_drop, rng=rng)
-                ctx.gp, ctx.w, ctx.mean, ctx.has_add = gp, w, bool(mean), add is not None
-                ctx.epi = (relu, p_drop, rng_used, None if bias is None else bias.shape)
-                # a learnable weight's gradient is the edge-dot of x with the pre-activation gradient: x is kept for it alone
-                ctx.want_gw = w is not None and ctx.needs_input_grad[1]
-                ctx.save_for_backward(y, *((x,) if ctx.want_gw else ()))
-                return y
-
-            @staticmethod
-            def backward(ctx, g):
-                y = ctx.saved_tensors[0]
-                ga, gb = eng._epi_bwd(g, y, *ctx.epi)
-                gp = ctx.gp
-                gx = gw = None
-                if ctx.needs_input_grad[2]:
-                    if ctx.mean:
-                        gx, _ = eng._spmm_fwd("mean_bwd", gp.bwd, gp.colT, ctx.w, ga, gp.N_src, aux=gp.fwd.rowptr)
-                    else:
-                        gx, _ = eng._spmm_fwd("sum", gp.bwd, gp.colT, ctx.w, ga, gp.N_src)
-                if ctx.want_gw:
-                    gw = eng._spmm_grad_w(gp, ctx.saved_tensors[1], ga, ctx.mean).view(ctx.w.shape)
-                return None, gw, gx, None, (ga if ctx.has_add else None), gb, None, None
-
-        class SegmentEpi(torch.autograd.Function):
-            """The same epilogue on segment_sum / segment_mean of f32 messages x[E, K] (ggl_segment_epi): the
-            message() + aggregate() route of a sampled SAGEConv block."""
-
-            @staticmethod
-            def forward(ctx, x, ids, N, mean, add, bias, relu):
-                dev = x.device
-                plan = eng.seg_plan(ids, N)
-                K = int(x.shape[1])
-                if int(x.shape[0]) != plan.E:
-                    raise IndexError("fisrt dimension of x and index should be same")
-                y = torch.empty((plan.N, K), dtype=torch.float32, device=dev)
-                part = eng._partial(plan, torch.float32, K, False, dev)
-                cs = plan.c_struct(part)
-                b = bias.contiguous().reshape(-1) if bias is not None else None
-                a = add.contiguous() if add is not None else None
-                eng._check(eng.lib.ggl_segment_epi(_ptr(x), ctypes.byref(cs), K, int(bool(mean)), _ptr(a), 0, _ptr(b),
-                                                   int(bool(relu)), 0.0, None, _ptr(y), eng._stream(dev)))
-                ctx.mean, ctx.has_add, ctx.x_shape = bool(mean), add is not None, x.shape
-                ctx.epi = (relu, 0.0, None, None if bias is None else bias.shape)
-                ctx.save_for_backward(y, ids, plan.rowptr)
-                return y
-
-            @staticmethod
-            def backward(ctx, g):
-                y, ids, rowptr = ctx.saved_tensors
-                ga, gb = eng._epi_bwd(g, y, *ctx.epi)
-                gx = None
-                if ctx.needs_input_grad[0]:
-                    gx = eng._segment_bwd(ga, ids, ctx.x_shape, rowptr if ctx.mean else None)
-                return gx, None, None, None, (ga if ctx.has_add else None), gb, None
-
-        class GATHeadMean(torch.autograd.Function):
-            """y_i = 1/H sum_h sum_j alpha_ijh (x_j W_h) for a head-averaging GAT layer (gat_conv.py:98-122 with
-            concat=False), aggregated BEFORE it is transformed: y_i = 1/H (sum_j alpha_ijh x_j) W_h, logits from
-            el = x (W a_src), er = x (W a_dst).  The three walks gather the F-float input row / the C-float output
-            gradient instead of the H x C transformed row (gat.hip, ggl_gat_sh_*); everything dense runs as GEMMs."""
-
-            @staticmethod
-            def forward(ctx, gp, x, W, att, slope, p_drop):
-                dev = x.device
-                N, F = int(x.shape[0]), int(x.shape[1])
-                H = 8
-                C = int(W.shape[1]) // H
-                Wr = W.view(F, H, C)
-                a_src, a_dst = att[0, :, :C], att[0, :, C:]
-                U, V = (Wr * a_src).sum(-1), (Wr * a_dst).sum(-1)           # [F, H]
-                el, er = (x @ U).contiguous(), (x @ V).contiguous()         # [N, H]
-                rowmax = torch.empty((N, H), dtype=torch.float32, device=dev)
-                den = torch.empty((N, H), dtype=torch.float32, device=dev)
-                A = torch.empty((N, H, F), dtype=torch.float32, device=dev)
-                part = eng._gat_sh_partial(gp.fwd, F, dev)
-                cs = gp.fwd.c_struct(part)
-                rng, rng_used = eng._draw(dev, p_drop)
-                eng._check(eng.lib.ggl_gat_sh_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(el), _ptr(er), _ptr(x), F,
-                                                  float(slope), float(p_drop), _ptr(rng), _ptr(rowmax), _ptr(A),
-                                                  _ptr(den), eng._stream(dev)))
-                Wst = Wr.permute(1, 0, 2).reshape(H * F, C)
-                y = (A.view(N, H * F) @ Wst) / H
-                ctx.gp, ctx.slope, ctx.p_drop, ctx.rng_used = gp, float(slope), float(p_drop), rng_used
-                ctx.save_for_backward(x, W, att, el, er, rowmax, den, A)
-                return y
-
-            @staticmethod
-            def backward(ctx, gy):
-                gp = ctx.gp
-                x, W, att, el, er, rowmax, den, A = ctx.saved_tensors
-                dev = gy.device
-                N, F = int(x.shape[0]), int(x.shape[1])
-                H = 8
-                C = int(W.shape[1]) // H
-                Cp = C + (-C) % 4
-                Wr = W.view(F, H, C)
-                a_src, a_dst = att[0, :, :C], att[0, :, C:]
-                U, V = (Wr * a_src).sum(-1), (Wr * a_dst).sum(-1)
-                Wst = Wr.permute(1, 0, 2).reshape(H * F, C)
-                gyh = gy.contiguous() / H
-                gyp = torch.nn.functional.pad(gyh, (0, Cp - C)).contiguous()
-                G = (gyh @ Wst.t()).view(N, H, F).contiguous()               # dL/dA
-                # {er, m, 1 / (den + 1e-16), <G, A>} per (row, head) in one pass (was: product + reduce + reciprocal + stack)
-                stats = torch.empty((N, H, 4), dtype=torch.float32, device=dev)
-                eng._check(eng.lib.ggl_gat_sh_stats(_ptr(er), _ptr(rowmax), _ptr(den), _ptr(G), _ptr(A), N, F, _ptr(stats),
-                                                    eng._stream(dev)))
-                z = torch.nn.functional.pad((x @ W).view(N, H, C), (0, Cp - C)).contiguous()
-                ger = torch.empty((N, H), dtype=torch.float32, device=dev)
-                gel = torch.empty((N, H), dtype=torch.float32, device=dev)
-                T = torch.empty((N, H, Cp), dtype=torch.float32, device=dev)
-                bwd = gp.bwd
-                # forward plan's partial: four doubles per hub chunk and head (the destination walk's row sums, round 6)
-                part_f, part_t = eng._gat_sh_partial(gp.fwd, 8, dev), eng._gat_sh_partial(bwd, Cp, dev)
-                cs, csT = gp.fwd.c_struct(part_f), bwd.c_struct(part_t)
-                posT = gp.posT if ctx.p_drop > 0 else None
-                eng._check(eng.lib.ggl_gat_sh_bwd(ctypes.byref(cs), _ptr(gp.col), ctypes.byref(csT), _ptr(gp.colT),
-                                                  _ptr(posT), _ptr(el), _ptr(x), F, _ptr(G), _ptr(stats), _ptr(z),
-                                                  _ptr(gyp), Cp, ctx.slope, ctx.p_drop, _ptr(ctx.rng_used), _ptr(ger),
-                                                  _ptr(T), _ptr(gel), eng._stream(dev)))
-                gx = torch.einsum("nhc,fhc->nf", T[:, :, :C], Wr) + gel @ U.t() + ger @ V.t()
-                # reductions over the N nodes: slab-split two-level sums (dense.wgrad), not one GEMM with an N-long accumulation per
-                # element (round 6: a tuned kernel choice for the latter left these 1e-3 from a float64 evaluation)
-                from .dense import wgrad
-
-                gU, gV = wgrad(x, gel), wgrad(x, ger)                       # x^T gel, x^T ger: [F, H]
-                gW = wgrad(A.view(N, H * F), gyh).view(H, F, C).permute(1, 0, 2) \
-                    + gU.unsqueeze(-1) * a_src + gV.unsqueeze(-1) * a_dst
-                gatt = torch.cat([torch.einsum("fh,fhc->hc", gU, Wr), torch.einsum("fh,fhc->hc", gV, Wr)], dim=-1)
-                return None, gx, gW.reshape(F, H * C), gatt.unsqueeze(0), None, None
-
-        self.GATHeadMean = GATHeadMean
-        class BlockMeanEpi(torch.autograd.Function):
-            """relu(mean_{j in block row i} x[j] + add_i + bias) over a sampler Block (static capacities,
-            device-side sizes): forward = the rectangular SpMM-mean with the epilogue in its store; backward
-            = the MEANBWD walk of the block's CSC, which is built on the device without a host read."""
-
-            @staticmethod
-            def forward(ctx, x, blk, add, bias, relu):
-                dev = x.device
-                K = int(x.shape[1])
-                if int(x.shape[0]) != blk.n_src_cap:
-                    raise RuntimeError(f"block expects {blk.n_src_cap} source rows, got {x.shape[0]}")
-                y = torch.empty((blk.n_dst_cap, K), dtype=torch.float32, device=dev)
-                b = bias.contiguous().reshape(-1) if bias is not None else None
-                a = add.contiguous() if add is not None else None
-                eng.spmm_epi_into(blk.plan, blk.col, None, x, y, mean=True, add=a, bias=b, relu=relu)
-                ctx.blk, ctx.has_add = blk, add is not None
-                ctx.epi = (relu, 0.0, None, None if bias is None else bias.shape)
-                ctx.save_for_backward(y)
-                return y
-
-            @staticmethod
-            def backward(ctx, g):
-                (y,) = ctx.saved_tensors
-                ga, gb = eng._epi_bwd(g, y, *ctx.epi)
-                gx = None
-                if ctx.needs_input_grad[0]:
-                    blk = ctx.blk
-                    planT, dstT = blk.transposed()
-                    gx, _ = eng._spmm_fwd("mean_bwd", planT, dstT, None, ga, blk.n_src_cap, aux=blk.rowptr)
-                return gx, None, (ga if ctx.has_add else None), gb, None
-
-        self.BlockMeanEpi = BlockMeanEpi
-        class SpMMRows(torch.autograd.Function):
-            """y[r] = sum_{j -> rows[r]} w x_j + bias for a sorted list of destination rows: the aggregate of a layer whose
-            consumer reads only those rows (the loss over the training nodes), on the restricted plan pair
-            (Engine.rows_plan).  Backward: gx = the transposed restricted walk over the compact [R, K] gradient, written
-            into a full [N_src, K] result; gbias = ggl_bias_grad_rows.  Same bits as spmm_epi(...)[rows] and its backward."""
-
-            @staticmethod
-            def forward(ctx, gp, w, x, rows, bias):
-                dev = x.device
-                K = int(x.shape[1])
-                rp = eng.rows_plan(gp, w, rows)
-                y = torch.empty((rp.R, K), dtype=torch.float32, device=dev)
-                b = bias.contiguous().reshape(-1) if bias is not None else None
-                eng.spmm_epi_into(rp.fwd, rp.col, rp.w_fwd, x, y, bias=b)
-                ctx.rp, ctx.bshape, ctx.K = rp, (None if bias is None else bias.shape), K
-                return y
-
-            @staticmethod
-            @once_differentiable
-            def backward(ctx, g):
-                rp, K = ctx.rp, ctx.K
-                g = g.contiguous()
-                dev = g.device
-                gb = None
-                if ctx.bshape is not None and ctx.needs_input_grad[4]:
-                    gb = torch.empty(K, dtype=torch.float32, device=dev)
-                    wsb = eng.lib.ggl_bias_act_bwd_workspace_bytes(rp.N_dst, K)
-                    ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=dev)
-                    eng._check(eng.lib.ggl_bias_grad_rows(_ptr(g), _ptr(rp.rows), rp.R, rp.N_dst, K, _ptr(gb), _ptr(ws), wsb,
-                                                          eng._stream(dev)))
-                    gb = gb.reshape(ctx.bshape)
-                gx = None
-                if ctx.needs_input_grad[2]:
-                    gx = torch.empty((rp.N_src, K), dtype=torch.float32, device=dev)
-                    eng.spmm_sum_into(rp.bwd, rp.colT, rp.w_bwd, g, gx)
-                return None, None, gx, None, gb
-
-        self.SpMMRows = SpMMRows
-        self.SpMMEpi, self.SegmentEpi = SpMMEpi, SegmentEpi
-        self.BiasAct = BiasAct
-        self.BiasAdd = BiasAdd
-        self.SegmentSum, self.SegmentMean, self.SegmentMax = SegmentSum, SegmentMean, SegmentMax
-        self.SegmentSoftmax = SegmentSoftmax
-        self.SpMMSum, self.SpMMMean, self.SpMMMax = SpMMSum, SpMMMean, SpMMMax
-        self.BSpMMSum, self.GATFused = BSpMMSum, GATFused
-
     # ---- the seven reference entry points (src/operators.cpp:51-59) + the fused GAT op ---------
     def _seg_args(self, x, index, N):
         self._dev(x, index)
@@ -1516,16 +722,16 @@ class Engine:
         return x.contiguous(), index, int(N)
 
     def c_segment_sum(self, x, index, N):
-        return self.SegmentSum.apply(*self._seg_args(x, index, N))
+        return autograd.SegmentSum.apply(self, *self._seg_args(x, index, N))
 
     def c_segment_mean(self, x, index, N):
-        return self.SegmentMean.apply(*self._seg_args(x, index, N))
+        return autograd.SegmentMean.apply(self, *self._seg_args(x, index, N))
 
     def c_segment_max(self, x, index, N):
-        return self.SegmentMax.apply(*self._seg_args(x, index, N))[0]
+        return autograd.SegmentMax.apply(self, *self._seg_args(x, index, N))[0]
 
     def segment_max_with_arg(self, x, index, N):
-        return self.SegmentMax.apply(*self._seg_args(x, index, N))
+        return autograd.SegmentMax.apply(self, *self._seg_args(x, index, N))
 
     def segment_softmax_supported(self, x):
         """Does the native edge softmax take `x` (f32, rows of a width the library has a kernel for)?"""
@@ -1539,9 +745,9 @@ class Engine:
         segment_reduce is for the sums)."""
         if isinstance(index, SegPlan):
             self._dev(x)
-            return self.SegmentSoftmax.apply(x.contiguous(), index)
+            return autograd.SegmentSoftmax.apply(self, x.contiguous(), index)
         x, index, N = self._seg_args(x, index, N)
-        return self.SegmentSoftmax.apply(x, self.seg_plan(index, N))
+        return autograd.SegmentSoftmax.apply(self, x, self.seg_plan(index, N))
 
     def _spmm_args(self, index, weight, x, x16=False):
         self._dev(index, weight, x)
@@ -1555,10 +761,10 @@ class Engine:
     def c_spmm_sum(self, index, weight, x, out_dtype=None):
         """c_spmm_sum of the reference for f32 x; bf16 / f16 x (an extension) is summed in f32 and returned in x's dtype,
         or unrounded with out_dtype=torch.float32."""
-        return self.SpMMSum.apply(*self._spmm_args(index, weight, x, True), self._out_dtype(x, out_dtype))
+        return autograd.SpMMSum.apply(self, *self._spmm_args(index, weight, x, True), self._out_dtype(x, out_dtype))
 
     def c_spmm_mean(self, index, weight, x, out_dtype=None):
-        return self.SpMMMean.apply(*self._spmm_args(index, weight, x, True), self._out_dtype(x, out_dtype))
+        return autograd.SpMMMean.apply(self, *self._spmm_args(index, weight, x, True), self._out_dtype(x, out_dtype))
 
     @staticmethod
     def _out_dtype(x, out_dtype):
@@ -1580,7 +786,7 @@ class Engine:
         return self._spmm_grad_w(gp, x.contiguous(), grad, mean)
 
     def c_spmm_max(self, index, weight, x):
-        return self.SpMMMax.apply(*self._spmm_args(index, weight, x))
+        return autograd.SpMMMax.apply(self, *self._spmm_args(index, weight, x))
 
     def c_bspmm_sum(self, index, weight, x):
         if x.dim() != 3:
@@ -1588,14 +794,18 @@ class Engine:
         gp, weight, x = self._spmm_args(index, weight, x)
         if weight is None or weight.dim() != 2 or weight.shape[1] != x.shape[1]:
             raise RuntimeError("bspmm expects weight of shape [num_edges, heads]")
+        return self._head_padded(gp, x, lambda xp: autograd.BSpMMSum.apply(self, gp, weight, xp.contiguous()))
+
+    def _head_padded(self, gp, x, apply):
+        """apply(x [N, H, C]) with the head width padded to `ggl_policy_head_channels` and the pad sliced off the result:
+        odd channel counts (41 classes per head: [N, H, 44]) get one zero-padded copy of x, which keeps the row walks and
+        the per-edge weight-gradient dots on 16-byte slices (Reddit-sized fused GAT, 8 x 41: forward 50 -> 20 ms); the pad
+        channels aggregate to zero and are dropped."""
         C = int(x.shape[2])
         Cp = int(self.lib.ggl_policy_head_channels(C, gp.E, int(x.shape[0])))
         if Cp != C:
-            # odd channel counts (41 classes per head ...): one zero-padded copy of x keeps the row walks and the
-            # per-edge weight-gradient dots on 16-byte slices; the pad channels sum to zero and are dropped
-            xp = torch.nn.functional.pad(x, (0, Cp - C))
-            return self.BSpMMSum.apply(gp, weight, xp.contiguous())[:, :, :C]
-        return self.BSpMMSum.apply(gp, weight, x)
+            return apply(torch.nn.functional.pad(x, (0, Cp - C)))[:, :, :C]
+        return apply(x)
 
     def gat_fused(self, index, el, er, x, negative_slope=0.2, num_nodes=None, dropout_rate=0.0, training=True,
                   out_dtype=None):
@@ -1613,17 +823,8 @@ class Engine:
         p = float(dropout_rate) if training else 0.0
         if not 0.0 <= p < 1.0:
             raise ValueError("dropout_rate must be in [0, 1)")
-        C = int(x.shape[2])
-        Cp = int(self.lib.ggl_policy_head_channels(C, gp.E, int(x.shape[0])))
-        if Cp != C:
-            # e.g. 41 classes per head: one zero-padded copy of x ([N,H,44]) keeps every walk on 16-byte slices
-            # (Reddit-sized, 8 x 41: forward 50 -> 20 ms); the pad channels aggregate to zero and are dropped
-            xp = torch.nn.functional.pad(x, (0, Cp - C))
-            out = self.GATFused.apply(gp, el.contiguous(), er.contiguous(), xp.contiguous(), negative_slope, p,
-                                      out_dtype)
-            return out[:, :, :C]
-        return self.GATFused.apply(gp, el.contiguous(), er.contiguous(), x.contiguous(),
-                                   negative_slope, p, out_dtype)
+        return self._head_padded(gp, x, lambda xp: autograd.GATFused.apply(
+            self, gp, el.contiguous(), er.contiguous(), xp.contiguous(), negative_slope, p, out_dtype))
 
     def _check_weight(self, weight, gp):
         """An edge-weight vector handed to a kernel as a raw pointer: f32 (spmm_sum_cpu.cpp:22 would raise
@@ -1643,12 +844,12 @@ class Engine:
         self._dev(x, weight)
         (self._check_f32 if reduce == "max" else self._check_f32_or_x16)("x", x)
         weight = self._check_weight(weight, gp)
-        fn = {"sum": self.SpMMSum, "mean": self.SpMMMean, "max": self.SpMMMax}[reduce]
+        fn = {"sum": autograd.SpMMSum, "mean": autograd.SpMMMean, "max": autograd.SpMMMax}[reduce]
         if reduce == "max":
             if out_dtype not in (None, x.dtype):
                 raise RuntimeError("spmm(max) returns x's dtype")
-            return fn.apply(gp, weight, x.contiguous())
-        return fn.apply(gp, weight, x.contiguous(), self._out_dtype(x, out_dtype))
+            return fn.apply(self, gp, weight, x.contiguous())
+        return fn.apply(self, gp, weight, x.contiguous(), self._out_dtype(x, out_dtype))
 
     def colsum(self, g):
         """out[k] = sum_r g[r, k] for a row-major f32 [N, K] matrix (deterministic two-stage kernel)."""
@@ -1664,7 +865,7 @@ class Engine:
 
     def bias_add(self, x, bias):
         """x + bias with the bias gradient computed by ggl_colsum_f32 (gcn_conv.py:105-106)."""
-        return self.BiasAdd.apply(x, bias)
+        return autograd.BiasAdd.apply(self, x, bias)
 
     def _rng_state(self, dev):
         """Device-resident Philox state {seed, offset} for the fused dropout, seeded from torch's RNG."""
@@ -1734,21 +935,13 @@ class Engine:
         self._dev(a, bias)
         self._check_f32("a", a)
         p = float(p_drop) if training else 0.0
-        return self.BiasAct.apply(a, bias, bool(relu), p)
+        return autograd.BiasAct.apply(self, a, bias, bool(relu), p)
 
     def spmm_bias_act(self, gp, weight, x, bias=None, relu=False, p_drop=0.0, training=True):
         """dropout(relu(A x + bias)) for a GraphPlan `gp` (what GCNConv + the model's ReLU/dropout compute,
         gcn_conv.py:78-108, models/gcn.py:55-59).  One kernel when the feature width is a multiple of 4
         (16-byte rows); otherwise the SpMM and the epilogue kernel run back to back — same values."""
-        self._dev(x, weight, bias)
-        self._check_f32("x", x)
-        weight = self._check_weight(weight, gp)
-        if bias is not None:
-            self._check_f32("bias", bias)
-        p = float(p_drop) if training else 0.0
-        if x.dim() == 2 and x.shape[1] % 4 == 0:
-            return self.SpMMEpi.apply(gp, weight, x.contiguous(), False, None, bias, bool(relu), p)
-        return self.BiasAct.apply(self.SpMMSum.apply(gp, weight, x.contiguous()), bias, bool(relu), p)
+        return self.spmm_epi(gp, weight, x, "sum", None, bias, relu, p_drop, training)
 
     def spmm_epi(self, gp, weight, x, reduce="sum", add=None, bias=None, relu=False, p_drop=0.0, training=True):
         """dropout(relu(reduce_{j->i} w x_j + add_i + bias)), reduce in {'sum', 'mean'}: one kernel for 16-byte
@@ -1763,11 +956,11 @@ class Engine:
             raise RuntimeError("add must be [destination rows, feature width]")
         p = float(p_drop) if training else 0.0
         if x.dim() == 2 and x.shape[1] % 4 == 0:
-            return self.SpMMEpi.apply(gp, weight, x.contiguous(), reduce == "mean", add, bias, bool(relu), p)
+            return autograd.SpMMEpi.apply(self, gp, weight, x.contiguous(), reduce == "mean", add, bias, bool(relu), p)
         out = self.spmm(gp, weight, x, reduce)
         if add is not None:
             out = out + add
-        return self.BiasAct.apply(out, bias, bool(relu), p)
+        return autograd.BiasAct.apply(self, out, bias, bool(relu), p)
 
     def segment_epi(self, msg, ids, N, reduce="mean", add=None, bias=None, relu=False):
         """relu(segment_{sum,mean}(msg, ids, N) + add + bias) for f32 messages [E, K] — one kernel."""
@@ -1781,7 +974,7 @@ class Engine:
                 self._check_f32(n, t)
         if add is not None and tuple(add.shape) != (N, msg.shape[1]):
             raise RuntimeError("add must be [num_segments, feature width]")
-        return self.SegmentEpi.apply(msg, ids, N, reduce == "mean", add, bias, bool(relu))
+        return autograd.SegmentEpi.apply(self, msg, ids, N, reduce == "mean", add, bias, bool(relu))
 
     def gat_headmean_supported(self, heads, in_channels, out_channels):
         return bool(self.gat_fast and self.lib.ggl_gat_sh_supported(int(heads), int(in_channels), int(out_channels)))
@@ -1797,13 +990,13 @@ class Engine:
             raise RuntimeError("gat_headmean runs on square graphs (every destination is also a source row)")
         gp = index if isinstance(index, GraphPlan) else self.graph_plan(index, n, n)
         p = float(dropout_rate) if training else 0.0
-        return self.GATHeadMean.apply(gp, x.contiguous(), W.contiguous(), att.contiguous(), negative_slope, p)
+        return autograd.GATHeadMean.apply(self, gp, x.contiguous(), W.contiguous(), att.contiguous(), negative_slope, p)
 
     def block_mean_epi(self, x, blk, add=None, bias=None, relu=False):
         """SAGEConv(mean) over a sampler Block: relu(mean of the sampled neighbours + add + bias), one kernel."""
         self._dev(x, add, bias)
         self._check_f32("x", x)
-        return self.BlockMeanEpi.apply(x.contiguous(), blk, add, bias, bool(relu))
+        return autograd.BlockMeanEpi.apply(self, x.contiguous(), blk, add, bias, bool(relu))
 
     def set_option(self, name, value):
         self._check(self.lib.ggl_set_option(name.encode(), int(value)))
@@ -1815,7 +1008,7 @@ class Engine:
         out = torch.empty((gp.N_dst,) + tuple(x.shape[1:]), dtype=torch.float32, device=dev)
         part = self._partial(gp.fwd, torch.float32, K, False, dev)
         cs = gp.fwd.c_struct(part)
-        if getattr(gp.fwd, "order_fn", None) is not None:
+        if gp.fwd.order_fn is not None:
             # a plan's row hand-out order is computed on its SECOND launch (SegPlan.c_struct); the kernel is timed the way a training
             # step runs it — on a plan that comes back.  (Round 6: with the step on torch.ops.ggl this engine's plan can arrive
             # here unused; without the order the products aggregate measured 23.7 instead of 13.5 ms.)

@@ -15,7 +15,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import engine as _engine
-from .ops import _ptr
+from ._lib import _ptr
+from .plans import SegPlan
 
 
 _BIG = 1 << 62
@@ -226,18 +227,13 @@ class Block:
     read, so the aggregate over it and its backward capture into a hipGraph."""
 
     def __init__(self, eng, rowptr, col, e_pos, counts, n_dst_cap, n_src_cap, fanout):
-        from .ops import SegPlan
-
         self.eng, self.rowptr, self.col, self.e_pos, self.counts = eng, rowptr, col, e_pos, counts
         self.n_dst_cap, self.n_src_cap, self.fanout = int(n_dst_cap), int(n_src_cap), int(fanout)
         self.e_cap = int(col.shape[0])
         self.size = (self.n_src_cap, self.n_dst_cap)           # EdgeIndex.size convention: (sources, targets)
-        p = SegPlan()
-        p.N, p.E, p.rowptr, p.perm, p.is_sorted = self.n_dst_cap, self.e_cap, rowptr, None, True
-        p.max_len, p.chunk, p.n_long, p.n_chunks = self.fanout, 1 << 62, 0, 0
-        p.long_rows = p.chunk_ptr = p.row_order = None
-        p.device, p.uid = rowptr.device, -1
-        self.plan = p
+        # no long-row table (its size would have to be read back) and no order_fn: the plan never gets a row order, so nothing
+        # is allocated while the step is captured into a hipGraph
+        self.plan = SegPlan(self.n_dst_cap, self.e_cap, rowptr, 1 << 62, self.fanout, rowptr.device)
         self._T = None
 
     def transposed(self):
@@ -245,8 +241,6 @@ class Block:
         device without a host read (ggl_block_transpose); hub sources are walked in one piece (no long-row table:
         its size would have to be read back)."""
         if self._T is None:
-            from .ops import SegPlan
-
             eng, dev = self.eng, self.rowptr.device
             rowptrT = torch.empty(self.n_src_cap + 1, dtype=torch.int64, device=dev)
             dstT = torch.empty(max(self.e_cap, 1), dtype=torch.int32, device=dev)
@@ -255,12 +249,7 @@ class Block:
             eng._check(eng.lib.ggl_block_transpose(_ptr(self.rowptr), _ptr(self.col), self.n_dst_cap, self.n_src_cap,
                                                    self.e_cap, _ptr(rowptrT), _ptr(dstT), _ptr(ws), wsb,
                                                    eng._stream(dev)))
-            p = SegPlan()
-            p.N, p.E, p.rowptr, p.perm, p.is_sorted = self.n_src_cap, self.e_cap, rowptrT, None, True
-            p.max_len, p.chunk, p.n_long, p.n_chunks = self.e_cap, 1 << 62, 0, 0
-            p.long_rows = p.chunk_ptr = p.row_order = None
-            p.device, p.uid = dev, -1
-            self._T = (p, dstT)
+            self._T = (SegPlan(self.n_src_cap, self.e_cap, rowptrT, 1 << 62, self.e_cap, dev), dstT)
         return self._T
 
 

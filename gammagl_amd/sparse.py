@@ -12,7 +12,7 @@ reference's argsort leaves them unspecified).
 import torch
 
 from . import engine as _engine
-from .ops import _ptr
+from ._lib import _ptr
 
 
 def ind2ptr(ind, M, eng=None):

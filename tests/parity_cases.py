@@ -1606,6 +1606,8 @@ def check_bspmm_gradw_sorted(eng, dev, oracle):
     to the thread-per-item kernel it replaces.  Graphs with empty rows, duplicate edges and a hub."""
     import numpy as np
 
+    from gammagl_amd import autograd
+
     rng = np.random.default_rng(21)
     names = (b"col_block_min_edges", b"col_block_min_degree")
     old = [eng.lib.ggl_get_option(n) for n in names]
@@ -1659,7 +1661,7 @@ def check_bspmm_gradw_sorted(eng, dev, oracle):
             res = []
             for plan in (gp, gp2):
                 wt, xt = ws.clone().requires_grad_(True), xs.clone().requires_grad_(True)
-                eng.BSpMMSum.apply(plan, wt, xt).backward(gos)
+                autograd.BSpMMSum.apply(eng, plan, wt, xt).backward(gos)
                 res.append((wt.grad, xt.grad))
             assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1]), (C2, sorted_walk)
         finally:

@@ -181,3 +181,83 @@ def test_dgnn_dropin_for_the_fused_gat_layer(tmp_path, oracle):
     import parity_cases as pc
 
     pc.check_dgnn_dropin(torch.device("cpu"), oracle, tmp_path)
+
+
+def _state_steps(eng, ei, w, x, xh, wh, s, a, b, gos):
+    """Forward then backward of four ops on `eng`, one step per call of next(): every tensor a leaf of this run alone.
+    Yields after each step; the last value is the dict of every result and gradient."""
+    w, x, xh, wh, s, a, b = (t.clone().requires_grad_(True) for t in (w, x, xh, wh, s, a, b))
+    ei = ei.clone()      # a fresh edge list: its plans are built by this run, on this engine
+    out = {}
+    out["mean"] = eng.spmm(eng.graph_plan(ei, x.shape[0]), w, x, "mean")
+    yield
+    out["bspmm"] = eng.c_bspmm_sum(ei, wh, xh)
+    yield
+    out["softmax"] = eng.segment_softmax(s, ei[1].contiguous(), x.shape[0])
+    yield
+    out["act"] = eng.bias_act(a, b, relu=True, p_drop=0.5)
+    yield
+    for (name, leaves), go in zip((("mean", (w, x)), ("bspmm", (wh, xh)), ("softmax", (s,)), ("act", (a, b))), gos):
+        out[name].backward(go)
+        for i, t in enumerate(leaves):
+            out[f"{name}_grad{i}"] = t.grad
+        yield
+    yield {k: v.detach().clone() for k, v in out.items()}
+
+
+def test_engines_share_no_state_through_the_shared_autograd_classes():
+    """The autograd Functions are module-level classes that take the engine as an argument: two engines with different
+    A/B switches, run step by step in turn on the same inputs, each give the bits they give alone, count their own plans,
+    cache plans that name them as their engine, and keep their own dropout counter."""
+    import gammagl_amd
+    from gammagl_amd import _lib
+    from gammagl_amd.ops import Engine
+
+    host = gammagl_amd.host_engine()
+    other = Engine(_lib.host_lib(), require_cuda=False, cpu_only=True)
+    other.gradw_sorted = other.mean_bwd_prescale = False
+    engines = (host, other)
+    N, E, K = 11, 60, 4
+    g = torch.Generator().manual_seed(11)
+    ei = torch.randint(0, N, (2, E), generator=g)
+    inputs = (ei, torch.rand(E, generator=g), torch.randn(N, K, generator=g), torch.randn(N, 2, K, generator=g),
+              torch.rand(E, 2, generator=g), torch.randn(E, K, generator=g), torch.randn(N, K, generator=g),
+              torch.randn(K, generator=g))
+    gos = [torch.randn(s, generator=g) for s in ((N, K), (N, 2, K), (E, K), (N, K))]
+    cpu = torch.device("cpu")
+    kept = {k: v.clone() for k, v in host._rng.items()}     # (the process-wide engine gets its dropout state back)
+    try:
+        with torch.random.fork_rng():
+            def reseed():
+                for e in engines:
+                    e._rng.clear()
+                    torch.manual_seed(7)
+                    e._rng_state(cpu)
+
+            def run(order):
+                """the steps of the engines in `order`, taken in turn: [(results, plans built)] per engine"""
+                before = [e.stats["plans_built"] for e in order]
+                its = [_state_steps(e, *inputs, gos) for e in order]
+                for _ in range(8):
+                    for it in its:
+                        next(it)
+                return [(next(it), e.stats["plans_built"] - b) for it, e, b in zip(its, order, before)]
+
+            reseed()
+            (alone, built_alone) = zip(*(run((e,))[0] for e in engines))
+            reseed()
+            (both, built_both) = zip(*run(engines))
+            assert built_alone[0] > 0 and list(built_both) == list(built_alone)
+            for e, want, got in zip(engines, alone, both):
+                assert set(got) == set(want) and len(got) == 11
+                for k in want:
+                    assert torch.equal(got[k], want[k]), (k, e is host)
+                assert all(val.engine is e for _, val, _, _ in e.graph_cache.d.values())
+            # a draw on one engine moves its own counter only
+            at = [int(e._rng_state(cpu)[1]) for e in engines]
+            host.bias_act(inputs[6], None, p_drop=0.5)
+            assert [int(e._rng_state(cpu)[1]) for e in engines] == [at[0] + 1, at[1]]
+            other.bias_act(inputs[6], None, p_drop=0.5)
+            assert [int(e._rng_state(cpu)[1]) for e in engines] == [at[0] + 1, at[1] + 1]
+    finally:
+        host._rng = kept

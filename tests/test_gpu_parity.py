@@ -156,6 +156,17 @@ def test_plan_cache(eng, dev):
     pc.check_plan_cache(eng, dev)
 
 
+def test_every_plan_hands_the_kernels_what_it_did(eng, dev):
+    """the launch struct of every kind of plan (tests/plan_structs.py) built from cuda tensors: the recorded lines"""
+    import os
+
+    import plan_structs
+
+    want = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan_structs.txt")).read().splitlines()
+    got = plan_structs.table(eng, dev)
+    assert len(got) == len(want) == 48 and not [(g, w) for g, w in zip(got, want) if g != w]
+
+
 def test_engines_never_take_the_other_devices_tensors(eng, dev):
     """The MI355X engine refuses CPU tensors and the host build refuses GPU tensors: nothing is moved between devices
     behind the caller's back, and a GPU tensor's result can only ever come from the HIP library."""
