@@ -118,6 +118,10 @@ SIGNATURES = {
     "ggl_bias_act_bwd": (c_int, [_V, _V, c_int64, c_int64, c_int, c_float, _V, _V, _V, _V, c_size_t, _V]),
     "ggl_spmm_epi_ex": (c_int, [_P, _V, _V, c_int, _V, c_int64, c_int64, _V, c_int64, c_int, c_int, _V, c_int64,
                                 _V, c_int, c_float, _V, c_int64, c_int64, c_int, _V]),
+    "ggl_spmm_epi_x16": (c_int, [_P, _V, _V, c_int, c_int, _V, c_int64, c_int64, c_int, _V, c_int64, c_int, _V, c_int64,
+                                 _V, c_int, c_float, _V, c_int64, c_int64, c_int, _V]),
+    "ggl_bias_act_fwd_x16": (c_int, [c_int, _V, _V, c_int64, c_int64, c_int, c_float, _V, _V, _V]),
+    "ggl_bias_act_bwd_x16": (c_int, [c_int, _V, _V, c_int64, c_int64, c_int, c_float, _V, _V, _V, _V, c_size_t, _V]),
     "ggl_segment_epi": (c_int, [_V, _P, c_int64, c_int, _V, c_int64, _V, c_int, c_float, _V, _V, _V]),
     "ggl_gat_fused_fwd": (c_int, [_P, _V, _V, _V, _V, c_float, c_int64, c_int64, c_float, _V, _V, _V, _V, _V]),
     "ggl_gat_partial_bytes": (c_size_t, [c_int64, c_int64, c_int64]),

@@ -313,14 +313,17 @@ class BiasAct(torch.autograd.Function):
 class SpMMEpi(torch.autograd.Function):
     """y = dropout(relu(reduce(A x) + add + bias)), reduce = sum | mean, in ONE kernel (ggl_spmm_epi_ex):
     GCNConv's "+ bias" (gcn_conv.py:105-106) and SAGEConv's "mean + fc_self(x_dst) + bias -> act"
-    (sage_conv.py:100-108) applied to each finished row in registers."""
+    (sage_conv.py:100-108) applied to each finished row in registers.  bf16 / f16 x and add (ggl_spmm_epi_x16): the same f32
+    operations, y rounded once to x's dtype (or f32 with out_dtype); the backward is the f32 one step by step on the stored
+    values — ga and gx in x's dtype, gbias and gw f32."""
 
     @staticmethod
-    def forward(ctx, eng, gp, w, x, mean, add, bias, relu, p_drop):
+    def forward(ctx, eng, gp, w, x, mean, add, bias, relu, p_drop, out_dtype=None):
         ctx.eng = eng
         dev = x.device
         K = int(x.shape[1])
-        y = torch.empty((gp.N_dst, K), dtype=torch.float32, device=dev)
+        y = torch.empty((gp.N_dst, K), dtype=out_dtype or x.dtype, device=dev)
+        ctx.x_dtype = x.dtype
         rng, rng_used = eng._draw(dev, p_drop)
         b, a = _flat(bias, add)
         eng.spmm_epi_into(gp.fwd, gp.col, w, x, y, mean=mean, add=a, bias=b, relu=relu, p_drop=p_drop, rng=rng)
@@ -339,10 +342,11 @@ class SpMMEpi(torch.autograd.Function):
         gp = ctx.gp
         gx = gw = None
         if ctx.needs_input_grad[3]:
-            gx = eng._spmm_bwd_x(gp, ctx.w, ga, torch.float32, ctx.mean)
+            gx = eng._spmm_bwd_x(gp, ctx.w, ga, ctx.x_dtype, ctx.mean)
         if ctx.want_gw:
             gw = eng._spmm_grad_w(gp, ctx.saved_tensors[1], ga, ctx.mean).view(ctx.w.shape)
-        return None, None, gw, gx, None, (ga if ctx.has_add else None), gb, None, None
+        gadd = (ga if ga.dtype == ctx.x_dtype else ga.to(ctx.x_dtype)) if ctx.has_add else None
+        return None, None, gw, gx, None, gadd, gb, None, None, None
 
 
 class SegmentEpi(torch.autograd.Function):

@@ -15,16 +15,35 @@
 
 namespace ggl {
 
-template <int VEC> __device__ __forceinline__ void ldv(const float *__restrict__ p, float (&t)[VEC]) {
-  if (VEC == 4) {
+// T = float, or mxbf16_t / mxf16_t (common.hpp): 16-bit STORAGE of a / y / g / ga, widened at the load, every operation the
+// f32 one, one rounding at the store (ggl_bias_act_{fwd,bwd}_x16).  Four columns per lane either way — an 8-byte access at
+// 16 bits — so the row-to-partial geometry, and with it every bit of gbias, is the f32 kernel's.
+struct alignas(8) H4 { uint16_t v[4]; };
+template <typename T, int VEC> __device__ __forceinline__ void ldv(const typename TT<T>::S *__restrict__ p, float (&t)[VEC]) {
+  if constexpr (!std::is_same<T, float>::value) {
+    if (VEC == 4) {
+      const H4 v = *reinterpret_cast<const H4 *>(p);   // global_load_dwordx2
+      t[0] = TT<T>::load(v.v[0]); t[1 % VEC] = TT<T>::load(v.v[1]); t[2 % VEC] = TT<T>::load(v.v[2]); t[3 % VEC] = TT<T>::load(v.v[3]);
+    } else {
+      t[0] = TT<T>::load(p[0]);
+    }
+  } else if (VEC == 4) {
     const float4 v = *reinterpret_cast<const float4 *>(p);
     t[0] = v.x; t[1 % VEC] = v.y; t[2 % VEC] = v.z; t[3 % VEC] = v.w;
   } else {
     t[0] = p[0];
   }
 }
-template <int VEC> __device__ __forceinline__ void stv(float *__restrict__ p, const float (&t)[VEC]) {
-  if (VEC == 4) {
+template <typename T, int VEC> __device__ __forceinline__ void stv(typename TT<T>::S *__restrict__ p, const float (&t)[VEC]) {
+  if constexpr (!std::is_same<T, float>::value) {
+    if (VEC == 4) {
+      H4 o;
+      o.v[0] = TT<T>::store(t[0]); o.v[1] = TT<T>::store(t[1 % VEC]); o.v[2] = TT<T>::store(t[2 % VEC]); o.v[3] = TT<T>::store(t[3 % VEC]);
+      *reinterpret_cast<H4 *>(p) = o;
+    } else {
+      p[0] = TT<T>::store(t[0]);
+    }
+  } else if (VEC == 4) {
     float4 o;
     o.x = t[0]; o.y = t[1 % VEC]; o.z = t[2 % VEC]; o.w = t[3 % VEC];
     *reinterpret_cast<float4 *>(p) = o;
@@ -36,11 +55,11 @@ constexpr int kRowUnroll = 4;  // rows in flight per lane: the loads of 4 rows a
 
 // Threads of a block are `groups` groups of `kp` lanes; a lane owns VEC consecutive columns (loaded once
 // from bias), a group walks rows r0 + j, + groups, ...  Random word for vector (r, c): Philox(r * KV + c).
-template <int VEC>
-__global__ __launch_bounds__(kBlock) void bias_act_fwd_kernel(const float *__restrict__ a,
+template <typename T, int VEC>
+__global__ __launch_bounds__(kBlock) void bias_act_fwd_kernel(const typename TT<T>::S *__restrict__ a,
                                                               const float *__restrict__ bias,
                                                               const int64_t *__restrict__ rng,
-                                                              float *__restrict__ y, int64_t N, int64_t K,
+                                                              typename TT<T>::S *__restrict__ y, int64_t N, int64_t K,
                                                               int64_t nblocks, int64_t rows_per_block, int kp,
                                                               int groups,
                                                               int relu, uint32_t drop_thresh, float scale) {
@@ -74,19 +93,19 @@ __global__ __launch_bounds__(kBlock) void bias_act_fwd_kernel(const float *__res
         if (drop_thresh) v = (rw[i] >= drop_thresh) ? __fmul_rn(v, scale) : 0.0f;  // keep with prob 1 - p
         t[i] = v;
       }
-      stv<VEC>(y + r * K + c * VEC, t);
+      stv<T, VEC>(y + r * K + c * VEC, t);
     };
     int64_t r = r0 + j;
     for (; r + (int64_t)(kRowUnroll - 1) * groups < r1; r += (int64_t)kRowUnroll * groups) {
       float t[kRowUnroll][VEC];
 #pragma unroll
-      for (int u = 0; u < kRowUnroll; ++u) ldv<VEC>(a + (r + (int64_t)u * groups) * K + c * VEC, t[u]);
+      for (int u = 0; u < kRowUnroll; ++u) ldv<T, VEC>(a + (r + (int64_t)u * groups) * K + c * VEC, t[u]);
 #pragma unroll
       for (int u = 0; u < kRowUnroll; ++u) finish(r + (int64_t)u * groups, t[u]);
     }
     for (; r < r1; r += groups) {
       float t[VEC];
-      ldv<VEC>(a + r * K + c * VEC, t);
+      ldv<T, VEC>(a + r * K + c * VEC, t);
       finish(r, t);
     }
   }
@@ -99,10 +118,10 @@ __global__ void rng_advance_kernel(int64_t *rng, int64_t inc) {
 // backward + first stage of the bias gradient.  Same thread geometry as the forward; every lane keeps a
 // running column sum of the ga values it produces and writes it to partial[(block * groups + j), :];
 // ggl_colsum_f32 (backward.hip) then reduces the [P, K] partial matrix.
-template <int VEC, int MASKED>
-__global__ __launch_bounds__(kBlock) void bias_act_bwd_kernel(const float *__restrict__ g,
-                                                              const float *__restrict__ y,
-                                                              float *__restrict__ ga, int64_t N,
+template <typename T, int VEC, int MASKED>
+__global__ __launch_bounds__(kBlock) void bias_act_bwd_kernel(const typename TT<T>::S *__restrict__ g,
+                                                              const typename TT<T>::S *__restrict__ y,
+                                                              typename TT<T>::S *__restrict__ ga, int64_t N,
                                                               int64_t K, int64_t nblocks,
                                                               int64_t rows_per_block, int kp,
                                                               int groups, float scale,
@@ -139,15 +158,15 @@ __global__ __launch_bounds__(kBlock) void bias_act_bwd_kernel(const float *__res
         else if (masked == 3) gv[i] = (rw[i] >= drop_thresh) ? __fmul_rn(gv[i], scale) : 0.0f;
         acc[i] = __fadd_rn(acc[i], gv[i]);  // rows in ascending order, unrolled or not
       }
-      stv<VEC>(ga + r * K + c * VEC, gv);
+      stv<T, VEC>(ga + r * K + c * VEC, gv);
     };
     int64_t r = r0 + j;
     for (; r + (int64_t)(kRowUnroll - 1) * groups < r1; r += (int64_t)kRowUnroll * groups) {
       float gv[kRowUnroll][VEC], yv[kRowUnroll][VEC];
 #pragma unroll
       for (int u = 0; u < kRowUnroll; ++u) {
-        ldv<VEC>(g + (r + (int64_t)u * groups) * K + c * VEC, gv[u]);
-        if (MASKED == 1 || MASKED == 2) ldv<VEC>(y + (r + (int64_t)u * groups) * K + c * VEC, yv[u]);
+        ldv<T, VEC>(g + (r + (int64_t)u * groups) * K + c * VEC, gv[u]);
+        if (MASKED == 1 || MASKED == 2) ldv<T, VEC>(y + (r + (int64_t)u * groups) * K + c * VEC, yv[u]);
         else yv[u][0] = 0.0f;
       }
 #pragma unroll
@@ -155,8 +174,8 @@ __global__ __launch_bounds__(kBlock) void bias_act_bwd_kernel(const float *__res
     }
     for (; r < r1; r += groups) {
       float gv[VEC], yv[VEC];
-      ldv<VEC>(g + r * K + c * VEC, gv);
-      if (MASKED == 1 || MASKED == 2) ldv<VEC>(y + r * K + c * VEC, yv);
+      ldv<T, VEC>(g + r * K + c * VEC, gv);
+      if (MASKED == 1 || MASKED == 2) ldv<T, VEC>(y + r * K + c * VEC, yv);
       else yv[0] = 0.0f;
       finish(r, gv, yv);
     }
@@ -206,7 +225,7 @@ __global__ __launch_bounds__(kBlock) void bias_grad_rows_kernel(const float *__r
       if (r >= r1) break;
       if ((int)(r - r0) % groups != j) continue;   // (r - r0 < rows_per_block: fits an int)
       float gv[4];
-      ldv<4>(g + i * K + c * 4, gv);
+      ldv<float, 4>(g + i * K + c * 4, gv);
 #pragma unroll
       for (int k = 0; k < 4; ++k) acc[k] = __fadd_rn(acc[k], gv[k]);
     }
@@ -225,8 +244,14 @@ int rng_advance(int64_t *rng_state, void *stream) {
 
 using namespace ggl;
 
-extern "C" int ggl_bias_act_fwd(const float *a, const float *bias, int64_t N, int64_t K, int relu,
-                                float p_drop, int64_t *rng_state, float *y, void *stream) {
+// the 4-column lanes' accesses: 16 bytes of f32, 8 bytes of 16-bit storage
+template <typename T> static inline bool aligned_v4(const void *p) {
+  return (reinterpret_cast<uintptr_t>(p) & (4 * sizeof(typename TT<T>::S) - 1)) == 0;
+}
+
+template <typename T>
+static int bias_act_fwd(const typename TT<T>::S *a, const float *bias, int64_t N, int64_t K, int relu, float p_drop,
+                        int64_t *rng_state, typename TT<T>::S *y, void *stream) {
   GGL_REQUIRE(N >= 0 && K >= 0 && p_drop >= 0.0f && p_drop < 1.0f, GGL_EINVAL, "bad arguments");
   const int64_t total = N * K;
   if (total == 0) return GGL_OK;
@@ -237,19 +262,40 @@ extern "C" int ggl_bias_act_fwd(const float *a, const float *bias, int64_t N, in
   float scale;
   dropout_params(p_drop, &thresh, &scale);
   hipStream_t s = as_stream(stream);
-  const bool vec4 = (K % 4 == 0) && aligned16(a) && aligned16(y);
+  const bool vec4 = (K % 4 == 0) && aligned_v4<T>(a) && aligned_v4<T>(y);
   int kp, groups;
   int64_t grid, rpb;
   geometry(N, K, vec4, &kp, &groups, &grid, &rpb);
   if (vec4)
-    GGL_LAUNCH((bias_act_fwd_kernel<4>), grid, kBlock, s, a, bias, (const int64_t *)rng_state, y, N, K, grid, rpb,
+    GGL_LAUNCH((bias_act_fwd_kernel<T, 4>), grid, kBlock, s, a, bias, (const int64_t *)rng_state, y, N, K, grid, rpb,
                kp, groups, relu, thresh, scale);
   else
-    GGL_LAUNCH((bias_act_fwd_kernel<1>), grid, kBlock, s, a, bias, (const int64_t *)rng_state, y, N, K, grid, rpb,
+    GGL_LAUNCH((bias_act_fwd_kernel<T, 1>), grid, kBlock, s, a, bias, (const int64_t *)rng_state, y, N, K, grid, rpb,
                kp, groups, relu, thresh, scale);
   GGL_LAUNCH_CHECK();
   if (thresh) return rng_advance(rng_state, stream);
   return GGL_OK;
+}
+
+extern "C" int ggl_bias_act_fwd(const float *a, const float *bias, int64_t N, int64_t K, int relu,
+                                float p_drop, int64_t *rng_state, float *y, void *stream) {
+  return bias_act_fwd<float>(a, bias, N, K, relu, p_drop, rng_state, y, stream);
+}
+
+static int x16_dtype_ok(int dtype, const char *what) {
+  if (dtype == GGL_F16 || dtype == GGL_BF16) return GGL_OK;
+  set_error("x16: %s must be f16 or bf16 (got dtype code %d)", what, dtype);
+  return GGL_EDTYPE;
+}
+
+// y16 == ggl_bias_act_fwd(a16.float(), ...).to(dtype): same words, same state motion, one rounding at the store
+extern "C" int ggl_bias_act_fwd_x16(int dtype, const void *a, const float *bias, int64_t N, int64_t K, int relu,
+                                    float p_drop, int64_t *rng_state, void *y, void *stream) {
+  if (int rc = x16_dtype_ok(dtype, "a / y")) return rc;
+  const uint16_t *a16 = static_cast<const uint16_t *>(a);
+  uint16_t *y16 = static_cast<uint16_t *>(y);
+  return dtype == GGL_BF16 ? bias_act_fwd<mxbf16_t>(a16, bias, N, K, relu, p_drop, rng_state, y16, stream)
+                           : bias_act_fwd<mxf16_t>(a16, bias, N, K, relu, p_drop, rng_state, y16, stream);
 }
 
 static inline size_t bwd_partial_bytes(int64_t N, int64_t K) {
@@ -267,9 +313,10 @@ extern "C" size_t ggl_bias_act_bwd_workspace_bytes(int64_t N, int64_t K) {
   return part + ggl_colsum_workspace_bytes((int64_t)(part / sizeof(float) / (size_t)(K > 0 ? K : 1)), K);
 }
 
-extern "C" int ggl_bias_act_bwd(const float *g, const float *y, int64_t N, int64_t K, int relu,
-                                float p_drop, const int64_t *rng_used, float *ga, float *gbias,
-                                void *workspace, size_t workspace_bytes, void *stream) {
+template <typename T>
+static int bias_act_bwd(const typename TT<T>::S *g, const typename TT<T>::S *y, int64_t N, int64_t K, int relu,
+                        float p_drop, const int64_t *rng_used, typename TT<T>::S *ga, float *gbias,
+                        void *workspace, size_t workspace_bytes, void *stream) {
   GGL_REQUIRE(N >= 0 && K >= 0 && p_drop >= 0.0f && p_drop < 1.0f, GGL_EINVAL, "bad arguments");
   if (K == 0) return GGL_OK;
   GGL_REQUIRE((g && ga) || N == 0, GGL_EINVAL, "NULL pointer");
@@ -287,14 +334,14 @@ extern "C" int ggl_bias_act_bwd(const float *g, const float *y, int64_t N, int64
   GGL_REQUIRE(!masked || masked == 3 || y || N == 0, GGL_EINVAL, "y is needed to rebuild the ReLU/dropout mask");
   GGL_REQUIRE(!gbias || (workspace && workspace_bytes >= ggl_bias_act_bwd_workspace_bytes(N, K)),
               GGL_EWORKSPACE, "bias_act_bwd workspace too small");
-  const bool vec4 = (K % 4 == 0) && aligned16(g) && aligned16(ga) && (!masked || masked == 3 || aligned16(y));
+  const bool vec4 = (K % 4 == 0) && aligned_v4<T>(g) && aligned_v4<T>(ga) && (!masked || masked == 3 || aligned_v4<T>(y));
   int kp, groups;
   int64_t blocks, rpb;
   geometry(N, K, vec4, &kp, &groups, &blocks, &rpb);
   hipStream_t s = as_stream(stream);
   float *partial = gbias ? static_cast<float *>(workspace) : nullptr;
 #define GGL_BAB(V, M)                                                                                    \
-  GGL_LAUNCH((bias_act_bwd_kernel<V, M>), blocks, kBlock, s, g, y, ga, N, K, blocks, rpb, kp, groups, scale, \
+  GGL_LAUNCH((bias_act_bwd_kernel<T, V, M>), blocks, kBlock, s, g, y, ga, N, K, blocks, rpb, kp, groups, scale, \
              redraw ? rng_used : nullptr, thresh, partial)
   if (vec4) {
     if (masked == 0) GGL_BAB(4, 0); else if (masked == 1) GGL_BAB(4, 1); else if (masked == 2) GGL_BAB(4, 2); else GGL_BAB(4, 3);
@@ -309,6 +356,26 @@ extern "C" int ggl_bias_act_bwd(const float *g, const float *y, int64_t N, int64
                           workspace_bytes - part, stream);
   }
   return GGL_OK;
+}
+
+extern "C" int ggl_bias_act_bwd(const float *g, const float *y, int64_t N, int64_t K, int relu,
+                                float p_drop, const int64_t *rng_used, float *ga, float *gbias,
+                                void *workspace, size_t workspace_bytes, void *stream) {
+  return bias_act_bwd<float>(g, y, N, K, relu, p_drop, rng_used, ga, gbias, workspace, workspace_bytes, stream);
+}
+
+// ga16 == ggl_bias_act_bwd(g16.float(), y16.float(), ...).ga.to(dtype); gbias is that call's, on the bits: the column sums
+// add the f32 values before they are rounded, in the same geometry, and ggl_colsum_f32 finishes them.  The ReLU mask is read
+// off the stored y16 > 0.  Workspace: ggl_bias_act_bwd_workspace_bytes(N, K).
+extern "C" int ggl_bias_act_bwd_x16(int dtype, const void *g, const void *y, int64_t N, int64_t K, int relu, float p_drop,
+                                    const int64_t *rng_used, void *ga, float *gbias, void *workspace,
+                                    size_t workspace_bytes, void *stream) {
+  if (int rc = x16_dtype_ok(dtype, "g / y / ga")) return rc;
+  const uint16_t *g16 = static_cast<const uint16_t *>(g), *y16 = static_cast<const uint16_t *>(y);
+  uint16_t *ga16 = static_cast<uint16_t *>(ga);
+  return dtype == GGL_BF16
+             ? bias_act_bwd<mxbf16_t>(g16, y16, N, K, relu, p_drop, rng_used, ga16, gbias, workspace, workspace_bytes, stream)
+             : bias_act_bwd<mxf16_t>(g16, y16, N, K, relu, p_drop, rng_used, ga16, gbias, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ggl_bias_grad_rows(const float *g, const int64_t *rows, int64_t R, int64_t N, int64_t K, float *gbias,

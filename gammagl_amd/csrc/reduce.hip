@@ -98,7 +98,7 @@ template <typename S> struct RPtrs {
   const int64_t *__restrict__ aux_arg;
   const float *__restrict__ epi_bias;
   const int64_t *__restrict__ epi_rng;
-  const float *__restrict__ epi_add;
+  const S *__restrict__ epi_add;   // (x's storage type: 16-bit beside 16-bit rows, widened at the add)
 };
 
 // ---- VEC-wide loads / stores of storage elements ------------------------------------------------
@@ -401,34 +401,49 @@ __device__ __forceinline__ void seed_acc(const ReduceDims &d, const typename TO<
 // The epilogue's own operands (bias, the per-row `add` term), requested BEFORE the row is walked: read in
 // finish_row they were one more dependent round trip at the end of every row — 7 % of a 13-batch row (measured on
 // the 64-column-block launches of the products-sized K = 256 aggregate: 3.65 ms plain, 3.93 ms with a bias).
-template <int VEC> struct EpiPre {
-  float b[VEC], a[VEC];
-  uint32_t rw[4];   // the row's dropout words: ALU work that can run under the walk's memory latency instead of after it
+// A 16-byte lane of 16-bit rows owns EIGHT columns = two Philox vectors (or eight single-word draws).  Held across the walk
+// with 8 bias + 8 add values they cost it 12-40 registers (the plain 16-bit walk: 64-74, 6-8 wavefronts; with the operands
+// prefetched 78-96, 5-6 wavefronts, and the ragged form 109-115 with 20 bytes of scratch), so for VEC = 8 the same requests
+// are made AFTER the walk (epi_late): the walk keeps the plain walk's registers and the row pays one round trip at its end.
+template <typename S, int VEC> struct EpiPre {
+  float b[VEC];
+  S a[VEC];
+  uint32_t rw[VEC > 4 ? VEC : 4];   // the row's dropout words: ALU work that can run under the walk's memory latency instead of after it
 };
+constexpr bool epi_late(int vec) { return vec > 4; }
+// the dropout words of the VEC columns from full-row column kg on (epi_vec = 4: kg is a multiple of 4)
+template <int VEC, bool RAG>
+__device__ __forceinline__ void epi_words(const int64_t *__restrict__ rng, const ReduceDims &d, int64_t row, int64_t kg, int nv,
+                                          uint32_t (&rw)[VEC > 4 ? VEC : 4]) {
+#pragma unroll
+  for (int i = 0; i < (VEC > 4 ? VEC : 4); ++i) rw[i] = 0xffffffffu;
+  if (!d.epi_thresh) return;
+  const int64_t ev = d.epi_vec;
+  const int sh = ev == 4 ? 2 : 0;                       // ev is 1 or 4
+  const int64_t KV = (d.epi_K + ev - 1) >> sh;
+  if (VEC > 1 && ev == 1 && (RAG || VEC > 4)) {  // one Philox word per ELEMENT (epi_K % 4 != 0): component x of its own draw
+#pragma unroll
+    for (int i = 0; i < VEC; ++i)
+      rw[i] = i < nv ? philox4x32_10((uint64_t)(row * KV + kg + i), (uint64_t)rng[1], (uint64_t)rng[0]).x : 0xffffffffu;
+  } else {
+#pragma unroll
+    for (int v = 0; v < (VEC > 4 ? VEC / 4 : 1); ++v) {
+      const U4 u = philox4x32_10((uint64_t)(row * KV + (kg >> sh) + v), (uint64_t)rng[1], (uint64_t)rng[0]);
+      rw[4 * v] = u.x; rw[4 * v + 1] = u.y; rw[4 * v + 2] = u.z; rw[4 * v + 3] = u.w;
+    }
+  }
+}
 template <typename T, int VEC, int MODE, bool RAG>
 __device__ __forceinline__ void epi_prefetch(const RPtrs<typename TT<T>::S> &q, const ReduceDims &d, int64_t row,
-                                             int64_t kk, EpiPre<VEC> &pre) {
+                                             int64_t kk, EpiPre<typename TT<T>::S, VEC> &pre) {
   if (!epi_mode(MODE)) return;
+  using S = typename TT<T>::S;
   const int nv = valid_lanes<VEC, RAG>(d.K, kk);
 #pragma unroll
   for (int i = 0; i < VEC; ++i) pre.b[i] = (q.epi_bias && (!RAG || i < nv)) ? q.epi_bias[kk + i] : 0.0f;
-  if (q.epi_add) RowIO<float, VEC, RAG>::load(q.epi_add + row * d.add_ld + kk, pre.a, nv);
-  pre.rw[0] = pre.rw[1] = pre.rw[2] = pre.rw[3] = 0xffffffffu;
-  if (d.epi_thresh) {
-    const int64_t ev = d.epi_vec;
-    const int64_t kg = d.epi_col0 + kk;  // column of acc[0] in the full epi_K-wide row
-    const int sh = ev == 4 ? 2 : 0;                       // ev is 1 or 4
-    const int64_t KV = (d.epi_K + ev - 1) >> sh;
-    if (RAG && VEC > 1 && ev == 1) {  // one Philox word per ELEMENT (epi_K % 4 != 0): component x of its own draw
-#pragma unroll
-      for (int i = 0; i < (VEC < 4 ? VEC : 4); ++i)
-        pre.rw[i] = i < nv ? philox4x32_10((uint64_t)(row * KV + kg + i), (uint64_t)q.epi_rng[1], (uint64_t)q.epi_rng[0]).x
-                           : 0xffffffffu;
-    } else {
-      const U4 u = philox4x32_10((uint64_t)(row * KV + (kg >> sh)), (uint64_t)q.epi_rng[1], (uint64_t)q.epi_rng[0]);
-      pre.rw[0] = u.x; pre.rw[1] = u.y; pre.rw[2] = u.z; pre.rw[3] = u.w;
-    }
-  }
+  if (q.epi_add) RowIO<S, VEC, RAG>::load(q.epi_add + row * d.add_ld + kk, pre.a, nv);
+  // (column of acc[0] in the full epi_K-wide row: epi_col0 + kk)
+  epi_words<VEC, RAG>(q.epi_rng, d, row, d.epi_col0 + kk, nv, pre.rw);
 }
 
 // mean / store epilogue of a finished row
@@ -437,7 +452,7 @@ __device__ __forceinline__ void finish_row(const RPtrs<typename TT<T>::S> &q, co
                                            typename TO<T>::O *__restrict__ out,
                                            int64_t *__restrict__ argout, int64_t K, int64_t row,
                                            int64_t len, int64_t kk, typename TT<T>::A (&acc)[VEC],
-                                           const argreg_t (&arg)[VEC], const EpiPre<VEC> &pre) {
+                                           const argreg_t (&arg)[VEC], const EpiPre<typename TT<T>::S, VEC> &pre) {
   using O = typename TO<T>::O;
   const int nv = valid_lanes<VEC, RAG>(K, kk);
   if (OP == OP_MEAN) {
@@ -457,14 +472,15 @@ __device__ __forceinline__ void finish_row(const RPtrs<typename TT<T>::S> &q, co
     }
   }
   if (epi_mode(MODE)) {
-    const uint32_t (&rw)[4] = pre.rw;
     const int64_t ev = d.epi_vec;
     const int64_t kg = d.epi_col0 + kk;  // column of acc[0] in the full epi_K-wide row
-    const bool own_words = RAG && VEC > 1 && ev == 1;
+    const uint32_t (&rw)[VEC > 4 ? VEC : 4] = pre.rw;
+    // a word per element (own draws, or the two vectors of an eight-column lane), else the element's component of the one vector
+    const bool own_words = VEC > 4 || (RAG && VEC > 1 && ev == 1);
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
       float v = (float)acc[i];
-      if (q.epi_add) v = __fadd_rn(v, pre.a[i]);
+      if (q.epi_add) v = __fadd_rn(v, (float)TT<T>::load(pre.a[i]));
       if (q.epi_bias && (!RAG || i < nv)) v = __fadd_rn(v, pre.b[i]);
       if (d.epi_relu) v = (v < 0.0f) ? 0.0f : v;
       if (d.epi_thresh) v = (rw[own_words ? i : (int)((kg + i) & (ev - 1))] >= d.epi_thresh) ? __fmul_rn(v, d.epi_scale) : 0.0f;
@@ -487,7 +503,7 @@ __device__ __forceinline__ void finish_row(const RPtrs<typename TT<T>::S> &q, co
       const float *__restrict__ w, const int64_t *__restrict__ rowptr,                             \
       const int64_t *__restrict__ aux_rowptr, const int64_t *__restrict__ aux_arg,                 \
       const float *__restrict__ epi_bias, const int64_t *__restrict__ epi_rng,                      \
-      const float *__restrict__ epi_add
+      const S *__restrict__ epi_add
 #define GGL_RPTR_PACK(S) RPtrs<S> q{x, perm, col, w, rowptr, aux_rowptr, aux_arg, epi_bias, epi_rng, epi_add}
 
 // ---- the one launch: chunks of long rows first, then every row with len <= chunk -----------------
@@ -585,9 +601,10 @@ __global__ __launch_bounds__(kBlock) GGL_RR_WAVES(T, VEC, OP, U, RAG) void row_r
     argreg_t arg[VEC];
     init_acc<T, VEC, OP>(acc, arg, d.arg_fill);
     seed_acc<T, VEC, OP, RAG>(d, out, row, kk, acc);
-    EpiPre<VEC> pre;
-    epi_prefetch<T, VEC, MODE, RAG>(q, d, row, kk, pre);
+    EpiPre<S, VEC> pre;
+    if (!epi_late(VEC)) epi_prefetch<T, VEC, MODE, RAG>(q, d, row, kk, pre);
     reduce_range<T, VEC, OP, MODE, IDX, U, RAG>(q, d, row, beg, end, kk, acc, arg);
+    if (epi_late(VEC)) epi_prefetch<T, VEC, MODE, RAG>(q, d, row, kk, pre);
     finish_row<T, VEC, OP, MODE, RAG>(q, d, out, argout, d.K, row, len, kk, acc, arg, pre);
   }
 }
@@ -602,7 +619,7 @@ __global__ __launch_bounds__(kBlock) void long_final_kernel(const int64_t *__res
                                                             int64_t *__restrict__ argout,
                                                             const float *__restrict__ epi_bias,
                                                             const int64_t *__restrict__ epi_rng,
-                                                            const float *__restrict__ epi_add,
+                                                            const typename TT<T>::S *__restrict__ epi_add,
                                                             const ReduceDims d) {
   using A = typename TT<T>::A;
   RPtrs<typename TT<T>::S> q{};
@@ -630,7 +647,7 @@ __global__ __launch_bounds__(kBlock) void long_final_kernel(const int64_t *__res
         acc[0] = TT<T>::add(acc[0], v);
       }
     }
-    EpiPre<1> pre;
+    EpiPre<typename TT<T>::S, 1> pre;
     epi_prefetch<T, 1, MODE, false>(q, d, row, k, pre);
     finish_row<T, 1, OP, MODE>(q, d, out, argout, d.K, row, len, k, acc, arg, pre);
   }
@@ -668,7 +685,7 @@ struct ReduceArgs {  // host-side bundle: everything one logical op needs
   int epi_relu;
   uint32_t epi_thresh;
   float epi_scale;
-  const float *epi_add;
+  const void *epi_add;     // x's storage type
   int64_t add_ld;
   int64_t epi_K, epi_col0; // 0 / 0 = the launch covers whole rows
   // column-block launches whose hub rows are walked ONCE per aggregate (launch_f32_cols): 0 = the whole op (hub walk, row
@@ -686,7 +703,7 @@ static inline int pow2_ceil_log2(int64_t v) {
 }
 
 #define GGL_RPTR_ARGS(S)                                                                           \
-  static_cast<const S *>(a.x), a.perm, a.col, a.w, a.rowptr, a.aux_rowptr, a.aux_arg, a.epi_bias, a.epi_rng, a.epi_add
+  static_cast<const S *>(a.x), a.perm, a.col, a.w, a.rowptr, a.aux_rowptr, a.aux_arg, a.epi_bias, a.epi_rng, static_cast<const S *>(a.epi_add)
 
 // f32 sums whose long rows are reduced in the reference's serial order instead of chunk by chunk (hubf32.hip): every
 // mode whose value is "an element, times its weight" — segment sum / mean, SpMM sum / mean, bspmm, with or without the
@@ -694,7 +711,7 @@ static inline int pow2_ceil_log2(int64_t v) {
 template <typename T, int OP, int MODE> constexpr bool exact_long_mode() {
   return OP != OP_MAX && ((std::is_same<T, float>::value && (seg_like(MODE) || spmm_like(MODE) || MODE == MODE_BSPMM)) ||
                           (std::is_same<T, double>::value && (MODE == MODE_SEG)) ||
-                          (mx_code<T>::value != 0 && MODE == MODE_SPMM));   // 16-bit storage, f32 sums: the f32 walk's conditions
+                          (mx_code<T>::value != 0 && spmm_like(MODE)));   // 16-bit storage, f32 sums: the f32 walk's conditions
 }
 
 // ... and whether this launch takes it (positions travel as int32 in the hub kernel's registers, like the plan's own perm
@@ -805,7 +822,7 @@ static int launch_idx(const ReduceArgs &a_in, ReduceDims d, hipStream_t stream) 
   if (a.n_long > 0) {
     GGL_LAUNCH((long_final_kernel<T, OP, MODE>), a.n_long, kBlock, stream, a.rowptr, a.long_rows,
                a.chunk_ptr, static_cast<const P *>(a.partial), (const int64_t *)a.partial_arg, out,
-               a.arg, a.epi_bias, a.epi_rng, a.epi_add, d);
+               a.arg, a.epi_bias, a.epi_rng, static_cast<const S *>(a.epi_add), d);
     GGL_LAUNCH_CHECK();
   }
   return GGL_OK;
@@ -968,7 +985,7 @@ static int launch_f32_cols(const ReduceArgs &a0, hipStream_t stream) {
       [&](ReduceArgs &a, int64_t c0) {   // the epilogue's operands follow the block; its dropout word stays the full-width one
         if (a0.epi_bias) a.epi_bias = a0.epi_bias + c0;
         if (a0.epi_add) {
-          a.epi_add = a0.epi_add + c0;
+          a.epi_add = static_cast<const float *>(a0.epi_add) + c0;
           a.add_ld = a0.add_ld > 0 ? a0.add_ld : a0.K;
         }
         a.epi_K = a0.epi_K > 0 ? a0.epi_K : a0.K;
@@ -1049,10 +1066,14 @@ static int launch_seg(int dtype, const ReduceArgs &a, hipStream_t stream) {
 // wherever the f32 op itself is the serial sum.  A lane moves 16 bytes = EIGHT columns and keeps eight f32 sums.
 template <typename T, int OP, int MODE>
 static int launch_x16_typed(const ReduceArgs &a, hipStream_t stream) {
-  constexpr bool kStatic = MODE == MODE_SPMM;
+  constexpr bool kStatic = spmm_like(MODE);
+  // the epilogue's `add` rows move with the same 16-byte accesses; its dropout words assume a lane starts on a multiple of 4
+  // columns of the full row wherever words come four to a draw (epi_K % 4 == 0)
+  const bool add_wide = !a.epi_add || (aligned16(a.epi_add) && a.add_ld % 8 == 0);
+  const bool col_ok = MODE != MODE_SPMM_EPI || a.epi_col0 % 4 == 0 || (a.epi_K > 0 ? a.epi_K : a.K) % 4 != 0;
   // (rows of <= 8 columns: one element per lane, as the 16-bit segment sums do — eight per lane would leave one lane per row)
-  if (wide_ok(a, 8) && a.K > 8) return launch_typed<T, 8, OP, MODE, kStatic>(a, stream);
-  if (ragged16_ok<OP>(a)) return launch_typed<T, 8, OP, MODE, false, true>(a, stream);
+  if (wide_ok(a, 8) && a.K > 8 && add_wide && col_ok) return launch_typed<T, 8, OP, MODE, kStatic>(a, stream);
+  if (ragged16_ok<OP>(a) && col_ok) return launch_typed<T, 8, OP, MODE, false, true>(a, stream);
   return launch_typed<T, 1, OP, MODE, false>(a, stream);
 }
 template <int OP, int MODE>
@@ -1083,17 +1104,28 @@ extern "C" int64_t ggl_spmm_col_blocks_x16(const ggl_segplan_t *plan, int64_t K)
   return bw > 0 ? (K + bw - 1) / bw : 1;
 }
 
-template <int OP>
+template <int OP, int MODE = MODE_SPMM>
 static int launch_x16_cols(int xd, int od, const ReduceArgs &a0, hipStream_t stream) {
+  static_assert(MODE == MODE_SPMM || MODE == MODE_SPMM_EPI, "column blocks: sum / mean SpMM only");
   const int64_t bw = col_block_width16(a0.E, a0.K, a0.N);
-  if (bw <= 0 || a0.N <= 0) return launch_x16<OP, MODE_SPMM>(xd, od, a0, stream);
+  if (bw <= 0 || a0.N <= 0) return launch_x16<OP, MODE>(xd, od, a0, stream);
   // (the conditions of the exact walk are the same for both 16-bit types; the hub args are made per type)
   return launch_col_blocks(
-      a0, bw, sizeof(uint16_t), dtype_size(od), hub_once(a0, exact_long_applies<mxbf16_t, OP, MODE_SPMM>(a0)),
+      a0, bw, sizeof(uint16_t), dtype_size(od), hub_once(a0, exact_long_applies<mxbf16_t, OP, MODE>(a0)),
       [&](int64_t x_ld) {
-        return xd == GGL_BF16 ? hub_args_of<mxbf16_t, MODE_SPMM>(a0, x_ld) : hub_args_of<mxf16_t, MODE_SPMM>(a0, x_ld);
+        return xd == GGL_BF16 ? hub_args_of<mxbf16_t, MODE>(a0, x_ld) : hub_args_of<mxf16_t, MODE>(a0, x_ld);
       },
-      [](ReduceArgs &, int64_t) {}, [&](const ReduceArgs &a) { return launch_x16<OP, MODE_SPMM>(xd, od, a, stream); }, stream);
+      [&](ReduceArgs &a, int64_t c0) {   // as launch_f32_cols: bias (f32) and add (2 bytes per column) follow the block
+        if (MODE != MODE_SPMM_EPI) return;
+        if (a0.epi_bias) a.epi_bias = a0.epi_bias + c0;
+        if (a0.epi_add) {
+          a.epi_add = static_cast<const uint16_t *>(a0.epi_add) + c0;
+          a.add_ld = a0.add_ld > 0 ? a0.add_ld : a0.K;
+        }
+        a.epi_K = a0.epi_K > 0 ? a0.epi_K : a0.K;
+        a.epi_col0 = a0.epi_col0 + c0;
+      },
+      [&](const ReduceArgs &a) { return launch_x16<OP, MODE>(xd, od, a, stream); }, stream);
 }
 
 static int fill_plan(ReduceArgs &a, const ggl_segplan_t *plan, int dtype, int64_t K, bool with_arg) {
@@ -1226,7 +1258,7 @@ extern "C" int ggl_spmm_sum_ex(const ggl_segplan_t *plan, const int32_t *col, co
 }
 
 // the epilogue both fused entries below apply (each checks its own row strides first)
-static int fill_epilogue(ReduceArgs &a, const float *add, int64_t add_ld, const float *bias, int relu, float p_drop,
+static int fill_epilogue(ReduceArgs &a, const void *add, int64_t add_ld, const float *bias, int relu, float p_drop,
                          int64_t *rng_state) {
   GGL_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, GGL_EINVAL, "p_drop must be in [0, 1)");
   GGL_REQUIRE(p_drop == 0.0f || rng_state, GGL_EINVAL, "dropout needs an rng_state");
@@ -1362,6 +1394,28 @@ extern "C" int ggl_spmm_mean_x16(const ggl_segplan_t *plan, const int32_t *col, 
   int rc = spmm16_common(a, plan, col, w, w_by_pos, x_dtype, x, x_ld, K, out_dtype, out, out_ld);
   if (rc) return rc;
   return launch_x16_cols<OP_MEAN>(x_dtype, out_dtype, a, as_stream(stream));
+}
+
+// ggl_spmm_epi_ex on 16-bit rows: the sum (or mean), + add, + bias, ReLU and the dropout scale in f32 in finish_row's order,
+// ONE rounding at the store (none with out_dtype = GGL_F32); the mask and the rng state's motion are the f32 entry's.
+// `add` has x's dtype.  No accumulate: adding onto a rounded partial result would round twice.
+extern "C" int ggl_spmm_epi_x16(const ggl_segplan_t *plan, const int32_t *col, const float *w, int w_by_pos, int x_dtype,
+                                const void *x, int64_t x_ld, int64_t K, int out_dtype, void *out, int64_t out_ld, int mean,
+                                const void *add, int64_t add_ld, const float *bias, int relu, float p_drop, int64_t *rng_state,
+                                int64_t epi_K, int64_t epi_col0, int advance_rng, void *stream) {
+  ReduceArgs a{};
+  int rc = spmm16_common(a, plan, col, w, w_by_pos, x_dtype, x, x_ld, K, out_dtype, out, out_ld);
+  if (rc) return rc;
+  GGL_REQUIRE(add_ld == 0 || add_ld >= K, GGL_EINVAL, "row stride < K");
+  rc = fill_epilogue(a, add, add_ld, bias, relu, p_drop, rng_state);
+  if (rc) return rc;
+  GGL_REQUIRE(epi_col0 >= 0 && (epi_K == 0 || epi_col0 + K <= epi_K), GGL_EINVAL, "column block outside the row");
+  a.epi_K = epi_K; a.epi_col0 = epi_col0;
+  rc = !mean ? launch_x16_cols<OP_SUM, MODE_SPMM_EPI>(x_dtype, out_dtype, a, as_stream(stream))
+             : launch_x16_cols<OP_MEAN, MODE_SPMM_EPI>(x_dtype, out_dtype, a, as_stream(stream));
+  if (rc) return rc;
+  if (a.epi_thresh && advance_rng && plan->N > 0 && K > 0) return rng_advance(rng_state, stream);
+  return GGL_OK;
 }
 
 // gx[src] += g[dst] / count[dst] * w, divide and multiply in f32 as ggl_spmm_mean_bwd makes them, on a 16-bit g

@@ -72,7 +72,8 @@ using torch::autograd::variable_list;
   X(ggl_segment_softmax_supported) X(ggl_segment_softmax_partial_bytes) X(ggl_segment_softmax_fwd) X(ggl_segment_softmax_bwd) \
   X(ggl_policy_softmax_sublanes) X(ggl_spmm_sum_x16) X(ggl_spmm_mean_x16) X(ggl_spmm_mean_bwd_x16)                    \
   X(ggl_plan_rows_workspace_bytes) X(ggl_plan_rows_rank) X(ggl_plan_rows_fwd_rowptr) X(ggl_plan_rows_fwd_fill)        \
-  X(ggl_plan_rows_bwd_rowptr) X(ggl_plan_rows_bwd_fill) X(ggl_bias_grad_rows)
+  X(ggl_plan_rows_bwd_rowptr) X(ggl_plan_rows_bwd_fill) X(ggl_bias_grad_rows)                                          \
+  X(ggl_spmm_epi_x16) X(ggl_bias_act_fwd_x16) X(ggl_bias_act_bwd_x16)
 
 struct Api {
   void *handle = nullptr;
@@ -1219,10 +1220,11 @@ static std::tuple<Tensor, Tensor, Tensor> gat_csr_backward_kernel(const Tensor &
 }
 
 // y = dropout(relu(a + bias))                                                      (gcn_conv.py:105-106, models/gcn.py:55-59)
+// a may be STORED as f16 / bf16 (ggl_bias_act_*_x16: the f32 operations and words, y rounded once); bias and gbias stay f32
 static std::tuple<Tensor, Tensor> bias_act_forward_kernel(const Tensor &a_, const OptT_ &bias, bool relu, double p) {
   Tensor a = a_.contiguous(), b = opt(bias);
   same_device({&a, &b});
-  f32("a", a);
+  if (!is_x16(a)) f32("a", a);
   TORCH_CHECK(p >= 0.0 && p < 1.0, "p_drop must be in [0, 1)");
   c10::OptionalDeviceGuard guard(a.device());
   const Api &api = api_for(a.device());
@@ -1234,8 +1236,12 @@ static std::tuple<Tensor, Tensor> bias_act_forward_kernel(const Tensor &a_, cons
   }
   Tensor y = at::empty_like(a);
   const Draw d = draw(a.device(), p);
-  check(api, api.ggl_bias_act_fwd(a.data_ptr<float>(), b.defined() ? b.data_ptr<float>() : nullptr, N, K, relu ? 1 : 0,
-                                  static_cast<float>(p), d.ptr(), y.data_ptr<float>(), stream_of(a.device())));
+  if (is_x16(a))
+    check(api, api.ggl_bias_act_fwd_x16(dtype_code(a), a.data_ptr(), b.defined() ? b.data_ptr<float>() : nullptr, N, K,
+                                        relu ? 1 : 0, static_cast<float>(p), d.ptr(), y.data_ptr(), stream_of(a.device())));
+  else
+    check(api, api.ggl_bias_act_fwd(a.data_ptr<float>(), b.defined() ? b.data_ptr<float>() : nullptr, N, K, relu ? 1 : 0,
+                                    static_cast<float>(p), d.ptr(), y.data_ptr<float>(), stream_of(a.device())));
   return {y, d.used};
 }
 // (ga, gbias): the mask is rebuilt from y, the bias gradient reduced in the same pass (epilogue.hip)
@@ -1246,28 +1252,45 @@ static std::tuple<Tensor, Tensor> bias_act_backward_kernel(const Tensor &g_, con
   const Api &api = api_for(g.device());
   const int64_t N = g.dim() > 0 ? g.size(0) : 1, K = N > 0 ? g.numel() / N : width_of(g.sizes());
   if (!relu && p <= 0 && !has_bias) return {g, Tensor()};
-  Tensor ga = at::empty_like(g), gb = has_bias ? at::empty({K}, g.options()) : Tensor();
+  if (!is_x16(g)) f32("grad", g);
+  TORCH_CHECK(g.scalar_type() == y.scalar_type(), "expected scalar type Float: the gradient (", g.scalar_type(),
+              ") must have the output's dtype (", y.scalar_type(), ")");
+  const auto f32o = g.options().dtype(at::kFloat);
+  Tensor ga = at::empty_like(g), gb = has_bias ? at::empty({K}, f32o) : Tensor();
   const size_t wsb = api.ggl_bias_act_bwd_workspace_bytes(N, K);
   Tensor ws = at::empty({static_cast<int64_t>(std::max<size_t>(wsb, 4))}, g.options().dtype(at::kByte));
-  check(api, api.ggl_bias_act_bwd(g.data_ptr<float>(), y.data_ptr<float>(), N, K, relu ? 1 : 0, static_cast<float>(p),
-                                  used_ptr(p, rng_used), ga.data_ptr<float>(), gb.defined() ? gb.data_ptr<float>() : nullptr,
-                                  ws.data_ptr(), wsb, stream_of(g.device())));
-  return {ga, gb.defined() ? gb : at::empty({0}, g.options())};
+  Tensor yc = y.contiguous();
+  if (is_x16(g))
+    check(api, api.ggl_bias_act_bwd_x16(dtype_code(g), g.data_ptr(), yc.data_ptr(), N, K, relu ? 1 : 0, static_cast<float>(p),
+                                        used_ptr(p, rng_used), ga.data_ptr(), gb.defined() ? gb.data_ptr<float>() : nullptr,
+                                        ws.data_ptr(), wsb, stream_of(g.device())));
+  else
+    check(api, api.ggl_bias_act_bwd(g.data_ptr<float>(), yc.data_ptr<float>(), N, K, relu ? 1 : 0, static_cast<float>(p),
+                                    used_ptr(p, rng_used), ga.data_ptr<float>(), gb.defined() ? gb.data_ptr<float>() : nullptr,
+                                    ws.data_ptr(), wsb, stream_of(g.device())));
+  return {ga, gb.defined() ? gb : at::empty({0}, f32o)};
 }
 
-// y = dropout(relu(reduce_{j -> i} w x_j + add_i + bias)) in ONE kernel (reduce.hip MODE_SPMM_EPI): 2-D x, K % 4 == 0
+// y = dropout(relu(reduce_{j -> i} w x_j + add_i + bias)) in ONE kernel (reduce.hip MODE_SPMM_EPI): 2-D x, K % 4 == 0.
+// x (and add) may be STORED as f16 / bf16: ggl_spmm_epi_x16, any width, the f32 operations, y rounded once to x's dtype.
 static std::tuple<Tensor, Tensor> spmm_epi_forward_kernel(const Tensor &index, const OptT_ &weight, const Tensor &x, bool mean,
                                                           const OptT_ &add_, const OptT_ &bias_, bool relu, double p) {
   c10::OptionalDeviceGuard guard(x.device());
-  SpArgs s = spmm_args(index, weight, x);
+  SpArgs s = spmm_args(index, weight, x, true);
   Tensor add = opt(add_), bias = opt(bias_);
   same_device({&x, &add, &bias});
-  TORCH_CHECK(s.x.dim() == 2 && s.x.size(1) % 4 == 0, "spmm_epi_forward needs a 2-D x whose width is a multiple of 4");
+  const bool x16 = is_x16(s.x);
+  TORCH_CHECK(s.x.dim() == 2 && (x16 || s.x.size(1) % 4 == 0), "spmm_epi_forward needs a 2-D x whose width is a multiple of 4");
   TORCH_CHECK(p >= 0.0 && p < 1.0, "p_drop must be in [0, 1)");
   const Api &a = api_for(x.device());
   const int64_t K = s.x.size(1);
   if (add.defined()) {
-    f32("add", add);
+    if (x16) {
+      TORCH_CHECK(add.scalar_type() == s.x.scalar_type(), "expected scalar type Float (add in x's dtype, ", s.x.scalar_type(),
+                  ") but found ", add.scalar_type(), " (add)");
+    } else {
+      f32("add", add);
+    }
     TORCH_CHECK(add.dim() == 2 && add.size(0) == s.gp->N_dst && add.size(1) == K, "add must be [destination rows, feature width]");
     add = add.contiguous();
   }
@@ -1278,11 +1301,25 @@ static std::tuple<Tensor, Tensor> spmm_epi_forward_kernel(const Tensor &index, c
   }
   const SegPlan &p_ = *s.gp->fwd;
   Tensor y = at::empty({s.gp->N_dst, K}, s.x.options());
-  Tensor part = partial_for(a, p_, s.x, K, false);
+  Tensor part;
+  if (x16) {   // f32 partials, as spmm_fwd16's
+    if (p_.n_long > 0)
+      part = at::empty({static_cast<int64_t>(a.ggl_partial_bytes(GGL_F32, p_.n_chunks, K, 0)) + 16}, s.x.options().dtype(at::kByte));
+  } else {
+    part = partial_for(a, p_, s.x, K, false);
+  }
   ggl_segplan_t cs = p_.c(part);
   Tensor keep;
   auto [wp, by_pos] = weights_for(a, *s.gp, p_, s.w, keep);
   const Draw d = draw(x.device(), p);
+  if (x16) {
+    const int xc = dtype_code(s.x);
+    check(a, a.ggl_spmm_epi_x16(&cs, s.gp->col.data_ptr<int32_t>(), wp, by_pos, xc, s.x.data_ptr(), K, K, xc, y.data_ptr(), K,
+                                mean ? 1 : 0, add.defined() ? add.data_ptr() : nullptr, add.defined() ? K : 0,
+                                bias.defined() ? bias.data_ptr<float>() : nullptr, relu ? 1 : 0, static_cast<float>(p), d.ptr(),
+                                0, 0, 1, stream_of(x.device())));
+    return {y, d.used};
+  }
   check(a, a.ggl_spmm_epi_ex(&cs, s.gp->col.data_ptr<int32_t>(), wp, by_pos, s.x.data_ptr<float>(), K, K, y.data_ptr<float>(),
                              K, 0, mean ? 1 : 0, add.defined() ? add.data_ptr<float>() : nullptr, add.defined() ? K : 0,
                              bias.defined() ? bias.data_ptr<float>() : nullptr, relu ? 1 : 0, static_cast<float>(p),
@@ -1831,7 +1868,7 @@ struct SpMMEpiFn : public torch::autograd::Function<SpMMEpiFn> {
 // one kernel for 16-byte rows; the reduce op followed by the adds and the epilogue pass otherwise (same values)
 static Tensor spmm_epi_autograd(const Tensor &index, const OptT_ &weight, const Tensor &x, bool mean, const OptT_ &add,
                                 const OptT_ &bias, bool relu, double p) {
-  if (x.dim() == 2 && x.size(1) % 4 == 0) return SpMMEpiFn::apply(index, weight, x, mean, add, bias, relu, p);
+  if (x.dim() == 2 && (x.size(1) % 4 == 0 || is_x16(x))) return SpMMEpiFn::apply(index, weight, x, mean, add, bias, relu, p);
   Tensor out = mean ? spmm_mean_autograd(index, weight, x) : spmm_sum_autograd(index, weight, x);
   if (opt(add).defined()) out = out + *add;
   return BiasActFn::apply(out, bias, relu, p);
@@ -1979,7 +2016,7 @@ static std::tuple<Tensor, Tensor> bias_fwd_meta(const Tensor &a, const OptT_ &, 
 }
 static std::tuple<Tensor, Tensor> bias_bwd_meta(const Tensor &g, const Tensor &, bool hb, bool, double, const Tensor &) {
   const int64_t N = g.dim() > 0 ? g.size(0) : 1;
-  return {at::empty_like(g), at::empty({hb && N > 0 ? g.numel() / N : 0}, g.options())};
+  return {at::empty_like(g), at::empty({hb && N > 0 ? g.numel() / N : 0}, g.options().dtype(at::kFloat))};
 }
 static Tensor bias_meta(const Tensor &a, const OptT_ &, bool, double) { return at::empty_like(a); }
 static std::tuple<Tensor, Tensor> epi_fwd_meta(const Tensor &, const OptT_ &, const Tensor &x, bool, const OptT_ &, const OptT_ &,

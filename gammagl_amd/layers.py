@@ -141,7 +141,16 @@ class MessagePassing(nn.Module):
 CACHE_GCN_NORM = True    # False: every GCNConv.forward recomputes its normalisation, as the reference does (bench.py's side figure)
 
 
+_X16 = (torch.bfloat16, torch.float16)
+
+
 class GCNConv(MessagePassing):
+    # bf16 / f16 activations (torch.autocast): True = "+ bias", ReLU and dropout ride on the mixed-precision aggregate's
+    # store (Engine.spmm_epi on 16-bit rows: every step in f32, ONE rounding, the library's Philox dropout).  Off for a
+    # bare layer, which keeps the composition "aggregate, round, + bias.to(dtype), relu, dropout" in torch; GCNModel
+    # switches it on for its layers.
+    fuse_epilogue16 = False
+
     def __init__(self, in_channels, out_channels, norm='both', add_bias=True):
         super().__init__()
         if norm not in ['left', 'right', 'none', 'both']:
@@ -214,11 +223,18 @@ class GCNConv(MessagePassing):
             eng = _engine(x)
             out = eng.spmm_bias_act(eng.graph_plan(edge_index, num_nodes), weights, x, bias, relu=relu,
                                     p_drop=p_drop, training=training)
+        elif (self.fuse_epilogue16 and x.dim() == 2 and x.dtype in _X16
+              and (bias is None or bias.dtype == torch.float32)):
+            # bf16 / f16 activations (torch.autocast) with the fused form on: the f32 bias, ReLU and dropout applied to the
+            # f32 sums in registers, one rounding at the aggregate's only store
+            eng = _engine(x)
+            out = eng.spmm_epi(eng.graph_plan(edge_index, num_nodes), weights, x, "sum", None, bias, relu=relu,
+                               p_drop=p_drop, training=training)
         else:
             out = self.propagate(x, edge_index, edge_weight=weights, num_nodes=num_nodes)
             if out.dtype != torch.float32:
-                # bf16 / f16 activations (torch.autocast): the mixed-precision aggregate (f32 sums, rounded once), then the
-                # epilogue in torch — bias_act is f32 only
+                # bf16 / f16 activations (torch.autocast), the bare layer: the mixed-precision aggregate (f32 sums, rounded
+                # once), then the epilogue in torch, each step rounding again (fuse_epilogue16 = True fuses it)
                 out = out + bias.to(out.dtype) if bias is not None else out
                 out = torch.relu(out) if relu else out
                 out = torch.nn.functional.dropout(out, p_drop, training) if p_drop > 0 else out
@@ -293,15 +309,20 @@ class SAGEConv(MessagePassing):
                 return out
             src_feat = self.fc_neigh(src_feat)
             big = edge.shape[1] >= FUSED_MIN_EDGES
+            # bf16 / f16 rows (torch.autocast) take the fused SpMM-mean whatever the edge count and width: it sums in f32
+            # and rounds once, where the segment route would sum in the storage type (the rule of propagate())
+            x16 = src_feat.dtype in _X16 and (self.bias is None or self.bias.dtype == torch.float32)
             # (a small block whose width is not a multiple of 4 — e.g. the 47-class output layer — has no fused form:
             # it goes straight to propagate() below without computing fc_self / the gather here first and again there)
-            if (SAGE_FUSE_EPILOGUE and src_feat.dim() == 2 and src_feat.dtype == torch.float32 and fused_act
-                    and (big or src_feat.shape[1] % 4 == 0)):
+            if (SAGE_FUSE_EPILOGUE and src_feat.dim() == 2 and fused_act
+                    and ((src_feat.dtype == torch.float32 and (big or src_feat.shape[1] % 4 == 0)) or x16)):
                 # "mean + fc_self(x_dst) + bias -> act" (sage_conv.py:100-108) rides on the aggregate's store:
                 # the fused rectangular SpMM-mean for big edge lists, the segment route for sampled blocks
                 eng = _engine(src_feat)
                 self_term = self.fc_self(dst_feat)
-                if big:
+                if x16 and self_term.dtype != src_feat.dtype:
+                    self_term = self_term.to(src_feat.dtype)
+                if big or x16:
                     gp = eng.graph_plan(edge, num_nodes, int(src_feat.shape[0]))
                     return eng.spmm_epi(gp, None, src_feat, "mean", add=self_term, bias=self.bias,
                                         relu=self.act is not None)
@@ -417,7 +438,9 @@ class FusedGATConv(GATConv):
 class GCNModel(nn.Module):
     """models/gcn.py:30-64."""
 
-    def __init__(self, feature_dim, hidden_dim, num_class, drop_rate=0.2, num_layers=2, norm='both'):
+    def __init__(self, feature_dim, hidden_dim, num_class, drop_rate=0.2, num_layers=2, norm='both', fuse_epilogue16=True):
+        """`fuse_epilogue16`: under torch.autocast the layers apply bias, ReLU and dropout in the 16-bit aggregate's store
+        (GCNConv.fuse_epilogue16); False keeps the torch composition after the aggregate.  No effect on f32 activations."""
         super().__init__()
         self.num_layers = num_layers
         if num_layers == 1:
@@ -428,6 +451,8 @@ class GCNModel(nn.Module):
                 self.conv.append(GCNConv(hidden_dim, hidden_dim, norm=norm))
             self.conv.append(GCNConv(hidden_dim, num_class, norm=norm))
         self.dropout = nn.Dropout(drop_rate)
+        for conv in self.conv:
+            conv.fuse_epilogue16 = bool(fuse_epilogue16)
 
     def forward(self, x, edge_index, edge_weight, num_nodes):
         if self.num_layers == 1:

@@ -100,6 +100,8 @@ def gspmm(index, weight=None, x=None, reduce='sum'):
     (what a preceding Linear produces under ``torch.autocast``).  Every product and add is then made in f32, in the f32
     op's order, and the result is rounded once to x's dtype: ``gspmm(i, w, x16) == gspmm(i, w, x16.float()).to(x16.dtype)``
     bit for bit; the gradient w.r.t. x follows the same rule.  ``weight`` stays f32.  'max' and ``bspmm`` are f32 only.
+    (The layer epilogue on such rows — f32 bias, ReLU, dropout, one rounding at the aggregate's store — is ``Engine.spmm_epi`` /
+    ``torch.ops.ggl.spmm_epi``; nothing here applies it in torch.)
 
     A second extension: 'sum' and 'mean' differentiate with respect to ``weight`` (the reference's extension returns no
     weight gradient, gspmm.cpp:79).  ``weight.grad[e] = sum_k x[src_e, k] * g[dst_e, k]`` — for 'mean' with ``g`` divided

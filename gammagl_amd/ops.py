@@ -453,9 +453,10 @@ class Engine:
         return gx
 
     @staticmethod
-    def _row_stride(t, what):
-        if t.dim() != 2 or t.stride(1) != 1 or t.dtype != torch.float32:
-            raise RuntimeError(f"{what} must be a 2-D f32 matrix with unit column stride (a column block is fine)")
+    def _row_stride(t, what, dtype=torch.float32):
+        if t.dim() != 2 or t.stride(1) != 1 or t.dtype != dtype:
+            raise RuntimeError(f"{what} must be a 2-D {'f32' if dtype == torch.float32 else dtype} matrix with unit "
+                               "column stride (a column block is fine)")
         return int(t.stride(0))
 
     def spmm_sum_into(self, plan, col, w, x, out, accumulate=False):
@@ -487,7 +488,8 @@ class Engine:
     def spmm_epi_into(self, plan, col, w, x, out, accumulate=False, mean=False, add=None, bias=None, relu=False,
                       p_drop=0.0, rng=None, epi_K=0, col0=0, advance_rng=True):
         """out = dropout(relu(reduce(A x) (+ out) + add + bias)) on column blocks, no autograd — ggl_spmm_epi_ex.
-        `bias` [>= col0 + K] is the full-width bias; `add` a [N, K] block view."""
+        `bias` [>= col0 + K] is the full-width bias; `add` a [N, K] block view.  bf16 / f16 `x` (and `add`) take
+        ggl_spmm_epi_x16: f32 arithmetic, `out` in x's dtype (rounded once) or f32; no accumulate there."""
         dev = x.device
         K = int(x.shape[1])
         if out.shape[1] != K or out.shape[0] != plan.N:
@@ -498,6 +500,16 @@ class Engine:
         b = None
         if bias is not None:
             b = ctypes.c_void_p(bias.data_ptr() + 4 * int(col0))
+        if x.dtype in _X16_DTYPES:
+            if accumulate:
+                raise RuntimeError("spmm_epi_into: no accumulate on 16-bit rows (a rounded partial result would round twice)")
+            self._check(self.lib.ggl_spmm_epi_x16(
+                ctypes.byref(cs), _ptr(col), _ptr(w), w_by_pos, _DTYPE_CODE[x.dtype], _ptr(x),
+                self._row_stride(x, "x", x.dtype), K, _DTYPE_CODE[out.dtype], _ptr(out),
+                self._row_stride(out, "out", out.dtype), int(bool(mean)), _ptr(add),
+                (self._row_stride(add, "add", x.dtype) if add is not None else 0), b, int(bool(relu)), float(p_drop),
+                _ptr(rng), int(epi_K), int(col0), int(bool(advance_rng)), self._stream(dev)))
+            return out
         self._check(self.lib.ggl_spmm_epi_ex(
             ctypes.byref(cs), _ptr(col), _ptr(w), w_by_pos, _ptr(x), self._row_stride(x, "x"), K, _ptr(out),
             self._row_stride(out, "out"), int(bool(accumulate)), int(bool(mean)), _ptr(add),
@@ -892,10 +904,15 @@ class Engine:
         return N, (t.numel() // N if N > 0 else int(math.prod(t.shape[1:])))
 
     def _epi_fwd(self, a, bias, relu, p_drop, rng):
-        """y = dropout(relu(a + bias)) of a contiguous f32 `a` in one kernel (ggl_bias_act_fwd); `rng` from _draw."""
+        """y = dropout(relu(a + bias)) of a contiguous f32 `a` in one kernel (ggl_bias_act_fwd); `rng` from _draw.
+        A bf16 / f16 `a` takes ggl_bias_act_fwd_x16: the same f32 operations and words, y rounded once to a's dtype."""
         N, K = self._rows_cols(a)
         y = torch.empty_like(a)
         b = bias.contiguous().reshape(-1) if bias is not None else None
+        if a.dtype in _X16_DTYPES:
+            self._check(self.lib.ggl_bias_act_fwd_x16(_DTYPE_CODE[a.dtype], _ptr(a), _ptr(b), N, K, int(relu), float(p_drop),
+                                                      _ptr(rng), _ptr(y), self._stream(a.device)))
+            return y
         self._check(self.lib.ggl_bias_act_fwd(_ptr(a), _ptr(b), N, K, int(relu), float(p_drop), _ptr(rng), _ptr(y),
                                               self._stream(a.device)))
         return y
@@ -903,18 +920,25 @@ class Engine:
     def _epi_bwd(self, g, y, relu, p_drop, rng_used, bias_shape):
         """Back through dropout / ReLU / + bias (/ + add) in one pass (ggl_bias_act_bwd): the mask is redrawn from
         `rng_used` (the forward's _draw) and the ReLU read off the saved output `y`.  Returns (ga, gbias), gbias in
-        `bias_shape` or None without a bias; g itself when there is nothing to undo."""
+        `bias_shape` or None without a bias; g itself when there is nothing to undo.  bf16 / f16 g and y (the
+        forward's dtype) take ggl_bias_act_bwd_x16: ga in that dtype, gbias f32 and never rounded."""
         g = g.contiguous()
         if not (relu or p_drop > 0 or bias_shape is not None):
             return g, None
+        if g.dtype != y.dtype:
+            raise RuntimeError(f"expected scalar type Float: the gradient ({g.dtype}) must have the output's dtype ({y.dtype})")
         dev = g.device
         N, K = self._rows_cols(g)
         ga = torch.empty_like(g)
         gb = torch.empty(K, dtype=torch.float32, device=dev) if bias_shape is not None else None
         wsb = self.lib.ggl_bias_act_bwd_workspace_bytes(N, K)
         ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=dev)
-        self._check(self.lib.ggl_bias_act_bwd(_ptr(g), _ptr(y), N, K, int(relu), float(p_drop), _ptr(rng_used),
-                                              _ptr(ga), _ptr(gb), _ptr(ws), wsb, self._stream(dev)))
+        if g.dtype in _X16_DTYPES:
+            self._check(self.lib.ggl_bias_act_bwd_x16(_DTYPE_CODE[g.dtype], _ptr(g), _ptr(y), N, K, int(relu), float(p_drop),
+                                                      _ptr(rng_used), _ptr(ga), _ptr(gb), _ptr(ws), wsb, self._stream(dev)))
+        else:
+            self._check(self.lib.ggl_bias_act_bwd(_ptr(g), _ptr(y), N, K, int(relu), float(p_drop), _ptr(rng_used),
+                                                  _ptr(ga), _ptr(gb), _ptr(ws), wsb, self._stream(dev)))
         return ga, (gb.reshape(bias_shape) if gb is not None else None)
 
     def reseed(self, seed=None):
@@ -931,9 +955,12 @@ class Engine:
             torch.manual_seed(seed)
 
     def bias_act(self, a, bias=None, relu=False, p_drop=0.0, training=True):
-        """dropout(relu(a + bias)) — the step after every aggregate (gcn_conv.py:105-106, models/gcn.py:55-59)."""
+        """dropout(relu(a + bias)) — the step after every aggregate (gcn_conv.py:105-106, models/gcn.py:55-59).
+        `a` f32, or bf16 / f16 storage (f32 arithmetic, the result rounded once to a's dtype); `bias` stays f32."""
         self._dev(a, bias)
-        self._check_f32("a", a)
+        self._check_f32_or_x16("a", a)
+        if bias is not None:
+            self._check_f32("bias", bias)
         p = float(p_drop) if training else 0.0
         return autograd.BiasAct.apply(self, a, bias, bool(relu), p)
 
@@ -943,18 +970,29 @@ class Engine:
         (16-byte rows); otherwise the SpMM and the epilogue kernel run back to back — same values."""
         return self.spmm_epi(gp, weight, x, "sum", None, bias, relu, p_drop, training)
 
-    def spmm_epi(self, gp, weight, x, reduce="sum", add=None, bias=None, relu=False, p_drop=0.0, training=True):
+    def spmm_epi(self, gp, weight, x, reduce="sum", add=None, bias=None, relu=False, p_drop=0.0, training=True,
+                 out_dtype=None):
         """dropout(relu(reduce_{j->i} w x_j + add_i + bias)), reduce in {'sum', 'mean'}: one kernel for 16-byte
-        rows (feature width a multiple of 4), the reduce op followed by the adds and the epilogue pass otherwise."""
+        rows (feature width a multiple of 4), the reduce op followed by the adds and the epilogue pass otherwise.
+        bf16 / f16 `x` (with `add` in x's dtype; weight and bias stay f32): every operation is the f32 one on the widened
+        rows and the result is rounded once, at the store — or returned as f32 with out_dtype=torch.float32; one kernel
+        at every width."""
         self._dev(x, weight, bias, add)
-        self._check_f32("x", x)
+        self._check_f32_or_x16("x", x)
         weight = self._check_weight(weight, gp)
-        for n, t in (("bias", bias), ("add", add)):
-            if t is not None:
-                self._check_f32(n, t)
+        if bias is not None:
+            self._check_f32("bias", bias)
+        if add is not None and add.dtype != x.dtype:
+            raise RuntimeError(f"expected scalar type Float (add in x's dtype, {x.dtype}) but found {add.dtype} for add")
+        out_dtype = self._out_dtype(x, out_dtype)
         if add is not None and tuple(add.shape) != (gp.N_dst, x.shape[1]):
             raise RuntimeError("add must be [destination rows, feature width]")
         p = float(p_drop) if training else 0.0
+        if x.dtype in _X16_DTYPES:
+            if x.dim() != 2:
+                raise RuntimeError("spmm_epi on bf16 / f16 rows expects x of shape [num_nodes, features]")
+            return autograd.SpMMEpi.apply(self, gp, weight, x.contiguous(), reduce == "mean", add, bias, bool(relu), p,
+                                          out_dtype)
         if x.dim() == 2 and x.shape[1] % 4 == 0:
             return autograd.SpMMEpi.apply(self, gp, weight, x.contiguous(), reduce == "mean", add, bias, bool(relu), p)
         out = self.spmm(gp, weight, x, reduce)

@@ -13,8 +13,9 @@ class GCNTrainer:
     def __init__(self, feature_dim, hidden_dim, num_class, num_layers=3, drop_rate=0.5, lr=0.01,
                  l2_coef=5e-4, norm="both", seed=0, device="cuda", amp_dtype=None):
         """`amp_dtype` = torch.bfloat16 / torch.float16: mixed precision — parameters and Adam state stay f32, the forward
-        runs under torch.autocast (the Linears produce 16-bit activations, every aggregate sums them in f32 and rounds
-        once), the loss is taken in f32, and f16 gradients go through a GradScaler.  None: the f32 step, unchanged."""
+        runs under torch.autocast (the Linears produce 16-bit activations, every aggregate sums them in f32, applies the f32
+        bias, ReLU and the library's dropout in registers and rounds once, at its only store: GCNModel(fuse_epilogue16=True)),
+        the loss is taken in f32, and f16 gradients go through a GradScaler.  None: the f32 step, unchanged."""
         if amp_dtype not in (None, torch.bfloat16, torch.float16):
             raise ValueError("amp_dtype must be None, torch.bfloat16 or torch.float16")
         torch.manual_seed(seed)

@@ -65,6 +65,8 @@ extern "C" {
  *   aggregates were in 10. */
 /* still 11: + ggl_spmm_grad_w, ggl_spmm_grad_w_scratch_bytes (gspmm's sum / mean gradient with respect to the edge weights, on
  *   f32 / bf16 / f16 rows).  Purely additive again. */
+/* still 11: + ggl_spmm_epi_x16, ggl_bias_act_fwd_x16, ggl_bias_act_bwd_x16 (the fused epilogue and the bias / ReLU / dropout
+ *   pass on bf16 / f16 rows: f32 arithmetic, one rounding at the store).  Purely additive again. */
 #define GGL_ABI_VERSION 11
 
 /* dtype codes (AT_DISPATCH_ALL_TYPES_AND2(Half, BFloat16), segment_sum_cpu.cpp:32-33) */
@@ -437,6 +439,29 @@ int ggl_spmm_epi_ex(const ggl_segplan_t *plan, const int32_t *col, const float *
                     const float *x, int64_t x_ld, int64_t K, float *out, int64_t out_ld, int accumulate,
                     int mean, const float *add, int64_t add_ld, const float *bias, int relu, float p_drop,
                     int64_t *rng_state, int64_t epi_K, int64_t epi_col0, int advance_rng, void *stream);
+/* ggl_spmm_epi_ex on 16-bit rows (an extension, as ggl_spmm_*_x16): x and add are stored as GGL_BF16 or GGL_F16 (add has
+ * x's dtype), w and bias stay f32.  The sum (or mean), + add, + bias, ReLU and the dropout scale are each the f32 operation
+ * ggl_spmm_epi_ex makes, in its order, and the row is rounded ONCE, at the store (out_dtype == x_dtype), or not at all
+ * (out_dtype == GGL_F32).  With F = ggl_spmm_epi_ex on the same plan, weights and rng state:
+ *     out == round(F(widen(x), widen(add), bias, ...))  /  out == F(...)      bit for bit, the dropout mask included
+ * (the word of element (i, k) is F's; epi_col0 a multiple of 4 keeps the 16-byte lanes), and rng_state moves as F moves it.
+ * Any other dtype pair returns GGL_EDTYPE.  There is no accumulate: adding onto a rounded partial result would round twice.
+ * Wide rows run as column blocks of option "col_block16" columns, bias / add / the mask following the block. */
+int ggl_spmm_epi_x16(const ggl_segplan_t *plan, const int32_t *col, const float *w, int w_by_pos, int x_dtype, const void *x,
+                     int64_t x_ld, int64_t K, int out_dtype, void *out, int64_t out_ld, int mean, const void *add,
+                     int64_t add_ld, const float *bias, int relu, float p_drop, int64_t *rng_state, int64_t epi_K,
+                     int64_t epi_col0, int advance_rng, void *stream);
+/* ggl_bias_act_fwd / ggl_bias_act_bwd on 16-bit a / y / g / ga (dtype = GGL_BF16 or GGL_F16, else GGL_EDTYPE); bias, gbias
+ * and the partials stay f32:
+ *     y  == round(ggl_bias_act_fwd(widen(a), ...))            same words, same motion of rng_state
+ *     ga == round(ggl_bias_act_bwd(widen(g), widen(y), ...))   gbias == that call's gbias, bit for bit (the column sums add
+ *           the f32 values before they are rounded, in the f32 kernel's row-to-partial geometry)
+ * The ReLU mask is read off the stored y > 0.  workspace: ggl_bias_act_bwd_workspace_bytes(N, K). */
+int ggl_bias_act_fwd_x16(int dtype, const void *a, const float *bias, int64_t N, int64_t K, int relu, float p_drop,
+                         int64_t *rng_state, void *y, void *stream);
+int ggl_bias_act_bwd_x16(int dtype, const void *g, const void *y, int64_t N, int64_t K, int relu, float p_drop,
+                         const int64_t *rng_used, void *ga, float *gbias, void *workspace, size_t workspace_bytes,
+                         void *stream);
 /* segment_sum / segment_mean of f32 messages x[E, K] with the same epilogue on each finished row (the
  * message() + aggregate() route of a sampled SAGEConv block): bit-identical to ggl_segment_{sum,mean}
  * followed by "+ add + bias, relu, dropout". */
