@@ -272,6 +272,59 @@ class GATFused(torch.autograd.Function):
         return None, None, gel, ger, gx, None, None, None
 
 
+class EdgeSoftmaxAgg(torch.autograd.Function):
+    """edge-softmax + aggregate on per-edge logits z [E, H] (ggl_edge_softmax_agg_*): GATFused's general f32 kernels with
+    the logit read from z through the plan's perm.  The source walk runs only when x needs a gradient, gz is stored — by
+    the destination walk itself, in the caller's edge order — only when z does."""
+
+    @staticmethod
+    def forward(ctx, eng, gp, z, x, p_drop=0.0):
+        ctx.eng = eng
+        dev = x.device
+        N, H, C = gp.N_dst, int(x.shape[1]), int(x.shape[2])
+        out = torch.empty((N, H, C), dtype=torch.float32, device=dev)
+        rmax = torch.empty((N, H), dtype=torch.float32, device=dev)
+        rden = torch.empty((N, H), dtype=torch.float32, device=dev)
+        part = eng._gat_partial(gp.fwd, H, C, dev)
+        cs = gp.fwd.c_struct(part)
+        rng, rng_used = eng._draw(dev, p_drop)
+        eng._check(eng.lib.ggl_edge_softmax_agg_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(z), _ptr(x), H, C, float(p_drop),
+                                                    _ptr(rng), _ptr(out), _ptr(rmax), _ptr(rden), eng._stream(dev)))
+        ctx.gp, ctx.p_drop, ctx.rng_used = gp, float(p_drop), rng_used
+        ctx.save_for_backward(z, x, out, rmax, rden)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        eng = ctx.eng
+        gp = ctx.gp
+        z, x, out, rmax, rden = ctx.saved_tensors
+        need_z, need_x = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        if not (need_z or need_x):
+            return None, None, None, None, None
+        g = g.contiguous()
+        dev = g.device
+        H, C = int(x.shape[1]), int(x.shape[2])
+        st = eng._stream(dev)
+        alpha = torch.empty((max(gp.E, 1), H), dtype=torch.float32, device=dev) if need_x else None   # sorted positions
+        gz = torch.empty_like(z) if need_z else None                                                  # caller's order
+        part_f = eng._partial(gp.fwd, torch.float32, H, False, dev)  # must outlive the launch
+        cs = gp.fwd.c_struct(part_f)
+        eng._check(eng.lib.ggl_edge_softmax_agg_bwd_dst(
+            ctypes.byref(cs), _ptr(gp.col), _ptr(z), _ptr(x), _ptr(g), _ptr(out), _ptr(rmax), _ptr(rden), H, C,
+            ctx.p_drop, _ptr(ctx.rng_used), _ptr(alpha), _ptr(gz), st))
+        gx = None
+        if need_x:
+            bwd = gp.bwd
+            gx = torch.empty((gp.N_src, H, C), dtype=torch.float32, device=dev)
+            part = eng._partial(bwd, torch.float32, H * C + H, False, dev)
+            csT = bwd.c_struct(part)
+            eng._check(eng.lib.ggl_edge_softmax_agg_bwd_src(ctypes.byref(csT), _ptr(gp.colT), _ptr(gp.posT), _ptr(alpha),
+                                                            _ptr(g), H, C, _ptr(gx), st))
+        return None, None, gz, gx, None
+
+
 class BiasAdd(torch.autograd.Function):
     """out = x + bias (bias broadcast over rows); d bias = column sums of the gradient."""
 

@@ -48,3 +48,11 @@ def load_grad():
     the surface under ``ggl::`` is the reference's operators and their passes, pinned name by name."""
     load()
     return torch.ops.ggl_grad
+
+
+def load_attn():
+    """``torch.ops.ggl_attn`` (the same library): ``edge_softmax_aggregate(index, logits, x, num_nodes=None, dropout_rate=0.)``,
+    edge softmax + weighted aggregate on per-edge logits, with its ``_forward`` / ``_backward`` passes.  A namespace of its
+    own for the reason ``load_grad`` gives."""
+    load()
+    return torch.ops.ggl_attn

@@ -47,8 +47,10 @@ namespace ggl {
 // edge is affordable in every walk (with Philox4x32-10 a draw per edge doubled the forward: 4.1 -> 9.4 ms, and the
 // walks were aligned to multiples of 4 to share one 4-word block; the alignment is kept for the 16-byte index loads).
 // XT: how x is stored (float, or mxbf16_t / mxf16_t: 16-bit storage widened at the load; everything below is f32).
-template <typename XT, int VEC, bool DROP>
+// LS: where s_p comes from (gat_common.hpp Logit): el / er as above, or per-edge logits z read through `aux` = plan->perm.
+template <typename XT, int VEC, bool DROP, int LS = kLogitSeparable>
 __device__ __forceinline__ void gat_online(const int32_t *__restrict__ col, const float *__restrict__ el,
+                                           typename Logit<LS>::Aux __restrict__ aux,
                                            const typename TT<XT>::S *__restrict__ x, float er_i, float slope, int64_t H,
                                            int64_t K, int64_t h, int64_t kk, int64_t beg, int64_t end,
                                            const GatDims &d, const int64_t *__restrict__ rng,
@@ -73,27 +75,29 @@ __device__ __forceinline__ void gat_online(const int32_t *__restrict__ col, cons
 #pragma unroll
     for (int i = 0; i < VEC; ++i) acc[i] = __fadd_rn(acc[i], __fmul_rn(v[i], ek));
   };
+  using LP = Logit<LS>;
   auto single = [&](int64_t q) {
     const int64_t c0 = col[q];
+    const int64_t e0 = LP::rec(aux, col, q, c0);
     float v0[VEC];
     RowV<XT, VEC>::load(x + c0 * K + kk, v0);
-    absorb(DROP ? drop_word(q, H, h, offset, seed) : 0u, lrelu(__fadd_rn(el[c0 * H + h], er_i), slope), v0);
+    absorb(DROP ? drop_word(q, H, h, offset, seed) : 0u, LP::act(LP::raw(el[e0 * H + h], er_i), slope), v0);
   };
   int64_t p = beg;
   if (DROP) {  // walk up to a multiple of 4 so that each unrolled group shares one draw
     for (; p < end && (p & 3) != 0; ++p) single(p);
   }
   for (; p + 4 <= end; p += 4) {
-    int64_t c[4];
+    int64_t c[4], e[4];
     float v[4][VEC], s[4];
     U4 rw{0u, 0u, 0u, 0u};
     if (DROP) rw = drop_words4(p >> 2, H, h, offset, seed);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) c[u] = col[p + u];
+    for (int u = 0; u < 4; ++u) { c[u] = col[p + u]; e[u] = LP::rec(aux, col, p + u, c[u]); }
 #pragma unroll
     for (int u = 0; u < 4; ++u) RowV<XT, VEC>::load(x + c[u] * K + kk, v[u]);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) s[u] = lrelu(__fadd_rn(el[c[u] * H + h], er_i), slope);
+    for (int u = 0; u < 4; ++u) s[u] = LP::act(LP::raw(el[e[u] * H + h], er_i), slope);
 #pragma unroll
     for (int u = 0; u < 4; ++u) absorb(pick_word(rw, u), s[u], v[u]);
   }
@@ -101,11 +105,12 @@ __device__ __forceinline__ void gat_online(const int32_t *__restrict__ col, cons
 }
 
 // OT: how out is stored (XT, or float beside 16-bit rows: a last layer's logits).  The hub-chunk partials are f32.
-template <typename XT, typename OT, int VEC, bool DROP>
+// LS = kLogitEdge: `el` is z [E, H] and `er` plan->perm (gat_common.hpp Logit).
+template <typename XT, typename OT, int VEC, bool DROP, int LS = kLogitSeparable>
 __global__ __launch_bounds__(kBlock) void gat_fwd_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const int32_t *__restrict__ row_order, const int32_t *__restrict__ long_rows,
-    const int64_t *__restrict__ chunk_ptr, const float *__restrict__ el, const float *__restrict__ er,
+    const int64_t *__restrict__ chunk_ptr, const float *__restrict__ el, typename Logit<LS>::Aux __restrict__ er,
     const typename TT<XT>::S *__restrict__ x, typename TT<OT>::S *__restrict__ y, float *__restrict__ rowmax,
     float *__restrict__ rowden, float *__restrict__ pacc, float *__restrict__ pm,
     float *__restrict__ pd, const int64_t *__restrict__ rng, const GatDims d) {
@@ -126,9 +131,9 @@ __global__ __launch_bounds__(kBlock) void gat_fwd_kernel(
     const int64_t end = (beg + d.chunk < rend) ? beg + d.chunk : rend;
     for (int64_t kk = (int64_t)lane * VEC; kk < K; kk += (int64_t)kWave * VEC) {
       const int64_t h = kk / d.C;
-      const float er_i = er[row * H + h];
+      const float er_i = Logit<LS>::row(er, row * H + h);
       float m, dsum, acc[VEC];
-      gat_online<XT, VEC, DROP>(col, el, x, er_i, d.slope, H, K, h, kk, beg, end, d, rng, m, dsum, acc);
+      gat_online<XT, VEC, DROP, LS>(col, el, er, x, er_i, d.slope, H, K, h, kk, beg, end, d, rng, m, dsum, acc);
       F32V<VEC>::store(pacc + cid * K + kk, acc);
       if (kk == h * d.C) {
         pm[cid * H + h] = m;
@@ -147,9 +152,9 @@ __global__ __launch_bounds__(kBlock) void gat_fwd_kernel(
   if (end - beg > d.chunk) return;
   for (int64_t kk = (int64_t)li * VEC; kk < K; kk += (int64_t)L * VEC) {
     const int64_t h = kk / d.C;
-    const float er_i = er[row * H + h];
+    const float er_i = Logit<LS>::row(er, row * H + h);
     float m, dsum, acc[VEC];
-    gat_online<XT, VEC, DROP>(col, el, x, er_i, d.slope, H, K, h, kk, beg, end, d, rng, m, dsum, acc);
+    gat_online<XT, VEC, DROP, LS>(col, el, er, x, er_i, d.slope, H, K, h, kk, beg, end, d, rng, m, dsum, acc);
     const float inv = __fadd_rn(dsum, 1e-16f);  // softmax.py:35: exp / (sum + 1e-16)
 #pragma unroll
     for (int i = 0; i < VEC; ++i) acc[i] = __fdiv_rn(acc[i], inv);
@@ -213,11 +218,14 @@ __global__ __launch_bounds__(kBlock) void gat_long_final16_kernel(
 // + 2.7 ms on the Reddit-sized graph) with the same rounded operations in the same order.
 // XT: storage of x; GT: storage of g AND of the saved out (the forward's out type).  16-bit elements are widened at the
 // load; the dots run over the channels in ascending order whatever VEC is, so the bits do not depend on the load form.
-template <typename XT, typename GT, int VEC, int CREG>
+// LS = kLogitEdge (`el` = z, `er` = plan->perm): s_p = z[e_p, h] and no activation, so dv = ds; `de` is gz [E, H] and is
+// stored at e_p, the caller's edge number (no pass permutes it afterwards); alpha stays in position order.  alpha or de
+// may be NULL (x resp. z needs no gradient) and is then not stored; there is no per-row sum, ger / pger are not touched.
+template <typename XT, typename GT, int VEC, int CREG, int LS = kLogitSeparable>
 __global__ __launch_bounds__(kBlock) void gat_bwd_dst_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const int32_t *__restrict__ row_order, const int32_t *__restrict__ long_rows,
-    const int64_t *__restrict__ chunk_ptr, const float *__restrict__ el, const float *__restrict__ er,
+    const int64_t *__restrict__ chunk_ptr, const float *__restrict__ el, typename Logit<LS>::Aux __restrict__ er,
     const typename TT<XT>::S *__restrict__ x, const typename TT<GT>::S *__restrict__ g,
     const typename TT<GT>::S *__restrict__ out,
     const float *__restrict__ rowmax, const float *__restrict__ rowden, float *__restrict__ alpha,
@@ -225,6 +233,7 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_kernel(
     const int64_t *__restrict__ rng, const GatDims d) {
   using XS = typename TT<XT>::S;
   using GS = typename TT<GT>::S;
+  using LP = Logit<LS>;
   const int64_t H = d.H, K = d.K;
   const int64_t C = CREG > 0 ? (int64_t)CREG : d.C;
   const uint64_t seed = d.drop_thresh ? (uint64_t)rng[0] : 0, offset = d.drop_thresh ? (uint64_t)rng[1] : 0;
@@ -265,13 +274,13 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_kernel(
     } else {
       for (int64_t c = 0; c < C; ++c) dot = __fadd_rn(dot, __fmul_rn(TT<GT>::load(gi[c]), TT<GT>::load(oi[c])));
     }
-    const float er_i = er[row * H + h];
+    const float er_i = LP::row(er, row * H + h);
     const float m = rowmax[row * H + h];
     const float inv = __fadd_rn(rowden[row * H + h], 1e-16f);
     float gsum = 0.0f;
-    auto edge = [&](int64_t p, uint32_t word, float elv, const XS *__restrict__ xj) {
-      const float raw = __fadd_rn(elv, er_i);
-      const float al = __fdiv_rn(GGL_EXPF(__fadd_rn(lrelu(raw, d.slope), -m)), inv);
+    auto edge = [&](int64_t p, int64_t e, uint32_t word, float elv, const XS *__restrict__ xj) {
+      const float raw = LP::raw(elv, er_i);
+      const float al = __fdiv_rn(GGL_EXPF(__fadd_rn(LP::act(raw, d.slope), -m)), inv);
       float da = 0.0f;
       if (CREG > 0) {
 #pragma unroll
@@ -297,34 +306,42 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_kernel(
         da = keep ? __fmul_rn(da, d.drop_scale) : 0.0f;  // d out / d alpha_p = keep/(1-p) <g_i, x_j>
       }
       const float ds = __fmul_rn(al, __fadd_rn(da, -dot));
-      const float dv = raw > 0.0f ? ds : __fmul_rn(ds, d.slope);
-      alpha[(p * H + h) * d.es] = alk;
-      de[(p * H + h) * d.es] = dv;
-      gsum = __fadd_rn(gsum, dv);
+      const float dv = LP::dact(raw, ds, d.slope);
+      if constexpr (LS == kLogitEdge) {
+        if (alpha) alpha[p * H + h] = alk;
+        if (de) de[e * H + h] = dv;
+      } else {
+        alpha[(p * H + h) * d.es] = alk;
+        de[(p * H + h) * d.es] = dv;
+        gsum = __fadd_rn(gsum, dv);
+      }
     };
     auto single = [&](int64_t q) {
       const int64_t s0 = col[q];
-      edge(q, d.drop_thresh ? drop_word(q, H, h, offset, seed) : 0u, el[s0 * H + h], x + s0 * K + h * C);
+      const int64_t e0 = LP::rec(er, col, q, s0);
+      edge(q, e0, d.drop_thresh ? drop_word(q, H, h, offset, seed) : 0u, el[e0 * H + h], x + s0 * K + h * C);
     };
     int64_t p = beg;
     if (d.drop_thresh) {
       for (; p < end && (p & 3) != 0; ++p) single(p);
     }
     for (; p + 4 <= end; p += 4) {
-      int64_t sj[4];
+      int64_t sj[4], ej[4];
       float ev[4];
       U4 rw{0u, 0u, 0u, 0u};
       if (d.drop_thresh) rw = drop_words4(p >> 2, H, h, offset, seed);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) sj[u] = col[p + u];
+      for (int u = 0; u < 4; ++u) { sj[u] = col[p + u]; ej[u] = LP::rec(er, col, p + u, sj[u]); }
 #pragma unroll
-      for (int u = 0; u < 4; ++u) ev[u] = el[sj[u] * H + h];
+      for (int u = 0; u < 4; ++u) ev[u] = el[ej[u] * H + h];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) edge(p + u, pick_word(rw, u), ev[u], x + sj[u] * K + h * C);
+      for (int u = 0; u < 4; ++u) edge(p + u, ej[u], pick_word(rw, u), ev[u], x + sj[u] * K + h * C);
     }
     for (; p < end; ++p) single(p);
-    if (is_chunk) pger[item * H + h] = gsum;
-    else ger[row * H + h] = gsum;
+    if constexpr (LS == kLogitSeparable) {
+      if (is_chunk) pger[item * H + h] = gsum;
+      else ger[row * H + h] = gsum;
+    }
   }
 }
 
@@ -364,16 +381,18 @@ __device__ __forceinline__ void gat_wide_load(int vl, const typename TT<T>::S *_
   }
 }
 
-template <typename XT, typename GT, int VEC, int LOGG, int HH>
+// LS: as in gat_bwd_dst_kernel.
+template <typename XT, typename GT, int VEC, int LOGG, int HH, int LS = kLogitSeparable>
 __global__ __launch_bounds__(kBlock) void gat_bwd_dst_wide_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const int32_t *__restrict__ row_order, const int32_t *__restrict__ long_rows,
-    const int64_t *__restrict__ chunk_ptr, const float *__restrict__ el, const float *__restrict__ er,
+    const int64_t *__restrict__ chunk_ptr, const float *__restrict__ el, typename Logit<LS>::Aux __restrict__ er,
     const typename TT<XT>::S *__restrict__ x, const typename TT<GT>::S *__restrict__ g,
     const typename TT<GT>::S *__restrict__ out,
     const float *__restrict__ rowmax, const float *__restrict__ rowden, float *__restrict__ alpha,
     float *__restrict__ de, float *__restrict__ ger, float *__restrict__ pger,
     const int64_t *__restrict__ rng, const GatDims d) {
+  using LP = Logit<LS>;
   constexpr int G = 1 << LOGG;
   constexpr bool MB = gat_is16<XT>::value;  // only the 16-bit entry points can meet a panel aligned to less than VEC
   static_assert(G >= HH, "lane h finishes head h");
@@ -423,13 +442,13 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_wide_kernel(
   for (int h = 0; h < HH; ++h)
     if (sub == h) my_dot = dots[h];
   if (sub < H) {
-    my_er = er[row * H + sub];
+    my_er = LP::row(er, row * H + sub);
     my_m = rowmax[row * H + sub];
     my_inv = __fadd_rn(rowden[row * H + sub], 1e-16f);
   }
   const uint64_t seed = d.drop_thresh ? (uint64_t)rng[0] : 0, offset = d.drop_thresh ? (uint64_t)rng[1] : 0;
   float gsum = 0.0f;
-  auto one_edge = [&](int64_t p, int64_t j, const float (&xv)[HH][VEC]) {
+  auto one_edge = [&](int64_t p, int64_t e, const float (&xv)[HH][VEC]) {  // e: the edge's record of el
     float part[HH];
 #pragma unroll
     for (int h = 0; h < HH; ++h) {
@@ -443,8 +462,8 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_wide_kernel(
 #pragma unroll
       for (int h = 0; h < HH; ++h)
         if (sub == h) da = part[h];
-      const float raw = __fadd_rn(el[j * H + sub], my_er);
-      const float al = __fdiv_rn(GGL_EXPF(__fadd_rn(lrelu(raw, d.slope), -my_m)), my_inv);
+      const float raw = LP::raw(el[e * H + sub], my_er);
+      const float al = __fdiv_rn(GGL_EXPF(__fadd_rn(LP::act(raw, d.slope), -my_m)), my_inv);
       float alk = al;
       if (d.drop_thresh) {
         const bool keep = drop_word(p, H, sub, offset, seed) >= d.drop_thresh;
@@ -452,15 +471,21 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_wide_kernel(
         da = keep ? __fmul_rn(da, d.drop_scale) : 0.0f;
       }
       const float ds = __fmul_rn(al, __fadd_rn(da, -my_dot));
-      const float dv = raw > 0.0f ? ds : __fmul_rn(ds, d.slope);
-      alpha[(p * H + sub) * d.es] = alk;
-      de[(p * H + sub) * d.es] = dv;
-      gsum = __fadd_rn(gsum, dv);
+      const float dv = LP::dact(raw, ds, d.slope);
+      if constexpr (LS == kLogitEdge) {
+        if (alpha) alpha[p * H + sub] = alk;
+        if (de) de[e * H + sub] = dv;
+      } else {
+        alpha[(p * H + sub) * d.es] = alk;
+        de[(p * H + sub) * d.es] = dv;
+        gsum = __fadd_rn(gsum, dv);
+      }
     }
   };
   int64_t p = beg;
   for (; p + 2 <= end; p += 2) {  // two feature rows (2 x HH slices per lane) in flight
     const int64_t j0 = col[p], j1 = col[p + 1];
+    const int64_t e0 = LP::rec(er, col, p, j0), e1 = LP::rec(er, col, p + 1, j1);
     float x0[HH][VEC], x1[HH][VEC];
 #pragma unroll
     for (int h = 0; h < HH; ++h) {
@@ -471,11 +496,12 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_wide_kernel(
         gat_wide_load<XT, VEC, MB>(d.vl, x + j1 * K + h * C + c0, x1[h]);
       }
     }
-    one_edge(p, j0, x0);
-    one_edge(p + 1, j1, x1);
+    one_edge(p, e0, x0);
+    one_edge(p + 1, e1, x1);
   }
   for (; p < end; ++p) {
     const int64_t j0 = col[p];
+    const int64_t e0 = LP::rec(er, col, p, j0);
     float x0[HH][VEC];
 #pragma unroll
     for (int h = 0; h < HH; ++h) {
@@ -483,11 +509,13 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_wide_kernel(
       for (int q = 0; q < VEC; ++q) x0[h][q] = 0.0f;
       if (act && h < H) gat_wide_load<XT, VEC, MB>(d.vl, x + j0 * K + h * C + c0, x0[h]);
     }
-    one_edge(p, j0, x0);
+    one_edge(p, e0, x0);
   }
-  if (sub < H) {
-    if (is_chunk) pger[item * H + sub] = gsum;
-    else ger[row * H + sub] = gsum;
+  if constexpr (LS == kLogitSeparable) {
+    if (sub < H) {
+      if (is_chunk) pger[item * H + sub] = gsum;
+      else ger[row * H + sub] = gsum;
+    }
   }
 }
 #endif  // !GGL_EMULATE
@@ -513,6 +541,8 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_final_kernel(const int32_t
 // rounded operations in the same order as the bspmm + segment_sum pair this replaces (two walks, two
 // gathers of posT: 6.0 + 3.7 ms on the Reddit-sized graph), so the results are bit-identical to it.
 // GT: storage of g (widened at the load); OT (kernel): storage of gx, rounded once at the store.
+// GEL = false (the edge-softmax aggregate: no [N_src, H] result is wanted, and its gz is not in position order): no lane
+// leads, so de is never read and gel / pgel never written — both may be NULL.
 template <typename GT, int VEC>
 __device__ __forceinline__ void gat_src_walk(const int32_t *__restrict__ colT, const int32_t *__restrict__ posT,
                                              const float *__restrict__ alpha, const float *__restrict__ de,
@@ -553,7 +583,7 @@ __device__ __forceinline__ void gat_src_walk(const int32_t *__restrict__ colT, c
   }
 }
 
-template <typename GT, typename OT, int VEC>
+template <typename GT, typename OT, int VEC, bool GEL = true>
 __global__ __launch_bounds__(kBlock) void gat_bwd_src_kernel(
     const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colT, const int32_t *__restrict__ posT,
     const int32_t *__restrict__ row_order, const int32_t *__restrict__ long_rows,
@@ -577,7 +607,7 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_src_kernel(
     const int64_t end = (beg + d.chunk < rend) ? beg + d.chunk : rend;
     for (int64_t kk = (int64_t)lane * VEC; kk < K; kk += (int64_t)kWave * VEC) {
       const int64_t h = kk / d.C;
-      const bool lead = (kk == h * d.C);
+      const bool lead = GEL && (kk == h * d.C);
       float acc[VEC], gl;
       gat_src_walk<GT, VEC>(colT, posT, alpha, de, g, H, K, h, d.es, kk, lead, beg, end, acc, gl);
       F32V<VEC>::store(pacc + cid * K + kk, acc);
@@ -595,7 +625,7 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_src_kernel(
   if (end - beg > d.chunk) return;
   for (int64_t kk = (int64_t)li * VEC; kk < K; kk += (int64_t)L * VEC) {
     const int64_t h = kk / d.C;
-    const bool lead = (kk == h * d.C);
+    const bool lead = GEL && (kk == h * d.C);
     float acc[VEC], gl;
     gat_src_walk<GT, VEC>(colT, posT, alpha, de, g, H, K, h, d.es, kk, lead, beg, end, acc, gl);
     RowV<OT, VEC>::store(gx + row * K + kk, acc);
@@ -604,7 +634,7 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_src_kernel(
 }
 
 // long source rows: partial sums combined in chunk order (deterministic)
-template <typename OT>
+template <typename OT, bool GEL = true>
 __device__ __forceinline__ void gat_bwd_src_final_body(
     const int32_t *__restrict__ long_rows, const int64_t *__restrict__ chunk_ptr,
     const float *__restrict__ pacc, const float *__restrict__ pgel, typename TT<OT>::S *__restrict__ gx,
@@ -613,7 +643,7 @@ __device__ __forceinline__ void gat_bwd_src_final_body(
   if (j >= d.n_long) return;
   const int64_t row = long_rows[j];
   const int64_t c0 = chunk_ptr[j], c1 = chunk_ptr[j + 1];
-  for (int64_t k = threadIdx.x; k < d.K + d.H; k += kBlock) {
+  for (int64_t k = threadIdx.x; k < d.K + (GEL ? d.H : 0); k += kBlock) {
     float acc = 0.0f;
     if (k < d.K) {
       for (int64_t c = c0; c < c1; ++c) acc = __fadd_rn(acc, pacc[c * d.K + k]);
@@ -630,6 +660,11 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_src_final_kernel(
     const float *__restrict__ pacc, const float *__restrict__ pgel, float *__restrict__ gx,
     float *__restrict__ gel, const GatDims d) {
   gat_bwd_src_final_body<float>(long_rows, chunk_ptr, pacc, pgel, gx, gel, d);
+}
+__global__ __launch_bounds__(kBlock) void gat_bwd_src_final_gx_kernel(  // GEL = false: the gx partials alone
+    const int32_t *__restrict__ long_rows, const int64_t *__restrict__ chunk_ptr,
+    const float *__restrict__ pacc, float *__restrict__ gx, const GatDims d) {
+  gat_bwd_src_final_body<float, false>(long_rows, chunk_ptr, pacc, nullptr, gx, nullptr, d);
 }
 template <typename OT>
 __global__ __launch_bounds__(kBlock) void gat_bwd_src_final16_kernel(
@@ -655,8 +690,9 @@ extern "C" size_t ggl_gat_partial_bytes(int64_t n_chunks, int64_t H, int64_t C) 
 // and every vector-accessed pointer is aligned to 4 elements (16 bytes of f32, 8 of 16-bit), 16-bit rows also VEC = 8
 // (C % 8 == 0, 16 bytes), single elements otherwise.  No sum's order depends on VEC (the wide backward kernel keeps its
 // assignment, see there), so a 16-bit call computes the f32 call's bits on the widened rows whatever form it takes.
-template <typename XT, typename OT>
-static int gat_fwd_impl(const ggl_segplan_t *plan, const int32_t *col, const float *el, const float *er,
+// LS = kLogitEdge (ggl_edge_softmax_agg_*, f32 only): `el` is z [E, H], `er` plan->perm; slope is not read.
+template <typename XT, typename OT, int LS = kLogitSeparable>
+static int gat_fwd_impl(const ggl_segplan_t *plan, const int32_t *col, const float *el, typename Logit<LS>::Aux er,
                         const typename TT<XT>::S *x, float slope, int64_t H, int64_t C, float p_drop,
                         int64_t *rng_state, typename TT<OT>::S *out, float *rowmax, float *rowden, void *stream) {
   WalkPlan p;
@@ -664,7 +700,7 @@ static int gat_fwd_impl(const ggl_segplan_t *plan, const int32_t *col, const flo
   GGL_REQUIRE(H > 0 && C > 0, GGL_EINVAL, "H, C and chunk must be positive");
   const int64_t N = p.N;
   if (N == 0) return GGL_OK;
-  GGL_REQUIRE(er && out && rowmax && rowden, GGL_EINVAL, "NULL pointer");
+  GGL_REQUIRE((LS == kLogitEdge || er) && out && rowmax && rowden, GGL_EINVAL, "NULL pointer");
   GGL_REQUIRE((col && el && x) || p.E == 0, GGL_EINVAL, "NULL pointer");
   GatDims d{};
   d.slope = slope; d.N = N; d.H = H; d.C = C; d.K = H * C; d.E = p.E;
@@ -689,7 +725,7 @@ static int gat_fwd_impl(const ggl_segplan_t *plan, const int32_t *col, const flo
   GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "too many rows for one launch");
   hipStream_t s = as_stream(stream);
 #define GGL_GAT_FWD(V, DR)                                                                              \
-  GGL_LAUNCH((gat_fwd_kernel<XT, OT, V, DR>), grid, kBlock, s, plan->rowptr, col, p.order, plan->long_rows, \
+  GGL_LAUNCH((gat_fwd_kernel<XT, OT, V, DR, LS>), grid, kBlock, s, plan->rowptr, col, p.order, plan->long_rows, \
              plan->chunk_ptr, el, er, x, out, rowmax, rowden, pacc, pm, pd, (const int64_t *)rng_state, d)
   if (vec == 8) {  // (16-bit rows only: the f32 op has no such instantiation)
     if constexpr (gat_is16<XT>::value) {
@@ -722,8 +758,10 @@ extern "C" int ggl_gat_fused_fwd(const ggl_segplan_t *plan, const int32_t *col, 
   return gat_fwd_impl<float, float>(plan, col, el, er, x, slope, H, C, p_drop, rng_state, out, rowmax, rowden, stream);
 }
 
-template <typename XT, typename GT>
-static int gat_bwd_dst_impl(const ggl_segplan_t *plan, const int32_t *col, const float *el, const float *er,
+// LS = kLogitEdge: `el` is z, `er` plan->perm, `de` gz in the caller's edge order; alpha or de may be NULL (not stored),
+// ger and plan->partial are not written.
+template <typename XT, typename GT, int LS = kLogitSeparable>
+static int gat_bwd_dst_impl(const ggl_segplan_t *plan, const int32_t *col, const float *el, typename Logit<LS>::Aux er,
                             const typename TT<XT>::S *x, const typename TT<GT>::S *g,
                             const typename TT<GT>::S *out, const float *rowmax, const float *rowden, float slope,
                             int64_t H, int64_t C, float p_drop, const int64_t *rng_used, float *alpha, float *de,
@@ -733,11 +771,13 @@ static int gat_bwd_dst_impl(const ggl_segplan_t *plan, const int32_t *col, const
   GGL_REQUIRE(H > 0 && C > 0, GGL_EINVAL, "H, C and chunk must be positive");
   const int64_t N = p.N, E = p.E;
   if (N == 0) return GGL_OK;
-  GGL_REQUIRE(er && g && out && rowmax && rowden && ger, GGL_EINVAL, "NULL pointer");
-  GGL_REQUIRE((col && el && x && alpha && de) || E == 0, GGL_EINVAL, "NULL pointer");
+  constexpr bool edge = LS == kLogitEdge;
+  GGL_REQUIRE((edge || (er && ger)) && g && out && rowmax && rowden, GGL_EINVAL, "NULL pointer");
+  GGL_REQUIRE((col && el && x && (edge || (alpha && de))) || E == 0, GGL_EINVAL, "NULL pointer");
+  if (edge && !alpha && !de) return GGL_OK;  // neither gradient is wanted
   GatDims d{};
   d.slope = slope; d.N = N; d.H = H; d.C = C; d.K = H * C; d.E = E;
-  d.es = (de == alpha + 1) ? 2 : 1;  // de == alpha + 1: one interleaved [E,H,2] buffer
+  d.es = (!edge && de == alpha + 1) ? 2 : 1;  // de == alpha + 1: one interleaved [E,H,2] buffer
   d.chunk = p.chunk; d.n_long = p.n_long; d.n_chunks = p.n_chunks;
   if (int rc = set_dropout(d, p_drop, rng_used)) return rc;
   float *pger = p.partial;
@@ -770,7 +810,7 @@ static int gat_bwd_dst_impl(const ggl_segplan_t *plan, const int32_t *col, const
       if (logg < 4) logg = 4;  // >= 16 lanes: covers H <= 16 finishing lanes
       const int64_t wgrid = ceil_div(items << logg, (int64_t)kBlock);
 #define GGL_GAT_WIDE(V, LG, HH)                                                                          \
-  GGL_LAUNCH((gat_bwd_dst_wide_kernel<XT, GT, V, LG, HH>), wgrid, kBlock, s, plan->rowptr, col, order,    \
+  GGL_LAUNCH((gat_bwd_dst_wide_kernel<XT, GT, V, LG, HH, LS>), wgrid, kBlock, s, plan->rowptr, col, order,    \
              plan->long_rows, plan->chunk_ptr, el, er, x, g, out, rowmax, rowden, alpha, de, ger, pger,   \
              rng_used, d)
 #define GGL_GAT_WIDE_H(V, LG)                                                                            \
@@ -792,7 +832,7 @@ static int gat_bwd_dst_impl(const ggl_segplan_t *plan, const int32_t *col, const
 #undef GGL_GAT_WIDE_H
 #undef GGL_GAT_WIDE
       GGL_LAUNCH_CHECK();
-      if (plan->n_long > 0) {
+      if (!edge && plan->n_long > 0) {
         GGL_LAUNCH((gat_bwd_dst_final_kernel), gat_grid_for(plan->n_long * H), kBlock, s, plan->long_rows,
                    plan->chunk_ptr, (const float *)pger, ger, plan->n_long, H);
         GGL_LAUNCH_CHECK();
@@ -802,7 +842,7 @@ static int gat_bwd_dst_impl(const ggl_segplan_t *plan, const int32_t *col, const
   }
 #endif
 #define GGL_GAT_DST(V, CR)                                                                              \
-  GGL_LAUNCH((gat_bwd_dst_kernel<XT, GT, V, CR>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows, \
+  GGL_LAUNCH((gat_bwd_dst_kernel<XT, GT, V, CR, LS>), grid, kBlock, s, plan->rowptr, col, order, plan->long_rows, \
              plan->chunk_ptr, el, er, x, g, out, rowmax, rowden, alpha, de, ger, pger, rng_used, d)
   if (vec8) {  // (16-bit rows only)
     if constexpr (x16) {
@@ -816,7 +856,7 @@ static int gat_bwd_dst_impl(const ggl_segplan_t *plan, const int32_t *col, const
   else GGL_GAT_DST(1, 0);
 #undef GGL_GAT_DST
   GGL_LAUNCH_CHECK();
-  if (plan->n_long > 0) {
+  if (!edge && plan->n_long > 0) {
     GGL_LAUNCH((gat_bwd_dst_final_kernel), gat_grid_for(plan->n_long * H), kBlock, s, plan->long_rows,
                plan->chunk_ptr, (const float *)pger, ger, plan->n_long, H);
     GGL_LAUNCH_CHECK();
@@ -837,7 +877,8 @@ extern "C" int ggl_gat_fused_bwd_dst(const ggl_segplan_t *plan, const int32_t *c
 
 // Source-major half of the backward (gat_bwd_src_kernel above).  planT->partial must hold
 // ggl_partial_bytes(GGL_F32, n_chunks, H*C + H, 0) bytes when the transposed plan has long rows.
-template <typename GT, typename OT>
+// GEL = false: gx alone (ggl_edge_softmax_agg_bwd_src); de and gel are NULL.
+template <typename GT, typename OT, bool GEL = true>
 static int gat_bwd_src_impl(const ggl_segplan_t *planT, const int32_t *colT, const int32_t *posT, const float *alpha,
                             const float *de, const typename TT<GT>::S *g, int64_t H, int64_t C,
                             typename TT<OT>::S *gx, float *gel, void *stream) {
@@ -846,11 +887,11 @@ static int gat_bwd_src_impl(const ggl_segplan_t *planT, const int32_t *colT, con
   GGL_REQUIRE(H > 0 && C > 0, GGL_EINVAL, "H, C and chunk must be positive");
   const int64_t N = p.N;
   if (N == 0) return GGL_OK;
-  GGL_REQUIRE(gx && gel, GGL_EINVAL, "NULL pointer");
-  GGL_REQUIRE((colT && posT && alpha && de && g) || p.E == 0, GGL_EINVAL, "NULL pointer");
+  GGL_REQUIRE(gx && (gel || !GEL), GGL_EINVAL, "NULL pointer");
+  GGL_REQUIRE((colT && posT && alpha && (de || !GEL) && g) || p.E == 0, GGL_EINVAL, "NULL pointer");
   GatDims d{};
   d.N = N; d.H = H; d.C = C; d.K = H * C; d.E = p.E;
-  d.es = (de == alpha + 1) ? 2 : 1;
+  d.es = (GEL && de == alpha + 1) ? 2 : 1;
   d.chunk = p.chunk; d.n_long = p.n_long; d.n_chunks = p.n_chunks;
   float *pacc = p.partial, *pgel = nullptr;
   if (p.n_long > 0) {
@@ -870,7 +911,7 @@ static int gat_bwd_src_impl(const ggl_segplan_t *planT, const int32_t *colT, con
   GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "too many rows for one launch");
   hipStream_t s = as_stream(stream);
 #define GGL_GAT_SRC(V)                                                                                          \
-  GGL_LAUNCH((gat_bwd_src_kernel<GT, OT, V>), grid, kBlock, s, planT->rowptr, colT, posT, p.order, planT->long_rows, \
+  GGL_LAUNCH((gat_bwd_src_kernel<GT, OT, V, GEL>), grid, kBlock, s, planT->rowptr, colT, posT, p.order, planT->long_rows, \
              planT->chunk_ptr, alpha, de, g, gx, gel, pacc, pgel, d)
   if (vec == 8) {  // (16-bit gx only)
     if constexpr (gat_is16<OT>::value) GGL_GAT_SRC(8);
@@ -879,7 +920,10 @@ static int gat_bwd_src_impl(const ggl_segplan_t *planT, const int32_t *colT, con
 #undef GGL_GAT_SRC
   GGL_LAUNCH_CHECK();
   if (planT->n_long > 0) {
-    if constexpr (std::is_same<OT, float>::value)
+    if constexpr (!GEL)
+      GGL_LAUNCH((gat_bwd_src_final_gx_kernel), planT->n_long, kBlock, s, planT->long_rows, planT->chunk_ptr,
+                 (const float *)pacc, gx, d);
+    else if constexpr (std::is_same<OT, float>::value)
       GGL_LAUNCH((gat_bwd_src_final_kernel), planT->n_long, kBlock, s, planT->long_rows, planT->chunk_ptr,
                  (const float *)pacc, (const float *)pgel, gx, gel, d);
     else
@@ -895,6 +939,30 @@ extern "C" int ggl_gat_fused_bwd_src(const ggl_segplan_t *planT, const int32_t *
                                      const float *g, int64_t H, int64_t C, float *gx, float *gel,
                                      void *stream) {
   return gat_bwd_src_impl<float, float>(planT, colT, posT, alpha, de, g, H, C, gx, gel, stream);
+}
+
+// ---- The same three walks on per-edge logits z [E, H] in the caller's edge order (any attention layer that calls
+// segment_softmax on its logits and sums alpha * x[src]): the kernels above with the kLogitEdge policy, f32 only.
+// Contract in include/ggl_mpops.h; on z = LeakyReLU(el[src] + er[dst]) every output has ggl_gat_fused_*'s bits.
+extern "C" int ggl_edge_softmax_agg_fwd(const ggl_segplan_t *plan, const int32_t *col, const float *z, const float *x,
+                                        int64_t H, int64_t C, float p_drop, int64_t *rng_state, float *out,
+                                        float *rowmax, float *rowden, void *stream) {
+  return gat_fwd_impl<float, float, kLogitEdge>(plan, col, z, plan ? plan->perm : nullptr, x, 1.0f, H, C, p_drop,
+                                                rng_state, out, rowmax, rowden, stream);
+}
+
+extern "C" int ggl_edge_softmax_agg_bwd_dst(const ggl_segplan_t *plan, const int32_t *col, const float *z,
+                                            const float *x, const float *g, const float *out, const float *rowmax,
+                                            const float *rowden, int64_t H, int64_t C, float p_drop,
+                                            const int64_t *rng_used, float *alpha, float *gz, void *stream) {
+  return gat_bwd_dst_impl<float, float, kLogitEdge>(plan, col, z, plan ? plan->perm : nullptr, x, g, out, rowmax, rowden,
+                                                    1.0f, H, C, p_drop, rng_used, alpha, gz, nullptr, stream);
+}
+
+extern "C" int ggl_edge_softmax_agg_bwd_src(const ggl_segplan_t *planT, const int32_t *colT, const int32_t *posT,
+                                            const float *alpha, const float *g, int64_t H, int64_t C, float *gx,
+                                            void *stream) {
+  return gat_bwd_src_impl<float, float, false>(planT, colT, posT, alpha, nullptr, g, H, C, gx, nullptr, stream);
 }
 
 // ---- 16-bit storage (an extension: the reference's GAT is f32 only).  Contract in include/ggl_mpops.h: the f32 entry

@@ -25,6 +25,40 @@ struct GatDims {
 
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.0f ? v : __fmul_rn(v, slope); }
 
+// Where the general walks (gat.hip) take the logit s_p of sorted position p, head h, from.  The policy is a template parameter
+// of gat_online, gat_fwd_kernel, gat_bwd_dst_kernel and gat_bwd_dst_wide_kernel, separable by default; everything behind
+// s_p (online softmax, hub chunks and their merges, dropout words, row hand-out) is the same code for both.
+//   kLogitSeparable  GAT: s_p = LeakyReLU(el[col[p], h] + er[i, h]).  The kernels' (el, er) are the two [N, H] terms.
+//   kLogitEdge       any attention layer: s_p = z[e_p, h], e_p = perm ? perm[p] : p the CALLER's edge number, z [E, H] used
+//                    as it is.  The kernels' `el` is z and their `er` slot carries plan->perm (int32, NULL for ids that
+//                    arrived sorted); the backward's `de` is gz, stored at e_p — the caller's order — and may be NULL.
+// rec() is the record of `el` an edge reads: it is asked for next to col[p], so perm[p] -> z is in flight together with
+// col[p] -> x, not behind it.  The edge policy's load is UNCONDITIONAL — without a perm it re-reads col[p] (the line is
+// already on its way) and selects p: written as `perm ? perm[p] : p` the compiler branches around every load and waits
+// for each one (vmcnt(0) per element), which puts the four id / perm pairs of an unrolled group in series.
+enum { kLogitSeparable = 0, kLogitEdge = 1 };
+template <int LS> struct Logit {
+  using Aux = const float *;  // er [N, H]
+  static __device__ __forceinline__ float row(Aux er, int64_t i) { return er[i]; }
+  static __device__ __forceinline__ int64_t rec(Aux, const int32_t *__restrict__, int64_t, int64_t c) { return c; }
+  static __device__ __forceinline__ float raw(float v, float er_i) { return __fadd_rn(v, er_i); }
+  static __device__ __forceinline__ float act(float raw, float slope) { return raw > 0.0f ? raw : __fmul_rn(raw, slope); }
+  static __device__ __forceinline__ float dact(float raw, float ds, float slope) {
+    return raw > 0.0f ? ds : __fmul_rn(ds, slope);
+  }
+};
+template <> struct Logit<kLogitEdge> {
+  using Aux = const int32_t *;  // plan->perm [E] or NULL
+  static __device__ __forceinline__ float row(Aux, int64_t) { return 0.0f; }
+  static __device__ __forceinline__ int64_t rec(Aux perm, const int32_t *__restrict__ col, int64_t p, int64_t) {
+    const int64_t r = (perm ? perm : col)[p];
+    return perm ? r : p;
+  }
+  static __device__ __forceinline__ float raw(float v, float) { return v; }
+  static __device__ __forceinline__ float act(float raw, float) { return raw; }
+  static __device__ __forceinline__ float dact(float, float ds, float) { return ds; }
+};
+
 __device__ __forceinline__ uint32_t pick_word(const U4 &u, int c) {
   return c == 0 ? u.x : (c == 1 ? u.y : (c == 2 ? u.z : u.w));
 }

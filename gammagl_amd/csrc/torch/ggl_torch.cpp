@@ -62,6 +62,7 @@ using torch::autograd::variable_list;
   X(ggl_spmm_grad_w_scratch_bytes) X(ggl_spmm_grad_w)                                                                \
   X(ggl_gat_partial_bytes) X(ggl_gat_fused_fwd) X(ggl_gat_fused_bwd_dst) X(ggl_gat_fused_bwd_src)                      \
   X(ggl_gat_fused_fwd_x16) X(ggl_gat_fused_bwd_dst_x16) X(ggl_gat_fused_bwd_src_x16)                                    \
+  X(ggl_edge_softmax_agg_fwd) X(ggl_edge_softmax_agg_bwd_dst) X(ggl_edge_softmax_agg_bwd_src)                          \
   X(ggl_gat_fast_supported) X(ggl_gat_fast_fwd) X(ggl_gat_fast_bwd) X(ggl_bias_act_fwd)                                \
   X(ggl_bias_act_bwd_workspace_bytes) X(ggl_bias_act_bwd) X(ggl_spmm_epi_ex) X(ggl_segment_epi)                        \
   X(ggl_sample_hop_workspace_bytes) X(ggl_sample_hop)                                                                \
@@ -1120,6 +1121,73 @@ static std::tuple<Tensor, Tensor, Tensor> gat_fused_backward_kernel(const Tensor
                       rng_used, slope, p, fast);
 }
 
+// Edge softmax + aggregate on per-edge logits (ggl_edge_softmax_agg_*, include/ggl_mpops.h): the general GAT walks with the
+// logit read from z [E, H] in the caller's edge order.  out[i, h, :] = sum_{e -> i} dropout(softmax_i(z[:, h]))[e] x[src_e, h, :]
+static void esa_check(const Tensor &index, const Tensor &z, const Tensor &x) {
+  same_device({&z, &x});
+  f32("logits", z); f32("x", x);
+  TORCH_CHECK(index.dim() == 2 && index.size(0) == 2, "edge_softmax_aggregate expects index [2, E]");
+  TORCH_CHECK(x.dim() == 3 && z.dim() == 2 && z.size(1) == x.size(1) && z.size(0) == index.size(1),
+              "edge_softmax_aggregate expects logits [E, H] and x [N_src, H, C] (got logits ", z.sizes(), ", x ", x.sizes(),
+              " for ", index.size(1), " edges)");
+}
+// (out, rowmax, rowden, rng_used)
+static std::tuple<Tensor, Tensor, Tensor, Tensor> esa_forward_kernel(const Tensor &index, const Tensor &z_, const Tensor &x_,
+                                                                     int64_t num_nodes, double p) {
+  esa_check(index, z_, x_);
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout_rate must be in [0, 1)");
+  const auto dev = x_.device();
+  c10::OptionalDeviceGuard guard(dev);
+  auto gp = gat_plan(index, num_nodes, x_.size(0));
+  const Api &a = api_for(dev);
+  Tensor z = z_.contiguous(), x = x_.contiguous();
+  const int64_t N = gp->N_dst, H = x.size(1), C = x.size(2);
+  Tensor out = at::empty({N, H, C}, x.options()), rmax = at::empty({N, H}, x.options()), rden = at::empty({N, H}, x.options());
+  Tensor part;
+  if (gp->fwd->n_long > 0)
+    part = at::empty({static_cast<int64_t>(a.ggl_gat_partial_bytes(gp->fwd->n_chunks, H, C)) + 16}, x.options().dtype(at::kByte));
+  ggl_segplan_t cs = gp->fwd->c(part);
+  const Draw d = draw(dev, p);
+  check(a, a.ggl_edge_softmax_agg_fwd(&cs, gp->col.data_ptr<int32_t>(), z.data_ptr<float>(), x.data_ptr<float>(), H, C,
+                                      static_cast<float>(p), d.ptr(), out.data_ptr<float>(), rmax.data_ptr<float>(),
+                                      rden.data_ptr<float>(), stream_of(dev)));
+  return {out, rmax, rden, d.used};
+}
+// (gz, gx); a gradient that is not needed is not computed and comes back EMPTY: need_x = false skips the source walk,
+// need_z = false the gz stores
+static std::tuple<Tensor, Tensor> esa_backward_kernel(const Tensor &index, const Tensor &z_, const Tensor &x_, const Tensor &grad,
+                                                      const Tensor &out, const Tensor &rmax, const Tensor &rden,
+                                                      const Tensor &rng_used, int64_t num_nodes, double p, bool need_z,
+                                                      bool need_x) {
+  const auto dev = x_.device();
+  c10::OptionalDeviceGuard guard(dev);
+  const Api &a = api_for(dev);
+  Tensor idx = index.contiguous(), z = z_.contiguous(), x = x_.contiguous(), g = grad.contiguous(), oc = out.contiguous();
+  auto gp = gat_plan(idx, num_nodes, x.size(0));
+  const int64_t H = x.size(1), C = x.size(2), E = gp->E;
+  Tensor gz = need_z ? at::empty_like(z) : at::empty({0}, z.options());
+  Tensor gx = need_x ? at::empty({gp->N_src, H, C}, x.options()) : at::empty({0}, x.options());
+  if (!need_z && !need_x) return {gz, gx};
+  void *st = stream_of(dev);
+  Tensor alpha = need_x ? at::empty({std::max<int64_t>(E, 1), H}, x.options()) : Tensor();
+  Tensor part_f = partial_for(a, *gp->fwd, z, H, false);
+  ggl_segplan_t cs = gp->fwd->c(part_f);
+  check(a, a.ggl_edge_softmax_agg_bwd_dst(&cs, gp->col.data_ptr<int32_t>(), z.data_ptr<float>(), x.data_ptr<float>(),
+                                          g.data_ptr<float>(), oc.data_ptr<float>(), rmax.data_ptr<float>(),
+                                          rden.data_ptr<float>(), H, C, static_cast<float>(p), used_ptr(p, rng_used),
+                                          need_x ? alpha.data_ptr<float>() : nullptr,
+                                          need_z ? gz.data_ptr<float>() : nullptr, st));
+  if (need_x) {
+    gp->need_bwd(idx);
+    gp->need_posT(idx);
+    Tensor part_t = partial_for(a, *gp->bwd, z, H * C + H, false);
+    ggl_segplan_t csT = gp->bwd->c(part_t);
+    check(a, a.ggl_edge_softmax_agg_bwd_src(&csT, gp->colT.data_ptr<int32_t>(), gp->posT.data_ptr<int32_t>(),
+                                            alpha.data_ptr<float>(), g.data_ptr<float>(), H, C, gx.data_ptr<float>(), st));
+  }
+  return {gz, gx};
+}
+
 // The same op over a CSR the caller already holds — the argument list of dgNN's GATConvFuse
 // (layers/conv/fusedgat_conv.py:121): rows of the CSR aggregate, no sort.  The plan is cached on row_ptr.
 struct CsrExtra {   // what besides row_ptr identifies the five-tensor structure
@@ -1764,6 +1832,40 @@ static Tensor gat_fused_x16_autograd(const Tensor &index, const Tensor &el, cons
   return gat_autograd(index, el, er, x, slope, num_nodes, p, true, out_f32);
 }
 
+// edge_softmax_aggregate: forward and backward are ops of ggl_attn; gz / gx are asked for only where the input requires grad
+using EsaFwdSig = std::tuple<Tensor, Tensor, Tensor, Tensor>(const Tensor &, const Tensor &, const Tensor &, int64_t, double);
+using EsaBwdSig = std::tuple<Tensor, Tensor>(const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
+                                             const Tensor &, const Tensor &, const Tensor &, int64_t, double, bool, bool);
+struct EsaFn : public torch::autograd::Function<EsaFn> {
+  static Tensor forward(AutogradContext *ctx, const Tensor &index, const Tensor &z, const Tensor &x, int64_t n, double p) {
+    at::AutoDispatchBelowADInplaceOrView below;
+    static auto op = op_handle<EsaFwdSig>("ggl_attn::edge_softmax_aggregate_forward");
+    Tensor out, rmax, rden, used;
+    std::tie(out, rmax, rden, used) = op.call(index, z, x, n, p);
+    ctx->save_for_backward({index, z, x, out, rmax, rden, used});
+    ctx->saved_data["n"] = n;
+    ctx->saved_data["p"] = p;
+    return out;
+  }
+  static variable_list backward(AutogradContext *ctx, variable_list grads) {
+    auto s = ctx->get_saved_variables();
+    static auto op = op_handle<EsaBwdSig>("ggl_attn::edge_softmax_aggregate_backward");
+    const bool need_z = ctx->needs_input_grad(1), need_x = ctx->needs_input_grad(2);
+    auto r = op.call(s[0], s[1], s[2], grads[0], s[3], s[4], s[5], s[6], ctx->saved_data["n"].toInt(),
+                     ctx->saved_data["p"].toDouble(), need_z, need_x);
+    return {Tensor(), need_z ? std::get<0>(r) : Tensor(), need_x ? std::get<1>(r) : Tensor(), Tensor(), Tensor()};
+  }
+};
+// logits [E] with x [N, K] are one head
+static Tensor esa_autograd(const Tensor &index, const Tensor &z, const Tensor &x, c10::optional<int64_t> num_nodes, double p) {
+  if (z.dim() == 1 && x.dim() == 2)
+    return esa_autograd(index, z.unsqueeze(1), x.unsqueeze(1), num_nodes, p).squeeze(1);
+  esa_check(index, z, x);
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout_rate must be in [0, 1)");
+  const int64_t n = num_nodes.has_value() ? *num_nodes : x.size(0);
+  return with_head_pad(x, index.size(1), [&](const Tensor &xp) { return EsaFn::apply(index, z, xp, n, p); });
+}
+
 using GatCsrFwdSig = std::tuple<Tensor, Tensor, Tensor, Tensor, bool>(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                                                                        const Tensor &, const Tensor &, const Tensor &,
                                                                        const Tensor &, double, double);
@@ -1993,6 +2095,21 @@ static std::tuple<Tensor, Tensor, Tensor> gat_bwd_meta(const Tensor &, const Ten
 static Tensor gat_meta(const Tensor &, const Tensor &, const Tensor &, const Tensor &x, double, c10::optional<int64_t> n, double) {
   return at::empty({n.has_value() ? *n : x.size(0), x.size(1), x.size(2)}, x.options());
 }
+static std::tuple<Tensor, Tensor, Tensor, Tensor> esa_fwd_meta(const Tensor &, const Tensor &, const Tensor &x, int64_t n, double) {
+  auto o = x.options();
+  return {at::empty({n, x.size(1), x.size(2)}, o), at::empty({n, x.size(1)}, o), at::empty({n, x.size(1)}, o),
+          at::empty({0}, o.dtype(at::kLong))};
+}
+static std::tuple<Tensor, Tensor> esa_bwd_meta(const Tensor &, const Tensor &z, const Tensor &x, const Tensor &, const Tensor &,
+                                               const Tensor &, const Tensor &, const Tensor &, int64_t, double, bool need_z,
+                                               bool need_x) {
+  return {need_z ? at::empty_like(z) : at::empty({0}, z.options()), need_x ? at::empty_like(x) : at::empty({0}, x.options())};
+}
+static Tensor esa_meta(const Tensor &, const Tensor &z, const Tensor &x, c10::optional<int64_t> n, double) {
+  const int64_t N = n.has_value() ? *n : x.size(0);
+  if (z.dim() == 1 && x.dim() == 2) return at::empty({N, x.size(1)}, x.options());
+  return at::empty({N, x.size(1), x.size(2)}, x.options());
+}
 static std::tuple<Tensor, Tensor, Tensor, Tensor, bool> gat_csr_fwd_meta(const Tensor &rp, const Tensor &, const Tensor &,
                                                                          const Tensor &, const Tensor &, const Tensor &,
                                                                          const Tensor &, const Tensor &x, double, double) {
@@ -2219,3 +2336,26 @@ TORCH_LIBRARY(ggl_grad, m) {
 TORCH_LIBRARY_IMPL(ggl_grad, CPU, m) { m.impl("spmm_grad_w", ggl_torch::spmm_grad_w_kernel); }
 TORCH_LIBRARY_IMPL(ggl_grad, CUDA, m) { m.impl("spmm_grad_w", ggl_torch::spmm_grad_w_kernel); }
 TORCH_LIBRARY_IMPL(ggl_grad, Meta, m) { m.impl("spmm_grad_w", ggl_torch::spmm_grad_w_meta); }
+
+// Edge softmax + aggregate on per-edge logits, a namespace of its own for the same reason: the ggl:: surface is pinned.
+TORCH_LIBRARY(ggl_attn, m) {
+  m.def("edge_softmax_aggregate(Tensor index, Tensor logits, Tensor x, int? num_nodes=None, float dropout_rate=0.) -> Tensor");
+  m.def("edge_softmax_aggregate_forward(Tensor index, Tensor logits, Tensor x, int num_nodes, float dropout_rate) -> "
+        "(Tensor, Tensor, Tensor, Tensor)");
+  m.def("edge_softmax_aggregate_backward(Tensor index, Tensor logits, Tensor x, Tensor grad, Tensor out, Tensor rowmax, "
+        "Tensor rowden, Tensor rng_used, int num_nodes, float dropout_rate, bool need_logits, bool need_x) -> (Tensor, Tensor)");
+}
+#define GGL_ATTN_IMPL(KEY)                                                                          \
+  TORCH_LIBRARY_IMPL(ggl_attn, KEY, m) {                                                            \
+    m.impl("edge_softmax_aggregate_forward", ggl_torch::esa_forward_kernel);                        \
+    m.impl("edge_softmax_aggregate_backward", ggl_torch::esa_backward_kernel);                      \
+  }
+GGL_ATTN_IMPL(CPU)
+GGL_ATTN_IMPL(CUDA)
+#undef GGL_ATTN_IMPL
+TORCH_LIBRARY_IMPL(ggl_attn, Autograd, m) { m.impl("edge_softmax_aggregate", ggl_torch::esa_autograd); }
+TORCH_LIBRARY_IMPL(ggl_attn, Meta, m) {
+  m.impl("edge_softmax_aggregate", ggl_torch::esa_meta);
+  m.impl("edge_softmax_aggregate_forward", ggl_torch::esa_fwd_meta);
+  m.impl("edge_softmax_aggregate_backward", ggl_torch::esa_bwd_meta);
+}

@@ -22,6 +22,7 @@ from torch import nn
 from . import engine as _engine
 from .dense import Linear, _LinearFn, node_matmul
 from .sampler import Block
+from .utils.attention import edge_softmax_aggregate
 from .mpops import (bspmm, gspmm, unsorted_segment_max, unsorted_segment_mean,  # noqa: F401
                     unsorted_segment_sum, use_ext)
 
@@ -433,6 +434,34 @@ class FusedGATConv(GATConv):
         x = _engine(x).gat_fused(edge_index, el, er, x, self.negative_slope, num_nodes=num_nodes,
                                 dropout_rate=self.dropout_rate, training=self.training)
         return self._finish(x[:, :, :C] if pad else x)
+
+
+class AGNNConv(MessagePassing):
+    """agnn_conv.py:40-69: X' = P X with P_ij = softmax_j(beta * cos(x_i, x_j)) over the edges j -> i; `beta` is the only
+    parameter (uniform in [0, 1), or a constant 0 with require_grad=False).  fused=False is the reference's composition
+    (segment_softmax on the [E] logits, then the weighted message sum); fused=True hands the logits and x to
+    utils.edge_softmax_aggregate: one kernel per direction, no [E, K] message tensor."""
+
+    def __init__(self, in_channels, require_grad=True, fused=True):
+        super().__init__()
+        self.in_channels, self.fused = in_channels, fused
+        if require_grad:
+            self.beta = nn.Parameter(torch.rand(1))
+        else:
+            self.beta = nn.Parameter(torch.zeros(1), requires_grad=False)
+
+    def _logits(self, x, edge_index):
+        xn = torch.nn.functional.normalize(x, p=2.0, dim=-1, eps=1e-12)   # tlx.l2_normalize
+        cos = (xn[edge_index[0, :]] * xn[edge_index[1, :]]).sum(dim=-1)
+        return cos * self.beta
+
+    def forward(self, x, edge_index, num_nodes=None):
+        num_nodes = x.shape[0] if num_nodes is None else num_nodes
+        z = self._logits(x, edge_index)
+        if self.fused:
+            return edge_softmax_aggregate(edge_index, z, x, num_nodes)
+        alpha = segment_softmax(z, edge_index[1, :], num_nodes)
+        return self.propagate(x, edge_index, num_nodes=num_nodes, edge_weight=alpha)
 
 
 class GCNModel(nn.Module):

@@ -838,6 +838,29 @@ class Engine:
         return self._head_padded(gp, x, lambda xp: autograd.GATFused.apply(
             self, gp, el.contiguous(), er.contiguous(), xp.contiguous(), negative_slope, p, out_dtype))
 
+    def edge_softmax_aggregate(self, index, logits, x, num_nodes=None, dropout_rate=0.0, training=True):
+        """out[i,h,:] = sum_{e->i} dropout(softmax_i(logits[:,h]))[e] * x[src_e,h,:] in one kernel per direction
+        (ggl_edge_softmax_agg_*): gat_fused with the logit of every edge GIVEN — `logits` [E, H] f32 in the order of
+        `index`'s columns, used as they are — instead of built from el / er; what agnn_conv.py:54-66 and every layer that
+        calls segment_softmax on its logits and sums alpha * x[src] compose from three ops.  `index` [2, E] or a GraphPlan;
+        x [N_src, H, C] f32; logits [E] with x [N_src, K] are one head.  Gradients for logits and x."""
+        if logits.dim() == 1 and x.dim() == 2:
+            return self.edge_softmax_aggregate(index, logits.unsqueeze(1), x.unsqueeze(1), num_nodes, dropout_rate,
+                                               training).squeeze(1)
+        self._dev(index, logits, x)
+        self._check_f32("logits", logits)
+        self._check_f32("x", x)
+        n = x.shape[0] if num_nodes is None else num_nodes
+        gp = index if isinstance(index, GraphPlan) else self.graph_plan(index, n, x.shape[0])
+        if x.dim() != 3 or logits.dim() != 2 or logits.shape[0] != gp.E or logits.shape[1] != x.shape[1]:
+            raise RuntimeError(f"edge_softmax_aggregate expects logits [E, H] and x [N_src, H, C]: got logits "
+                               f"{tuple(logits.shape)}, x {tuple(x.shape)} for {gp.E} edges")
+        p = float(dropout_rate) if training else 0.0
+        if not 0.0 <= p < 1.0:
+            raise ValueError("dropout_rate must be in [0, 1)")
+        return self._head_padded(gp, x, lambda xp: autograd.EdgeSoftmaxAgg.apply(
+            self, gp, logits.contiguous(), xp.contiguous(), p))
+
     def _check_weight(self, weight, gp):
         """An edge-weight vector handed to a kernel as a raw pointer: f32 (spmm_sum_cpu.cpp:22 would raise
         "expected scalar type Float"), one value per edge."""

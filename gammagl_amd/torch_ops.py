@@ -18,12 +18,15 @@ points (+ the fused GAT op and the fused epilogue) are dispatcher ops:
     torch.ops.gammagl_amd.spmm_mean_x16(index, weight, x, out_f32) -> Tensor
     torch.ops.gammagl_amd.gat_fused_x16(index, el, er, x, negative_slope, num_nodes, dropout_rate, out_f32) -> Tensor
     torch.ops.gammagl_amd.spmm_grad_w(index, x, grad, mean) -> Tensor         (not in the reference, see below)
+    torch.ops.gammagl_amd.edge_softmax_aggregate(index, logits, x, num_nodes, dropout_rate) -> Tensor   (see below)
 
 ``spmm_sum`` / ``spmm_mean`` also take ``x`` stored as bf16 / f16 (the reference is f32 only): the sums are made in f32 and
 rounded once to x's dtype.  ``spmm_*_x16(..., out_f32=True)`` returns those f32 sums unrounded.  ``gat_fused`` does the
 same for its ``x`` (``el`` / ``er`` stay f32; softmax and sums in f32), ``gat_fused_x16`` adds the ``out_f32`` choice.
 ``spmm_sum`` / ``spmm_mean`` differentiate with respect to ``weight`` too (the reference's extension does not):
 ``spmm_grad_w`` is that gradient, ``gw[e] = sum_k x[src_e, k] * grad[dst_e, k]`` in f32 (``mean``: grad / edge count first).
+``edge_softmax_aggregate`` is ``gat_fused`` on per-edge logits ``[E, H]`` (any attention layer that calls segment_softmax on
+its logits and sums ``alpha * x[src]``): ``out[i, h] = sum_{e -> i} dropout(softmax_i(logits[:, h]))[e] * x[src_e, h]``, f32.
 
 Kernels are registered for ``CUDA`` / ``AutogradCUDA`` (= HIP on ROCm: libggl_mpops_hip.so) and for ``CPU`` /
 ``AutogradCPU`` (libggl_mpops_host.so, the host build of the same kernel sources) — the reference's ops dispatch
@@ -56,6 +59,7 @@ _SCHEMAS = {
     "gat_fused_x16": "(Tensor index, Tensor el, Tensor er, Tensor x, float negative_slope=0.2, "
                      "int? num_nodes=None, float dropout_rate=0.0, bool out_f32=False) -> Tensor",
     "spmm_grad_w": "(Tensor index, Tensor x, Tensor grad, bool mean) -> Tensor",
+    "edge_softmax_aggregate": "(Tensor index, Tensor logits, Tensor x, int? num_nodes=None, float dropout_rate=0.0) -> Tensor",
 }
 
 _DEF = Library(NS, "DEF")
@@ -84,6 +88,8 @@ def _kernels(get_engine):
         "gat_fused_x16": lambda index, el, er, x, negative_slope=0.2, num_nodes=None, dropout_rate=0.0, out_f32=False:
             _gat_x16(get_engine(), index, el, er, x, negative_slope, num_nodes, dropout_rate, out_f32),
         "spmm_grad_w": lambda index, x, grad, mean: get_engine().spmm_grad_w(index, x, grad, mean),
+        "edge_softmax_aggregate": lambda index, logits, x, num_nodes=None, dropout_rate=0.0:
+            get_engine().edge_softmax_aggregate(index, logits, x, num_nodes, dropout_rate, True),
     }
 
 
@@ -144,7 +150,11 @@ def _register_fakes():
         n = x.shape[0] if num_nodes is None else num_nodes
         return x.new_empty((n,) + tuple(x.shape[1:]), dtype=torch.float32 if out_f32 else x.dtype)
 
-    for name, fn in (("segment_sum", seg), ("segment_mean", seg), ("segment_max", seg_max),
+    def esa(index, logits, x, num_nodes=None, dropout_rate=0.0):
+        n = x.shape[0] if num_nodes is None else num_nodes
+        return x.new_empty((n,) + tuple(x.shape[1:]))
+
+    for name, fn in (("edge_softmax_aggregate", esa), ("segment_sum", seg), ("segment_mean", seg), ("segment_max", seg_max),
                      ("segment_softmax", lambda x, index, N: torch.empty_like(x)),
                      ("spmm_sum", like_x), ("spmm_mean", like_x), ("spmm_max", like_x),
                      ("bspmm_sum", like_x), ("gat_fused", gat),

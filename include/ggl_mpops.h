@@ -67,6 +67,8 @@ extern "C" {
  *   f32 / bf16 / f16 rows).  Purely additive again. */
 /* still 11: + ggl_spmm_epi_x16, ggl_bias_act_fwd_x16, ggl_bias_act_bwd_x16 (the fused epilogue and the bias / ReLU / dropout
  *   pass on bf16 / f16 rows: f32 arithmetic, one rounding at the store).  Purely additive again. */
+/* still 11: + ggl_edge_softmax_agg_{fwd,bwd_dst,bwd_src} (the fused GAT walks on per-edge logits: edge softmax + weighted
+ *   aggregate for any attention layer).  Purely additive again. */
 #define GGL_ABI_VERSION 11
 
 /* dtype codes (AT_DISPATCH_ALL_TYPES_AND2(Half, BFloat16), segment_sum_cpu.cpp:32-33) */
@@ -536,6 +538,33 @@ int ggl_gat_fused_bwd_dst_x16(const ggl_segplan_t *plan, const int32_t *col, con
 int ggl_gat_fused_bwd_src_x16(const ggl_segplan_t *planT, const int32_t *colT, const int32_t *posT, const float *alpha,
                               const float *de, int g_dtype, const void *g, int64_t H, int64_t C, int gx_dtype, void *gx,
                               float *gel, void *stream);
+/* Edge softmax + weighted aggregate on PER-EDGE logits (agnn_conv.py:54-66 and every layer that calls segment_softmax on its
+ * [E, H] logits and sums alpha * x[src]): the three general GAT walks above with the logit read from z instead of built from
+ * el / er.  f32 only.
+ *   out[i,h,:] = sum_{p in row i} drop(softmax_i(z[:,h]))[p] * x[col[p],h,:],   s[p,h] = z[e_p,h],  e_p = perm ? perm[p] : p
+ * z [E,H] is in the CALLER's edge order (plan->perm maps a sorted position to it; NULL for ids that arrived sorted) and is
+ * used as it is: no activation.  Everything behind s is ggl_gat_fused_*'s code: -FLT_MAX start and strict <, one-walk online
+ * softmax, out = acc / (den + 1e-16f), zeros for an empty row, hub chunks merged in chunk order, the same dropout word of
+ * (sorted position, head, seed, offset).  So on z = LeakyReLU(el[src] + er[dst]) (computed in f32) out, rowmax, rowden, alpha
+ * and gx are ggl_gat_fused_fwd / _bwd_dst / _bwd_src's bit for bit, and gz is their `de` in the caller's order.  A row
+ * whose logits are all -inf gives zeros like an empty row (no -inf beats the -FLT_MAX start, every exp(-inf + FLT_MAX) is 0),
+ * one that holds a NaN keeps the maximum of the others (NaN loses the strict <) and gets NaN sums: what the GAT kernels
+ * give for the same s.
+ *   ggl_edge_softmax_agg_fwd     : plan->partial = ggl_gat_partial_bytes(n_chunks, H, C) bytes when the plan has long rows.
+ *   ggl_edge_softmax_agg_bwd_dst : alpha[E,H] by SORTED POSITION (what _bwd_src reads through posT), gz[E,H] = alpha (keep/(1-p)
+ *       <g_i, x_j> - <g_i, out_i>) by the CALLER's edge number, written by the walk itself.  alpha or gz may be NULL: that
+ *       store is skipped (x resp. z needs no gradient).  plan->partial: as ggl_gat_fused_bwd_dst, ggl_partial_bytes(GGL_F32,
+ *       n_chunks, H, 0) bytes when the plan has long rows (the shared preamble asks for it; there is no row sum to keep in it).
+ *   ggl_edge_softmax_agg_bwd_src : gx[j,h,:] = sum_q alpha[posT[q],h] * g[colT[q],h,:]; planT->partial =
+ *       ggl_partial_bytes(GGL_F32, n_chunks, H*C + H, 0) bytes when it has long rows (as ggl_gat_fused_bwd_src). */
+int ggl_edge_softmax_agg_fwd(const ggl_segplan_t *plan, const int32_t *col, const float *z, const float *x, int64_t H,
+                             int64_t C, float p_drop, int64_t *rng_state, float *out, float *rowmax, float *rowden,
+                             void *stream);
+int ggl_edge_softmax_agg_bwd_dst(const ggl_segplan_t *plan, const int32_t *col, const float *z, const float *x,
+                                 const float *g, const float *out, const float *rowmax, const float *rowden, int64_t H,
+                                 int64_t C, float p_drop, const int64_t *rng_used, float *alpha, float *gz, void *stream);
+int ggl_edge_softmax_agg_bwd_src(const ggl_segplan_t *planT, const int32_t *colT, const int32_t *posT, const float *alpha,
+                                 const float *g, int64_t H, int64_t C, float *gx, void *stream);
 /* Fast path of the same op for heads of C = 4, 8, 16, 32 or 64 channels with H * C <= 256
  * (ggl_gat_fast_supported; e.g. the Reddit GAT's 8 x 8): same walks with ~5x fewer vector-ALU instructions
  * (v_exp_f32, one rescale per 4-8 edges, 16-byte index loads, 32-bit panel offsets, FMA) and a backward that
