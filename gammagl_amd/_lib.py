@@ -131,6 +131,9 @@ SIGNATURES = {
     "ggl_edge_softmax_agg_fwd": (c_int, [_P, _V, _V, _V, c_int64, c_int64, c_float, _V, _V, _V, _V, _V]),
     "ggl_edge_softmax_agg_bwd_dst": (c_int, [_P, _V, _V, _V, _V, _V, _V, _V, c_int64, c_int64, c_float, _V, _V, _V, _V]),
     "ggl_edge_softmax_agg_bwd_src": (c_int, [_P, _V, _V, _V, _V, c_int64, c_int64, _V, _V]),
+    "ggl_dot_attn_supported": (c_int, [c_int64, c_int64]),
+    "ggl_policy_dot_attn_fused": (c_int, [c_int64, c_int64, c_int64, c_int64]),
+    "ggl_dot_attn_fwd": (c_int, [_P, _V, _V, _V, _V, c_float, c_int64, c_int64, c_float, _V, _V, _V, _V, _V, _V]),
     "ggl_gat_fused_fwd_x16": (c_int, [_P, _V, _V, _V, c_int, _V, c_float, c_int64, c_int64, c_float, _V, c_int, _V, _V, _V,
                                       _V]),
     "ggl_gat_fused_bwd_dst_x16": (c_int, [_P, _V, _V, _V, c_int, _V, c_int, _V, c_int, _V, _V, _V, c_float, c_int64,

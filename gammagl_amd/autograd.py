@@ -139,6 +139,27 @@ class SpMMMax(torch.autograd.Function):  # src/gspmm.cpp:143-202
         return None, None, None, gx
 
 
+def _edge_dot(eng, gp, x, g, out):
+    """out[e, h] = <x[src(e), h, :], g[dst(e), h, :]> in f32, channels ascending, e the CALLER's edge number: bspmm's weight
+    gradient, and the logits of dot-product attention (x = k, g = q)."""
+    H, C = int(x.shape[1]), int(x.shape[2])
+    # a plan built from the caller's CSR has no COO edge list to walk (gp.index is None): it always takes the
+    # sorted route, whose plain kernel covers any channel count
+    if gp.index is None or (eng.gradw_sorted and eng.lib.ggl_policy_gradw_sorted(H, C)):
+        # along the destination-sorted forward plan, strips staged through LDS (edgedot.hip): the g rows
+        # of a batch are a handful of rows, only x[src] is a random gather — and a coalesced one
+        sb = eng.lib.ggl_bspmm_grad_w_sorted_scratch_bytes(gp.E, gp.N_dst, H, C)
+        scratch = torch.empty(sb // 4, dtype=torch.float32, device=g.device) if sb else None
+        cs = gp.fwd.c_struct(None)
+        eng._check(eng.lib.ggl_bspmm_grad_w_sorted(ctypes.byref(cs), _ptr(gp.col), _ptr(gp.rowidx), _ptr(x),
+                                                   _ptr(g), H, C, _ptr(out), _ptr(scratch),
+                                                   eng._stream(g.device)))
+    else:
+        eng._check(eng.lib.ggl_bspmm_grad_w(_ptr(gp.index), _ptr(x), _ptr(g), gp.E, H, C,
+                                            _ptr(out), eng._stream(g.device)))
+    return out
+
+
 class BSpMMSum(torch.autograd.Function):  # src/gspmm.cpp:204-260
     @staticmethod
     def forward(ctx, eng, gp, w, x):
@@ -155,22 +176,7 @@ class BSpMMSum(torch.autograd.Function):  # src/gspmm.cpp:204-260
         w, x = ctx.saved_tensors
         g = g.contiguous()
         gx = eng._bspmm_fwd(gp.bwd, gp.colT, w, g, gp.N_src)
-        H, C = int(x.shape[1]), int(x.shape[2])
-        gw = torch.empty_like(w)
-        # a plan built from the caller's CSR has no COO edge list to walk (gp.index is None): it always takes the
-        # sorted route, whose plain kernel covers any channel count
-        if gp.index is None or (eng.gradw_sorted and eng.lib.ggl_policy_gradw_sorted(H, C)):
-            # along the destination-sorted forward plan, strips staged through LDS (edgedot.hip): the g rows
-            # of a batch are a handful of rows, only x[src] is a random gather — and a coalesced one
-            sb = eng.lib.ggl_bspmm_grad_w_sorted_scratch_bytes(gp.E, gp.N_dst, H, C)
-            scratch = torch.empty(sb // 4, dtype=torch.float32, device=g.device) if sb else None
-            cs = gp.fwd.c_struct(None)
-            eng._check(eng.lib.ggl_bspmm_grad_w_sorted(ctypes.byref(cs), _ptr(gp.col), _ptr(gp.rowidx), _ptr(x),
-                                                       _ptr(g), H, C, _ptr(gw), _ptr(scratch),
-                                                       eng._stream(g.device)))
-        else:
-            eng._check(eng.lib.ggl_bspmm_grad_w(_ptr(gp.index), _ptr(x), _ptr(g), gp.E, H, C,
-                                                _ptr(gw), eng._stream(g.device)))
+        gw = _edge_dot(eng, gp, x, g, torch.empty_like(w))
         # the reference returns grad_weight although it marked weight non-differentiable
         # (gspmm.cpp:208,259): w.grad is populated there, and here.
         return None, None, gw, gx
@@ -323,6 +329,95 @@ class EdgeSoftmaxAgg(torch.autograd.Function):
             eng._check(eng.lib.ggl_edge_softmax_agg_bwd_src(ctypes.byref(csT), _ptr(gp.colT), _ptr(gp.posT), _ptr(alpha),
                                                             _ptr(g), H, C, _ptr(gx), st))
         return None, None, gz, gx, None
+
+
+def _bspmm_by_perm(eng, plan, col, w, x, n_out):
+    """bspmm_sum over `plan` with the weights read through its permutation in the kernel (w_by_pos = 0): for weights that
+    live for one launch, which the sorted-weight cache should neither remember nor gather."""
+    return eng._bspmm_fwd(plan, col, w, x, n_out, perm_override=plan.perm if plan.perm is not None else plan.wperm)
+
+
+class DotAttention(torch.autograd.Function):
+    """Scaled dot-product graph attention: z[e, h] = scale * <q[dst(e), h], k[src(e), h]>, then EdgeSoftmaxAgg on (z, v).
+    Forward, fused route (ggl_dot_attn_fwd, GPU build, where ggl_dot_attn_supported and the policy say so): the dot is formed
+    inside the aggregate's walk; z is stored — by that walk, in the caller's edge order — only when a backward will read it
+    (or the caller asked for it), so a forward without grad touches no [E, H] array.  Composed route (any other shape, CPU
+    tensors): z = scale * edge dot, chosen as BSpMMSum.backward chooses, then ggl_edge_softmax_agg_fwd.  Both routes run the
+    same backward on the saved z: ggl_edge_softmax_agg_bwd_dst (alpha, gz), _bwd_src (gv), gs = gz * scale, gq = bspmm_sum
+    (plan, gs, k), gk = bspmm_sum(planT, gs, q); a walk whose gradient nobody needs is skipped.
+    Returns (out, z); z is not differentiable and is an empty tensor when it was not formed."""
+
+    @staticmethod
+    def forward(ctx, eng, gp, q, k, v, scale, p_drop=0.0, keep_z=False):
+        ctx.eng = eng
+        dev = v.device
+        N, H, C = gp.N_dst, int(v.shape[1]), int(v.shape[2])
+        need = any(ctx.needs_input_grad[2:5])
+        fused = bool(eng.dot_attn_fused and v.is_cuda and eng.lib.ggl_dot_attn_supported(H, C)
+                     and eng.lib.ggl_policy_dot_attn_fused(H, C, gp.E, gp.N_src))
+        out = torch.empty((N, H, C), dtype=torch.float32, device=dev)
+        rmax = torch.empty((N, H), dtype=torch.float32, device=dev)
+        rden = torch.empty((N, H), dtype=torch.float32, device=dev)
+        part = eng._gat_partial(gp.fwd, H, C, dev)
+        cs = gp.fwd.c_struct(part)
+        z = None
+        if need or keep_z or not fused:
+            z = torch.empty((gp.E, H), dtype=torch.float32, device=dev)
+        if not fused:
+            _edge_dot(eng, gp, k, q, z).mul_(scale)   # one rounded f32 multiply per element
+        rng, rng_used = eng._draw(dev, p_drop)
+        if fused:
+            eng._check(eng.lib.ggl_dot_attn_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(q), _ptr(k), _ptr(v), float(scale), H, C,
+                                                float(p_drop), _ptr(rng), _ptr(out), _ptr(rmax), _ptr(rden), _ptr(z),
+                                                eng._stream(dev)))
+        else:
+            eng._check(eng.lib.ggl_edge_softmax_agg_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(z), _ptr(v), H, C, float(p_drop),
+                                                        _ptr(rng), _ptr(out), _ptr(rmax), _ptr(rden), eng._stream(dev)))
+        eng.stats["dot_attention"] = {"fused": fused, "logits_bytes": 0 if z is None else z.numel() * 4,
+                                      "logits_saved": bool(need)}
+        ctx.gp, ctx.scale, ctx.p_drop, ctx.rng_used = gp, float(scale), float(p_drop), rng_used
+        if need:
+            ctx.save_for_backward(z, q, k, v, out, rmax, rden)
+        zr = z if (keep_z and z is not None) else out.new_empty(0)
+        ctx.mark_non_differentiable(zr)
+        return out, zr
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _gz_unused):
+        eng = ctx.eng
+        gp = ctx.gp
+        need_q, need_k, need_v = ctx.needs_input_grad[2:5]
+        if not (need_q or need_k or need_v):
+            return (None,) * 8
+        z, q, k, v, out, rmax, rden = ctx.saved_tensors
+        g = g.contiguous()
+        dev = g.device
+        H, C = int(v.shape[1]), int(v.shape[2])
+        st = eng._stream(dev)
+        need_z = need_q or need_k
+        alpha = torch.empty((max(gp.E, 1), H), dtype=torch.float32, device=dev) if need_v else None   # sorted positions
+        gs = torch.empty_like(z) if need_z else None                                                  # caller's order
+        part_f = eng._partial(gp.fwd, torch.float32, H, False, dev)  # must outlive the launch
+        cs = gp.fwd.c_struct(part_f)
+        eng._check(eng.lib.ggl_edge_softmax_agg_bwd_dst(
+            ctypes.byref(cs), _ptr(gp.col), _ptr(z), _ptr(v), _ptr(g), _ptr(out), _ptr(rmax), _ptr(rden), H, C,
+            ctx.p_drop, _ptr(ctx.rng_used), _ptr(alpha), _ptr(gs), st))
+        gq = gk = gv = None
+        if need_v:
+            bwd = gp.bwd
+            gv = torch.empty((gp.N_src, H, C), dtype=torch.float32, device=dev)
+            part = eng._partial(bwd, torch.float32, H * C + H, False, dev)
+            csT = bwd.c_struct(part)
+            eng._check(eng.lib.ggl_edge_softmax_agg_bwd_src(ctypes.byref(csT), _ptr(gp.colT), _ptr(gp.posT), _ptr(alpha),
+                                                            _ptr(g), H, C, _ptr(gv), st))
+        if need_z:
+            gs.mul_(ctx.scale)   # d z / d <q, k>
+        if need_q:
+            gq = _bspmm_by_perm(eng, gp.fwd, gp.col, gs, k, gp.N_dst)
+        if need_k:
+            gk = _bspmm_by_perm(eng, gp.bwd, gp.colT, gs, q, gp.N_src)
+        return None, None, gq, gk, gv, None, None, None
 
 
 class BiasAdd(torch.autograd.Function):

@@ -52,7 +52,8 @@ def load_grad():
 
 def load_attn():
     """``torch.ops.ggl_attn`` (the same library): ``edge_softmax_aggregate(index, logits, x, num_nodes=None, dropout_rate=0.)``,
-    edge softmax + weighted aggregate on per-edge logits, with its ``_forward`` / ``_backward`` passes.  A namespace of its
-    own for the reason ``load_grad`` gives."""
+    edge softmax + weighted aggregate on per-edge logits, with its ``_forward`` / ``_backward`` passes, and
+    ``dot_attention(index, q, k, v, num_nodes=None, scale=None, dropout_rate=0.)``, the same with the logits formed from
+    ``scale * <q[dst], k[src]>``, with its passes.  A namespace of its own for the reason ``load_grad`` gives."""
     load()
     return torch.ops.ggl_attn

@@ -42,6 +42,16 @@ extern "C" int ggl_gat_sh_bwd(const ggl_segplan_t *, const int32_t *, const ggl_
   return no_gpu();
 }
 
+// gammagl_amd/csrc/dotattn.hip (its dot is a butterfly of wave shuffles): here dot-product attention is composed from the
+// edge dot and the edge-softmax aggregate, which this build has
+extern "C" int ggl_dot_attn_supported(int64_t, int64_t) { return 0; }
+extern "C" int ggl_policy_dot_attn_fused(int64_t, int64_t, int64_t, int64_t) { return 0; }
+extern "C" int ggl_dot_attn_fwd(const ggl_segplan_t *, const int32_t *, const float *, const float *, const float *, float,
+                                int64_t, int64_t, float, int64_t *, float *, float *, float *, float *, void *) {
+  ggl::set_error("the fused dot-product attention forward exists in the GPU build only");
+  return GGL_EINVAL;
+}
+
 // gammagl_amd/csrc/hub16.hip (LDS + barriers) has no host-emulated build either: the emulated library reports the
 // path as unsupported and the 16-bit sums keep walking their hub rows with the row kernel of reduce.hip.
 extern "C" int ggl_segment_hub16_supported(int, int64_t, const void *, const void *) { return 0; }

@@ -63,6 +63,7 @@ using torch::autograd::variable_list;
   X(ggl_gat_partial_bytes) X(ggl_gat_fused_fwd) X(ggl_gat_fused_bwd_dst) X(ggl_gat_fused_bwd_src)                      \
   X(ggl_gat_fused_fwd_x16) X(ggl_gat_fused_bwd_dst_x16) X(ggl_gat_fused_bwd_src_x16)                                    \
   X(ggl_edge_softmax_agg_fwd) X(ggl_edge_softmax_agg_bwd_dst) X(ggl_edge_softmax_agg_bwd_src)                          \
+  X(ggl_dot_attn_supported) X(ggl_policy_dot_attn_fused) X(ggl_dot_attn_fwd)                                           \
   X(ggl_gat_fast_supported) X(ggl_gat_fast_fwd) X(ggl_gat_fast_bwd) X(ggl_bias_act_fwd)                                \
   X(ggl_bias_act_bwd_workspace_bytes) X(ggl_bias_act_bwd) X(ggl_spmm_epi_ex) X(ggl_segment_epi)                        \
   X(ggl_sample_hop_workspace_bytes) X(ggl_sample_hop)                                                                \
@@ -1188,6 +1189,129 @@ static std::tuple<Tensor, Tensor> esa_backward_kernel(const Tensor &index, const
   return {gz, gx};
 }
 
+// Scaled dot-product graph attention (hgt_conv.py:115-153): z[e, h] = scale * <q[dst_e, h, :], k[src_e, h, :]>, then the op above on
+// (z, v).  Fused route (ggl_dot_attn_fwd, GPU build, where ggl_dot_attn_supported and the policy say so): the dot is formed in
+// the aggregate's walk and z is stored — by that walk, in the caller's edge order — only with keep_logits.  Composed route (any
+// other shape, CPU tensors): z = scale * edge dot (chosen as bspmm_sum_backward_kernel chooses), then ggl_edge_softmax_agg_fwd.
+static void dot_check(const Tensor &index, const Tensor &q, const Tensor &k, const Tensor &v) {
+  same_device({&q, &k, &v});
+  f32("q", q); f32("k", k); f32("v", v);
+  TORCH_CHECK(index.dim() == 2 && index.size(0) == 2, "dot_attention expects index [2, E]");
+  TORCH_CHECK(q.dim() == 3 && k.dim() == 3 && v.dim() == 3 && k.size(0) == v.size(0) && k.size(1) == q.size(1) &&
+                  k.size(2) == q.size(2) && v.size(1) == q.size(1),
+              "dot_attention expects q [N_dst, H, C] and k, v [N_src, H, C]: got q ", q.sizes(), ", k ", k.sizes(), ", v ", v.sizes());
+  TORCH_CHECK(v.size(2) == q.size(2), "dot_attention needs v of k's head width (Cv == C): got C = ", q.size(2), ", Cv = ", v.size(2));
+}
+// out[e, h] = <x[src_e, h, :], g[dst_e, h, :]> in the caller's edge order
+static void edge_dot(const Api &a, GraphPlan &gp, const Tensor &index, const Tensor &x, const Tensor &g, Tensor &out) {
+  const int64_t H = x.size(1), C = x.size(2);
+  void *st = stream_of(g.device());
+  if (a.ggl_policy_gradw_sorted(H, C)) {
+    gp.need_rowidx(index);
+    const size_t sb = a.ggl_bspmm_grad_w_sorted_scratch_bytes(gp.E, gp.N_dst, H, C);
+    Tensor scratch = sb > 0 ? at::empty({static_cast<int64_t>(sb / 4)}, g.options()) : Tensor();
+    ggl_segplan_t cs = gp.fwd->c(Tensor());
+    check(a, a.ggl_bspmm_grad_w_sorted(&cs, gp.col.data_ptr<int32_t>(), gp.rowidx.data_ptr<int32_t>(), x.data_ptr<float>(),
+                                       g.data_ptr<float>(), H, C, out.data_ptr<float>(),
+                                       scratch.defined() ? scratch.data_ptr<float>() : nullptr, st));
+  } else {
+    check(a, a.ggl_bspmm_grad_w(index.data_ptr<int64_t>(), x.data_ptr<float>(), g.data_ptr<float>(), gp.E, H, C,
+                                out.data_ptr<float>(), st));
+  }
+}
+// bspmm_sum with the weights read through the plan's perm in the kernel (w_by_pos = 0): one-launch weights stay out of the
+// sorted-weight cache
+static Tensor bspmm_by_perm(const SegPlan &p, const Tensor &col, const Tensor &w, const Tensor &x, int64_t n_out) {
+  const Api &a = api_for(x.device());
+  const int64_t H = x.size(1), C = x.size(2);
+  Tensor out = at::empty({n_out, H, C}, x.options());
+  Tensor part = partial_for(a, p, x, H * C, false);
+  ggl_segplan_t cs = p.c(part);
+  check(a, a.ggl_bspmm_sum(&cs, col.data_ptr<int32_t>(), w.data_ptr<float>(), 0, x.data_ptr<float>(), H, C,
+                           out.data_ptr<float>(), stream_of(x.device())));
+  return out;
+}
+// (out, rowmax, rowden, rng_used, logits); logits [E, H] in the caller's edge order, or EMPTY when they were not formed
+static std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> dot_forward_kernel(const Tensor &index, const Tensor &q_, const Tensor &k_,
+                                                                             const Tensor &v_, int64_t num_nodes, double scale,
+                                                                             double p, bool keep_logits) {
+  dot_check(index, q_, k_, v_);
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout_rate must be in [0, 1)");
+  const auto dev = v_.device();
+  c10::OptionalDeviceGuard guard(dev);
+  Tensor idx = index.contiguous();
+  auto gp = gat_plan(idx, num_nodes, k_.size(0));
+  TORCH_CHECK(gp->N_dst == q_.size(0), "dot_attention: the graph has ", gp->N_dst, " destinations, q has ", q_.size(0), " rows");
+  const Api &a = api_for(dev);
+  Tensor q = q_.contiguous(), k = k_.contiguous(), v = v_.contiguous();
+  const int64_t N = gp->N_dst, H = v.size(1), C = v.size(2), E = gp->E;
+  const bool fused = dev.is_cuda() && a.ggl_dot_attn_supported(H, C) && a.ggl_policy_dot_attn_fused(H, C, E, gp->N_src);
+  Tensor out = at::empty({N, H, C}, v.options()), rmax = at::empty({N, H}, v.options()), rden = at::empty({N, H}, v.options());
+  Tensor part;
+  if (gp->fwd->n_long > 0)
+    part = at::empty({static_cast<int64_t>(a.ggl_gat_partial_bytes(gp->fwd->n_chunks, H, C)) + 16}, v.options().dtype(at::kByte));
+  ggl_segplan_t cs = gp->fwd->c(part);
+  Tensor z = (keep_logits || !fused) ? at::empty({E, H}, v.options()) : Tensor();
+  if (!fused) {
+    edge_dot(a, *gp, idx, k, q, z);
+    z.mul_(static_cast<float>(scale));   // one rounded f32 multiply per element
+  }
+  const Draw d = draw(dev, p);
+  if (fused)
+    check(a, a.ggl_dot_attn_fwd(&cs, gp->col.data_ptr<int32_t>(), q.data_ptr<float>(), k.data_ptr<float>(), v.data_ptr<float>(),
+                                static_cast<float>(scale), H, C, static_cast<float>(p), d.ptr(), out.data_ptr<float>(),
+                                rmax.data_ptr<float>(), rden.data_ptr<float>(), z.defined() ? z.data_ptr<float>() : nullptr,
+                                stream_of(dev)));
+  else
+    check(a, a.ggl_edge_softmax_agg_fwd(&cs, gp->col.data_ptr<int32_t>(), z.data_ptr<float>(), v.data_ptr<float>(), H, C,
+                                        static_cast<float>(p), d.ptr(), out.data_ptr<float>(), rmax.data_ptr<float>(),
+                                        rden.data_ptr<float>(), stream_of(dev)));
+  return {out, rmax, rden, d.used, keep_logits ? z : at::empty({0}, v.options())};
+}
+// (gq, gk, gv) from the saved logits: the edge-softmax aggregate's two backward walks, gs = gz * scale, gq = bspmm_sum(plan, gs, k),
+// gk = bspmm_sum(planT, gs, q).  A gradient that is not needed is not computed and comes back EMPTY.
+static std::tuple<Tensor, Tensor, Tensor> dot_backward_kernel(const Tensor &index, const Tensor &q_, const Tensor &k_, const Tensor &v_,
+                                                              const Tensor &z_, const Tensor &grad, const Tensor &out,
+                                                              const Tensor &rmax, const Tensor &rden, const Tensor &rng_used,
+                                                              int64_t num_nodes, double scale, double p, bool need_q, bool need_k,
+                                                              bool need_v) {
+  const auto dev = v_.device();
+  c10::OptionalDeviceGuard guard(dev);
+  const Api &a = api_for(dev);
+  Tensor idx = index.contiguous(), q = q_.contiguous(), k = k_.contiguous(), v = v_.contiguous(), z = z_.contiguous(),
+         g = grad.contiguous(), oc = out.contiguous();
+  auto gp = gat_plan(idx, num_nodes, k.size(0));
+  const int64_t H = v.size(1), C = v.size(2), E = gp->E;
+  auto none = [&]() { return at::empty({0}, v.options()); };   // (outputs of an op may not alias one another)
+  if (!need_q && !need_k && !need_v) return {none(), none(), none()};
+  TORCH_CHECK(z.dim() == 2 && z.size(0) == E && z.size(1) == H, "dot_attention_backward needs the forward's logits [E, H]");
+  const bool need_z = need_q || need_k;
+  void *st = stream_of(dev);
+  Tensor alpha = need_v ? at::empty({std::max<int64_t>(E, 1), H}, v.options()) : Tensor();
+  Tensor gs = need_z ? at::empty_like(z) : Tensor();
+  Tensor part_f = partial_for(a, *gp->fwd, z, H, false);
+  ggl_segplan_t cs = gp->fwd->c(part_f);
+  check(a, a.ggl_edge_softmax_agg_bwd_dst(&cs, gp->col.data_ptr<int32_t>(), z.data_ptr<float>(), v.data_ptr<float>(),
+                                          g.data_ptr<float>(), oc.data_ptr<float>(), rmax.data_ptr<float>(),
+                                          rden.data_ptr<float>(), H, C, static_cast<float>(p), used_ptr(p, rng_used),
+                                          need_v ? alpha.data_ptr<float>() : nullptr,
+                                          need_z ? gs.data_ptr<float>() : nullptr, st));
+  Tensor gq = none(), gk = none(), gv = none();
+  if (need_v || need_k) gp->need_bwd(idx);
+  if (need_v) {
+    gp->need_posT(idx);
+    gv = at::empty({gp->N_src, H, C}, v.options());
+    Tensor part_t = partial_for(a, *gp->bwd, z, H * C + H, false);
+    ggl_segplan_t csT = gp->bwd->c(part_t);
+    check(a, a.ggl_edge_softmax_agg_bwd_src(&csT, gp->colT.data_ptr<int32_t>(), gp->posT.data_ptr<int32_t>(),
+                                            alpha.data_ptr<float>(), g.data_ptr<float>(), H, C, gv.data_ptr<float>(), st));
+  }
+  if (need_z) gs.mul_(static_cast<float>(scale));
+  if (need_q) gq = bspmm_by_perm(*gp->fwd, gp->col, gs, k, gp->N_dst);
+  if (need_k) gk = bspmm_by_perm(*gp->bwd, gp->colT, gs, q, gp->N_src);
+  return {gq, gk, gv};
+}
+
 // The same op over a CSR the caller already holds — the argument list of dgNN's GATConvFuse
 // (layers/conv/fusedgat_conv.py:121): rows of the CSR aggregate, no sort.  The plan is cached on row_ptr.
 struct CsrExtra {   // what besides row_ptr identifies the five-tensor structure
@@ -1866,6 +1990,48 @@ static Tensor esa_autograd(const Tensor &index, const Tensor &z, const Tensor &x
   return with_head_pad(x, index.size(1), [&](const Tensor &xp) { return EsaFn::apply(index, z, xp, n, p); });
 }
 
+// dot_attention: as edge_softmax_aggregate; the logits are kept by the forward only where q, k or v requires grad
+using DotFwdSig = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor>(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
+                                                                     int64_t, double, double, bool);
+using DotBwdSig = std::tuple<Tensor, Tensor, Tensor>(const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
+                                                     const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
+                                                     int64_t, double, double, bool, bool, bool);
+struct DotFn : public torch::autograd::Function<DotFn> {
+  static Tensor forward(AutogradContext *ctx, const Tensor &index, const Tensor &q, const Tensor &k, const Tensor &v, int64_t n,
+                        double scale, double p, bool need) {
+    at::AutoDispatchBelowADInplaceOrView below;
+    static auto op = op_handle<DotFwdSig>("ggl_attn::dot_attention_forward");
+    Tensor out, rmax, rden, used, z;
+    std::tie(out, rmax, rden, used, z) = op.call(index, q, k, v, n, scale, p, need);
+    if (need) ctx->save_for_backward({index, q, k, v, z, out, rmax, rden, used});
+    ctx->saved_data["n"] = n;
+    ctx->saved_data["scale"] = scale;
+    ctx->saved_data["p"] = p;
+    return out;
+  }
+  static variable_list backward(AutogradContext *ctx, variable_list grads) {
+    auto s = ctx->get_saved_variables();
+    static auto op = op_handle<DotBwdSig>("ggl_attn::dot_attention_backward");
+    const bool need_q = ctx->needs_input_grad(1), need_k = ctx->needs_input_grad(2), need_v = ctx->needs_input_grad(3);
+    auto r = op.call(s[0], s[1], s[2], s[3], s[4], grads[0], s[5], s[6], s[7], s[8], ctx->saved_data["n"].toInt(),
+                     ctx->saved_data["scale"].toDouble(), ctx->saved_data["p"].toDouble(), need_q, need_k, need_v);
+    return {Tensor(), need_q ? std::get<0>(r) : Tensor(), need_k ? std::get<1>(r) : Tensor(), need_v ? std::get<2>(r) : Tensor(),
+            Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+// q [N, C] with k, v [N, C] are one head
+static Tensor dot_autograd(const Tensor &index, const Tensor &q, const Tensor &k, const Tensor &v, c10::optional<int64_t> num_nodes,
+                           c10::optional<double> scale, double p) {
+  if (q.dim() == 2 && k.dim() == 2 && v.dim() == 2)
+    return dot_autograd(index, q.unsqueeze(1), k.unsqueeze(1), v.unsqueeze(1), num_nodes, scale, p).squeeze(1);
+  dot_check(index, q, k, v);
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout_rate must be in [0, 1)");
+  const int64_t n = num_nodes.has_value() ? *num_nodes : q.size(0);
+  const double sc = scale.has_value() ? *scale : 1.0 / std::sqrt(static_cast<double>(q.size(2)));
+  const bool need = at::GradMode::is_enabled() && (q.requires_grad() || k.requires_grad() || v.requires_grad());
+  return DotFn::apply(index, q, k, v, n, sc, p, need);
+}
+
 using GatCsrFwdSig = std::tuple<Tensor, Tensor, Tensor, Tensor, bool>(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                                                                        const Tensor &, const Tensor &, const Tensor &,
                                                                        const Tensor &, double, double);
@@ -2110,6 +2276,24 @@ static Tensor esa_meta(const Tensor &, const Tensor &z, const Tensor &x, c10::op
   if (z.dim() == 1 && x.dim() == 2) return at::empty({N, x.size(1)}, x.options());
   return at::empty({N, x.size(1), x.size(2)}, x.options());
 }
+static std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> dot_fwd_meta(const Tensor &index, const Tensor &q, const Tensor &,
+                                                                       const Tensor &v, int64_t n, double, double, bool keep) {
+  auto o = v.options();
+  return {at::empty({n, v.size(1), v.size(2)}, o), at::empty({n, v.size(1)}, o), at::empty({n, v.size(1)}, o),
+          at::empty({0}, o.dtype(at::kLong)), keep ? at::empty({index.size(1), v.size(1)}, o) : at::empty({0}, o)};
+}
+static std::tuple<Tensor, Tensor, Tensor> dot_bwd_meta(const Tensor &, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &,
+                                                       const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
+                                                       int64_t, double, double, bool need_q, bool need_k, bool need_v) {
+  auto e = [&]() { return at::empty({0}, v.options()); };
+  return {need_q ? at::empty_like(q) : e(), need_k ? at::empty_like(k) : e(), need_v ? at::empty_like(v) : e()};
+}
+static Tensor dot_meta(const Tensor &, const Tensor &q, const Tensor &, const Tensor &v, c10::optional<int64_t> n,
+                       c10::optional<double>, double) {
+  const int64_t N = n.has_value() ? *n : q.size(0);
+  if (v.dim() == 2) return at::empty({N, v.size(1)}, v.options());
+  return at::empty({N, v.size(1), v.size(2)}, v.options());
+}
 static std::tuple<Tensor, Tensor, Tensor, Tensor, bool> gat_csr_fwd_meta(const Tensor &rp, const Tensor &, const Tensor &,
                                                                          const Tensor &, const Tensor &, const Tensor &,
                                                                          const Tensor &, const Tensor &x, double, double) {
@@ -2344,18 +2528,33 @@ TORCH_LIBRARY(ggl_attn, m) {
         "(Tensor, Tensor, Tensor, Tensor)");
   m.def("edge_softmax_aggregate_backward(Tensor index, Tensor logits, Tensor x, Tensor grad, Tensor out, Tensor rowmax, "
         "Tensor rowden, Tensor rng_used, int num_nodes, float dropout_rate, bool need_logits, bool need_x) -> (Tensor, Tensor)");
+  m.def("dot_attention(Tensor index, Tensor q, Tensor k, Tensor v, int? num_nodes=None, float? scale=None, "
+        "float dropout_rate=0.) -> Tensor");
+  m.def("dot_attention_forward(Tensor index, Tensor q, Tensor k, Tensor v, int num_nodes, float scale, float dropout_rate, "
+        "bool keep_logits) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("dot_attention_backward(Tensor index, Tensor q, Tensor k, Tensor v, Tensor logits, Tensor grad, Tensor out, "
+        "Tensor rowmax, Tensor rowden, Tensor rng_used, int num_nodes, float scale, float dropout_rate, bool need_q, "
+        "bool need_k, bool need_v) -> (Tensor, Tensor, Tensor)");
 }
 #define GGL_ATTN_IMPL(KEY)                                                                          \
   TORCH_LIBRARY_IMPL(ggl_attn, KEY, m) {                                                            \
     m.impl("edge_softmax_aggregate_forward", ggl_torch::esa_forward_kernel);                        \
     m.impl("edge_softmax_aggregate_backward", ggl_torch::esa_backward_kernel);                      \
+    m.impl("dot_attention_forward", ggl_torch::dot_forward_kernel);                                 \
+    m.impl("dot_attention_backward", ggl_torch::dot_backward_kernel);                               \
   }
 GGL_ATTN_IMPL(CPU)
 GGL_ATTN_IMPL(CUDA)
 #undef GGL_ATTN_IMPL
-TORCH_LIBRARY_IMPL(ggl_attn, Autograd, m) { m.impl("edge_softmax_aggregate", ggl_torch::esa_autograd); }
+TORCH_LIBRARY_IMPL(ggl_attn, Autograd, m) {
+  m.impl("edge_softmax_aggregate", ggl_torch::esa_autograd);
+  m.impl("dot_attention", ggl_torch::dot_autograd);
+}
 TORCH_LIBRARY_IMPL(ggl_attn, Meta, m) {
   m.impl("edge_softmax_aggregate", ggl_torch::esa_meta);
   m.impl("edge_softmax_aggregate_forward", ggl_torch::esa_fwd_meta);
   m.impl("edge_softmax_aggregate_backward", ggl_torch::esa_bwd_meta);
+  m.impl("dot_attention", ggl_torch::dot_meta);
+  m.impl("dot_attention_forward", ggl_torch::dot_fwd_meta);
+  m.impl("dot_attention_backward", ggl_torch::dot_bwd_meta);
 }

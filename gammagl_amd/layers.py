@@ -14,15 +14,18 @@ here); every tlx call they make on this path maps 1:1 onto torch (``tlx.gather``
 * ``GATConv``         — layers/conv/gat_conv.py:98-122 (unfused: segment_softmax + propagate)
 * ``FusedGATConv``    — layers/conv/fusedgat_conv.py:89-130 with our single-kernel op in place of
   the external dgNN GATConvFuse
+* ``HGTConv``         — layers/conv/hgt_conv.py:41-153 (fused: utils.dot_attention per edge type)
 * ``GCNModel``        — models/gcn.py:30-64
 """
+import math
+
 import torch
 from torch import nn
 
 from . import engine as _engine
 from .dense import Linear, _LinearFn, node_matmul
 from .sampler import Block
-from .utils.attention import edge_softmax_aggregate
+from .utils.attention import dot_attention, edge_softmax_aggregate
 from .mpops import (bspmm, gspmm, unsorted_segment_max, unsorted_segment_mean,  # noqa: F401
                     unsorted_segment_sum, use_ext)
 
@@ -464,6 +467,82 @@ class AGNNConv(MessagePassing):
         return self.propagate(x, edge_index, num_nodes=num_nodes, edge_weight=alpha)
 
 
+class HGTConv(MessagePassing):
+    """hgt_conv.py:41-153, the Heterogeneous Graph Transformer layer: per node type k / q / v / a linears (relu6, as the
+    reference's Linear(act='relu6')) and a sigmoid skip gate; per edge type (src, rel, dst) the head-wise maps a_rel, m_rel
+    [H, D, D] and the prior p_rel [H].  For an edge type, with k' = k[src_type] a_rel and v' = v[src_type] m_rel on the nodes,
+        alpha = softmax_dst(<k'_j, q_i> * p_rel / sqrt(D)),   out_i = sum_j dropout(alpha) v'_j;
+    the outputs of the edge types that end in a node type are grouped (`group`: sum as the reference, mean, min, max), sent
+    through a_lin and mixed with the input by the gate (in_channels of that type must equal out_channels, as there).
+    fused=False is the reference's message(): three [E, H, D] gathers, segment_softmax, torch dropout on alpha.  fused=True
+    hands q * (p_rel / sqrt(D)) — the prior applied on the nodes, where torch differentiates it — k' and v' to
+    utils.dot_attention with scale = 1: no [E, H, D] tensor, attention dropout from the library's draw."""
+
+    def __init__(self, in_channels, out_channels, metadata, heads=1, group='sum', dropout_rate=0., fused=True):
+        super().__init__()
+        if not isinstance(in_channels, dict):
+            in_channels = {node_type: in_channels for node_type in metadata[0]}
+        if out_channels % heads != 0:
+            raise ValueError("out_channels must be a multiple of heads")
+        if group not in ('sum', 'mean', 'min', 'max'):
+            raise ValueError(f"group={group!r}: sum, mean, min or max")
+        self.in_channels, self.out_channels, self.heads, self.group = in_channels, out_channels, heads, group
+        self.dropout_rate, self.fused = dropout_rate, fused
+        self.dropout = nn.Dropout(dropout_rate)
+        self.k_lin, self.q_lin, self.v_lin, self.a_lin = nn.ModuleDict(), nn.ModuleDict(), nn.ModuleDict(), nn.ModuleDict()
+        self.skip = nn.ParameterDict()
+        for node_type, c in in_channels.items():
+            self.k_lin[node_type] = Linear(c, out_channels)
+            self.q_lin[node_type] = Linear(c, out_channels)
+            self.v_lin[node_type] = Linear(c, out_channels)
+            self.a_lin[node_type] = Linear(out_channels, out_channels)
+            self.skip[node_type] = nn.Parameter(torch.tensor(1.0))
+        self.a_rel, self.m_rel, self.p_rel = nn.ParameterDict(), nn.ParameterDict(), nn.ParameterDict()
+        dim = out_channels // heads
+        for edge_type in metadata[1]:
+            name = '__'.join(edge_type)
+            for table in (self.a_rel, self.m_rel):   # tlx.initializers.TruncatedNormal(): mean 0, stddev 0.05, cut at 2 sigma
+                table[name] = nn.Parameter(nn.init.trunc_normal_(torch.empty(heads, dim, dim), std=0.05, a=-0.1, b=0.1))
+            self.p_rel[name] = nn.Parameter(torch.ones(heads))
+
+    def forward(self, x_dict, edge_index_dict):
+        H, D = self.heads, self.out_channels // self.heads
+        act = torch.nn.functional.relu6
+        k_dict, q_dict, v_dict, out_dict = {}, {}, {}, {}
+        for node_type, x in x_dict.items():
+            k_dict[node_type] = act(self.k_lin[node_type](x)).reshape(-1, H, D)
+            q_dict[node_type] = act(self.q_lin[node_type](x)).reshape(-1, H, D)
+            v_dict[node_type] = act(self.v_lin[node_type](x)).reshape(-1, H, D)
+            out_dict[node_type] = []
+        for edge_type, edge_index in edge_index_dict.items():
+            src_type, _, dst_type = edge_type
+            name = '__'.join(edge_type)
+            k = (k_dict[src_type].transpose(0, 1) @ self.a_rel[name]).transpose(0, 1)
+            v = (v_dict[src_type].transpose(0, 1) @ self.m_rel[name]).transpose(0, 1)
+            q, rel = q_dict[dst_type], self.p_rel[name]
+            n_dst = x_dict[dst_type].shape[0]
+            if self.fused:
+                out = dot_attention(edge_index, q * (rel / math.sqrt(D))[None, :, None], k, v, num_nodes=n_dst, scale=1.0,
+                                    dropout_rate=self.dropout_rate, training=self.training)
+            else:
+                src, dst = edge_index[0, :], edge_index[1, :]
+                alpha = (k[src] * q[dst]).sum(dim=-1) * rel / math.sqrt(D)
+                alpha = self.dropout(segment_softmax(alpha, dst, n_dst))
+                out = self.aggregate(v[src] * alpha.unsqueeze(-1), edge_index, num_nodes=n_dst, aggr='sum')
+            out_dict[dst_type].append(out.reshape(-1, self.out_channels))
+        for node_type, outs in out_dict.items():
+            if not outs:    # no edge type ends here (the reference's tlx.stack([]) raises)
+                out_dict[node_type] = None
+                continue
+            outs = torch.stack(outs)
+            out = {'sum': lambda t: t.sum(0), 'mean': lambda t: t.mean(0), 'min': lambda t: t.min(0)[0],
+                   'max': lambda t: t.max(0)[0]}[self.group](outs)
+            out = act(self.a_lin[node_type](out))
+            gate = torch.sigmoid(self.skip[node_type])
+            out_dict[node_type] = gate * out + (1 - gate) * x_dict[node_type]
+        return out_dict
+
+
 class GCNModel(nn.Module):
     """models/gcn.py:30-64."""
 
@@ -588,5 +667,5 @@ class GraphSAGESampleModel(nn.Module):
         return feat
 
 
-__all__ = ["MessagePassing", "GCNConv", "SAGEConv", "GATConv", "FusedGATConv", "GCNModel", "GATModel", "GraphSAGEFullModel", "GraphSAGESampleModel", "degree",
+__all__ = ["MessagePassing", "GCNConv", "SAGEConv", "GATConv", "FusedGATConv", "HGTConv", "GCNModel", "GATModel", "GraphSAGEFullModel", "GraphSAGESampleModel", "degree",
            "calc_gcn_norm", "segment_softmax", "add_self_loops"]

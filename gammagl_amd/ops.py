@@ -46,6 +46,7 @@ class Engine:
         self.row_order_window, self.row_order_heavy = int(win.value), int(heavy.value)   # see _row_order (0 = global sort)
         self.xcd_run_rows = -1   # -1 = per graph (ggl_policy_xcd_run_rows on the plan's locality), >= 0 forces it
         self.gradw_sorted = True    # bspmm weight gradient along the sorted plan with LDS-staged strips (A/B switch)
+        self.dot_attn_fused = True  # dot-product attention: the dot inside the aggregate's walk (GPU build only; A/B switch)
 
     def clear_caches(self):
         """Drop every cached plan, sorted-weight copy and graph-constant (e.g. GCN norms).  Plans are keyed on
@@ -860,6 +861,45 @@ class Engine:
             raise ValueError("dropout_rate must be in [0, 1)")
         return self._head_padded(gp, x, lambda xp: autograd.EdgeSoftmaxAgg.apply(
             self, gp, logits.contiguous(), xp.contiguous(), p))
+
+    def dot_attention(self, index, q, k, v, num_nodes=None, scale=None, dropout_rate=0.0, training=True,
+                      return_logits=False):
+        """Scaled dot-product graph attention (hgt_conv.py:115-153, every graph-transformer layer):
+        out[i,h,:] = sum_{e->i} dropout(softmax_i(z[:,h]))[e] * v[src_e,h,:] with z[e,h] = scale * <q[dst_e,h,:], k[src_e,h,:]>.
+        q [N_dst, H, C], k and v [N_src, H, C] f32 (q [N, C] with k, v [N, C] are one head); `scale` a float, 1/sqrt(C) by
+        default; a per-head factor (HGT's p_rel) belongs on q.  `index` [2, E] or a GraphPlan; rectangular graphs, empty rows,
+        dropout and `training` as edge_softmax_aggregate.  On the GPU the dot is formed inside the aggregate's walk
+        (ggl_dot_attn_fwd) for C = 8, 16, 32, 64; other widths and CPU tensors compose the edge dot with
+        edge_softmax_aggregate.  Either way everything behind z is edge_softmax_aggregate on (z, v), bit for bit, and z is
+        stored only for a backward.  Gradients for q, k and v.  return_logits=True returns (out, z), z [E, H] in the order
+        of `index`'s columns, detached."""
+        if q.dim() == 2 and k.dim() == 2 and v.dim() == 2:
+            r = self.dot_attention(index, q.unsqueeze(1), k.unsqueeze(1), v.unsqueeze(1), num_nodes, scale, dropout_rate,
+                                   training, return_logits)
+            return (r[0].squeeze(1), r[1].squeeze(1)) if return_logits else r.squeeze(1)
+        self._dev(index, q, k, v)
+        for name, t in (("q", q), ("k", k), ("v", v)):
+            self._check_f32(name, t)
+        if q.dim() != 3 or k.dim() != 3 or v.dim() != 3 or k.shape[0] != v.shape[0] or k.shape[1:] != q.shape[1:] \
+                or v.shape[1] != q.shape[1]:
+            raise RuntimeError(f"dot_attention expects q [N_dst, H, C] and k, v [N_src, H, C]: got q {tuple(q.shape)}, "
+                               f"k {tuple(k.shape)}, v {tuple(v.shape)}")
+        if v.shape[2] != q.shape[2]:
+            raise RuntimeError(f"dot_attention needs v of k's head width (Cv == C): got C = {q.shape[2]}, Cv = {v.shape[2]}")
+        n = q.shape[0] if num_nodes is None else num_nodes
+        gp = index if isinstance(index, GraphPlan) else self.graph_plan(index, n, k.shape[0])
+        if gp.N_dst != q.shape[0] or gp.N_src != k.shape[0]:
+            raise RuntimeError(f"dot_attention: the graph has {gp.N_dst} destinations and {gp.N_src} sources, q has "
+                               f"{q.shape[0]} rows and k {k.shape[0]}")
+        p = float(dropout_rate) if training else 0.0
+        if not 0.0 <= p < 1.0:
+            raise ValueError("dropout_rate must be in [0, 1)")
+        sc = 1.0 / math.sqrt(q.shape[2]) if scale is None else float(scale)
+        if not torch.is_grad_enabled():   # nothing will run backward: no logits are kept (or, fused, formed) for it
+            q, k, v = q.detach(), k.detach(), v.detach()
+        out, z = autograd.DotAttention.apply(self, gp, q.contiguous(), k.contiguous(), v.contiguous(), sc, p,
+                                             bool(return_logits))
+        return (out, z) if return_logits else out
 
     def _check_weight(self, weight, gp):
         """An edge-weight vector handed to a kernel as a raw pointer: f32 (spmm_sum_cpu.cpp:22 would raise

@@ -19,6 +19,7 @@ points (+ the fused GAT op and the fused epilogue) are dispatcher ops:
     torch.ops.gammagl_amd.gat_fused_x16(index, el, er, x, negative_slope, num_nodes, dropout_rate, out_f32) -> Tensor
     torch.ops.gammagl_amd.spmm_grad_w(index, x, grad, mean) -> Tensor         (not in the reference, see below)
     torch.ops.gammagl_amd.edge_softmax_aggregate(index, logits, x, num_nodes, dropout_rate) -> Tensor   (see below)
+    torch.ops.gammagl_amd.dot_attention(index, q, k, v, num_nodes, scale, dropout_rate) -> Tensor        (see below)
 
 ``spmm_sum`` / ``spmm_mean`` also take ``x`` stored as bf16 / f16 (the reference is f32 only): the sums are made in f32 and
 rounded once to x's dtype.  ``spmm_*_x16(..., out_f32=True)`` returns those f32 sums unrounded.  ``gat_fused`` does the
@@ -27,6 +28,8 @@ same for its ``x`` (``el`` / ``er`` stay f32; softmax and sums in f32), ``gat_fu
 ``spmm_grad_w`` is that gradient, ``gw[e] = sum_k x[src_e, k] * grad[dst_e, k]`` in f32 (``mean``: grad / edge count first).
 ``edge_softmax_aggregate`` is ``gat_fused`` on per-edge logits ``[E, H]`` (any attention layer that calls segment_softmax on
 its logits and sums ``alpha * x[src]``): ``out[i, h] = sum_{e -> i} dropout(softmax_i(logits[:, h]))[e] * x[src_e, h]``, f32.
+``dot_attention`` is that op with the logits formed from node rows, ``logits[e, h] = scale * <q[dst_e, h], k[src_e, h]>``
+(``scale`` defaults to ``1 / sqrt(C)``) and ``x = v``: scaled dot-product attention over a graph, f32.
 
 Kernels are registered for ``CUDA`` / ``AutogradCUDA`` (= HIP on ROCm: libggl_mpops_hip.so) and for ``CPU`` /
 ``AutogradCPU`` (libggl_mpops_host.so, the host build of the same kernel sources) — the reference's ops dispatch
@@ -60,6 +63,8 @@ _SCHEMAS = {
                      "int? num_nodes=None, float dropout_rate=0.0, bool out_f32=False) -> Tensor",
     "spmm_grad_w": "(Tensor index, Tensor x, Tensor grad, bool mean) -> Tensor",
     "edge_softmax_aggregate": "(Tensor index, Tensor logits, Tensor x, int? num_nodes=None, float dropout_rate=0.0) -> Tensor",
+    "dot_attention": "(Tensor index, Tensor q, Tensor k, Tensor v, int? num_nodes=None, float? scale=None, "
+                     "float dropout_rate=0.0) -> Tensor",
 }
 
 _DEF = Library(NS, "DEF")
@@ -90,6 +95,8 @@ def _kernels(get_engine):
         "spmm_grad_w": lambda index, x, grad, mean: get_engine().spmm_grad_w(index, x, grad, mean),
         "edge_softmax_aggregate": lambda index, logits, x, num_nodes=None, dropout_rate=0.0:
             get_engine().edge_softmax_aggregate(index, logits, x, num_nodes, dropout_rate, True),
+        "dot_attention": lambda index, q, k, v, num_nodes=None, scale=None, dropout_rate=0.0:
+            get_engine().dot_attention(index, q, k, v, num_nodes, scale, dropout_rate, True),
     }
 
 
@@ -154,7 +161,11 @@ def _register_fakes():
         n = x.shape[0] if num_nodes is None else num_nodes
         return x.new_empty((n,) + tuple(x.shape[1:]))
 
-    for name, fn in (("edge_softmax_aggregate", esa), ("segment_sum", seg), ("segment_mean", seg), ("segment_max", seg_max),
+    def dot(index, q, k, v, num_nodes=None, scale=None, dropout_rate=0.0):
+        n = q.shape[0] if num_nodes is None else num_nodes
+        return v.new_empty((n,) + tuple(v.shape[1:]))
+
+    for name, fn in (("dot_attention", dot), ("edge_softmax_aggregate", esa), ("segment_sum", seg), ("segment_mean", seg), ("segment_max", seg_max),
                      ("segment_softmax", lambda x, index, N: torch.empty_like(x)),
                      ("spmm_sum", like_x), ("spmm_mean", like_x), ("spmm_max", like_x),
                      ("bspmm_sum", like_x), ("gat_fused", gat),

@@ -12,7 +12,7 @@ cut into chunks, attention dropout from the library's counter-based draw.
 from .. import engine as _engine
 from .. import mpops
 
-__all__ = ["edge_softmax_aggregate"]
+__all__ = ["edge_softmax_aggregate", "dot_attention"]
 
 
 def edge_softmax_aggregate(edge_index, logits, x, num_nodes=None, dropout_rate=0.0, training=True):
@@ -47,3 +47,33 @@ def edge_softmax_aggregate(edge_index, logits, x, num_nodes=None, dropout_rate=0
         ops = cpp_ops.load_attn()
     n = None if num_nodes is None else int(num_nodes)
     return ops.edge_softmax_aggregate(mpops._ids(edge_index, x), logits, x, n, p)
+
+
+def dot_attention(edge_index, q, k, v, num_nodes=None, scale=None, dropout_rate=0.0, training=True):
+    """Scaled dot-product attention over a graph: ``z[e, h] = scale * <q[dst(e), h, :], k[src(e), h, :]>`` and
+    ``out[i, h, :] = sum over edges e with dst(e) = i of drop(softmax_i(z[:, h]))[e] * v[src(e), h, :]``.
+
+    What hgt_conv.py:115-153 writes as ``reduce_sum(k_j * q_i, -1) * rel / sqrt(D)`` -> ``segment_softmax`` -> ``v_j * alpha``
+    with three ``[E, H, C]`` gathers.  ``q`` [N_dst, H, C], ``k`` and ``v`` [N_src, H, C] f32 (``v`` has k's head width;
+    2-d tensors are one head); ``scale`` is a float, ``1 / sqrt(C)`` by default — a learnable per-head factor such as HGT's
+    ``p_rel`` is applied to ``q`` on the nodes, where torch differentiates it.  ``num_nodes``, ``dropout_rate`` and
+    ``training`` as :func:`edge_softmax_aggregate`, whose numerics everything behind ``z`` shares bit for bit.
+
+    On the GPU, for C = 8, 16, 32 or 64, the dot is formed inside the aggregate's walk (``ggl_dot_attn_fwd``):
+    the edge list is read once and ``z`` is written only when a backward will read it — a forward without grad touches no
+    ``[E, H]`` array.  Other widths and CPU tensors compose the library's edge dot with :func:`edge_softmax_aggregate`.
+    The two routes sum the C products of a dot in different orders, so their ``z`` agree to
+    ``gamma_{C+1} |scale| sum_c |q_c k_c|`` of the exact value each, not bit for bit.  Differentiable in q, k and v.
+
+    Route: as :func:`edge_softmax_aggregate` (``torch.ops.ggl_attn`` on the shipped library)."""
+    _engine(v)._dev(edge_index, q, k, v)
+    p = float(dropout_rate) if training else 0.0
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout_rate must be in [0, 1)")
+    ops = mpops._ops_for(v)
+    if ops is not mpops._py_ops:
+        from .. import cpp_ops
+
+        ops = cpp_ops.load_attn()
+    n = None if num_nodes is None else int(num_nodes)
+    return ops.dot_attention(mpops._ids(edge_index, v), q, k, v, n, None if scale is None else float(scale), p)

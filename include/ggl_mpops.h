@@ -69,6 +69,8 @@ extern "C" {
  *   pass on bf16 / f16 rows: f32 arithmetic, one rounding at the store).  Purely additive again. */
 /* still 11: + ggl_edge_softmax_agg_{fwd,bwd_dst,bwd_src} (the fused GAT walks on per-edge logits: edge softmax + weighted
  *   aggregate for any attention layer).  Purely additive again. */
+/* still 11: + ggl_dot_attn_supported, ggl_dot_attn_fwd, ggl_policy_dot_attn_fused (scaled dot-product graph attention: the
+ *   logit formed inside the aggregate's walk).  Purely additive again. */
 #define GGL_ABI_VERSION 11
 
 /* dtype codes (AT_DISPATCH_ALL_TYPES_AND2(Half, BFloat16), segment_sum_cpu.cpp:32-33) */
@@ -565,6 +567,28 @@ int ggl_edge_softmax_agg_bwd_dst(const ggl_segplan_t *plan, const int32_t *col, 
                                  int64_t C, float p_drop, const int64_t *rng_used, float *alpha, float *gz, void *stream);
 int ggl_edge_softmax_agg_bwd_src(const ggl_segplan_t *planT, const int32_t *colT, const int32_t *posT, const float *alpha,
                                  const float *g, int64_t H, int64_t C, float *gx, void *stream);
+/* Scaled dot-product graph attention, forward (hgt_conv.py:115-153 and every graph-transformer layer), f32, GPU build only
+ * (csrc/dotattn.hip; the host build answers supported = 0 and fails the launch):
+ *   z[e,h]     = scale * <q[dst(e),h,:], k[src(e),h,:]>            q [N_dst,H,C], k, v [N_src,H,C]
+ *   out[i,h,:] = sum_{p in row i} drop(softmax_i(z[:,h]))[p] * v[col[p],h,:]
+ * in ONE walk of the destination-sorted plan: the g = C / 4 lanes of a head multiply their four channels (ascending) and add
+ * the partial sums with a butterfly of wave shuffles, which leaves the same bits in every lane; everything behind z is
+ * ggl_edge_softmax_agg_fwd's code.  Hence the contract: with z_out != NULL the logits the walk used are stored, [E,H] in the
+ * CALLER's edge order (through plan->perm), and out / rowmax / rowden are ggl_edge_softmax_agg_fwd(plan, col, z_out, v, ...)'s
+ * bit for bit — hub chunks and dropout with the same rng_state included; with z_out == NULL out has the same bits and no
+ * [E,H] array is touched.  z itself is within gamma_{C+1} |scale| sum_c |q_c k_c| of the exact value (gamma_n = n u / (1 - n u),
+ * u = 2^-24); it does not have the bits of ggl_bspmm_grad_w*, which adds the C products serially.  The backward is composed
+ * by the caller from ggl_edge_softmax_agg_bwd_dst / _bwd_src on z_out and two ggl_bspmm_sum walks with gz * scale.
+ * q, k, v, out and plan->partial must be 16-byte aligned; plan->partial = ggl_gat_partial_bytes(n_chunks, H, C) bytes when the
+ * plan has long rows; rng_state as ggl_gat_fused_fwd.
+ *   ggl_dot_attn_supported(H, C)           : 1 for C = 8, 16, 32, 64 and any H > 0.
+ *   ggl_policy_dot_attn_fused(H, C, E, N_in): 1 where the fused forward is the default over edge dot + ggl_edge_softmax_agg_fwd
+ *       (profiles/dot_attention.txt); never 1 for an unsupported shape. */
+int ggl_dot_attn_supported(int64_t H, int64_t C);
+int ggl_policy_dot_attn_fused(int64_t H, int64_t C, int64_t E, int64_t N_in);
+int ggl_dot_attn_fwd(const ggl_segplan_t *plan, const int32_t *col, const float *q, const float *k, const float *v,
+                     float scale, int64_t H, int64_t C, float p_drop, int64_t *rng_state, float *out, float *rowmax,
+                     float *rowden, float *z_out, void *stream);
 /* Fast path of the same op for heads of C = 4, 8, 16, 32 or 64 channels with H * C <= 256
  * (ggl_gat_fast_supported; e.g. the Reddit GAT's 8 x 8): same walks with ~5x fewer vector-ALU instructions
  * (v_exp_f32, one rescale per 4-8 edges, 16-byte index loads, 32-bit panel offsets, FMA) and a backward that

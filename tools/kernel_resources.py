@@ -15,8 +15,8 @@ for ln in p.stderr.splitlines():
     if m:
         cur = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip().split("(")[0]
         d = {}
-    for k in ("VGPRs", "AGPRs", "SGPRs", "Occupancy", "ScratchSize"):
-        m = re.search(r" " + k + r"[^:]*: (\d+)", ln)
+    for k in ("VGPRs", "AGPRs", "SGPRs", "VGPRs Spill", "SGPRs Spill", "Occupancy", "ScratchSize"):
+        m = re.search(r" " + k + r"(?: \[[^\]]*\])?: (\d+)", ln)   # "VGPRs: 88" is not "VGPRs Spill: 0"
         if m:
             d[k] = int(m.group(1))
     if "LDS Size" in ln and cur and flt in cur:
