@@ -412,4 +412,20 @@ __device__ __forceinline__ int64_t xcd_remap(int64_t b, int64_t nb, int swizzle)
   return ((k / B) * 8 + xcd) * B + (k % B);
 }
 
+// Chunk `cid` of a plan's long rows: slot = the last j with chunk_ptr[j] <= cid (the long row that owns the chunk),
+// row = long_rows[slot], [beg, end) = the chunk's sorted positions.
+struct HubChunk { int64_t slot, row, beg, end; };
+__device__ __forceinline__ HubChunk hub_chunk(const int64_t *rowptr, const int32_t *long_rows, const int64_t *chunk_ptr,
+                                              int64_t n_long, int64_t chunk, int64_t cid) {
+  int64_t lo = 0, hi = n_long - 1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) >> 1;
+    if (chunk_ptr[mid] <= cid) lo = mid; else hi = mid - 1;
+  }
+  const int64_t row = long_rows[lo];
+  const int64_t beg = rowptr[row] + (cid - chunk_ptr[lo]) * chunk;
+  const int64_t rend = rowptr[row + 1];
+  return HubChunk{lo, row, beg, (beg + chunk < rend) ? beg + chunk : rend};
+}
+
 }  // namespace ggl

@@ -8,7 +8,8 @@
 // [E,.] intermediates in HBM.
 //
 // Forward (ONE launch + a tiny combine for hub rows): a lane group owns one destination row, each lane
-// VEC channels of one head, and walks the row ONCE with an online softmax (gat_online below): running
+// VEC channels of one head, and walks the row ONCE with an online softmax (gat_online / gat_fwd_kernel,
+// gat_common.hpp: the walk is shared with dotattn.hip): running
 // max, denominator and weighted sum, rescaled when the max moves; out = acc / (den + 1e-16).  (The first
 // version walked the row three times as the in-tree math does — max, denominator, weighted sum — and
 // was latency-bound on the two extra index/el walks: 9.3 ms on the Reddit-sized graph.)
@@ -31,140 +32,6 @@
 #include "gat_common.hpp"
 
 namespace ggl {
-
-// One walk over positions [beg, end) of a destination row for head h, channels [kk, kk+VEC):
-//   m   = max_p s_p,   s_p = LeakyReLU(el[col[p],h] + er_i)
-//   den = sum_p exp(s_p - m)
-//   acc = sum_p exp(s_p - m) * x[col[p], kk:kk+VEC]
-// computed online: the running (den, acc) are rescaled by exp(m_old - m_new) whenever a new maximum
-// appears (O(log len) times on average), so every feature row, el value and column index is read exactly
-// once.  The in-tree chain (softmax.py:29-35) makes three passes (max, sum, weighted sum); the one-walk
-// form differs from it only in rounding (a few ulp per rescale; the parity bar for float reductions is
-// 1e-5 relative and is tested against the oracle's three-pass restatement).  Four feature rows in flight.
-// DROP: attention dropout — the softmax statistics (m, den) see every edge, the weighted sum only the
-// kept ones, scaled by 1/(1-p): out = sum_p keep_p alpha_p x_p / (1-p), alpha = softmax over ALL edges.
-// Random word of (position p, head h): drop_word(p, h) above — a 15-instruction counter-based mix, so a draw per
-// edge is affordable in every walk (with Philox4x32-10 a draw per edge doubled the forward: 4.1 -> 9.4 ms, and the
-// walks were aligned to multiples of 4 to share one 4-word block; the alignment is kept for the 16-byte index loads).
-// XT: how x is stored (float, or mxbf16_t / mxf16_t: 16-bit storage widened at the load; everything below is f32).
-// LS: where s_p comes from (gat_common.hpp Logit): el / er as above, or per-edge logits z read through `aux` = plan->perm.
-template <typename XT, int VEC, bool DROP, int LS = kLogitSeparable>
-__device__ __forceinline__ void gat_online(const int32_t *__restrict__ col, const float *__restrict__ el,
-                                           typename Logit<LS>::Aux __restrict__ aux,
-                                           const typename TT<XT>::S *__restrict__ x, float er_i, float slope, int64_t H,
-                                           int64_t K, int64_t h, int64_t kk, int64_t beg, int64_t end,
-                                           const GatDims &d, const int64_t *__restrict__ rng,
-                                           float &m, float &den, float (&acc)[VEC]) {
-  m = -FLT_MAX;  // unsorted_segment_max: lowest() fill, strict <
-  den = 0.0f;
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) acc[i] = 0.0f;
-  const uint64_t seed = DROP ? (uint64_t)rng[0] : 0, offset = DROP ? (uint64_t)rng[1] : 0;
-  auto absorb = [&](uint32_t word, float s, const float (&v)[VEC]) {
-    if (m < s) {  // new maximum: bring the running sums to the new reference point
-      const float sc = GGL_EXPF(__fadd_rn(m, -s));  // m = -FLT_MAX on the first element: exp(-inf) = 0
-      den = __fmul_rn(den, sc);
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) acc[i] = __fmul_rn(acc[i], sc);
-      m = s;
-    }
-    const float e = GGL_EXPF(__fadd_rn(s, -m));
-    den = __fadd_rn(den, e);
-    float ek = e;
-    if (DROP) ek = (word >= d.drop_thresh) ? __fmul_rn(e, d.drop_scale) : 0.0f;
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) acc[i] = __fadd_rn(acc[i], __fmul_rn(v[i], ek));
-  };
-  using LP = Logit<LS>;
-  auto single = [&](int64_t q) {
-    const int64_t c0 = col[q];
-    const int64_t e0 = LP::rec(aux, col, q, c0);
-    float v0[VEC];
-    RowV<XT, VEC>::load(x + c0 * K + kk, v0);
-    absorb(DROP ? drop_word(q, H, h, offset, seed) : 0u, LP::act(LP::raw(el[e0 * H + h], er_i), slope), v0);
-  };
-  int64_t p = beg;
-  if (DROP) {  // walk up to a multiple of 4 so that each unrolled group shares one draw
-    for (; p < end && (p & 3) != 0; ++p) single(p);
-  }
-  for (; p + 4 <= end; p += 4) {
-    int64_t c[4], e[4];
-    float v[4][VEC], s[4];
-    U4 rw{0u, 0u, 0u, 0u};
-    if (DROP) rw = drop_words4(p >> 2, H, h, offset, seed);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { c[u] = col[p + u]; e[u] = LP::rec(aux, col, p + u, c[u]); }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) RowV<XT, VEC>::load(x + c[u] * K + kk, v[u]);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) s[u] = LP::act(LP::raw(el[e[u] * H + h], er_i), slope);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) absorb(pick_word(rw, u), s[u], v[u]);
-  }
-  for (; p < end; ++p) single(p);
-}
-
-// OT: how out is stored (XT, or float beside 16-bit rows: a last layer's logits).  The hub-chunk partials are f32.
-// LS = kLogitEdge: `el` is z [E, H] and `er` plan->perm (gat_common.hpp Logit).
-template <typename XT, typename OT, int VEC, bool DROP, int LS = kLogitSeparable>
-__global__ __launch_bounds__(kBlock) void gat_fwd_kernel(
-    const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-    const int32_t *__restrict__ row_order, const int32_t *__restrict__ long_rows,
-    const int64_t *__restrict__ chunk_ptr, const float *__restrict__ el, typename Logit<LS>::Aux __restrict__ er,
-    const typename TT<XT>::S *__restrict__ x, typename TT<OT>::S *__restrict__ y, float *__restrict__ rowmax,
-    float *__restrict__ rowden, float *__restrict__ pacc, float *__restrict__ pm,
-    float *__restrict__ pd, const int64_t *__restrict__ rng, const GatDims d) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = threadIdx.x >> 6;
-  const int64_t H = d.H, K = d.K;
-  if (block_id() < d.chunk_blocks) {  // one wavefront per chunk of a long row
-    const int64_t cid = block_id() * kWavesPerBlock + wave;
-    if (cid >= d.n_chunks) return;
-    int64_t lo = 0, hi = d.n_long - 1;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi + 1) >> 1;
-      if (chunk_ptr[mid] <= cid) lo = mid; else hi = mid - 1;
-    }
-    const int64_t row = long_rows[lo];
-    const int64_t beg = rowptr[row] + (cid - chunk_ptr[lo]) * d.chunk;
-    const int64_t rend = rowptr[row + 1];
-    const int64_t end = (beg + d.chunk < rend) ? beg + d.chunk : rend;
-    for (int64_t kk = (int64_t)lane * VEC; kk < K; kk += (int64_t)kWave * VEC) {
-      const int64_t h = kk / d.C;
-      const float er_i = Logit<LS>::row(er, row * H + h);
-      float m, dsum, acc[VEC];
-      gat_online<XT, VEC, DROP, LS>(col, el, er, x, er_i, d.slope, H, K, h, kk, beg, end, d, rng, m, dsum, acc);
-      F32V<VEC>::store(pacc + cid * K + kk, acc);
-      if (kk == h * d.C) {
-        pm[cid * H + h] = m;
-        pd[cid * H + h] = dsum;
-      }
-    }
-    return;
-  }
-  const int L = 1 << d.logL;
-  const int64_t slot = ((block_id() - d.chunk_blocks) * kWavesPerBlock + wave) * (kWave >> d.logL) +
-                       (lane >> d.logL);
-  if (slot >= d.N) return;
-  const int64_t row = row_order ? (int64_t)row_order[slot] : slot;
-  const int li = lane & (L - 1);
-  const int64_t beg = rowptr[row], end = rowptr[row + 1];
-  if (end - beg > d.chunk) return;
-  for (int64_t kk = (int64_t)li * VEC; kk < K; kk += (int64_t)L * VEC) {
-    const int64_t h = kk / d.C;
-    const float er_i = Logit<LS>::row(er, row * H + h);
-    float m, dsum, acc[VEC];
-    gat_online<XT, VEC, DROP, LS>(col, el, er, x, er_i, d.slope, H, K, h, kk, beg, end, d, rng, m, dsum, acc);
-    const float inv = __fadd_rn(dsum, 1e-16f);  // softmax.py:35: exp / (sum + 1e-16)
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) acc[i] = __fdiv_rn(acc[i], inv);
-    RowV<OT, VEC>::store(y + row * K + kk, acc);  // the one rounding of a 16-bit out
-    if (kk == h * d.C) {  // first lane of the head records the softmax statistics
-      rowmax[row * H + h] = m;
-      rowden[row * H + h] = dsum;
-    }
-  }
-}
 
 template <typename OT>
 __device__ __forceinline__ void gat_long_final_body(
@@ -244,15 +111,8 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_kernel(
   const bool is_chunk = item < d.n_chunks;
   int64_t row, beg, end;
   if (is_chunk) {  // chunks carry the lowest item ids: the hub work is dispatched first
-    int64_t lo = 0, hi = d.n_long - 1;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi + 1) >> 1;
-      if (chunk_ptr[mid] <= item) lo = mid; else hi = mid - 1;
-    }
-    row = long_rows[lo];
-    beg = rowptr[row] + (item - chunk_ptr[lo]) * d.chunk;
-    const int64_t rend = rowptr[row + 1];
-    end = (beg + d.chunk < rend) ? beg + d.chunk : rend;
+    const HubChunk hc = hub_chunk(rowptr, long_rows, chunk_ptr, d.n_long, d.chunk, item);
+    row = hc.row; beg = hc.beg; end = hc.end;
   } else {
     const int64_t slot = item - d.n_chunks;
     row = row_order ? (int64_t)row_order[slot] : slot;
@@ -356,12 +216,6 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_kernel(
 // dot; lane h finishes head h (alpha, de, running ger sum in position order).  The host emulation build
 // cannot shuffle between its sequentially executed lanes and keeps using gat_bwd_dst_kernel for every C.
 #ifndef GGL_EMULATE
-template <int LOGG> __device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = (1 << LOGG) >> 1; o > 0; o >>= 1) v = __fadd_rn(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // 16-bit storage (XT / GT as in gat_bwd_dst_kernel) keeps the f32 form's ASSIGNMENT: four channels per lane (8-byte
 // loads of 16-bit rows), the same LOGG and HH for a head shape.  The butterfly's association depends on which
 // channels a lane holds, so this is what keeps alpha / de / ger equal, bit for bit, to the f32 kernel on the widened
@@ -403,15 +257,8 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_dst_wide_kernel(
   const bool is_chunk = item < d.n_chunks;
   int64_t row, beg, end;
   if (is_chunk) {
-    int64_t lo = 0, hi = d.n_long - 1;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi + 1) >> 1;
-      if (chunk_ptr[mid] <= item) lo = mid; else hi = mid - 1;
-    }
-    row = long_rows[lo];
-    beg = rowptr[row] + (item - chunk_ptr[lo]) * d.chunk;
-    const int64_t rend = rowptr[row + 1];
-    end = (beg + d.chunk < rend) ? beg + d.chunk : rend;
+    const HubChunk hc = hub_chunk(rowptr, long_rows, chunk_ptr, d.n_long, d.chunk, item);
+    row = hc.row; beg = hc.beg; end = hc.end;
   } else {
     const int64_t slot = item - d.n_chunks;
     row = row_order ? (int64_t)row_order[slot] : slot;
@@ -596,15 +443,8 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_src_kernel(
   if (block_id() < d.chunk_blocks) {  // one wavefront per chunk of a long row
     const int64_t cid = block_id() * kWavesPerBlock + wave;
     if (cid >= d.n_chunks) return;
-    int64_t lo = 0, hi = d.n_long - 1;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi + 1) >> 1;
-      if (chunk_ptr[mid] <= cid) lo = mid; else hi = mid - 1;
-    }
-    const int64_t row = long_rows[lo];
-    const int64_t beg = rowptr[row] + (cid - chunk_ptr[lo]) * d.chunk;
-    const int64_t rend = rowptr[row + 1];
-    const int64_t end = (beg + d.chunk < rend) ? beg + d.chunk : rend;
+    const HubChunk hc = hub_chunk(rowptr, long_rows, chunk_ptr, d.n_long, d.chunk, cid);
+    const int64_t beg = hc.beg, end = hc.end;
     for (int64_t kk = (int64_t)lane * VEC; kk < K; kk += (int64_t)kWave * VEC) {
       const int64_t h = kk / d.C;
       const bool lead = GEL && (kk == h * d.C);
@@ -702,31 +542,21 @@ static int gat_fwd_impl(const ggl_segplan_t *plan, const int32_t *col, const flo
   if (N == 0) return GGL_OK;
   GGL_REQUIRE((LS == kLogitEdge || er) && out && rowmax && rowden, GGL_EINVAL, "NULL pointer");
   GGL_REQUIRE((col && el && x) || p.E == 0, GGL_EINVAL, "NULL pointer");
-  GatDims d{};
-  d.slope = slope; d.N = N; d.H = H; d.C = C; d.K = H * C; d.E = p.E;
-  d.chunk = p.chunk; d.n_long = p.n_long; d.n_chunks = p.n_chunks;
-  if (int rc = set_dropout(d, p_drop, rng_state)) return rc;
-  float *pacc = p.partial, *pm = nullptr, *pd = nullptr;
-  if (p.n_long > 0) {
-    pm = pacc + p.n_chunks * d.K;
-    pd = pm + p.n_chunks * H;
-    d.chunk_blocks = ceil_div(p.n_chunks, kWavesPerBlock);
-  }
+  GatFwd f;
+  if (int rc = gat_fwd_setup(p, slope, H, C, p_drop, rng_state, f)) return rc;
+  const GatDims &d = f.d;
   auto vec_ok = [&](int v) {
-    return (C % v == 0) && gat_aligned<XT>(x, v) && gat_aligned<OT>(out, v) && gat_aligned<float>(pacc, v) &&
+    return (C % v == 0) && gat_aligned<XT>(x, v) && gat_aligned<OT>(out, v) && gat_aligned<float>(f.pacc, v) &&
            !options().force_generic;
   };
   const bool vec8 = gat_is16<XT>::value && vec_ok(8);
   const bool vec4 = vec8 || vec_ok(4);
   const int vec = vec8 ? 8 : (vec4 ? 4 : 1);
-  d.logL = pow2_log2(ceil_div(d.K, vec));
-  d.nblocks = ceil_div(N, (int64_t)kWavesPerBlock * (kWave >> d.logL));
-  const int64_t grid = d.chunk_blocks + d.nblocks;
-  GGL_REQUIRE(grid < ((int64_t)1 << 31), GGL_EINVAL, "too many rows for one launch");
-  hipStream_t s = as_stream(stream);
-#define GGL_GAT_FWD(V, DR)                                                                              \
-  GGL_LAUNCH((gat_fwd_kernel<XT, OT, V, DR, LS>), grid, kBlock, s, plan->rowptr, col, p.order, plan->long_rows, \
-             plan->chunk_ptr, el, er, x, out, rowmax, rowden, pacc, pm, pd, (const int64_t *)rng_state, d)
+  if (int rc = gat_fwd_grid(f, vec)) return rc;
+#define GGL_GAT_FWD(V, DR)                                                                                           \
+  GGL_LAUNCH((gat_fwd_kernel<XT, OT, V, DR, LS>), f.grid, kBlock, as_stream(stream), plan->rowptr, col, p.order,     \
+             plan->long_rows, plan->chunk_ptr, el, er, x, out, rowmax, rowden, f.pacc, f.pm, f.pd,                   \
+             (const int64_t *)rng_state, d)
   if (vec == 8) {  // (16-bit rows only: the f32 op has no such instantiation)
     if constexpr (gat_is16<XT>::value) {
       if (d.drop_thresh) GGL_GAT_FWD(8, true);
@@ -737,18 +567,7 @@ static int gat_fwd_impl(const ggl_segplan_t *plan, const int32_t *col, const flo
   else if (d.drop_thresh) GGL_GAT_FWD(1, true);
   else GGL_GAT_FWD(1, false);
 #undef GGL_GAT_FWD
-  GGL_LAUNCH_CHECK();
-  if (plan->n_long > 0) {
-    if constexpr (std::is_same<OT, float>::value)
-      GGL_LAUNCH((gat_long_final_kernel), plan->n_long, kBlock, s, plan->long_rows, plan->chunk_ptr,
-                 (const float *)pacc, (const float *)pm, (const float *)pd, out, rowmax, rowden, d);
-    else
-      GGL_LAUNCH((gat_long_final16_kernel<OT>), plan->n_long, kBlock, s, plan->long_rows, plan->chunk_ptr,
-                 (const float *)pacc, (const float *)pm, (const float *)pd, out, rowmax, rowden, d);
-    GGL_LAUNCH_CHECK();
-  }
-  if (d.drop_thresh) return rng_advance(rng_state, stream);  // the next call draws a new mask
-  return GGL_OK;
+  return gat_fwd_finish<OT>(plan, f, out, rowmax, rowden, rng_state, stream);
 }
 
 extern "C" int ggl_gat_fused_fwd(const ggl_segplan_t *plan, const int32_t *col, const float *el,
@@ -1059,27 +878,6 @@ __device__ __forceinline__ int64_t ssm_elem(const int32_t *__restrict__ perm, in
   return perm ? (int64_t)perm[p] : p;
 }
 
-// long-row slot of chunk `cid`: the last j with chunk_ptr[j] <= cid
-__device__ __forceinline__ int64_t ssm_long_slot(const int64_t *__restrict__ chunk_ptr, int64_t n_long, int64_t cid) {
-  int64_t lo = 0, hi = n_long - 1;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (chunk_ptr[mid] <= cid) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// positions [beg, end) of chunk `cid` (long-row slot *slot)
-__device__ __forceinline__ void ssm_chunk_range(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ long_rows,
-                                                const int64_t *__restrict__ chunk_ptr, const SsmDims &d, int64_t cid,
-                                                int64_t &slot, int64_t &beg, int64_t &end) {
-  slot = ssm_long_slot(chunk_ptr, d.n_long, cid);
-  const int64_t row = long_rows[slot];
-  beg = rowptr[row] + (cid - chunk_ptr[slot]) * d.chunk;
-  const int64_t rend = rowptr[row + 1];
-  end = (beg + d.chunk < rend) ? beg + d.chunk : rend;
-}
-
 // Sub-lanes (GPU build only).  With LOGS > 0 a work item's column is shared by S = 2^LOGS lanes that take every S-th
 // sorted position (lane s: beg + s, beg + s + S, ...): for K = 1 a 64-lane load of perm is 64 consecutive entries, a row
 // of 500 elements is 8 steps of a wavefront instead of 500 of a lane, and the lanes of a wavefront finish together.
@@ -1195,8 +993,8 @@ __global__ __launch_bounds__(kBlock) void ssm_fwd_chunk_kernel(const int64_t *__
   int64_t cid, k, s;
   ssm_decode<LOGS>(d.K, cid, k, s);
   if (cid >= d.n_chunks) return;  // whole lane groups leave together: the butterflies stay inside a group
-  int64_t slot, beg, end;
-  ssm_chunk_range(rowptr, long_rows, chunk_ptr, d, cid, slot, beg, end);
+  const HubChunk hc = hub_chunk(rowptr, long_rows, chunk_ptr, d.n_long, d.chunk, cid);
+  const int64_t beg = hc.beg, end = hc.end;
   float m;
   double D;
   ssm_max_den<LOGS>(x, perm, d.K, k, s, beg, end, m, D);
@@ -1243,10 +1041,10 @@ __global__ __launch_bounds__(kBlock) void ssm_fwd_kernel(const int64_t *__restri
   float m;
   double D;
   if (item < d.n_chunks) {  // chunks carry the lowest item ids: the hub work is dispatched first
-    int64_t slot;
-    ssm_chunk_range(rowptr, long_rows, chunk_ptr, d, item, slot, beg, end);
-    m = (float)rowp[(slot * d.K + k) * 2];  // merged once per row by ssm_fwd_merge_kernel
-    D = rowp[(slot * d.K + k) * 2 + 1];
+    const HubChunk hc = hub_chunk(rowptr, long_rows, chunk_ptr, d.n_long, d.chunk, item);
+    beg = hc.beg; end = hc.end;
+    m = (float)rowp[(hc.slot * d.K + k) * 2];  // merged once per row by ssm_fwd_merge_kernel
+    D = rowp[(hc.slot * d.K + k) * 2 + 1];
   } else {
     const int64_t slot = item - d.n_chunks;
     const int64_t row = row_order ? (int64_t)row_order[slot] : slot;
@@ -1309,8 +1107,8 @@ __global__ __launch_bounds__(kBlock) void ssm_bwd_chunk_kernel(const int64_t *__
   int64_t cid, k, s;
   ssm_decode<LOGS>(d.K, cid, k, s);
   if (cid >= d.n_chunks) return;
-  int64_t slot, beg, end;
-  ssm_chunk_range(rowptr, long_rows, chunk_ptr, d, cid, slot, beg, end);
+  const HubChunk hc = hub_chunk(rowptr, long_rows, chunk_ptr, d.n_long, d.chunk, cid);
+  const int64_t beg = hc.beg, end = hc.end;
   double Ssum;
   float ym;
   int64_t pw;
@@ -1363,11 +1161,10 @@ __global__ __launch_bounds__(kBlock) void ssm_bwd_kernel(const int64_t *__restri
   ssm_decode<LOGS>(d.K, item, k, s);
   if (item >= d.n_chunks + d.N) return;
   if (item < d.n_chunks) {
-    int64_t slot, beg, end;
-    ssm_chunk_range(rowptr, long_rows, chunk_ptr, d, item, slot, beg, end);
-    const double Ssum = rowp[(slot * d.K + k) * 2];  // merged once per row by ssm_bwd_merge_kernel
-    const int64_t pwin = (int64_t)rowp[(slot * d.K + k) * 2 + 1];
-    const double T = ssm_bwd_write<LOGS>(y, g, perm, d.K, k, s, beg, end, Ssum, pwin, gx);
+    const HubChunk hc = hub_chunk(rowptr, long_rows, chunk_ptr, d.n_long, d.chunk, item);
+    const double Ssum = rowp[(hc.slot * d.K + k) * 2];  // merged once per row by ssm_bwd_merge_kernel
+    const int64_t pwin = (int64_t)rowp[(hc.slot * d.K + k) * 2 + 1];
+    const double T = ssm_bwd_write<LOGS>(y, g, perm, d.K, k, s, hc.beg, hc.end, Ssum, pwin, gx);
     if (s == 0) part[(item * d.K + k) * 4 + 3] = T;
     return;
   }

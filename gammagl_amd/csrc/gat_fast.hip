@@ -66,16 +66,9 @@ __device__ __forceinline__ bool gat_item(const GatDims &d, const int64_t *__rest
   it.cid = item;
   it.first_chunk = false;
   if (it.is_chunk) {
-    int64_t lo = 0, hi = d.n_long - 1;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi + 1) >> 1;
-      if (chunk_ptr[mid] <= item) lo = mid; else hi = mid - 1;
-    }
-    it.row = long_rows[lo];
-    it.first_chunk = (item == chunk_ptr[lo]);
-    it.beg = rowptr[it.row] + (item - chunk_ptr[lo]) * d.chunk;
-    const int64_t rend = rowptr[it.row + 1];
-    it.end = (it.beg + d.chunk < rend) ? it.beg + d.chunk : rend;
+    const HubChunk hc = hub_chunk(rowptr, long_rows, chunk_ptr, d.n_long, d.chunk, item);
+    it.row = hc.row; it.beg = hc.beg; it.end = hc.end;
+    it.first_chunk = (item == chunk_ptr[hc.slot]);
     return true;
   }
   const int64_t slot = item - d.n_chunks;

@@ -544,17 +544,8 @@ __global__ __launch_bounds__(kBlock) GGL_RR_WAVES(T, VEC, OP, U, RAG) void row_r
     const int c32 = __builtin_amdgcn_readfirstlane((int)(block_id() * kWavesPerBlock + wave));
     const int64_t cid = (int64_t)(uint32_t)c32;
     if (cid >= d.n_chunks) return;
-    // owning long row: last j with chunk_ptr[j] <= cid
-    int64_t lo = 0, hi = d.n_long - 1;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi + 1) >> 1;
-      if (chunk_ptr[mid] <= cid) lo = mid; else hi = mid - 1;
-    }
-    const int64_t row = long_rows[lo];
-    const int64_t local = cid - chunk_ptr[lo];
-    const int64_t rbeg = rowptr[row], rend = rowptr[row + 1];
-    const int64_t beg = rbeg + local * d.chunk;
-    const int64_t end = (beg + d.chunk < rend) ? beg + d.chunk : rend;
+    const HubChunk hc = hub_chunk(rowptr, long_rows, chunk_ptr, d.n_long, d.chunk, cid);
+    const int64_t row = hc.row, beg = hc.beg, end = hc.end;
     for (int64_t k0 = (int64_t)lane * VEC; k0 < d.K; k0 += (int64_t)kWave * VEC) {
       const int64_t kk = ragged_base<VEC, RAG>(d.K, k0);
       A acc[VEC];
@@ -1506,15 +1497,8 @@ __global__ __launch_bounds__(kBlock) void max_mask_seq_kernel(const int64_t *__r
   if (block_id() < chunk_blocks) {
     const int64_t cid = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(block_id() * kWavesPerBlock + wave));
     if (cid >= n_chunks) return;
-    int64_t lo = 0, hi = n_long - 1;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi + 1) >> 1;
-      if (chunk_ptr[mid] <= cid) lo = mid; else hi = mid - 1;
-    }
-    row = long_rows[lo];
-    beg = rowptr[row] + (cid - chunk_ptr[lo]) * chunk;
-    const int64_t rend = rowptr[row + 1];
-    end = beg + chunk < rend ? beg + chunk : rend;
+    const HubChunk hc = hub_chunk(rowptr, long_rows, chunk_ptr, n_long, chunk, cid);
+    row = hc.row; beg = hc.beg; end = hc.end;
   } else {
     row = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)((block_id() - chunk_blocks) * kWavesPerBlock + wave));
     if (row >= N) return;

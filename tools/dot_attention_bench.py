@@ -177,14 +177,15 @@ for (H, C), rows in verdict.items():
         + "; ".join(f"{r[0]}: composed {r[1]:.2f} fused {r[2]:.2f} ms, spread {100 * r[3]:.1f} %" for r in rows) + ")"
         + f"   library answers {eng.lib.ggl_policy_dot_attn_fused(H, C, 0, 0)}")
 
-say("\n## registers, scratch and occupancy of the new instantiations (tools/kernel_resources.py gammagl_amd/csrc/dotattn.hip dot_attn;")
-say("## dot_attn_fwd_kernel<log2(C / 4), dropout, z_out>), beside the walk it extends")
+say("\n## registers, scratch and occupancy of the dot instantiations of the shared walk (tools/kernel_resources.py")
+say("## gammagl_amd/csrc/dotattn.hip gat_fwd_kernel; gat_fwd_kernel<float, float, 4, dropout, kLogitDot + 2 log2(C / 4) + z_out>,")
+say("## kLogitDot = 2), beside the edge-logit instantiation of the same walk")
 if args.resources_from:
     with open(args.resources_from) as f:
         res = f.read()
 else:
     tool = os.path.join(REPO, "tools", "kernel_resources.py")
-    res = subprocess.run([sys.executable, tool, os.path.join(REPO, "gammagl_amd", "csrc", "dotattn.hip"), "dot_attn"],
+    res = subprocess.run([sys.executable, tool, os.path.join(REPO, "gammagl_amd", "csrc", "dotattn.hip"), "gat_fwd_kernel"],
                          capture_output=True, text=True).stdout
     res += subprocess.run([sys.executable, tool, os.path.join(REPO, "gammagl_amd", "csrc", "gat.hip"),
                            "gat_fwd_kernel<float, float, 4, false, 1>"], capture_output=True, text=True).stdout
