@@ -116,6 +116,9 @@ SIGNATURES = {
     "ggl_bias_act_fwd": (c_int, [_V, _V, c_int64, c_int64, c_int, c_float, _V, _V, _V]),
     "ggl_bias_act_bwd_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "ggl_bias_act_bwd": (c_int, [_V, _V, c_int64, c_int64, c_int, c_float, _V, _V, _V, _V, c_size_t, _V]),
+    "ggl_linear_bias_act_bwd": (c_int, [_V, c_int64, _V, _V, c_int64, c_int64, c_int64, c_int, c_float, _V, _V, _V, _V, c_size_t,
+                                        _V]),
+    "ggl_policy_linear_epi_bwd": (c_int, [c_int64, c_int64, c_int64]),
     "ggl_spmm_epi_ex": (c_int, [_P, _V, _V, c_int, _V, c_int64, c_int64, _V, c_int64, c_int, c_int, _V, c_int64,
                                 _V, c_int, c_float, _V, c_int64, c_int64, c_int, _V]),
     "ggl_spmm_epi_x16": (c_int, [_P, _V, _V, c_int, c_int, _V, c_int64, c_int64, c_int, _V, c_int64, c_int, _V, c_int64,

@@ -258,6 +258,21 @@ __global__ __launch_bounds__(kBlock) void colsum_stage1_kernel(const float *__re
   for (int64_t k = k0; k < K; k += kp) {
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;  // 4 independent chains, combined in a fixed order
     int64_t r = r0 + j;
+    // A thread walks at most 64 rows and the launch is small (a [16384, 256] partial matrix is 256 blocks, the level
+    // behind it 4): what it waits for is latency, so the 16 loads of four steps are issued before the first add.  The
+    // adds are the four-row step's below, in its order: same chains, same bits.
+    for (; r + 15 * (int64_t)groups < r1; r += 16 * (int64_t)groups) {
+      float v[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) v[i] = g[(r + i * (int64_t)groups) * K + k];
+#pragma unroll
+      for (int i = 0; i < 16; i += 4) {
+        a0 = __fadd_rn(a0, v[i]);
+        a1 = __fadd_rn(a1, v[i + 1]);
+        a2 = __fadd_rn(a2, v[i + 2]);
+        a3 = __fadd_rn(a3, v[i + 3]);
+      }
+    }
     for (; r + 3 * (int64_t)groups < r1; r += 4 * (int64_t)groups) {
       a0 = __fadd_rn(a0, g[r * K + k]);
       a1 = __fadd_rn(a1, g[(r + groups) * K + k]);
@@ -276,6 +291,18 @@ __global__ __launch_bounds__(kBlock) void colsum_stage2_kernel(const float *__re
   if (k >= K) return;
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;  // 4 independent chains, combined in a fixed order
   int64_t p = 0;
+  for (; p + 16 <= P; p += 16) {   // loads first, then the four-row step's adds in its order (see stage 1)
+    float v[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = partial[(p + i) * K + k];
+#pragma unroll
+    for (int i = 0; i < 16; i += 4) {
+      a0 = __fadd_rn(a0, v[i]);
+      a1 = __fadd_rn(a1, v[i + 1]);
+      a2 = __fadd_rn(a2, v[i + 2]);
+      a3 = __fadd_rn(a3, v[i + 3]);
+    }
+  }
   for (; p + 4 <= P; p += 4) {
     a0 = __fadd_rn(a0, partial[p * K + k]);
     a1 = __fadd_rn(a1, partial[(p + 1) * K + k]);

@@ -115,6 +115,32 @@ __global__ void rng_advance_kernel(int64_t *rng, int64_t inc) {
   if (block_id() == 0 && threadIdx.x == 0) rng[1] += inc;
 }
 
+// One finished vector of the backward: mask and scale the VEC gradients gv of row r, vector c (the three mask modes below),
+// add them to the lane's running column sums and store them.  Shared by bias_act_bwd_kernel, whose gv is a loaded
+// gradient, and linear_bias_act_bwd_kernel, whose gv is the g . W it formed in registers: one body, the same bits.
+template <typename T, int VEC, int MASKED>
+__device__ __forceinline__ void bwd_finish(int64_t r, int64_t c, float (&gv)[VEC], const float (&yv)[VEC], float (&acc)[VEC],
+                                           typename TT<T>::S *__restrict__ ga, int64_t K, int64_t KVm, int ev, float scale,
+                                           const int64_t *__restrict__ rng, uint32_t drop_thresh) {
+  constexpr int masked = MASKED;  // compile-time: the common ReLU case carries no Philox code at all
+  uint32_t rw[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+  if (MASKED == 3) {  // the mask the forward drew: same word for vector (r, c)
+    const U4 u = philox4x32_10((uint64_t)(r * KVm + (c * VEC) / ev), (uint64_t)rng[1], (uint64_t)rng[0]);
+    rw[0] = u.x; rw[1] = u.y; rw[2] = u.z; rw[3] = u.w;
+    if (VEC == 1) rw[0] = rw[(c * VEC) % ev];
+  }
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) {
+    // masked: 1 = y > 0 (ReLU, with or without dropout: exact), 2 = y != 0 (dropout without ReLU and
+    // without an rng state), 3 = redrawn dropout mask (dropout without ReLU)
+    if (masked == 1) gv[i] = (yv[i] > 0.0f) ? __fmul_rn(gv[i], scale) : 0.0f;
+    else if (masked == 2) gv[i] = (yv[i] != 0.0f) ? __fmul_rn(gv[i], scale) : 0.0f;
+    else if (masked == 3) gv[i] = (rw[i] >= drop_thresh) ? __fmul_rn(gv[i], scale) : 0.0f;
+    acc[i] = __fadd_rn(acc[i], gv[i]);  // rows in ascending order, unrolled or not
+  }
+  stv<T, VEC>(ga + r * K + c * VEC, gv);
+}
+
 // backward + first stage of the bias gradient.  Same thread geometry as the forward; every lane keeps a
 // running column sum of the ga values it produces and writes it to partial[(block * groups + j), :];
 // ggl_colsum_f32 (backward.hip) then reduces the [P, K] partial matrix.
@@ -142,23 +168,7 @@ __global__ __launch_bounds__(kBlock) void bias_act_bwd_kernel(const typename TT<
 #pragma unroll
     for (int i = 0; i < VEC; ++i) acc[i] = 0.0f;
     auto finish = [&](int64_t r, float (&gv)[VEC], const float (&yv)[VEC]) {
-      constexpr int masked = MASKED;  // compile-time: the common ReLU case carries no Philox code at all
-      uint32_t rw[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-      if (MASKED == 3) {  // the mask the forward drew: same word for vector (r, c)
-        const U4 u = philox4x32_10((uint64_t)(r * KVm + (c * VEC) / ev), (uint64_t)rng[1], (uint64_t)rng[0]);
-        rw[0] = u.x; rw[1] = u.y; rw[2] = u.z; rw[3] = u.w;
-        if (VEC == 1) rw[0] = rw[(c * VEC) % ev];
-      }
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) {
-        // masked: 1 = y > 0 (ReLU, with or without dropout: exact), 2 = y != 0 (dropout without ReLU and
-        // without an rng state), 3 = redrawn dropout mask (dropout without ReLU)
-        if (masked == 1) gv[i] = (yv[i] > 0.0f) ? __fmul_rn(gv[i], scale) : 0.0f;
-        else if (masked == 2) gv[i] = (yv[i] != 0.0f) ? __fmul_rn(gv[i], scale) : 0.0f;
-        else if (masked == 3) gv[i] = (rw[i] >= drop_thresh) ? __fmul_rn(gv[i], scale) : 0.0f;
-        acc[i] = __fadd_rn(acc[i], gv[i]);  // rows in ascending order, unrolled or not
-      }
-      stv<T, VEC>(ga + r * K + c * VEC, gv);
+      bwd_finish<T, VEC, MASKED>(r, c, gv, yv, acc, ga, K, KVm, ev, scale, rng, drop_thresh);
     };
     int64_t r = r0 + j;
     for (; r + (int64_t)(kRowUnroll - 1) * groups < r1; r += (int64_t)kRowUnroll * groups) {
@@ -182,6 +192,103 @@ __global__ __launch_bounds__(kBlock) void bias_act_bwd_kernel(const typename TT<
     if (partial) {
 #pragma unroll
       for (int i = 0; i < VEC; ++i) partial[(block_id() * groups + j) * K + c * VEC + i] = acc[i];
+    }
+  }
+}
+
+// The output layer's input gradient formed inside that pass: s[r, :] = g[r, 0:J] . w[0:J, :] (serial fmas, ascending j,
+// from 0.0f) takes the place of the loaded gradient and bwd_finish does the rest, so (ga, partial) are
+// bias_act_bwd_kernel<float, 4, MASKED>'s on s, bit for bit — same geometry, same rows per (block, group), ascending.
+// The [N, K] product is never written: at K = 256, J = 47 the pass moves g (0.19 KB a row) + y + ga instead of
+// s written, s read, y, ga.  w is staged once per block in LDS; a lane carries kLinRows rows, so one 16-byte LDS read
+// of w[j, 4c..4c+3] feeds 4 x kLinRows fmas (8 rows: the LDS pipe of a CU then has half the work of its vector pipes,
+// at 4 they tie), and the y loads of those rows are issued before the j loop and consumed behind it.
+// UNIFORM (a wavefront's lanes share their row and are all live: kp % 64 == 0, KV % kp == 0): lane l loads g[r, l]
+// once, coalesced, and g[r, j] comes out of that register with v_readlane; otherwise every lane reads its row's g[r, j].
+// The host build reads w and g where they lie (no LDS, no cross-lane reads there).
+constexpr int kLinRows = 8;
+template <int R, int MASKED, bool UNIFORM>
+__device__ __forceinline__ void linear_rows(const float *__restrict__ g, int64_t g_ld, const float4 *wv,
+                                            const float *__restrict__ y, float *__restrict__ ga, int64_t J, int64_t K,
+                                            int64_t KV, int64_t c, int64_t r, int groups, float scale,
+                                            const int64_t *__restrict__ rng, uint32_t drop_thresh, float (&acc)[4]) {
+  float s[R][4], yv[R][4];
+  float gl[R];
+#pragma unroll
+  for (int u = 0; u < R; ++u) {
+    const int64_t ru = r + (int64_t)u * groups;
+    if (MASKED == 1 || MASKED == 2) ldv<float, 4>(y + ru * K + c * 4, yv[u]);
+    else yv[u][0] = 0.0f;
+    gl[u] = 0.0f;
+#ifndef GGL_EMULATE
+    if (UNIFORM) {
+      const int lane = threadIdx.x & (kWave - 1);
+      if (lane < J) gl[u] = g[ru * g_ld + lane];
+    }
+#endif
+    s[u][0] = 0.0f; s[u][1] = 0.0f; s[u][2] = 0.0f; s[u][3] = 0.0f;
+  }
+  auto step = [&](int64_t jj) {
+    const float4 wq = wv[jj * KV + c];
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+      float gs;
+#ifndef GGL_EMULATE
+      if (UNIFORM) gs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(gl[u]), (int)jj));
+      else
+#endif
+        gs = g[(r + (int64_t)u * groups) * g_ld + jj];
+      s[u][0] = __fmaf_rn(gs, wq.x, s[u][0]);
+      s[u][1] = __fmaf_rn(gs, wq.y, s[u][1]);
+      s[u][2] = __fmaf_rn(gs, wq.z, s[u][2]);
+      s[u][3] = __fmaf_rn(gs, wq.w, s[u][3]);
+    }
+  };
+  // four steps a trip, written out (a loop around a cross-lane read is not unrolled with a remainder for the asking): the LDS
+  // reads of the four go out in front of their fmas
+  int64_t jj = 0;
+  for (; jj + 4 <= J; jj += 4) {
+    step(jj); step(jj + 1); step(jj + 2); step(jj + 3);
+  }
+  for (; jj < J; ++jj) step(jj);
+#pragma unroll
+  for (int u = 0; u < R; ++u)
+    bwd_finish<float, 4, MASKED>(r + (int64_t)u * groups, c, s[u], yv[u], acc, ga, K, K / 4, 4, scale, rng, drop_thresh);
+}
+
+template <int MASKED, bool UNIFORM>
+__global__ __launch_bounds__(kBlock) void linear_bias_act_bwd_kernel(const float *__restrict__ g, int64_t g_ld,
+                                                                     const float *__restrict__ w,
+                                                                     const float *__restrict__ y, float *__restrict__ ga,
+                                                                     int64_t N, int64_t J, int64_t K, int64_t nblocks,
+                                                                     int64_t rows_per_block, int kp, int groups, float scale,
+                                                                     const int64_t *__restrict__ rng, uint32_t drop_thresh,
+                                                                     float *__restrict__ partial) {
+  if (block_id() >= nblocks) return;  // padding block of a folded grid (the whole block: nobody waits at the barrier)
+  const int64_t KV = K / 4;
+#ifndef GGL_EMULATE
+  extern __shared__ float4 w_lds[];   // [J, K / 4]
+  for (int64_t i = threadIdx.x; i < J * KV; i += kBlock) w_lds[i] = reinterpret_cast<const float4 *>(w)[i];
+  __syncthreads();
+  const float4 *wv = w_lds;
+#else
+  const float4 *wv = reinterpret_cast<const float4 *>(w);
+#endif
+  const int j = threadIdx.x / kp;
+  const int c0 = threadIdx.x - j * kp;
+  if (j >= groups) return;
+  const int64_t r0 = block_id() * rows_per_block;
+  const int64_t r1 = (r0 + rows_per_block < N) ? r0 + rows_per_block : N;
+  for (int64_t c = c0; c < KV; c += kp) {
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    int64_t r = r0 + j;
+    for (; r + (int64_t)(kLinRows - 1) * groups < r1; r += (int64_t)kLinRows * groups)
+      linear_rows<kLinRows, MASKED, UNIFORM>(g, g_ld, wv, y, ga, J, K, KV, c, r, groups, scale, rng, drop_thresh, acc);
+    for (; r < r1; r += groups)
+      linear_rows<1, MASKED, UNIFORM>(g, g_ld, wv, y, ga, J, K, KV, c, r, groups, scale, rng, drop_thresh, acc);
+    if (partial) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) partial[(block_id() * groups + j) * K + c * 4 + i] = acc[i];
     }
   }
 }
@@ -376,6 +483,70 @@ extern "C" int ggl_bias_act_bwd_x16(int dtype, const void *g, const void *y, int
   return dtype == GGL_BF16
              ? bias_act_bwd<mxbf16_t>(g16, y16, N, K, relu, p_drop, rng_used, ga16, gbias, workspace, workspace_bytes, stream)
              : bias_act_bwd<mxf16_t>(g16, y16, N, K, relu, p_drop, rng_used, ga16, gbias, workspace, workspace_bytes, stream);
+}
+
+// The shapes the fused form takes (and wins at): float4 lanes, one coalesced load of a g row per wavefront at most, and
+// a staged w of at most 64 KiB so that two blocks and more share a CU's LDS.
+extern "C" int ggl_policy_linear_epi_bwd(int64_t N, int64_t J, int64_t K) {
+  (void)N;
+  return K > 0 && K % 4 == 0 && J >= 1 && J <= 64 && J * K * (int64_t)sizeof(float) <= 64 * 1024;
+}
+
+extern "C" int ggl_linear_bias_act_bwd(const float *g, int64_t g_ld, const float *w, const float *y, int64_t N, int64_t J,
+                                       int64_t K, int relu, float p_drop, const int64_t *rng_used, float *ga, float *gbias,
+                                       void *workspace, size_t workspace_bytes, void *stream) {
+  GGL_REQUIRE(N >= 0 && J >= 0 && K >= 0 && g_ld >= J && p_drop >= 0.0f && p_drop < 1.0f, GGL_EINVAL, "bad arguments");
+  if (K == 0) return GGL_OK;
+  GGL_REQUIRE(ggl_policy_linear_epi_bwd(N, J, K), GGL_EINVAL,
+              "linear_bias_act_bwd needs K %% 4 == 0, 1 <= J <= 64 and J * K floats within 64 KiB (got J = %lld, K = %lld)",
+              (long long)J, (long long)K);
+  GGL_REQUIRE(w && ((g && ga) || N == 0), GGL_EINVAL, "NULL pointer");
+  const bool redraw = p_drop > 0.0f && rng_used != nullptr && !relu;   // the modes of ggl_bias_act_bwd, chosen the same way
+  const int masked = relu ? 1 : (redraw ? 3 : (p_drop > 0.0f ? 2 : 0));
+  uint32_t thresh;
+  float scale;
+  dropout_params(p_drop, &thresh, &scale);
+  GGL_REQUIRE(!masked || masked == 3 || y || N == 0, GGL_EINVAL, "y is needed to rebuild the ReLU/dropout mask");
+  GGL_REQUIRE(!gbias || (workspace && workspace_bytes >= ggl_bias_act_bwd_workspace_bytes(N, K)),
+              GGL_EWORKSPACE, "linear_bias_act_bwd workspace too small (ggl_bias_act_bwd_workspace_bytes(N, K))");
+  GGL_REQUIRE(aligned16(g) && aligned16(w) && aligned16(ga) && (!masked || masked == 3 || aligned16(y)), GGL_EINVAL,
+              "g, w, y and ga must be 16-byte aligned");
+  int kp, groups;
+  int64_t blocks, rpb;
+  geometry(N, K, true, &kp, &groups, &blocks, &rpb);   // the float4 geometry of ggl_bias_act_bwd on the [N, K] product
+  hipStream_t s = as_stream(stream);
+  float *partial = gbias ? static_cast<float *>(workspace) : nullptr;
+  const int64_t *rng = redraw ? rng_used : nullptr;
+#ifdef GGL_EMULATE
+#define GGL_LBAB(M, U)                                                                                               \
+  GGL_LAUNCH((linear_bias_act_bwd_kernel<M, false>), blocks, kBlock, s, g, g_ld, w, y, ga, N, J, K, blocks, rpb, kp, groups, \
+             scale, rng, thresh, partial)
+  const bool uniform = false;
+#else
+  // (GGL_LAUNCH carries no dynamic LDS: the fold is the same)
+#define GGL_LBAB(M, U)                                                                                               \
+  do {                                                                                                               \
+    unsigned gx_, gy_;                                                                                               \
+    fold_grid(blocks, &gx_, &gy_);                                                                                   \
+    hipLaunchKernelGGL((linear_bias_act_bwd_kernel<M, U>), dim3(gx_, gy_), dim3((unsigned)kBlock),                    \
+                       (size_t)(J * K) * sizeof(float), s, g, g_ld, w, y, ga, N, J, K, blocks, rpb, kp, groups, scale, rng, \
+                       thresh, partial);                                                                             \
+  } while (0)
+  const bool uniform = kp % kWave == 0 && (K / 4) % kp == 0;
+#endif
+  if (uniform) {
+    if (masked == 0) GGL_LBAB(0, true); else if (masked == 1) GGL_LBAB(1, true); else if (masked == 2) GGL_LBAB(2, true); else GGL_LBAB(3, true);
+  } else {
+    if (masked == 0) GGL_LBAB(0, false); else if (masked == 1) GGL_LBAB(1, false); else if (masked == 2) GGL_LBAB(2, false); else GGL_LBAB(3, false);
+  }
+#undef GGL_LBAB
+  GGL_LAUNCH_CHECK();
+  if (gbias) {  // second stage: column sums of the [P, K] partial matrix
+    const size_t part = bwd_partial_bytes(N, K);
+    return ggl_colsum_f32(partial, blocks * groups, K, gbias, static_cast<char *>(workspace) + part,
+                          workspace_bytes - part, stream);
+  }
+  return GGL_OK;
 }
 
 extern "C" int ggl_bias_grad_rows(const float *g, const int64_t *rows, int64_t R, int64_t N, int64_t K, float *gbias,

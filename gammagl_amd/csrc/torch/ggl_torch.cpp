@@ -75,7 +75,8 @@ using torch::autograd::variable_list;
   X(ggl_policy_softmax_sublanes) X(ggl_spmm_sum_x16) X(ggl_spmm_mean_x16) X(ggl_spmm_mean_bwd_x16)                    \
   X(ggl_plan_rows_workspace_bytes) X(ggl_plan_rows_rank) X(ggl_plan_rows_fwd_rowptr) X(ggl_plan_rows_fwd_fill)        \
   X(ggl_plan_rows_bwd_rowptr) X(ggl_plan_rows_bwd_fill) X(ggl_bias_grad_rows)                                          \
-  X(ggl_spmm_epi_x16) X(ggl_bias_act_fwd_x16) X(ggl_bias_act_bwd_x16)
+  X(ggl_spmm_epi_x16) X(ggl_bias_act_fwd_x16) X(ggl_bias_act_bwd_x16)                                                \
+  X(ggl_linear_bias_act_bwd) X(ggl_policy_linear_epi_bwd)
 
 struct Api {
   void *handle = nullptr;
@@ -1463,6 +1464,31 @@ static std::tuple<Tensor, Tensor> bias_act_backward_kernel(const Tensor &g_, con
   return {ga, gb.defined() ? gb : at::empty({0}, f32o)};
 }
 
+// bias_act_backward on a gradient that is the narrow product grad[:, :J] @ weight (weight [J, K]: the Linear that reads y),
+// without that [N, K] product in memory (ggl_linear_bias_act_bwd: serial fmas in ascending j, then bias_act_backward's bits)
+static std::tuple<Tensor, Tensor> linear_bias_act_backward_kernel(const Tensor &g_, const Tensor &w_, const Tensor &y, bool has_bias,
+                                                                  bool relu, double p, const Tensor &rng_used) {
+  Tensor g = g_.contiguous(), w = w_.contiguous(), yc = y.contiguous();
+  same_device({&g, &w, &yc});
+  f32("grad", g);
+  f32("weight", w);
+  f32("y", yc);
+  TORCH_CHECK(g.dim() == 2 && w.dim() == 2 && yc.dim() == 2 && g.size(1) >= w.size(0) && yc.size(0) == g.size(0) &&
+                  yc.size(1) == w.size(1),
+              "linear_bias_act_backward: grad ", g.sizes(), ", weight ", w.sizes(), ", y ", yc.sizes(), " do not fit");
+  c10::OptionalDeviceGuard guard(g.device());
+  const Api &api = api_for(g.device());
+  const int64_t N = g.size(0), J = w.size(0), K = w.size(1);
+  const auto f32o = g.options().dtype(at::kFloat);
+  Tensor ga = at::empty_like(yc), gb = has_bias ? at::empty({K}, f32o) : Tensor();
+  const size_t wsb = api.ggl_bias_act_bwd_workspace_bytes(N, K);
+  Tensor ws = at::empty({static_cast<int64_t>(std::max<size_t>(wsb, 4))}, g.options().dtype(at::kByte));
+  check(api, api.ggl_linear_bias_act_bwd(g.data_ptr<float>(), g.size(1), w.data_ptr<float>(), yc.data_ptr<float>(), N, J, K,
+                                         relu ? 1 : 0, static_cast<float>(p), used_ptr(p, rng_used), ga.data_ptr<float>(),
+                                         gb.defined() ? gb.data_ptr<float>() : nullptr, ws.data_ptr(), wsb, stream_of(g.device())));
+  return {ga, gb.defined() ? gb : at::empty({0}, f32o)};
+}
+
 // y = dropout(relu(reduce_{j -> i} w x_j + add_i + bias)) in ONE kernel (reduce.hip MODE_SPMM_EPI): 2-D x, K % 4 == 0.
 // x (and add) may be STORED as f16 / bf16: ggl_spmm_epi_x16, any width, the f32 operations, y rounded once to x's dtype.
 static std::tuple<Tensor, Tensor> spmm_epi_forward_kernel(const Tensor &index, const OptT_ &weight, const Tensor &x, bool mean,
@@ -2320,6 +2346,10 @@ static std::tuple<Tensor, Tensor> bias_bwd_meta(const Tensor &g, const Tensor &,
   return {at::empty_like(g), at::empty({hb && N > 0 ? g.numel() / N : 0}, g.options().dtype(at::kFloat))};
 }
 static Tensor bias_meta(const Tensor &a, const OptT_ &, bool, double) { return at::empty_like(a); }
+static std::tuple<Tensor, Tensor> lin_bias_bwd_meta(const Tensor &g, const Tensor &w, const Tensor &y, bool hb, bool, double,
+                                                    const Tensor &) {
+  return {at::empty_like(y), at::empty({hb ? w.size(1) : 0}, g.options().dtype(at::kFloat))};
+}
 static std::tuple<Tensor, Tensor> epi_fwd_meta(const Tensor &, const OptT_ &, const Tensor &x, bool, const OptT_ &, const OptT_ &,
                                                bool, double) {
   return {at::empty_like(x), at::empty({0}, x.options().dtype(at::kLong))};
@@ -2514,12 +2544,25 @@ TORCH_LIBRARY_IMPL(ggl, Meta, m) {
 // gspmm's weight gradient as a dispatcher op.  It lives in a namespace of its own: the operator surface under ggl:: is
 // pinned name by name (tests/golden/ggl_schemas.txt), and the autograd formulas of spmm_sum / spmm_mean / spmm_*_x16 /
 // spmm_epi above need an OP to call so that their backward traces under FakeTensor like the others.
+// linear_bias_act_backward — bias_act_backward under a Linear, the [N, K] product formed in registers — lives here for the same
+// reason.
 TORCH_LIBRARY(ggl_grad, m) {
   m.def("spmm_grad_w(Tensor index, Tensor x, Tensor grad, bool mean) -> Tensor");
+  m.def("linear_bias_act_backward(Tensor grad, Tensor weight, Tensor y, bool has_bias, bool relu, float p_drop, Tensor rng_used) "
+        "-> (Tensor, Tensor)");
 }
-TORCH_LIBRARY_IMPL(ggl_grad, CPU, m) { m.impl("spmm_grad_w", ggl_torch::spmm_grad_w_kernel); }
-TORCH_LIBRARY_IMPL(ggl_grad, CUDA, m) { m.impl("spmm_grad_w", ggl_torch::spmm_grad_w_kernel); }
-TORCH_LIBRARY_IMPL(ggl_grad, Meta, m) { m.impl("spmm_grad_w", ggl_torch::spmm_grad_w_meta); }
+TORCH_LIBRARY_IMPL(ggl_grad, CPU, m) {
+  m.impl("spmm_grad_w", ggl_torch::spmm_grad_w_kernel);
+  m.impl("linear_bias_act_backward", ggl_torch::linear_bias_act_backward_kernel);
+}
+TORCH_LIBRARY_IMPL(ggl_grad, CUDA, m) {
+  m.impl("spmm_grad_w", ggl_torch::spmm_grad_w_kernel);
+  m.impl("linear_bias_act_backward", ggl_torch::linear_bias_act_backward_kernel);
+}
+TORCH_LIBRARY_IMPL(ggl_grad, Meta, m) {
+  m.impl("spmm_grad_w", ggl_torch::spmm_grad_w_meta);
+  m.impl("linear_bias_act_backward", ggl_torch::lin_bias_bwd_meta);
+}
 
 // Edge softmax + aggregate on per-edge logits, a namespace of its own for the same reason: the ggl:: surface is pinned.
 TORCH_LIBRARY(ggl_attn, m) {

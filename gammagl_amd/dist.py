@@ -42,6 +42,10 @@ A2A_MODE = os.environ.get("GGL_HALO_A2A", "a2a")            # "a2a": all_to_all_
 # 1: the output layer of a one-GPU training step aggregates only the rows the loss reads (spmm_rows on the restricted plan
 # pair of the train list); 0: every row, indexed afterwards (A/B runs and the equality tests; same results either way)
 OUT_ROWS = os.environ.get("GGL_OUT_ROWS", "1") != "0"
+# 1: the last hidden GCN layer of a one-GPU training step and the output layer's Linear are one autograd node whose backward
+# forms the output layer's input gradient inside the ReLU / dropout mask pass (ggl_linear_bias_act_bwd); 0: the GEMM writes it
+# and ggl_bias_act_bwd reads it back (A/B runs and the tests; the gradients agree to rounding, not on the bits: DESIGN.md §5)
+LIN_EPI_BWD = os.environ.get("GGL_LIN_EPI_BWD", "1") != "0"
 
 
 def balanced_bounds(dst, num_nodes, world):
@@ -294,15 +298,24 @@ class PartitionedGraph:
         """Undo what constructing this graph changed process-wide (the GGL_DIST_EXACT=0 switch of `exact_long_rows`)."""
         _restore_dist_exact(self)
 
-    def aggregate(self, h, bias=None, relu=False, p_drop=0.0, training=True, halo_included=False, out_rows=None):
+    def aggregate(self, h, bias=None, relu=False, p_drop=0.0, training=True, halo_included=False, out_rows=None,
+                  then_linear=None):
         """out[i] = dropout(relu(sum_{j->i} w_ij h[j] + bias)) for the local rows i (autograd-aware).  The
         epilogue (gcn_conv.py:105-106, models/gcn.py:55-59) rides on the store of the LAST edge block added:
         the local SpMM when this rank has no halo, the halo-source SpMM otherwise.  `halo_included`: `h` holds
         n_local + n_halo rows, the halo rows already in place behind the local ones (`with_halo`, or rows this rank
         computed from them): nothing is exchanged, and the gradient comes back with the same n_local + n_halo rows.
         `out_rows` (one GPU, no halo, a layer without ReLU / dropout): a sorted, duplicate-free int64 list of local rows —
-        only those rows are aggregated and returned ([len(out_rows), K], equal to the full result indexed by them)."""
+        only those rows are aggregated and returned ([len(out_rows), K], equal to the full result indexed by them).
+        `then_linear` = (W, side stream, sink, pad_out) (one GPU, no halo, f32 rows of a multiple of 4 columns): returns
+        `out @ pad(W)^T` instead, the aggregate and that Linear being one autograd node (`_AggregateThenLinear`)."""
         p = float(p_drop) if training else 0.0
+        if then_linear is not None:
+            if self.comm or halo_included or out_rows is not None or h.shape[1] % 4 != 0 or h.dtype != torch.float32:
+                raise RuntimeError("aggregate(then_linear=...) is the one-GPU last hidden layer's form: no halo, every row, "
+                                   "f32 features whose width is a multiple of 4")
+            w_next, side, sink, pad_out = then_linear
+            return _AggregateThenLinear.apply(h, w_next, self, bias, bool(relu), p, side, sink, int(pad_out))
         if out_rows is not None:
             if self.comm or halo_included or relu or p > 0 or h.shape[1] % 4 != 0:
                 raise RuntimeError("aggregate(out_rows=...) is the one-GPU output layer's form: no halo, no ReLU / dropout, "
@@ -568,6 +581,70 @@ class _LinearSideWgrad(torch.autograd.Function):
         return gx, gw, None, None, None
 
 
+class _AggregateThenLinear(torch.autograd.Function):
+    """The last hidden layer's aggregate + epilogue and the output layer's Linear as ONE node, on one GPU without a halo:
+    out = dropout(relu(A h + bias)) @ pad(W)^T.  The forward makes today's calls in today's order (the route's fused
+    aggregate, then the GEMM).  The backward never writes the [N, K] gradient g @ W of the saved activation: it has rank
+    J (47 classes), and `ggl_linear_bias_act_bwd` forms it in registers inside the mask pass that used to read it back —
+    0.5 + 2.5 + 2.5 GB moved instead of 10.5 GB in two launches at products size (profiles/lin_epi_bwd.txt).  Then the
+    weight gradient on the side stream into the sink (`_LinearSideWgrad`'s ordering and `join()` contract) and the route's
+    transposed aggregate.  That J-term product is summed in ascending j with fused multiply-adds, not in hipBLASLt's order:
+    the gradients behind it differ from the two-launch form in their last bits."""
+
+    @staticmethod
+    def forward(ctx, h, w, pg, bias, relu, p_drop, side, sink, pad_out):
+        eng = pg.eng
+        h = h.contiguous()
+        if h.shape[0] != pg.n_local:
+            raise RuntimeError(f"aggregate: expected {pg.n_local} rows, got {h.shape[0]}")
+        if pg.route == "cpp":
+            y, rng_used = _cpp_ops().spmm_epi_forward(pg.ei_loc, pg.w_loc, h, False, None, bias, relu, p_drop)
+        else:
+            K = h.shape[1]
+            rng, rng_used = eng._draw(h.device, p_drop)
+            y = torch.empty((pg.n_local, K), dtype=torch.float32, device=h.device)
+            eng.spmm_epi_into(pg.gp_loc.fwd, pg.gp_loc.col, pg.w_loc, h, y, relu=relu, p_drop=p_drop, rng=rng, epi_K=K,
+                              bias=bias.contiguous().reshape(-1) if bias is not None else None)
+        ctx.pg, ctx.side, ctx.sink = pg, side, sink
+        ctx.epi = (relu, p_drop, None if bias is None else bias.shape)
+        ctx.save_for_backward(y, w, rng_used)
+        return y @ (w.t() if not pad_out else F.pad(w, (0, 0, 0, int(pad_out))).t())
+
+    @staticmethod
+    def backward(ctx, g):
+        pg, side = ctx.pg, ctx.side
+        eng = pg.eng
+        y, w, rng_used = ctx.saved_tensors
+        relu, p_drop, bias_shape = ctx.epi
+        g = g.contiguous()      # [N, J + pad]: the entry reads J columns of rows that wide
+        if pg.route == "cpp":
+            from . import cpp_ops
+
+            ga, gb = cpp_ops.load_grad().linear_bias_act_backward(g, w, y, bias_shape is not None, relu, p_drop, rng_used)
+            gb = gb.reshape(bias_shape) if bias_shape is not None else None
+        else:
+            ga, gb = eng.linear_epi_bwd(g, w, y, relu, p_drop, rng_used, bias_shape)
+        gw = None
+        if ctx.needs_input_grad[1]:
+            n_out = w.shape[0]
+            if side is None or not g.is_cuda:
+                gw = wgrad(g, y)[:n_out]
+            else:   # as _LinearSideWgrad: behind the input gradient, under the transposed aggregate below
+                cur = torch.cuda.current_stream(g.device)
+                side.wait_stream(cur)
+                with torch.cuda.stream(side):
+                    gws = wgrad(g, y)[:n_out]
+                gws.record_stream(cur)
+                ctx.sink.append((w, gws, g, y))
+        gh = None
+        if ctx.needs_input_grad[0]:
+            if pg.route == "cpp":
+                gh = _cpp_ops().spmm_sum_backward(pg.ei_loc, pg.w_loc, ga)
+            else:
+                gh, _ = eng._spmm_fwd("sum", pg.gp_loc.bwd, pg.gp_loc.colT, pg.w_loc, ga, pg.n_local)
+        return gh, gw, None, gb, None, None, None, None, None
+
+
 class DistGCN(torch.nn.Module):
     """GCNModel(norm='none') on precomputed symmetric-normalised edge weights (models/gcn.py:30-64,
     gcn_conv.py:78-108 with norm='none'), each GCNConv's propagate replaced by the halo aggregate."""
@@ -605,6 +682,17 @@ class DistGCN(torch.nn.Module):
                 w.grad.add_(gw)
         self._sink.clear()
 
+    def _fuse_next_linear(self, pg, h, pre, pad):
+        """Whether the last hidden layer (its transform `h` in hand) and the output layer's Linear run as one
+        `_AggregateThenLinear` node: training, f32, one GPU without a halo, both layers in the A (X W) association, a
+        hidden width the fused epilogue takes as it is, and an output layer narrow enough for ggl_policy_linear_epi_bwd."""
+        if not LIN_EPI_BWD or not self.training or self.aggregate_first or pg.comm or pre or pad:
+            return False
+        if h.dtype != torch.float32 or h.shape[1] % 4 != 0:
+            return False
+        J = int(self.lin[-1].weight.shape[0])
+        return bool(pg.eng.lib.ggl_policy_linear_epi_bwd(int(h.shape[0]), J + ((-J) % 4 if J >= 8 else 0), int(h.shape[1])))
+
     def forward(self, x, pg, out_rows=None):
         """`out_rows` (a sorted, duplicate-free int64 list of local rows, e.g. the train nodes): return the logits of those
         rows only, [len(out_rows), num_class] — equal to forward(x, pg)[out_rows].  On one GPU without a halo the output
@@ -620,6 +708,7 @@ class DistGCN(torch.nn.Module):
         #                                                                          whether layer 1 issues collectives)
         if pre:
             x = pg.with_halo(x)
+        lin_next = None   # the next layer's x @ W^T where _AggregateThenLinear already made it
         for i in range(n):
             hidden = i < n - 1
             n_out = self.lin[i].weight.shape[0]
@@ -641,7 +730,18 @@ class DistGCN(torch.nn.Module):
                     x = _ConstInputLayer.apply(x, self.lin[i].weight, pg, bias, hidden,
                                                p if self.training else 0.0, pad)
                 else:
-                    h = _LinearSideWgrad.apply(x, self.lin[i].weight, self.side, self._sink, pad)
+                    if lin_next is not None:     # this layer's Linear ran inside the previous layer's node
+                        h, lin_next = lin_next, None
+                    else:
+                        h = _LinearSideWgrad.apply(x, self.lin[i].weight, self.side, self._sink, pad)
+                    if i == n - 2 and self._fuse_next_linear(pg, h, pre, pad):
+                        # aggregate + epilogue of the last hidden layer and the output layer's Linear as one node: its
+                        # backward forms the rank-47 gradient of this layer's output inside the mask pass
+                        pad_next = (-self.lin[i + 1].weight.shape[0]) % 4 if self.lin[i + 1].weight.shape[0] >= 8 else 0
+                        lin_next = pg.aggregate(h, bias, relu=True, p_drop=p, training=True,
+                                                then_linear=(self.lin[i + 1].weight, self.side, self._sink, pad_next))
+                        x = None    # (nothing reads the activation itself: the next layer starts from lin_next)
+                        continue
                     # + bias, ReLU and dropout ride on the store of the last edge block added to a row: the local SpMM
                     # on one GPU, the halo-source SpMM behind the exchange otherwise (reduce.hip MODE_SPMM_EPI)
                     rows = out_rows if (i == n - 1 and out_rows is not None and not pg.comm and not pre

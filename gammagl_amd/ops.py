@@ -1004,6 +1004,27 @@ class Engine:
                                                   _ptr(ga), _ptr(gb), _ptr(ws), wsb, self._stream(dev)))
         return ga, (gb.reshape(bias_shape) if gb is not None else None)
 
+    def linear_epi_bwd(self, g, w, y, relu, p_drop, rng_used, bias_shape):
+        """`_epi_bwd(g[:, :J] @ w, y, ...)` without the [N, K] product in memory (ggl_linear_bias_act_bwd): `g` [N, >= J] f32
+        rows (the output layer's gradient, 47 classes in rows of 48), `w` the [J, K] Linear weight, `y` the saved [N, K]
+        output.  The product is summed in ascending j with fused multiply-adds, not in a BLAS order; everything behind it
+        is _epi_bwd's on the bits.  Shapes ggl_policy_linear_epi_bwd accepts only.  Returns (ga, gbias)."""
+        g, w, y = g.contiguous(), w.contiguous(), y.contiguous()
+        self._check_f32("g", g)
+        self._check_f32("w", w)
+        self._check_f32("y", y)
+        dev = g.device
+        N, J, K = int(g.shape[0]), int(w.shape[0]), int(w.shape[1])
+        if g.dim() != 2 or g.shape[1] < J or tuple(y.shape) != (N, K):
+            raise RuntimeError(f"linear_epi_bwd: g {tuple(g.shape)}, w {tuple(w.shape)}, y {tuple(y.shape)} do not fit")
+        ga = torch.empty_like(y)
+        gb = torch.empty(K, dtype=torch.float32, device=dev) if bias_shape is not None else None
+        wsb = self.lib.ggl_bias_act_bwd_workspace_bytes(N, K)
+        ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=dev)
+        self._check(self.lib.ggl_linear_bias_act_bwd(_ptr(g), int(g.shape[1]), _ptr(w), _ptr(y), N, J, K, int(relu), float(p_drop),
+                                                     _ptr(rng_used), _ptr(ga), _ptr(gb), _ptr(ws), wsb, self._stream(dev)))
+        return ga, (gb.reshape(bias_shape) if gb is not None else None)
+
     def reseed(self, seed=None):
         """Forget the fused-dropout RNG state (the next use draws a new seed from torch's generator) — of this engine AND, for
         a product engine, of the C++ operator library (torch.ops.ggl keeps its own counter stream; since round 6 a one-rank

@@ -71,6 +71,8 @@ extern "C" {
  *   aggregate for any attention layer).  Purely additive again. */
 /* still 11: + ggl_dot_attn_supported, ggl_dot_attn_fwd, ggl_policy_dot_attn_fused (scaled dot-product graph attention: the
  *   logit formed inside the aggregate's walk).  Purely additive again. */
+/* still 11: + ggl_linear_bias_act_bwd, ggl_policy_linear_epi_bwd (the epilogue's backward on a gradient that is a narrow
+ *   product, formed in registers).  Purely additive again. */
 #define GGL_ABI_VERSION 11
 
 /* dtype codes (AT_DISPATCH_ALL_TYPES_AND2(Half, BFloat16), segment_sum_cpu.cpp:32-33) */
@@ -423,6 +425,21 @@ size_t ggl_bias_act_bwd_workspace_bytes(int64_t N, int64_t K);
 int ggl_bias_act_bwd(const float *g, const float *y, int64_t N, int64_t K, int relu, float p_drop,
                      const int64_t *rng_used, float *ga, float *gbias, void *workspace,
                      size_t workspace_bytes, void *stream);
+/* ggl_bias_act_bwd on a gradient that is a narrow product, s = g[N, J] . w[J, K], WITHOUT writing s: the backward of
+ * dropout(relu(. + bias)) followed by a Linear whose weight is w (GCN: the last hidden layer's epilogue under the output
+ * layer).  s[r, k] = sum_j g[r, j] * w[j, k], serial fused multiply-adds in ascending j from 0.0f (one rounding each;
+ * NOT a BLAS summation order), formed in registers; (ga, gbias) are then ggl_bias_act_bwd(s, y, ...)'s bit for bit — the
+ * same mask modes, geometry, partial sums and ggl_colsum_f32.  relu = 0, p_drop = 0, gbias = NULL returns s itself.
+ * g rows have stride g_ld >= J (47 classes in rows of 48); w is the row-major [J, K] Linear weight, staged in LDS.
+ * Shapes: K % 4 == 0, 1 <= J <= 64, J * K * 4 <= 64 KiB (else GGL_EINVAL); g, w, y, ga 16-byte aligned.
+ * workspace: ggl_bias_act_bwd_workspace_bytes(N, K) (needed with gbias only).
+ * ggl_policy_linear_epi_bwd: 1 = take this form for an [N, J] x [J, K] product (those shapes), 0 = GEMM, then
+ * ggl_bias_act_bwd.  At K = 256, J = 47 the fused pass moves 5.5 GB where the two launches move 10.5 GB
+ * (profiles/lin_epi_bwd.txt). */
+int ggl_linear_bias_act_bwd(const float *g, int64_t g_ld, const float *w, const float *y, int64_t N, int64_t J, int64_t K,
+                            int relu, float p_drop, const int64_t *rng_used, float *ga, float *gbias, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int ggl_policy_linear_epi_bwd(int64_t N, int64_t J, int64_t K);
 /* The bias gradient of ggl_bias_act_bwd(relu = 0, p_drop = 0) for a gradient that is zero outside the sorted rows[R] of
  * an [N, K] matrix, from the compact g[R, K] alone (K % 4 == 0, g 16-byte aligned): the same partial matrix — same
  * geometry, every listed row added into the slot and at the position its id gives it — reduced by the same
