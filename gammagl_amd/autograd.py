@@ -420,6 +420,125 @@ class DotAttention(torch.autograd.Function):
         return None, None, gq, gk, gv, None, None, None
 
 
+GATV2_BLOCK_BYTES = 256 << 20   # the composed route's [E_block, H, C] f32 scratch is at most this large
+
+
+def _gatv2_logits(gp, xl, xr, att, slope, z):
+    """z[e, h] = sum_c att[h, c] * leaky_relu(xl[src(e), h, c] + xr[dst(e), h, c]) in the caller's edge order, formed by torch
+    under no_grad in edge blocks of at most GATV2_BLOCK_BYTES of [E_block, H, C]: the composed route's logits."""
+    H, C = int(xl.shape[1]), int(xl.shape[2])
+    if gp.index is not None:
+        src, dst = gp.index[0], gp.index[1]
+    else:   # a plan built from the caller's CSR: its edge order is the CSR's
+        src = gp.col.long()
+        dst = torch.repeat_interleave(torch.arange(gp.N_dst, device=xl.device), gp.fwd.counts())
+    block = max(1, GATV2_BLOCK_BYTES // (4 * H * C))
+    with torch.no_grad():
+        for b in range(0, gp.E, block):
+            s = xl[src[b:b + block]] + xr[dst[b:b + block]]
+            z[b:b + block] = (att * torch.nn.functional.leaky_relu(s, slope)).sum(-1)
+    return z
+
+
+def _gatv2_logit_bwd(eng, plan, col, other, self_, gz, att, slope, add=None, want_rows=False):
+    """ggl_gatv2_logit_bwd over `plan` (include/ggl_mpops.h): (g_self, att_rows or None).  gz is read through the plan's
+    permutation in the kernel, as _bspmm_by_perm reads a weight."""
+    dev = self_.device
+    H, C = int(self_.shape[1]), int(self_.shape[2])
+    perm = plan.perm if plan.perm is not None else plan.wperm
+    part = eng._hub_partial(plan, lambda n: eng.lib.ggl_gatv2_logit_bwd_partial_bytes(n, H, C, 1 if want_rows else 0), dev)
+    cs = plan.c_struct(part, perm)
+    g_self = torch.empty_like(self_)
+    rows = torch.empty_like(self_) if want_rows else None
+    eng._check(eng.lib.ggl_gatv2_logit_bwd(ctypes.byref(cs), _ptr(col), _ptr(other), _ptr(self_), _ptr(gz), _ptr(att),
+                                           float(slope), H, C, _ptr(add), _ptr(g_self), _ptr(rows), eng._stream(dev)))
+    return g_self, rows
+
+
+class GATv2Attention(torch.autograd.Function):
+    """GATv2's additive attention: z[e, h] = sum_c att[h, c] * LeakyReLU(xl[src(e), h, c] + xr[dst(e), h, c]), then
+    EdgeSoftmaxAgg on (z, xl).  Forward, fused route (ggl_gatv2_fwd, GPU build, where ggl_gatv2_supported and the policy say
+    so): the logit is formed inside the aggregate's walk from the value row it gathers; z is stored — by that walk, in the
+    caller's edge order — only when a backward will read it (or the caller asked for it), so a forward without grad touches
+    no [E, H] array.  Composed route (any other shape, CPU tensors): _gatv2_logits in edge blocks, then
+    ggl_edge_softmax_agg_fwd.  Both routes run the same backward on the saved z: ggl_edge_softmax_agg_bwd_dst (alpha, gz),
+    _bwd_src (gv), then ggl_gatv2_logit_bwd on the forward plan (g_xr and R, g_att = colsum(R)) and on the transposed plan
+    with add = gv (the whole g_xl); a walk whose gradient nobody needs is skipped.  No [E, H, C] array in either.
+    Returns (out, z); z is not differentiable and is an empty tensor when it was not formed."""
+
+    @staticmethod
+    def forward(ctx, eng, gp, xl, xr, att, slope, p_drop=0.0, keep_z=False):
+        ctx.eng = eng
+        dev = xl.device
+        N, H, C = gp.N_dst, int(xl.shape[1]), int(xl.shape[2])
+        need = any(ctx.needs_input_grad[2:5])
+        fused = bool(eng.gatv2_fused and xl.is_cuda and eng.lib.ggl_gatv2_supported(H, C)
+                     and eng.lib.ggl_policy_gatv2_fused(H, C, gp.E, gp.N_src))
+        out = torch.empty((N, H, C), dtype=torch.float32, device=dev)
+        rmax = torch.empty((N, H), dtype=torch.float32, device=dev)
+        rden = torch.empty((N, H), dtype=torch.float32, device=dev)
+        part = eng._gat_partial(gp.fwd, H, C, dev)
+        cs = gp.fwd.c_struct(part)
+        z = None
+        if need or keep_z or not fused:
+            z = torch.empty((gp.E, H), dtype=torch.float32, device=dev)
+        if not fused:
+            _gatv2_logits(gp, xl, xr, att, slope, z)
+        rng, rng_used = eng._draw(dev, p_drop)
+        if fused:
+            eng._check(eng.lib.ggl_gatv2_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(xl), _ptr(xr), _ptr(att), float(slope), H, C,
+                                             float(p_drop), _ptr(rng), _ptr(out), _ptr(rmax), _ptr(rden), _ptr(z),
+                                             eng._stream(dev)))
+        else:
+            eng._check(eng.lib.ggl_edge_softmax_agg_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(z), _ptr(xl), H, C, float(p_drop),
+                                                        _ptr(rng), _ptr(out), _ptr(rmax), _ptr(rden), eng._stream(dev)))
+        eng.stats["gatv2_attention"] = {"fused": fused, "logits_bytes": 0 if z is None else z.numel() * 4,
+                                        "logits_saved": bool(need)}
+        ctx.gp, ctx.slope, ctx.p_drop, ctx.rng_used = gp, float(slope), float(p_drop), rng_used
+        if need:
+            ctx.save_for_backward(z, xl, xr, att, out, rmax, rden)
+        zr = z if (keep_z and z is not None) else out.new_empty(0)
+        ctx.mark_non_differentiable(zr)
+        return out, zr
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _gz_unused):
+        eng = ctx.eng
+        gp = ctx.gp
+        need_l, need_r, need_a = ctx.needs_input_grad[2:5]
+        if not (need_l or need_r or need_a):
+            return (None,) * 8
+        z, xl, xr, att, out, rmax, rden = ctx.saved_tensors
+        g = g.contiguous()
+        dev = g.device
+        H, C = int(xl.shape[1]), int(xl.shape[2])
+        st = eng._stream(dev)
+        alpha = torch.empty((max(gp.E, 1), H), dtype=torch.float32, device=dev) if need_l else None   # sorted positions
+        gz = torch.empty_like(z)                                                                      # caller's order
+        part_f = eng._partial(gp.fwd, torch.float32, H, False, dev)  # must outlive the launch
+        cs = gp.fwd.c_struct(part_f)
+        eng._check(eng.lib.ggl_edge_softmax_agg_bwd_dst(
+            ctypes.byref(cs), _ptr(gp.col), _ptr(z), _ptr(xl), _ptr(g), _ptr(out), _ptr(rmax), _ptr(rden), H, C,
+            ctx.p_drop, _ptr(ctx.rng_used), _ptr(alpha), _ptr(gz), st))
+        gl = gr = ga = None
+        if need_r or need_a:
+            gr, rows = _gatv2_logit_bwd(eng, gp.fwd, gp.col, xl, xr, gz, att, ctx.slope, None, need_a)
+            if need_a:
+                ga = eng.colsum(rows.reshape(gp.N_dst, H * C)).reshape(H, C)
+            if not need_r:
+                gr = None
+        if need_l:
+            bwd = gp.bwd
+            gv = torch.empty((gp.N_src, H, C), dtype=torch.float32, device=dev)
+            part = eng._partial(bwd, torch.float32, H * C + H, False, dev)
+            csT = bwd.c_struct(part)
+            eng._check(eng.lib.ggl_edge_softmax_agg_bwd_src(ctypes.byref(csT), _ptr(gp.colT), _ptr(gp.posT), _ptr(alpha),
+                                                            _ptr(g), H, C, _ptr(gv), st))
+            gl, _ = _gatv2_logit_bwd(eng, bwd, gp.colT, xr, xl, gz, att, ctx.slope, gv, False)
+        return None, None, gl, gr, ga, None, None, None
+
+
 class BiasAdd(torch.autograd.Function):
     """out = x + bias (bias broadcast over rows); d bias = column sums of the gradient."""
 

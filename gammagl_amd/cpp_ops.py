@@ -54,6 +54,7 @@ def load_attn():
     """``torch.ops.ggl_attn`` (the same library): ``edge_softmax_aggregate(index, logits, x, num_nodes=None, dropout_rate=0.)``,
     edge softmax + weighted aggregate on per-edge logits, with its ``_forward`` / ``_backward`` passes, and
     ``dot_attention(index, q, k, v, num_nodes=None, scale=None, dropout_rate=0.)``, the same with the logits formed from
-    ``scale * <q[dst], k[src]>``, with its passes.  A namespace of its own for the reason ``load_grad`` gives."""
+    ``scale * <q[dst], k[src]>``, with its passes, and ``gatv2_attention(index, xl, xr, att, num_nodes=None,
+    negative_slope=0.2, dropout_rate=0.)``, the same with GATv2's additive logits, with its passes.  A namespace of its own for the reason ``load_grad`` gives."""
     load()
     return torch.ops.ggl_attn

@@ -1308,3 +1308,6 @@ extern "C" int ggl_segment_softmax_bwd(const float *y, const float *g, const ggl
   }
   return GGL_OK;
 }
+
+// ---- GATv2: the logit's part of the backward (ggl_gatv2_logit_bwd); its forward is gatv2.hip ----
+#include "gatv2_bwd.hpp"

@@ -1,8 +1,8 @@
 // gammagl_amd/csrc/gat_common.hpp — what gat.hip (every head shape, also built for the host-emulated tests),
-// gat_fast.hip (the GPU-only fast paths) and dotattn.hip (dot-product attention, GPU only) share: launch dimensions,
-// the logit policies, the attention-dropout word, small helpers, the declarations of the hub-chunk combine kernels
-// defined in gat.hip, and the forward walk (gat_online, gat_fwd_kernel and its launch recipe) that gat.hip and
-// dotattn.hip both instantiate.
+// gat_fast.hip (the GPU-only fast paths), dotattn.hip (dot-product attention, GPU only) and gatv2.hip (GATv2's additive
+// attention, GPU only) share: launch dimensions, the logit policies, the attention-dropout word, small helpers, the
+// declarations of the hub-chunk combine kernels defined in gat.hip, and the forward walk (gat_online, gat_fwd_kernel and
+// its launch recipe) that gat.hip, dotattn.hip and gatv2.hip instantiate.
 #pragma once
 #include "common.hpp"
 
@@ -37,6 +37,9 @@ __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.0f ?
 //                    arrived sorted); the backward's `de` is gz, stored at e_p — the caller's order — and may be NULL.
 //   kLogitDot + ...  dot-product attention, forward only: s_p = slope * <q[i, h, :], k[col[p], h, :]>, formed by the lanes
 //                    of the head together (dotattn.hip, GPU build only).  `el` is k, `er` carries q, plan->perm and z.
+//   kLogitGatv2 + ... GATv2's additive attention, forward only: s_p = sum_c att[h, c] LeakyReLU(x[col[p], h, c] + xr[i, h, c]),
+//                    formed by the lanes of the head together from the VALUE row the walk gathers anyway (gatv2.hip, GPU
+//                    build only).  `el` is not read, `er` carries xr, att, the slope, plan->perm and z.
 // A policy supplies
 //   Aux          what travels in the kernels' `er` slot;
 //   Row, row()   the per-(row, head) state a lane keeps in registers for the whole walk: er[i, h], nothing, the lane's q.
@@ -52,7 +55,10 @@ __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.0f ?
 //   raw(), act(), dact()  the logit from (operand, row state), its activation and the activation's derivative;
 //   put()        what the forward keeps of s_p: nothing, or the dot's z[e_p, h] (stored by the head's first lane);
 //   kC           the head width where the policy fixes it at compile time, 0 = GatDims::C.
-enum { kLogitSeparable = 0, kLogitEdge = 1, kLogitDot = 2 };
+// A policy whose operand IS the lane's x row (LogitOnValue<LS>::value, false unless specialised) supplies of_value() in
+// place of load(): the walk hands it the row it has loaded and requests nothing more.
+enum { kLogitSeparable = 0, kLogitEdge = 1, kLogitDot = 2, kLogitGatv2 = 12 };
+template <int LS> struct LogitOnValue { static constexpr bool value = false; };
 template <int LS> struct Logit {
   using Aux = const float *__restrict__;  // er [N, H]
   using Row = float;
@@ -245,8 +251,16 @@ template <int LOGG> __device__ __forceinline__ float group_sum(float v) {
 }
 #endif
 
-// ---- the forward walk: the kernel of ggl_gat_fused_fwd(_x16), ggl_edge_softmax_agg_fwd (gat.hip) and ggl_dot_attn_fwd
-// (dotattn.hip) ----
+// the per-position operand of policy LS: its load(), or — LogitOnValue — what it makes of the x row v the walk holds
+template <int LS, int VEC>
+__device__ __forceinline__ typename Logit<LS>::Opnd logit_opnd(const float *__restrict__ el, int64_t eh, int64_t ck,
+                                                               const float (&v)[VEC]) {
+  if constexpr (LogitOnValue<LS>::value) return Logit<LS>::of_value(v);
+  else return Logit<LS>::load(el, eh, ck);
+}
+
+// ---- the forward walk: the kernel of ggl_gat_fused_fwd(_x16), ggl_edge_softmax_agg_fwd (gat.hip), ggl_dot_attn_fwd
+// (dotattn.hip) and ggl_gatv2_fwd (gatv2.hip) ----
 // One walk over positions [beg, end) of a destination row for head h, channels [kk, kk+VEC):
 //   m   = max_p s_p,   s_p = LeakyReLU(el[col[p],h] + er_i)   (or what the Logit policy LS makes of its operands)
 //   den = sum_p exp(s_p - m)
@@ -296,7 +310,7 @@ __device__ __forceinline__ void gat_online(const int32_t *__restrict__ col, cons
     const int64_t e0 = LP::rec(aux, col, q, c0);
     float v0[VEC];
     RowV<XT, VEC>::load(x + c0 * K + kk, v0);
-    const float s0 = LP::act(LP::raw(LP::load(el, e0 * H + h, c0 * K + kk), ri), slope);
+    const float s0 = LP::act(LP::raw(logit_opnd<LS, VEC>(el, e0 * H + h, c0 * K + kk, v0), ri), slope);
     LP::put(aux, e0 * H + h, kk == h * C, s0);
     absorb(DROP ? drop_word(q, H, h, offset, seed) : 0u, s0, v0);
   };
@@ -314,7 +328,8 @@ __device__ __forceinline__ void gat_online(const int32_t *__restrict__ col, cons
 #pragma unroll
     for (int u = 0; u < 4; ++u) RowV<XT, VEC>::load(x + c[u] * K + kk, v[u]);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) s[u] = LP::act(LP::raw(LP::load(el, e[u] * H + h, c[u] * K + kk), ri), slope);
+    for (int u = 0; u < 4; ++u)
+      s[u] = LP::act(LP::raw(logit_opnd<LS, VEC>(el, e[u] * H + h, c[u] * K + kk, v[u]), ri), slope);
 #pragma unroll
     for (int u = 0; u < 4; ++u) LP::put(aux, e[u] * H + h, kk == h * C, s[u]);
 #pragma unroll

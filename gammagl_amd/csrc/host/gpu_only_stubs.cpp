@@ -52,6 +52,16 @@ extern "C" int ggl_dot_attn_fwd(const ggl_segplan_t *, const int32_t *, const fl
   return GGL_EINVAL;
 }
 
+// gammagl_amd/csrc/gatv2.hip (the same butterfly): here GATv2 attention composes its logits in torch in front of the
+// edge-softmax aggregate; the logit's backward walk (ggl_gatv2_logit_bwd, gatv2_bwd.hpp) is in this build
+extern "C" int ggl_gatv2_supported(int64_t, int64_t) { return 0; }
+extern "C" int ggl_policy_gatv2_fused(int64_t, int64_t, int64_t, int64_t) { return 0; }
+extern "C" int ggl_gatv2_fwd(const ggl_segplan_t *, const int32_t *, const float *, const float *, const float *, float,
+                             int64_t, int64_t, float, int64_t *, float *, float *, float *, float *, void *) {
+  ggl::set_error("the fused GATv2 attention forward exists in the GPU build only");
+  return GGL_EINVAL;
+}
+
 // gammagl_amd/csrc/hub16.hip (LDS + barriers) has no host-emulated build either: the emulated library reports the
 // path as unsupported and the 16-bit sums keep walking their hub rows with the row kernel of reduce.hip.
 extern "C" int ggl_segment_hub16_supported(int, int64_t, const void *, const void *) { return 0; }

@@ -64,6 +64,8 @@ using torch::autograd::variable_list;
   X(ggl_gat_fused_fwd_x16) X(ggl_gat_fused_bwd_dst_x16) X(ggl_gat_fused_bwd_src_x16)                                    \
   X(ggl_edge_softmax_agg_fwd) X(ggl_edge_softmax_agg_bwd_dst) X(ggl_edge_softmax_agg_bwd_src)                          \
   X(ggl_dot_attn_supported) X(ggl_policy_dot_attn_fused) X(ggl_dot_attn_fwd)                                           \
+  X(ggl_gatv2_supported) X(ggl_policy_gatv2_fused) X(ggl_gatv2_fwd) X(ggl_gatv2_logit_bwd_partial_bytes)                \
+  X(ggl_gatv2_logit_bwd) X(ggl_colsum_workspace_bytes) X(ggl_colsum_f32)                                               \
   X(ggl_gat_fast_supported) X(ggl_gat_fast_fwd) X(ggl_gat_fast_bwd) X(ggl_bias_act_fwd)                                \
   X(ggl_bias_act_bwd_workspace_bytes) X(ggl_bias_act_bwd) X(ggl_spmm_epi_ex) X(ggl_segment_epi)                        \
   X(ggl_sample_hop_workspace_bytes) X(ggl_sample_hop)                                                                \
@@ -1313,6 +1315,134 @@ static std::tuple<Tensor, Tensor, Tensor> dot_backward_kernel(const Tensor &inde
   return {gq, gk, gv};
 }
 
+// GATv2's additive graph attention: z[e, h] = sum_c att[h, c] * LeakyReLU(xl[src_e, h, c] + xr[dst_e, h, c]), then
+// edge_softmax_aggregate on (z, xl).  Fused route (ggl_gatv2_fwd, GPU build, where ggl_gatv2_supported and the policy say so):
+// the logit is formed in the aggregate's walk from the value row and z is stored — by that walk, in the caller's edge order —
+// only with keep_logits.  Composed route (any other shape, CPU tensors): z by torch in edge blocks of at most 256 MiB of
+// [E_block, H, C], then ggl_edge_softmax_agg_fwd.
+static void gatv2_check(const Tensor &index, const Tensor &xl, const Tensor &xr, const Tensor &att) {
+  same_device({&xl, &xr, &att});
+  f32("xl", xl); f32("xr", xr); f32("att", att);
+  TORCH_CHECK(index.dim() == 2 && index.size(0) == 2, "gatv2_attention expects index [2, E]");
+  TORCH_CHECK(xl.dim() == 3 && xr.dim() == 3 && xl.size(1) == xr.size(1) && xl.size(2) == xr.size(2),
+              "gatv2_attention expects xl [N_src, H, C] and xr [N_dst, H, C]: got xl ", xl.sizes(), ", xr ", xr.sizes());
+  TORCH_CHECK(att.dim() == 2 && att.size(0) == xl.size(1) && att.size(1) == xl.size(2), "gatv2_attention expects att [H, C] = [",
+              xl.size(1), ", ", xl.size(2), "]: got ", att.sizes());
+}
+static void gatv2_logits(const Tensor &index, const Tensor &xl, const Tensor &xr, const Tensor &att, double slope, Tensor &z) {
+  at::NoGradGuard no_grad;
+  const int64_t E = index.size(1), H = xl.size(1), C = xl.size(2);
+  const int64_t block = std::max<int64_t>(1, (int64_t(256) << 20) / (4 * H * C));
+  Tensor src = index.select(0, 0), dst = index.select(0, 1);
+  for (int64_t b = 0; b < E; b += block) {
+    const int64_t n = std::min(block, E - b);
+    Tensor s = xl.index_select(0, src.narrow(0, b, n)) + xr.index_select(0, dst.narrow(0, b, n));
+    z.narrow(0, b, n).copy_((att * at::leaky_relu(s, slope)).sum(-1));
+  }
+}
+// (g_self, att_rows) of ggl_gatv2_logit_bwd over plan p; gz is read through p's perm in the kernel
+static std::pair<Tensor, Tensor> gatv2_logit_bwd(const SegPlan &p, const Tensor &col, const Tensor &other, const Tensor &self,
+                                                 const Tensor &gz, const Tensor &att, double slope, const Tensor &add,
+                                                 bool want_rows) {
+  const Api &a = api_for(self.device());
+  const int64_t H = self.size(1), C = self.size(2);
+  Tensor g_self = at::empty_like(self), rows = want_rows ? at::empty_like(self) : Tensor();
+  Tensor part;
+  if (p.n_long > 0)
+    part = at::empty({static_cast<int64_t>(a.ggl_gatv2_logit_bwd_partial_bytes(p.n_chunks, H, C, want_rows ? 1 : 0)) + 16},
+                     self.options().dtype(at::kByte));
+  ggl_segplan_t cs = p.c(part);
+  check(a, a.ggl_gatv2_logit_bwd(&cs, col.data_ptr<int32_t>(), other.data_ptr<float>(), self.data_ptr<float>(),
+                                 gz.data_ptr<float>(), att.data_ptr<float>(), static_cast<float>(slope), H, C,
+                                 add.defined() ? add.data_ptr<float>() : nullptr, g_self.data_ptr<float>(),
+                                 want_rows ? rows.data_ptr<float>() : nullptr, stream_of(self.device())));
+  return {g_self, rows};
+}
+// (out, rowmax, rowden, rng_used, logits); logits [E, H] in the caller's edge order, or EMPTY when they were not formed
+static std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> gatv2_forward_kernel(const Tensor &index, const Tensor &xl_, const Tensor &xr_,
+                                                                               const Tensor &att_, int64_t num_nodes, double slope,
+                                                                               double p, bool keep_logits) {
+  gatv2_check(index, xl_, xr_, att_);
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout_rate must be in [0, 1)");
+  const auto dev = xl_.device();
+  c10::OptionalDeviceGuard guard(dev);
+  Tensor idx = index.contiguous();
+  auto gp = gat_plan(idx, num_nodes, xl_.size(0));
+  TORCH_CHECK(gp->N_dst == xr_.size(0), "gatv2_attention: the graph has ", gp->N_dst, " destinations, xr has ", xr_.size(0), " rows");
+  const Api &a = api_for(dev);
+  Tensor xl = xl_.contiguous(), xr = xr_.contiguous(), att = att_.contiguous();
+  const int64_t N = gp->N_dst, H = xl.size(1), C = xl.size(2), E = gp->E;
+  const bool fused = dev.is_cuda() && a.ggl_gatv2_supported(H, C) && a.ggl_policy_gatv2_fused(H, C, E, gp->N_src);
+  Tensor out = at::empty({N, H, C}, xl.options()), rmax = at::empty({N, H}, xl.options()), rden = at::empty({N, H}, xl.options());
+  Tensor part;
+  if (gp->fwd->n_long > 0)
+    part = at::empty({static_cast<int64_t>(a.ggl_gat_partial_bytes(gp->fwd->n_chunks, H, C)) + 16}, xl.options().dtype(at::kByte));
+  ggl_segplan_t cs = gp->fwd->c(part);
+  Tensor z = (keep_logits || !fused) ? at::empty({E, H}, xl.options()) : Tensor();
+  if (!fused) gatv2_logits(idx, xl, xr, att, slope, z);
+  const Draw d = draw(dev, p);
+  if (fused)
+    check(a, a.ggl_gatv2_fwd(&cs, gp->col.data_ptr<int32_t>(), xl.data_ptr<float>(), xr.data_ptr<float>(), att.data_ptr<float>(),
+                             static_cast<float>(slope), H, C, static_cast<float>(p), d.ptr(), out.data_ptr<float>(),
+                             rmax.data_ptr<float>(), rden.data_ptr<float>(), z.defined() ? z.data_ptr<float>() : nullptr,
+                             stream_of(dev)));
+  else
+    check(a, a.ggl_edge_softmax_agg_fwd(&cs, gp->col.data_ptr<int32_t>(), z.data_ptr<float>(), xl.data_ptr<float>(), H, C,
+                                        static_cast<float>(p), d.ptr(), out.data_ptr<float>(), rmax.data_ptr<float>(),
+                                        rden.data_ptr<float>(), stream_of(dev)));
+  return {out, rmax, rden, d.used, keep_logits ? z : at::empty({0}, xl.options())};
+}
+// (g_xl, g_xr, g_att) from the saved logits: the edge-softmax aggregate's two backward walks (alpha, gz, gv), then
+// ggl_gatv2_logit_bwd on the plan (g_xr, R; g_att = ggl_colsum_f32(R)) and on its transpose with add = gv (g_xl).  A gradient
+// that is not needed is not computed and comes back EMPTY.
+static std::tuple<Tensor, Tensor, Tensor> gatv2_backward_kernel(const Tensor &index, const Tensor &xl_, const Tensor &xr_,
+                                                                const Tensor &att_, const Tensor &z_, const Tensor &grad,
+                                                                const Tensor &out, const Tensor &rmax, const Tensor &rden,
+                                                                const Tensor &rng_used, int64_t num_nodes, double slope, double p,
+                                                                bool need_l, bool need_r, bool need_a) {
+  const auto dev = xl_.device();
+  c10::OptionalDeviceGuard guard(dev);
+  const Api &a = api_for(dev);
+  Tensor idx = index.contiguous(), xl = xl_.contiguous(), xr = xr_.contiguous(), att = att_.contiguous(), z = z_.contiguous(),
+         g = grad.contiguous(), oc = out.contiguous();
+  auto gp = gat_plan(idx, num_nodes, xl.size(0));
+  const int64_t H = xl.size(1), C = xl.size(2), E = gp->E;
+  auto none = [&]() { return at::empty({0}, xl.options()); };   // (outputs of an op may not alias one another)
+  if (!need_l && !need_r && !need_a) return {none(), none(), none()};
+  TORCH_CHECK(z.dim() == 2 && z.size(0) == E && z.size(1) == H, "gatv2_attention_backward needs the forward's logits [E, H]");
+  void *st = stream_of(dev);
+  Tensor alpha = need_l ? at::empty({std::max<int64_t>(E, 1), H}, xl.options()) : Tensor();
+  Tensor gz = at::empty_like(z);
+  Tensor part_f = partial_for(a, *gp->fwd, z, H, false);
+  ggl_segplan_t cs = gp->fwd->c(part_f);
+  check(a, a.ggl_edge_softmax_agg_bwd_dst(&cs, gp->col.data_ptr<int32_t>(), z.data_ptr<float>(), xl.data_ptr<float>(),
+                                          g.data_ptr<float>(), oc.data_ptr<float>(), rmax.data_ptr<float>(),
+                                          rden.data_ptr<float>(), H, C, static_cast<float>(p), used_ptr(p, rng_used),
+                                          need_l ? alpha.data_ptr<float>() : nullptr, gz.data_ptr<float>(), st));
+  Tensor gl = none(), gr = none(), ga = none();
+  if (need_r || need_a) {
+    auto r = gatv2_logit_bwd(*gp->fwd, gp->col, xl, xr, gz, att, slope, Tensor(), need_a);
+    if (need_r) gr = r.first;
+    if (need_a) {
+      ga = at::empty({H, C}, xl.options());
+      const size_t wsb = a.ggl_colsum_workspace_bytes(gp->N_dst, H * C);
+      Tensor ws = at::empty({static_cast<int64_t>(std::max<size_t>(wsb, 4))}, xl.options().dtype(at::kByte));
+      check(a, a.ggl_colsum_f32(r.second.data_ptr<float>(), gp->N_dst, H * C, ga.data_ptr<float>(), ws.data_ptr(), wsb, st));
+    }
+  }
+  if (need_l) {
+    gp->need_bwd(idx);
+    gp->need_posT(idx);
+    Tensor gv = at::empty({gp->N_src, H, C}, xl.options());
+    Tensor part_t = partial_for(a, *gp->bwd, z, H * C + H, false);
+    ggl_segplan_t csT = gp->bwd->c(part_t);
+    check(a, a.ggl_edge_softmax_agg_bwd_src(&csT, gp->colT.data_ptr<int32_t>(), gp->posT.data_ptr<int32_t>(),
+                                            alpha.data_ptr<float>(), g.data_ptr<float>(), H, C, gv.data_ptr<float>(), st));
+    gl = gatv2_logit_bwd(*gp->bwd, gp->colT, xr, xl, gz, att, slope, gv, false).first;
+  }
+  return {gl, gr, ga};
+}
+
 // The same op over a CSR the caller already holds — the argument list of dgNN's GATConvFuse
 // (layers/conv/fusedgat_conv.py:121): rows of the CSR aggregate, no sort.  The plan is cached on row_ptr.
 struct CsrExtra {   // what besides row_ptr identifies the five-tensor structure
@@ -2058,6 +2188,42 @@ static Tensor dot_autograd(const Tensor &index, const Tensor &q, const Tensor &k
   return DotFn::apply(index, q, k, v, n, sc, p, need);
 }
 
+// gatv2_attention: as dot_attention; the logits are kept by the forward only where xl, xr or att requires grad
+struct Gatv2Fn : public torch::autograd::Function<Gatv2Fn> {
+  static Tensor forward(AutogradContext *ctx, const Tensor &index, const Tensor &xl, const Tensor &xr, const Tensor &att, int64_t n,
+                        double slope, double p, bool need) {
+    at::AutoDispatchBelowADInplaceOrView below;
+    static auto op = op_handle<DotFwdSig>("ggl_attn::gatv2_attention_forward");
+    Tensor out, rmax, rden, used, z;
+    std::tie(out, rmax, rden, used, z) = op.call(index, xl, xr, att, n, slope, p, need);
+    if (need) ctx->save_for_backward({index, xl, xr, att, z, out, rmax, rden, used});
+    ctx->saved_data["n"] = n;
+    ctx->saved_data["slope"] = slope;
+    ctx->saved_data["p"] = p;
+    return out;
+  }
+  static variable_list backward(AutogradContext *ctx, variable_list grads) {
+    auto s = ctx->get_saved_variables();
+    static auto op = op_handle<DotBwdSig>("ggl_attn::gatv2_attention_backward");
+    const bool need_l = ctx->needs_input_grad(1), need_r = ctx->needs_input_grad(2), need_a = ctx->needs_input_grad(3);
+    auto r = op.call(s[0], s[1], s[2], s[3], s[4], grads[0], s[5], s[6], s[7], s[8], ctx->saved_data["n"].toInt(),
+                     ctx->saved_data["slope"].toDouble(), ctx->saved_data["p"].toDouble(), need_l, need_r, need_a);
+    return {Tensor(), need_l ? std::get<0>(r) : Tensor(), need_r ? std::get<1>(r) : Tensor(), need_a ? std::get<2>(r) : Tensor(),
+            Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+// xl [N, C], xr [N, C] with att [C] are one head
+static Tensor gatv2_autograd(const Tensor &index, const Tensor &xl, const Tensor &xr, const Tensor &att,
+                             c10::optional<int64_t> num_nodes, double slope, double p) {
+  if (xl.dim() == 2 && xr.dim() == 2 && att.dim() == 1)
+    return gatv2_autograd(index, xl.unsqueeze(1), xr.unsqueeze(1), att.unsqueeze(0), num_nodes, slope, p).squeeze(1);
+  gatv2_check(index, xl, xr, att);
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout_rate must be in [0, 1)");
+  const int64_t n = num_nodes.has_value() ? *num_nodes : xr.size(0);
+  const bool need = at::GradMode::is_enabled() && (xl.requires_grad() || xr.requires_grad() || att.requires_grad());
+  return Gatv2Fn::apply(index, xl, xr, att, n, slope, p, need);
+}
+
 using GatCsrFwdSig = std::tuple<Tensor, Tensor, Tensor, Tensor, bool>(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                                                                        const Tensor &, const Tensor &, const Tensor &,
                                                                        const Tensor &, double, double);
@@ -2320,6 +2486,23 @@ static Tensor dot_meta(const Tensor &, const Tensor &q, const Tensor &, const Te
   if (v.dim() == 2) return at::empty({N, v.size(1)}, v.options());
   return at::empty({N, v.size(1), v.size(2)}, v.options());
 }
+static std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> gatv2_fwd_meta(const Tensor &index, const Tensor &xl, const Tensor &,
+                                                                         const Tensor &, int64_t n, double, double, bool keep) {
+  auto o = xl.options();
+  return {at::empty({n, xl.size(1), xl.size(2)}, o), at::empty({n, xl.size(1)}, o), at::empty({n, xl.size(1)}, o),
+          at::empty({0}, o.dtype(at::kLong)), keep ? at::empty({index.size(1), xl.size(1)}, o) : at::empty({0}, o)};
+}
+static std::tuple<Tensor, Tensor, Tensor> gatv2_bwd_meta(const Tensor &, const Tensor &xl, const Tensor &xr, const Tensor &att,
+                                                         const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
+                                                         const Tensor &, int64_t, double, double, bool need_l, bool need_r, bool need_a) {
+  auto e = [&]() { return at::empty({0}, xl.options()); };
+  return {need_l ? at::empty_like(xl) : e(), need_r ? at::empty_like(xr) : e(), need_a ? at::empty_like(att) : e()};
+}
+static Tensor gatv2_meta(const Tensor &, const Tensor &xl, const Tensor &xr, const Tensor &, c10::optional<int64_t> n, double, double) {
+  const int64_t N = n.has_value() ? *n : xr.size(0);
+  if (xl.dim() == 2) return at::empty({N, xl.size(1)}, xl.options());
+  return at::empty({N, xl.size(1), xl.size(2)}, xl.options());
+}
 static std::tuple<Tensor, Tensor, Tensor, Tensor, bool> gat_csr_fwd_meta(const Tensor &rp, const Tensor &, const Tensor &,
                                                                          const Tensor &, const Tensor &, const Tensor &,
                                                                          const Tensor &, const Tensor &x, double, double) {
@@ -2578,6 +2761,13 @@ TORCH_LIBRARY(ggl_attn, m) {
   m.def("dot_attention_backward(Tensor index, Tensor q, Tensor k, Tensor v, Tensor logits, Tensor grad, Tensor out, "
         "Tensor rowmax, Tensor rowden, Tensor rng_used, int num_nodes, float scale, float dropout_rate, bool need_q, "
         "bool need_k, bool need_v) -> (Tensor, Tensor, Tensor)");
+  m.def("gatv2_attention(Tensor index, Tensor xl, Tensor xr, Tensor att, int? num_nodes=None, float negative_slope=0.2, "
+        "float dropout_rate=0.) -> Tensor");
+  m.def("gatv2_attention_forward(Tensor index, Tensor xl, Tensor xr, Tensor att, int num_nodes, float negative_slope, "
+        "float dropout_rate, bool keep_logits) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("gatv2_attention_backward(Tensor index, Tensor xl, Tensor xr, Tensor att, Tensor logits, Tensor grad, Tensor out, "
+        "Tensor rowmax, Tensor rowden, Tensor rng_used, int num_nodes, float negative_slope, float dropout_rate, bool need_xl, "
+        "bool need_xr, bool need_att) -> (Tensor, Tensor, Tensor)");
 }
 #define GGL_ATTN_IMPL(KEY)                                                                          \
   TORCH_LIBRARY_IMPL(ggl_attn, KEY, m) {                                                            \
@@ -2585,6 +2775,8 @@ TORCH_LIBRARY(ggl_attn, m) {
     m.impl("edge_softmax_aggregate_backward", ggl_torch::esa_backward_kernel);                      \
     m.impl("dot_attention_forward", ggl_torch::dot_forward_kernel);                                 \
     m.impl("dot_attention_backward", ggl_torch::dot_backward_kernel);                               \
+    m.impl("gatv2_attention_forward", ggl_torch::gatv2_forward_kernel);                             \
+    m.impl("gatv2_attention_backward", ggl_torch::gatv2_backward_kernel);                           \
   }
 GGL_ATTN_IMPL(CPU)
 GGL_ATTN_IMPL(CUDA)
@@ -2592,6 +2784,7 @@ GGL_ATTN_IMPL(CUDA)
 TORCH_LIBRARY_IMPL(ggl_attn, Autograd, m) {
   m.impl("edge_softmax_aggregate", ggl_torch::esa_autograd);
   m.impl("dot_attention", ggl_torch::dot_autograd);
+  m.impl("gatv2_attention", ggl_torch::gatv2_autograd);
 }
 TORCH_LIBRARY_IMPL(ggl_attn, Meta, m) {
   m.impl("edge_softmax_aggregate", ggl_torch::esa_meta);
@@ -2600,4 +2793,7 @@ TORCH_LIBRARY_IMPL(ggl_attn, Meta, m) {
   m.impl("dot_attention", ggl_torch::dot_meta);
   m.impl("dot_attention_forward", ggl_torch::dot_fwd_meta);
   m.impl("dot_attention_backward", ggl_torch::dot_bwd_meta);
+  m.impl("gatv2_attention", ggl_torch::gatv2_meta);
+  m.impl("gatv2_attention_forward", ggl_torch::gatv2_fwd_meta);
+  m.impl("gatv2_attention_backward", ggl_torch::gatv2_bwd_meta);
 }

@@ -15,6 +15,8 @@ here); every tlx call they make on this path maps 1:1 onto torch (``tlx.gather``
 * ``FusedGATConv``    — layers/conv/fusedgat_conv.py:89-130 with our single-kernel op in place of
   the external dgNN GATConvFuse
 * ``HGTConv``         — layers/conv/hgt_conv.py:41-153 (fused: utils.dot_attention per edge type)
+* ``GATv2Conv``       — the GATv2 paper's layer (fused: utils.gatv2_attention); variant="reference" is
+  layers/conv/gatv2_conv.py:94-119, whose logit is separable
 * ``GCNModel``        — models/gcn.py:30-64
 """
 import math
@@ -25,7 +27,7 @@ from torch import nn
 from . import engine as _engine
 from .dense import Linear, _LinearFn, node_matmul
 from .sampler import Block
-from .utils.attention import dot_attention, edge_softmax_aggregate
+from .utils.attention import dot_attention, edge_softmax_aggregate, gatv2_attention
 from .mpops import (bspmm, gspmm, unsorted_segment_max, unsorted_segment_mean,  # noqa: F401
                     unsorted_segment_sum, use_ext)
 
@@ -467,6 +469,67 @@ class AGNNConv(MessagePassing):
         return self.propagate(x, edge_index, num_nodes=num_nodes, edge_weight=alpha)
 
 
+class GATv2Conv(MessagePassing):
+    """GATv2 ("How Attentive are Graph Attention Networks?").  variant="paper": xl = lin_l(x), xr = lin_r(x) (one Linear with
+    share_weights), att [H, C], and
+        z_ij = sum_c att[h, c] * LeakyReLU(xl_j + xr_i)[h, c],  alpha = softmax_i(z),  out_i = sum_j dropout(alpha_ij) xl_j,
+    then concat or head mean, then the bias.  The LeakyReLU sits inside the channel sum: the logit does not separate.
+    fused=True hands xl, xr and att to utils.gatv2_attention — no [E, H, C] tensor, attention dropout from the library's
+    draw; fused=False is the message formula in torch: two [E, H, C] gathers, segment_softmax, torch dropout on alpha.
+
+    variant="reference" reproduces layers/conv/gatv2_conv.py:94-119, which carries the name but scores an edge with
+    mean_c(LeakyReLU(x_j) * att_src + LeakyReLU(x_i) * att_dst): a separable, static logit el[src] + er[dst] with
+    el = mean_c(LeakyReLU(x) * att_src).  Parameters `linear` (no bias), `att_src`, `att_dst` [1, H, C], `bias`.  fused=True
+    forms el and er on the nodes and goes through utils.edge_softmax_aggregate; fused=False is the reference's composition."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout_rate=0., add_bias=True,
+                 share_weights=False, fused=True, variant="paper"):
+        super().__init__()
+        if variant not in ("paper", "reference"):
+            raise ValueError(f"variant={variant!r}: paper or reference")
+        self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, concat
+        self.negative_slope, self.dropout_rate, self.fused, self.variant = negative_slope, dropout_rate, fused, variant
+        self.share_weights = share_weights
+        self.dropout = nn.Dropout(dropout_rate)   # on the attention coefficients
+        if variant == "paper":
+            self.lin_l = Linear(in_channels, heads * out_channels)
+            self.lin_r = self.lin_l if share_weights else Linear(in_channels, heads * out_channels)
+            self.att = nn.Parameter(nn.init.xavier_uniform_(torch.empty(heads, out_channels)))
+        else:
+            self.linear = Linear(in_channels, heads * out_channels, bias=False)
+            self.att_src = nn.Parameter(nn.init.trunc_normal_(torch.empty(1, heads, out_channels), std=0.05, a=-0.1, b=0.1))
+            self.att_dst = nn.Parameter(nn.init.trunc_normal_(torch.empty(1, heads, out_channels), std=0.05, a=-0.1, b=0.1))
+        nb = heads * out_channels if concat else out_channels
+        self.bias = nn.Parameter(torch.zeros(nb)) if add_bias else None
+
+    def _finish(self, x):
+        x = x.reshape(-1, self.heads * self.out_channels) if self.concat else x.mean(dim=1)
+        return x + self.bias if self.bias is not None else x
+
+    def forward(self, x, edge_index, num_nodes=None):
+        H, C = self.heads, self.out_channels
+        n = x.shape[0] if num_nodes is None else num_nodes
+        src, dst = edge_index[0, :], edge_index[1, :]
+        lrelu = torch.nn.functional.leaky_relu
+        if self.variant == "paper":
+            xl = self.lin_l(x).reshape(-1, H, C)
+            xr = xl if self.share_weights else self.lin_r(x).reshape(-1, H, C)
+            if self.fused:
+                return self._finish(gatv2_attention(edge_index, xl, xr[:n], self.att, n, self.negative_slope,
+                                                    self.dropout_rate, self.training))
+            z = (self.att * lrelu(xl[src] + xr[dst], self.negative_slope)).sum(dim=-1)
+        else:
+            xl = self.linear(x).reshape(-1, H, C)
+            act = lrelu(xl, self.negative_slope)
+            if self.fused:   # the logit separates: its two terms are formed on the nodes
+                el, er = (act * self.att_src).mean(dim=-1), (act * self.att_dst).mean(dim=-1)
+                return self._finish(edge_softmax_aggregate(edge_index, el[src] + er[dst], xl, n, self.dropout_rate,
+                                                           self.training))
+            z = (act[src] * self.att_src + act[dst] * self.att_dst).mean(dim=-1)   # gatv2_conv.py:97-99
+        alpha = self.dropout(segment_softmax(z, dst, n))
+        return self._finish(self.aggregate(xl[src] * alpha.unsqueeze(-1), edge_index, num_nodes=n, aggr='sum'))
+
+
 class HGTConv(MessagePassing):
     """hgt_conv.py:41-153, the Heterogeneous Graph Transformer layer: per node type k / q / v / a linears (relu6, as the
     reference's Linear(act='relu6')) and a sigmoid skip gate; per edge type (src, rel, dst) the head-wise maps a_rel, m_rel
@@ -667,5 +730,5 @@ class GraphSAGESampleModel(nn.Module):
         return feat
 
 
-__all__ = ["MessagePassing", "GCNConv", "SAGEConv", "GATConv", "FusedGATConv", "HGTConv", "GCNModel", "GATModel", "GraphSAGEFullModel", "GraphSAGESampleModel", "degree",
+__all__ = ["MessagePassing", "GCNConv", "SAGEConv", "GATConv", "FusedGATConv", "HGTConv", "GATv2Conv", "GCNModel", "GATModel", "GraphSAGEFullModel", "GraphSAGESampleModel", "degree",
            "calc_gcn_norm", "segment_softmax", "add_self_loops"]

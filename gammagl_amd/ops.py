@@ -47,6 +47,7 @@ class Engine:
         self.xcd_run_rows = -1   # -1 = per graph (ggl_policy_xcd_run_rows on the plan's locality), >= 0 forces it
         self.gradw_sorted = True    # bspmm weight gradient along the sorted plan with LDS-staged strips (A/B switch)
         self.dot_attn_fused = True  # dot-product attention: the dot inside the aggregate's walk (GPU build only; A/B switch)
+        self.gatv2_fused = True     # GATv2 attention: the additive logit inside the aggregate's walk (GPU build only; A/B switch)
 
     def clear_caches(self):
         """Drop every cached plan, sorted-weight copy and graph-constant (e.g. GCN norms).  Plans are keyed on
@@ -899,6 +900,44 @@ class Engine:
             q, k, v = q.detach(), k.detach(), v.detach()
         out, z = autograd.DotAttention.apply(self, gp, q.contiguous(), k.contiguous(), v.contiguous(), sc, p,
                                              bool(return_logits))
+        return (out, z) if return_logits else out
+
+    def gatv2_attention(self, index, xl, xr, att, num_nodes=None, negative_slope=0.2, dropout_rate=0.0, training=True,
+                        return_logits=False):
+        """GATv2's additive graph attention ("How Attentive are Graph Attention Networks?"):
+        out[i,h,:] = sum_{e->i} dropout(softmax_i(z[:,h]))[e] * xl[src_e,h,:] with
+        z[e,h] = sum_c att[h,c] * LeakyReLU(xl[src_e,h,c] + xr[dst_e,h,c]) — the LeakyReLU inside the channel sum.
+        xl [N_src, H, C], xr [N_dst, H, C], att [H, C] f32 (2-d xl, xr with 1-d att are one head).  `index` [2, E] or a
+        GraphPlan; rectangular graphs, empty rows, dropout and `training` as edge_softmax_aggregate.  On the GPU the logit
+        is formed inside the aggregate's walk (ggl_gatv2_fwd) for C = 8, 16, 32, 64; other widths, CPU tensors and
+        `gatv2_fused = False` form z with torch in edge blocks in front of edge_softmax_aggregate's forward.  Either way
+        everything behind z is edge_softmax_aggregate on (z, xl), bit for bit, z is stored only for a backward, and no
+        [E, H, C] array is kept.  Gradients for xl, xr and att (ggl_gatv2_logit_bwd).  return_logits=True returns (out, z),
+        z [E, H] in the order of `index`'s columns, detached."""
+        if xl.dim() == 2 and xr.dim() == 2 and att.dim() == 1:
+            r = self.gatv2_attention(index, xl.unsqueeze(1), xr.unsqueeze(1), att.unsqueeze(0), num_nodes, negative_slope,
+                                     dropout_rate, training, return_logits)
+            return (r[0].squeeze(1), r[1].squeeze(1)) if return_logits else r.squeeze(1)
+        self._dev(index, xl, xr, att)
+        for name, t in (("xl", xl), ("xr", xr), ("att", att)):
+            self._check_f32(name, t)
+        if xl.dim() != 3 or xr.dim() != 3 or xl.shape[1:] != xr.shape[1:]:
+            raise RuntimeError(f"gatv2_attention expects xl [N_src, H, C] and xr [N_dst, H, C]: got xl {tuple(xl.shape)}, "
+                               f"xr {tuple(xr.shape)}")
+        if att.dim() != 2 or att.shape != xl.shape[1:]:
+            raise RuntimeError(f"gatv2_attention expects att [H, C] = {tuple(xl.shape[1:])}: got {tuple(att.shape)}")
+        n = xr.shape[0] if num_nodes is None else num_nodes
+        gp = index if isinstance(index, GraphPlan) else self.graph_plan(index, n, xl.shape[0])
+        if gp.N_dst != xr.shape[0] or gp.N_src != xl.shape[0]:
+            raise RuntimeError(f"gatv2_attention: the graph has {gp.N_dst} destinations and {gp.N_src} sources, xr has "
+                               f"{xr.shape[0]} rows and xl {xl.shape[0]}")
+        p = float(dropout_rate) if training else 0.0
+        if not 0.0 <= p < 1.0:
+            raise ValueError("dropout_rate must be in [0, 1)")
+        if not torch.is_grad_enabled():   # nothing will run backward: no logits are kept (or, fused, formed) for it
+            xl, xr, att = xl.detach(), xr.detach(), att.detach()
+        out, z = autograd.GATv2Attention.apply(self, gp, xl.contiguous(), xr.contiguous(), att.contiguous(),
+                                               float(negative_slope), p, bool(return_logits))
         return (out, z) if return_logits else out
 
     def _check_weight(self, weight, gp):

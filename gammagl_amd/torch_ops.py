@@ -20,6 +20,7 @@ points (+ the fused GAT op and the fused epilogue) are dispatcher ops:
     torch.ops.gammagl_amd.spmm_grad_w(index, x, grad, mean) -> Tensor         (not in the reference, see below)
     torch.ops.gammagl_amd.edge_softmax_aggregate(index, logits, x, num_nodes, dropout_rate) -> Tensor   (see below)
     torch.ops.gammagl_amd.dot_attention(index, q, k, v, num_nodes, scale, dropout_rate) -> Tensor        (see below)
+    torch.ops.gammagl_amd.gatv2_attention(index, xl, xr, att, num_nodes, negative_slope, dropout_rate) -> Tensor  (see below)
 
 ``spmm_sum`` / ``spmm_mean`` also take ``x`` stored as bf16 / f16 (the reference is f32 only): the sums are made in f32 and
 rounded once to x's dtype.  ``spmm_*_x16(..., out_f32=True)`` returns those f32 sums unrounded.  ``gat_fused`` does the
@@ -30,6 +31,8 @@ same for its ``x`` (``el`` / ``er`` stay f32; softmax and sums in f32), ``gat_fu
 its logits and sums ``alpha * x[src]``): ``out[i, h] = sum_{e -> i} dropout(softmax_i(logits[:, h]))[e] * x[src_e, h]``, f32.
 ``dot_attention`` is that op with the logits formed from node rows, ``logits[e, h] = scale * <q[dst_e, h], k[src_e, h]>``
 (``scale`` defaults to ``1 / sqrt(C)``) and ``x = v``: scaled dot-product attention over a graph, f32.
+``gatv2_attention`` is that op with GATv2's additive logits, ``logits[e, h] = sum_c att[h, c] * leaky_relu(xl[src_e, h, c] +
+xr[dst_e, h, c])`` and ``x = xl``, f32, differentiable in ``xl``, ``xr`` and ``att``.
 
 Kernels are registered for ``CUDA`` / ``AutogradCUDA`` (= HIP on ROCm: libggl_mpops_hip.so) and for ``CPU`` /
 ``AutogradCPU`` (libggl_mpops_host.so, the host build of the same kernel sources) — the reference's ops dispatch
@@ -65,6 +68,8 @@ _SCHEMAS = {
     "edge_softmax_aggregate": "(Tensor index, Tensor logits, Tensor x, int? num_nodes=None, float dropout_rate=0.0) -> Tensor",
     "dot_attention": "(Tensor index, Tensor q, Tensor k, Tensor v, int? num_nodes=None, float? scale=None, "
                      "float dropout_rate=0.0) -> Tensor",
+    "gatv2_attention": "(Tensor index, Tensor xl, Tensor xr, Tensor att, int? num_nodes=None, float negative_slope=0.2, "
+                       "float dropout_rate=0.0) -> Tensor",
 }
 
 _DEF = Library(NS, "DEF")
@@ -97,6 +102,8 @@ def _kernels(get_engine):
             get_engine().edge_softmax_aggregate(index, logits, x, num_nodes, dropout_rate, True),
         "dot_attention": lambda index, q, k, v, num_nodes=None, scale=None, dropout_rate=0.0:
             get_engine().dot_attention(index, q, k, v, num_nodes, scale, dropout_rate, True),
+        "gatv2_attention": lambda index, xl, xr, att, num_nodes=None, negative_slope=0.2, dropout_rate=0.0:
+            get_engine().gatv2_attention(index, xl, xr, att, num_nodes, negative_slope, dropout_rate, True),
     }
 
 
@@ -165,7 +172,11 @@ def _register_fakes():
         n = q.shape[0] if num_nodes is None else num_nodes
         return v.new_empty((n,) + tuple(v.shape[1:]))
 
-    for name, fn in (("dot_attention", dot), ("edge_softmax_aggregate", esa), ("segment_sum", seg), ("segment_mean", seg), ("segment_max", seg_max),
+    def gatv2(index, xl, xr, att, num_nodes=None, negative_slope=0.2, dropout_rate=0.0):
+        n = xr.shape[0] if num_nodes is None else num_nodes
+        return xl.new_empty((n,) + tuple(xl.shape[1:]))
+
+    for name, fn in (("gatv2_attention", gatv2), ("dot_attention", dot), ("edge_softmax_aggregate", esa), ("segment_sum", seg), ("segment_mean", seg), ("segment_max", seg_max),
                      ("segment_softmax", lambda x, index, N: torch.empty_like(x)),
                      ("spmm_sum", like_x), ("spmm_mean", like_x), ("spmm_max", like_x),
                      ("bspmm_sum", like_x), ("gat_fused", gat),

@@ -12,7 +12,7 @@ cut into chunks, attention dropout from the library's counter-based draw.
 from .. import engine as _engine
 from .. import mpops
 
-__all__ = ["edge_softmax_aggregate", "dot_attention"]
+__all__ = ["edge_softmax_aggregate", "dot_attention", "gatv2_attention"]
 
 
 def edge_softmax_aggregate(edge_index, logits, x, num_nodes=None, dropout_rate=0.0, training=True):
@@ -77,3 +77,34 @@ def dot_attention(edge_index, q, k, v, num_nodes=None, scale=None, dropout_rate=
         ops = cpp_ops.load_attn()
     n = None if num_nodes is None else int(num_nodes)
     return ops.dot_attention(mpops._ids(edge_index, v), q, k, v, n, None if scale is None else float(scale), p)
+
+
+def gatv2_attention(edge_index, xl, xr, att, num_nodes=None, negative_slope=0.2, dropout_rate=0.0, training=True):
+    """GATv2's additive attention over a graph ("How Attentive are Graph Attention Networks?"):
+    ``z[e, h] = sum_c att[h, c] * leaky_relu(xl[src(e), h, c] + xr[dst(e), h, c])`` and
+    ``out[i, h, :] = sum over edges e with dst(e) = i of drop(softmax_i(z[:, h]))[e] * xl[src(e), h, :]``.
+
+    The LeakyReLU sits inside the channel sum, so the logit is neither GAT's ``el[src] + er[dst]`` nor a dot product; written
+    with torch it needs ``xl[src] + xr[dst]`` as an ``[E, H, C]`` tensor, and a second one in the backward.  ``xl`` [N_src, H, C],
+    ``xr`` [N_dst, H, C], ``att`` [H, C] f32 (2-d ``xl``, ``xr`` with a 1-d ``att`` are one head).  ``num_nodes``,
+    ``dropout_rate`` and ``training`` as :func:`edge_softmax_aggregate`, whose numerics everything behind ``z`` shares bit for bit.
+
+    On the GPU, for C = 8, 16, 32 or 64, the logit is formed inside the aggregate's walk from the value row it gathers anyway
+    (``ggl_gatv2_fwd``): ``z`` is written only when a backward will read it.  Other widths and CPU tensors form
+    ``z`` with torch in edge blocks of at most 256 MiB in front of the aggregate.  The two routes add the C terms in different
+    orders, so their ``z`` agree to ``gamma_{C+2} sum_c |att_c| |leaky_relu(xl_c + xr_c)|`` of the exact value each, not bit
+    for bit.  Differentiable in xl, xr and att: the backward is the aggregate's two walks and ``ggl_gatv2_logit_bwd`` on the
+    graph and on its transpose; its peak memory is three ``[E, H]`` arrays plus node-sized ones.
+
+    Route: as :func:`edge_softmax_aggregate` (``torch.ops.ggl_attn`` on the shipped library)."""
+    _engine(xl)._dev(edge_index, xl, xr, att)
+    p = float(dropout_rate) if training else 0.0
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout_rate must be in [0, 1)")
+    ops = mpops._ops_for(xl)
+    if ops is not mpops._py_ops:
+        from .. import cpp_ops
+
+        ops = cpp_ops.load_attn()
+    n = None if num_nodes is None else int(num_nodes)
+    return ops.gatv2_attention(mpops._ids(edge_index, xl), xl, xr, att, n, float(negative_slope), p)

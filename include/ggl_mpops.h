@@ -73,6 +73,8 @@ extern "C" {
  *   logit formed inside the aggregate's walk).  Purely additive again. */
 /* still 11: + ggl_linear_bias_act_bwd, ggl_policy_linear_epi_bwd (the epilogue's backward on a gradient that is a narrow
  *   product, formed in registers).  Purely additive again. */
+/* still 11: + ggl_gatv2_supported, ggl_policy_gatv2_fused, ggl_gatv2_fwd, ggl_gatv2_logit_bwd, ggl_gatv2_logit_bwd_partial_bytes
+ *   (GATv2's additive attention: the logit formed inside the aggregate's walk, and its backward walk).  Purely additive again. */
 #define GGL_ABI_VERSION 11
 
 /* dtype codes (AT_DISPATCH_ALL_TYPES_AND2(Half, BFloat16), segment_sum_cpu.cpp:32-33) */
@@ -606,6 +608,42 @@ int ggl_policy_dot_attn_fused(int64_t H, int64_t C, int64_t E, int64_t N_in);
 int ggl_dot_attn_fwd(const ggl_segplan_t *plan, const int32_t *col, const float *q, const float *k, const float *v,
                      float scale, int64_t H, int64_t C, float p_drop, int64_t *rng_state, float *out, float *rowmax,
                      float *rowden, float *z_out, void *stream);
+/* GATv2 (additive) graph attention, f32:
+ *   z[e,h]     = sum_c att[h,c] * LeakyReLU(xl[src(e),h,c] + xr[dst(e),h,c])     xl [N_src,H,C], xr [N_dst,H,C], att [H,C]
+ *   out[i,h,:] = sum_{p in row i} drop(softmax_i(z[:,h]))[p] * xl[col[p],h,:]
+ * ggl_gatv2_fwd (csrc/gatv2.hip, GPU build only; the host build answers supported = 0 and fails the launch): ONE walk of the
+ * destination-sorted plan.  The g = C / 4 lanes of a head form __fmul_rn(att, lrelu(__fadd_rn(xl, xr))) for their four channels
+ * from the value row the walk gathers anyway, add them ascending from 0.0f and finish with ggl_dot_attn_fwd's butterfly;
+ * everything behind z is ggl_edge_softmax_agg_fwd's code.  Hence the contract of ggl_dot_attn_fwd: with z_out != NULL the
+ * logits are stored, [E,H] in the CALLER's edge order (through plan->perm), and out / rowmax / rowden are
+ * ggl_edge_softmax_agg_fwd(plan, col, z_out, xl, ...)'s bit for bit; with z_out == NULL out has the same bits and no [E,H]
+ * array is touched.  z is within gamma_{C+2} sum_c |att_c| |lrelu(xl_c + xr_c)| of the exact value (gamma_n = n u / (1 - n u),
+ * u = 2^-24).  xl, xr, att, out and plan->partial must be 16-byte aligned; plan->partial = ggl_gat_partial_bytes(n_chunks, H, C)
+ * bytes when the plan has long rows; rng_state as ggl_gat_fused_fwd.
+ *   ggl_gatv2_supported(H, C)            : 1 for C = 8, 16, 32, 64 and any H > 0.
+ *   ggl_policy_gatv2_fused(H, C, E, N_in): 1 where the fused forward is the default over logits composed in front of
+ *       ggl_edge_softmax_agg_fwd (profiles/gatv2_attention.txt); never 1 for an unsupported shape.
+ * The backward runs ggl_edge_softmax_agg_bwd_dst / _bwd_src on z (alpha, gz, the value part gv of xl's gradient) and then
+ * ggl_gatv2_logit_bwd (csrc/gatv2_bwd.hpp, every build), which carries LeakyReLU's derivative inside the channel dimension.
+ * For row r of the plan it is given, head h, channel c, positions p ascending, e_p = plan->perm ? plan->perm[p] : p:
+ *   s = __fadd_rn(other[col[p],h,c], self[r,h,c]);  w = gz[e_p,h]
+ *   accD = __fadd_rn(accD, s > 0 ? w : __fmul_rn(w, slope))
+ *   accA = __fadd_rn(accA, __fmul_rn(w, s > 0 ? s : __fmul_rn(s, slope)))              (only with att_rows != NULL)
+ *   g_self[r,h,c] = add ? __fadd_rn(add[r,h,c], __fmul_rn(att[h,c], accD)) : __fmul_rn(att[h,c], accD);  att_rows[r,h,c] = accA
+ * Rows longer than plan->chunk are walked in pieces of chunk positions, each summed from 0.0f, and merged in ascending chunk
+ * order from 0.0f before the att multiply and the add; plan->partial = ggl_gatv2_logit_bwd_partial_bytes(n_chunks, H, C,
+ * att_rows != NULL) bytes when the plan has long rows.  Forward plan (col, self = xr, other = xl, att_rows = R): g_xr, and
+ * g_att = column sums of R.  Transposed plan (colT, perm = the caller's edge number of every position, self = xl,
+ * other = xr, add = gv): the whole g_xl. */
+int ggl_gatv2_supported(int64_t H, int64_t C);
+int ggl_policy_gatv2_fused(int64_t H, int64_t C, int64_t E, int64_t N_in);
+int ggl_gatv2_fwd(const ggl_segplan_t *plan, const int32_t *col, const float *xl, const float *xr, const float *att,
+                  float slope, int64_t H, int64_t C, float p_drop, int64_t *rng_state, float *out, float *rowmax,
+                  float *rowden, float *z_out, void *stream);
+size_t ggl_gatv2_logit_bwd_partial_bytes(int64_t n_chunks, int64_t H, int64_t C, int with_att_rows);
+int ggl_gatv2_logit_bwd(const ggl_segplan_t *plan, const int32_t *col, const float *other, const float *self,
+                        const float *gz, const float *att, float slope, int64_t H, int64_t C, const float *add,
+                        float *g_self, float *att_rows, void *stream);
 /* Fast path of the same op for heads of C = 4, 8, 16, 32 or 64 channels with H * C <= 256
  * (ggl_gat_fast_supported; e.g. the Reddit GAT's 8 x 8): same walks with ~5x fewer vector-ALU instructions
  * (v_exp_f32, one rescale per 4-8 edges, 16-byte index loads, 32-bit panel offsets, FMA) and a backward that
