@@ -142,6 +142,9 @@ SIGNATURES = {
     "ggl_gatv2_fwd": (c_int, [_P, _V, _V, _V, _V, c_float, c_int64, c_int64, c_float, _V, _V, _V, _V, _V, _V]),
     "ggl_gatv2_logit_bwd_partial_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int]),
     "ggl_gatv2_logit_bwd": (c_int, [_P, _V, _V, _V, _V, _V, c_float, c_int64, c_int64, _V, _V, _V, _V]),
+    "ggl_segment_multi_partial_bytes": (c_size_t, [c_int64, c_int64, POINTER(c_int), c_int]),
+    "ggl_segment_multi_fwd": (c_int, [_V, _P, c_int64, c_int64, POINTER(c_int), c_int, c_int, _V, _V, _V, _V, _V]),
+    "ggl_segment_multi_bwd": (c_int, [_V, _V, _V, _V, _V, _V, _P, c_int64, c_int64, POINTER(c_int), c_int, _V, _V]),
     "ggl_gat_fused_fwd_x16": (c_int, [_P, _V, _V, _V, c_int, _V, c_float, c_int64, c_int64, c_float, _V, c_int, _V, _V, _V,
                                       _V]),
     "ggl_gat_fused_bwd_dst_x16": (c_int, [_P, _V, _V, _V, c_int, _V, c_int, _V, c_int, _V, _V, _V, c_float, c_int64,

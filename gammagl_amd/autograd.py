@@ -71,6 +71,32 @@ class SegmentMax(torch.autograd.Function):  # src/segment_max.cpp:37-61
         return None, gin, None, None
 
 
+class SegmentMulti(torch.autograd.Function):  # pna_conv.py:159-181: several statistics of the same rows, one walk each way
+    @staticmethod
+    def forward(ctx, eng, x, plan, codes, C, empty_zero, need_grad):
+        ctx.eng = eng   # (need_grad: x requires grad and grad mode is on — the caller's grad mode, which forward() cannot see)
+        sq = 4 in codes or 5 in codes
+        out, mean, amin, amax = eng._segment_multi_fwd(x, plan, codes, C, empty_zero, want_mean=need_grad and sq)
+        ctx.plan, ctx.codes, ctx.C, ctx.K = plan, codes, C, int(x.shape[1])
+        # only what the requested statistics' backward reads: x and mean for var / std, out for std, the witnesses for min / max
+        ctx.names = ()
+        if need_grad:
+            saved = {"x": x if sq else None, "mean": mean, "out": out if 5 in codes else None, "argmin": amin, "argmax": amax}
+            ctx.names = tuple(k for k, v in saved.items() if v is not None)
+            ctx.save_for_backward(*(saved[k] for k in ctx.names))
+        eng.stats["segment_multi"] = {"route": "fused", "saved": ctx.names}
+        ctx.mark_non_differentiable(*(t for t in (amin, amax) if t is not None))
+        return out, amin, amax
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _gmin, _gmax):
+        t = dict(zip(ctx.names, ctx.saved_tensors))
+        gx = ctx.eng._segment_multi_bwd(g, t.get("x"), t.get("out"), t.get("mean"), t.get("argmin"), t.get("argmax"),
+                                        ctx.plan, ctx.K, ctx.C, ctx.codes)
+        return None, gx, None, None, None, None, None
+
+
 class SegmentSoftmax(torch.autograd.Function):  # utils/softmax.py:29-35 as one op each way
     @staticmethod
     def forward(ctx, eng, x, plan):

@@ -50,6 +50,14 @@ def load_grad():
     return torch.ops.ggl_grad
 
 
+def load_agg():
+    """``torch.ops.ggl_agg`` (the same library): ``segment_multi(x, index, N, aggs, C, empty_zero=False)``, several statistics
+    (GGL_AGG_* codes: 0 sum, 1 mean, 2 min, 3 max, 4 var, 5 std) of ``x [E, K]`` per segment from one walk, with its
+    ``_forward`` / ``_backward`` passes.  A namespace of its own for the reason ``load_grad`` gives."""
+    load()
+    return torch.ops.ggl_agg
+
+
 def load_attn():
     """``torch.ops.ggl_attn`` (the same library): ``edge_softmax_aggregate(index, logits, x, num_nodes=None, dropout_rate=0.)``,
     edge softmax + weighted aggregate on per-edge logits, with its ``_forward`` / ``_backward`` passes, and

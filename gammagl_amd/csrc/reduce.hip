@@ -1149,6 +1149,8 @@ static int fill_plan(ReduceArgs &a, const ggl_segplan_t *plan, int dtype, int64_
 
 }  // namespace ggl
 
+#include "multiagg.hpp"   // ggl_segment_multi_{fwd,bwd}: several statistics of the same rows in one walk
+
 using namespace ggl;
 
 extern "C" size_t ggl_partial_bytes(int dtype, int64_t n_chunks, int64_t K, int with_arg) {

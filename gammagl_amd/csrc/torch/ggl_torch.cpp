@@ -78,7 +78,8 @@ using torch::autograd::variable_list;
   X(ggl_plan_rows_workspace_bytes) X(ggl_plan_rows_rank) X(ggl_plan_rows_fwd_rowptr) X(ggl_plan_rows_fwd_fill)        \
   X(ggl_plan_rows_bwd_rowptr) X(ggl_plan_rows_bwd_fill) X(ggl_bias_grad_rows)                                          \
   X(ggl_spmm_epi_x16) X(ggl_bias_act_fwd_x16) X(ggl_bias_act_bwd_x16)                                                \
-  X(ggl_linear_bias_act_bwd) X(ggl_policy_linear_epi_bwd)
+  X(ggl_linear_bias_act_bwd) X(ggl_policy_linear_epi_bwd)                                                             \
+  X(ggl_segment_multi_partial_bytes) X(ggl_segment_multi_fwd) X(ggl_segment_multi_bwd)
 
 struct Api {
   void *handle = nullptr;
@@ -2561,6 +2562,140 @@ static std::vector<int64_t> plan_stats() {
   return {static_cast<int64_t>(g_plans_built.load()), static_cast<int64_t>(g_plan_hits.load())};
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// ggl_agg::segment_multi — several statistics (GGL_AGG_* codes) of x [E, K] per segment in one walk each way
+// (ggl_segment_multi_fwd / _bwd, csrc/multiagg.hpp).  out [N, K / C, A, C] stored as [N, A * K].  The passes hand what was
+// not produced / is not needed as tensors of 0 elements.
+// ---------------------------------------------------------------------------------------------------------------
+struct MultiAggs {
+  std::vector<int> codes;
+  bool sq = false, mn = false, mx = false, sd = false;
+};
+static MultiAggs multi_aggs(c10::IntArrayRef aggs) {
+  MultiAggs m;
+  TORCH_CHECK(aggs.size() >= 1 && aggs.size() <= 6, "segment_multi: between 1 and 6 aggregators");
+  for (int64_t c : aggs) {
+    TORCH_CHECK(c >= GGL_AGG_SUM && c <= GGL_AGG_STD, "segment_multi: unknown aggregator code ", c);
+    TORCH_CHECK(std::find(m.codes.begin(), m.codes.end(), static_cast<int>(c)) == m.codes.end(), "segment_multi: aggregator code ", c,
+                " is given twice");
+    m.codes.push_back(static_cast<int>(c));
+    m.sq = m.sq || c == GGL_AGG_VAR || c == GGL_AGG_STD;
+    m.sd = m.sd || c == GGL_AGG_STD;
+    m.mn = m.mn || c == GGL_AGG_MIN;
+    m.mx = m.mx || c == GGL_AGG_MAX;
+  }
+  return m;
+}
+static void multi_check(const Tensor &x, const Tensor &index, int64_t C) {
+  seg_args(x, index);
+  f32("x", x);
+  TORCH_CHECK(x.dim() == 2, "segment_multi expects x [E, K], got ", x.sizes());
+  TORCH_CHECK(C > 0 && x.size(1) % C == 0, "segment_multi: C = ", C, " does not divide K = ", x.size(1));
+}
+template <typename T> static T *ptr_or_null(const Tensor &t) { return t.defined() && t.numel() > 0 ? t.data_ptr<T>() : nullptr; }
+
+static std::tuple<Tensor, Tensor, Tensor, Tensor> multi_forward_kernel(const Tensor &x_, const Tensor &index, int64_t N,
+                                                                       c10::IntArrayRef aggs, int64_t C, bool empty_zero,
+                                                                       bool want_mean) {
+  multi_check(x_, index, C);
+  const MultiAggs m = multi_aggs(aggs);
+  const auto dev = x_.device();
+  c10::OptionalDeviceGuard guard(dev);
+  const Api &a = api_for(dev);
+  Tensor x = x_.contiguous();
+  auto plan = seg_plan(index, N);
+  TORCH_CHECK_INDEX(x.size(0) == plan->E, "fisrt dimension of x and index should be same");
+  const int64_t K = x.size(1), A = static_cast<int64_t>(m.codes.size());
+  auto o = x.options();
+  Tensor out = at::empty({N, A * K}, o);
+  Tensor mean = want_mean && m.sq ? at::empty({N, K}, o) : at::empty({0}, o);
+  Tensor amin = m.mn ? at::empty({N, K}, o.dtype(at::kInt)) : at::empty({0}, o.dtype(at::kInt));
+  Tensor amax = m.mx ? at::empty({N, K}, o.dtype(at::kInt)) : at::empty({0}, o.dtype(at::kInt));
+  Tensor part;
+  if (plan->n_long > 0)
+    part = at::empty({static_cast<int64_t>(a.ggl_segment_multi_partial_bytes(plan->n_chunks, K, m.codes.data(), (int)A)) + 16},
+                     o.dtype(at::kByte));
+  ggl_segplan_t cs = plan->c(part);
+  check(a, a.ggl_segment_multi_fwd(ptr_or_null<float>(x), &cs, K, C, m.codes.data(), (int)A, empty_zero ? 1 : 0,
+                                   ptr_or_null<float>(out), ptr_or_null<float>(mean), ptr_or_null<int32_t>(amin),
+                                   ptr_or_null<int32_t>(amax), stream_of(dev)));
+  return {out, mean, amin, amax};
+}
+
+static Tensor multi_backward_kernel(const Tensor &grad, const Tensor &x_, const Tensor &out, const Tensor &mean, const Tensor &amin,
+                                    const Tensor &amax, const Tensor &index, int64_t N, c10::IntArrayRef aggs, int64_t C) {
+  same_device({&grad, &index});
+  const MultiAggs m = multi_aggs(aggs);
+  const auto dev = grad.device();
+  c10::OptionalDeviceGuard guard(dev);
+  const Api &a = api_for(dev);
+  Tensor g = grad.contiguous(), x = x_.contiguous();
+  f32("grad", g);
+  const int64_t A = static_cast<int64_t>(m.codes.size());
+  TORCH_CHECK(g.dim() == 2 && g.size(0) == N && g.size(1) % A == 0, "segment_multi backward: grad must be [N, A * K]");
+  const int64_t K = g.size(1) / A;
+  auto plan = seg_plan(index, N);    // (the forward's plan: a cache hit)
+  Tensor gx = at::empty({plan->E, K}, g.options());
+  ggl_segplan_t cs = plan->c(Tensor());
+  check(a, a.ggl_segment_multi_bwd(ptr_or_null<float>(g), ptr_or_null<float>(x), ptr_or_null<float>(out), ptr_or_null<float>(mean),
+                                   ptr_or_null<int32_t>(amin), ptr_or_null<int32_t>(amax), &cs, K, C, m.codes.data(), (int)A,
+                                   ptr_or_null<float>(gx), stream_of(dev)));
+  return gx;
+}
+
+using MultiFwdSig = std::tuple<Tensor, Tensor, Tensor, Tensor>(const Tensor &, const Tensor &, int64_t, c10::IntArrayRef, int64_t,
+                                                               bool, bool);
+using MultiBwdSig = Tensor(const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
+                           const Tensor &, int64_t, c10::IntArrayRef, int64_t);
+// saves only what the requested statistics' backward reads: x and mean for var / std, out for std, the witnesses for min / max
+struct MultiFn : public torch::autograd::Function<MultiFn> {
+  static Tensor forward(AutogradContext *ctx, const Tensor &x, const Tensor &index, int64_t N, std::vector<int64_t> aggs, int64_t C,
+                        bool empty_zero) {
+    at::AutoDispatchBelowADInplaceOrView below;
+    static auto op = op_handle<MultiFwdSig>("ggl_agg::segment_multi_forward");
+    const MultiAggs m = multi_aggs(aggs);
+    const bool need = x.requires_grad();
+    Tensor out, mean, amin, amax;
+    std::tie(out, mean, amin, amax) = op.call(x, index, N, aggs, C, empty_zero, need);
+    if (need) {
+      Tensor none = at::empty({0}, x.options());
+      ctx->save_for_backward({m.sq ? x : none, m.sd ? out : none, mean, amin, amax, index});
+    }
+    ctx->saved_data["N"] = N;
+    ctx->saved_data["C"] = C;
+    ctx->saved_data["aggs"] = aggs;
+    return out;
+  }
+  static variable_list backward(AutogradContext *ctx, variable_list grads) {
+    auto s = ctx->get_saved_variables();
+    static auto op = op_handle<MultiBwdSig>("ggl_agg::segment_multi_backward");
+    auto aggs = ctx->saved_data["aggs"].toIntVector();
+    Tensor gx = op.call(grads[0], s[0], s[1], s[2], s[3], s[4], s[5], ctx->saved_data["N"].toInt(), aggs,
+                        ctx->saved_data["C"].toInt());
+    return {gx, Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+  }
+};
+static Tensor multi_autograd(const Tensor &x, const Tensor &index, int64_t N, c10::IntArrayRef aggs, int64_t C, bool empty_zero) {
+  multi_check(x, index, C);
+  multi_aggs(aggs);
+  return MultiFn::apply(x, index, N, aggs.vec(), C, empty_zero);
+}
+static std::tuple<Tensor, Tensor, Tensor, Tensor> multi_fwd_meta(const Tensor &x, const Tensor &, int64_t N, c10::IntArrayRef aggs,
+                                                                 int64_t, bool, bool want_mean) {
+  const MultiAggs m = multi_aggs(aggs);
+  auto o = x.options(), i = x.options().dtype(at::kInt);
+  const int64_t K = x.size(1);
+  return {at::empty({N, static_cast<int64_t>(aggs.size()) * K}, o), want_mean && m.sq ? at::empty({N, K}, o) : at::empty({0}, o),
+          m.mn ? at::empty({N, K}, i) : at::empty({0}, i), m.mx ? at::empty({N, K}, i) : at::empty({0}, i)};
+}
+static Tensor multi_bwd_meta(const Tensor &grad, const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
+                             const Tensor &index, int64_t, c10::IntArrayRef aggs, int64_t) {
+  return at::empty({index.size(0), grad.size(1) / static_cast<int64_t>(aggs.size())}, grad.options());
+}
+static Tensor multi_meta(const Tensor &x, const Tensor &, int64_t N, c10::IntArrayRef aggs, int64_t, bool) {
+  return at::empty({N, static_cast<int64_t>(aggs.size()) * x.size(1)}, x.options());
+}
+
 }  // namespace ggl_torch
 
 TORCH_LIBRARY(ggl, m) {
@@ -2796,4 +2931,27 @@ TORCH_LIBRARY_IMPL(ggl_attn, Meta, m) {
   m.impl("gatv2_attention", ggl_torch::gatv2_meta);
   m.impl("gatv2_attention_forward", ggl_torch::gatv2_fwd_meta);
   m.impl("gatv2_attention_backward", ggl_torch::gatv2_bwd_meta);
+}
+
+// Several statistics of the same rows in one walk, a namespace of its own for the same reason: the ggl:: surface is pinned.
+TORCH_LIBRARY(ggl_agg, m) {
+  m.def("segment_multi(Tensor x, Tensor index, int N, int[] aggs, int C, bool empty_zero=False) -> Tensor");
+  m.def("segment_multi_forward(Tensor x, Tensor index, int N, int[] aggs, int C, bool empty_zero, bool want_mean) -> "
+        "(Tensor, Tensor, Tensor, Tensor)");
+  m.def("segment_multi_backward(Tensor grad, Tensor x, Tensor out, Tensor mean, Tensor argmin, Tensor argmax, Tensor index, "
+        "int N, int[] aggs, int C) -> Tensor");
+}
+#define GGL_AGG_IMPL(KEY)                                                                           \
+  TORCH_LIBRARY_IMPL(ggl_agg, KEY, m) {                                                             \
+    m.impl("segment_multi_forward", ggl_torch::multi_forward_kernel);                               \
+    m.impl("segment_multi_backward", ggl_torch::multi_backward_kernel);                             \
+  }
+GGL_AGG_IMPL(CPU)
+GGL_AGG_IMPL(CUDA)
+#undef GGL_AGG_IMPL
+TORCH_LIBRARY_IMPL(ggl_agg, Autograd, m) { m.impl("segment_multi", ggl_torch::multi_autograd); }
+TORCH_LIBRARY_IMPL(ggl_agg, Meta, m) {
+  m.impl("segment_multi", ggl_torch::multi_meta);
+  m.impl("segment_multi_forward", ggl_torch::multi_fwd_meta);
+  m.impl("segment_multi_backward", ggl_torch::multi_bwd_meta);
 }

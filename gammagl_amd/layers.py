@@ -17,6 +17,8 @@ here); every tlx call they make on this path maps 1:1 onto torch (``tlx.gather``
 * ``HGTConv``         — layers/conv/hgt_conv.py:41-153 (fused: utils.dot_attention per edge type)
 * ``GATv2Conv``       — the GATv2 paper's layer (fused: utils.gatv2_attention); variant="reference" is
   layers/conv/gatv2_conv.py:94-119, whose logit is separable
+* ``PNAConv``         — layers/conv/pna_conv.py:82-201 (fused: utils.segment_multi_aggregate, all statistics in one walk),
+  with the ``global_{sum,mean,max,min}_pool`` functions of layers/pool/glob.py:5-114
 * ``GCNModel``        — models/gcn.py:30-64
 """
 import math
@@ -28,8 +30,9 @@ from . import engine as _engine
 from .dense import Linear, _LinearFn, node_matmul
 from .sampler import Block
 from .utils.attention import dot_attention, edge_softmax_aggregate, gatv2_attention
+from .utils.aggregate import segment_multi_aggregate, segment_multi_composed
 from .mpops import (bspmm, gspmm, unsorted_segment_max, unsorted_segment_mean,  # noqa: F401
-                    unsorted_segment_sum, use_ext)
+                    unsorted_segment_min, unsorted_segment_sum, use_ext)
 
 
 def degree(index, num_nodes, dtype=torch.float32):
@@ -604,6 +607,138 @@ class HGTConv(MessagePassing):
             gate = torch.sigmoid(self.skip[node_type])
             out_dict[node_type] = gate * out + (1 - gate) * x_dict[node_type]
         return out_dict
+
+
+def _pool_size(batch, size):
+    return int(batch.max()) + 1 if size is None else int(size)
+
+
+def global_sum_pool(x, batch, size=None):
+    """layers/pool/glob.py:5-30; batch=None reduces dimension 0."""
+    if batch is None:
+        return x.sum(dim=0, keepdim=True)
+    return unsorted_segment_sum(x, batch, _pool_size(batch, size))
+
+
+def global_mean_pool(x, batch, size=None):
+    """layers/pool/glob.py:33-58."""
+    if batch is None:
+        return x.mean(dim=0, keepdim=True)
+    return unsorted_segment_mean(x, batch, _pool_size(batch, size))
+
+
+def global_max_pool(x, batch, size=None):
+    """layers/pool/glob.py:61-86."""
+    if batch is None:
+        return x.max(dim=0, keepdim=True)[0]
+    return unsorted_segment_max(x, batch, _pool_size(batch, size))
+
+
+def global_min_pool(x, batch, size=None):
+    """layers/pool/glob.py:89-114."""
+    if batch is None:
+        return x.min(dim=0, keepdim=True)[0]
+    return unsorted_segment_min(x, batch, _pool_size(batch, size))
+
+
+class PNAConv(MessagePassing):
+    """pna_conv.py:82-201, Principal Neighbourhood Aggregation: per tower an edge MLP h(x_i, x_j[, edge_attr]) (pre_nns), the
+    statistics named in `aggregators` (sum, mean, min, max, var, std) of the messages per destination, each degree scaler of
+    `scalers` (identity, amplification, attenuation, linear, inverse_linear) applied to their concatenation, a node MLP
+    (post_nns) on [x, scaled statistics] and one output Linear.  `deg` is the in-degree histogram the scalers normalise by.
+    The edge MLP and the scalers (node-sized) stay in torch.  As in the reference (lines 186-200) a scaler multiplies the
+    result of the scalers before it, and the destination degree is clamped at 1.
+    fused=True aggregates through utils.segment_multi_aggregate (C = F_in, empty_zero): one walk of the [E, T, F_in] messages
+    instead of one per statistic plus a tensor of squares.  fused=False is the reference's composition on the mpops ops
+    (utils.segment_multi_composed), with min / max of destinations without edges zeroed the same way; its backward is the
+    fused walk's formula written in torch in the same operation order, so the two routes agree on the bits, gradients
+    included, wherever every destination's edges are walked in one piece."""
+
+    AGGREGATORS = ("sum", "mean", "min", "max", "var", "std")
+    SCALERS = ("identity", "amplification", "attenuation", "linear", "inverse_linear")
+
+    def __init__(self, in_channels, out_channels, aggregators, scalers, deg, edge_dim=None, towers=1, pre_layers=1,
+                 post_layers=1, divide_input=False, fused=True):
+        super().__init__()
+        if divide_input and in_channels % towers != 0:
+            raise ValueError("divide_input: in_channels must be a multiple of towers")
+        if out_channels % towers != 0:
+            raise ValueError("out_channels must be a multiple of towers")
+        for a in aggregators:
+            if a not in self.AGGREGATORS:
+                raise ValueError(f'Unknown aggregator "{a}".')
+        for s in scalers:
+            if s not in self.SCALERS:
+                raise ValueError(f'Unknown scaler "{s}".')
+        if len(set(aggregators)) != len(aggregators):
+            raise ValueError("aggregators must be distinct")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.aggregators, self.scalers = tuple(aggregators), tuple(scalers)
+        self.edge_dim, self.towers, self.divide_input, self.fused = edge_dim, towers, divide_input, fused
+        self.F_in = in_channels // towers if divide_input else in_channels
+        self.F_out = out_channels // towers
+        deg = torch.as_tensor(deg).to(torch.float32).cpu()
+        num_nodes = int(deg.sum())
+        bins = torch.arange(deg.numel(), dtype=torch.float32)
+        self.avg_deg = {'lin': float((bins * deg).sum()) / num_nodes,
+                        'log': float((torch.log(bins + 1) * deg).sum()) / num_nodes,
+                        'exp': float((torch.exp(bins) * deg).sum()) / num_nodes}
+        if edge_dim is not None:
+            self.edge_encoder = Linear(edge_dim, self.F_in)
+        self.pre_nns, self.post_nns = nn.ModuleList(), nn.ModuleList()
+        for _ in range(towers):
+            mods = [Linear((3 if edge_dim else 2) * self.F_in, self.F_in)]
+            for _ in range(pre_layers - 1):
+                mods += [nn.ReLU(), Linear(self.F_in, self.F_in)]
+            self.pre_nns.append(nn.Sequential(*mods))
+            mods = [Linear((len(aggregators) * len(scalers) + 1) * self.F_in, self.F_out)]
+            for _ in range(post_layers - 1):
+                mods += [nn.ReLU(), Linear(self.F_out, self.F_out)]
+            self.post_nns.append(nn.Sequential(*mods))
+        self.lin = Linear(out_channels, out_channels)
+
+    def forward(self, x, edge_index, edge_attr=None):
+        if self.divide_input:
+            x = x.reshape(-1, self.towers, self.F_in)
+        else:
+            x = torch.stack([x for _ in range(self.towers)], dim=1)
+        n = x.shape[0]
+        out = self.aggregate(self.message(x, edge_index, edge_attr), edge_index, num_nodes=n)
+        out = torch.cat([x, out], dim=-1)
+        out = torch.cat([net(out[:, i]) for i, net in enumerate(self.post_nns)], dim=1)
+        return self.lin(out)
+
+    def message(self, x, edge_index, edge_attr=None):
+        x_j, x_i = x[edge_index[0]], x[edge_index[1]]
+        if edge_attr is not None:
+            e = self.edge_encoder(edge_attr)
+            h = torch.cat([x_i, x_j, torch.stack([e for _ in range(self.towers)], dim=1)], dim=-1)
+        else:
+            h = torch.cat([x_i, x_j], dim=-1)
+        return torch.stack([net(h[:, i]) for i, net in enumerate(self.pre_nns)], dim=1)
+
+    def aggregate(self, inputs, index, num_nodes=None, aggr=None):
+        dst = index[1]
+        dst = dst if dst.is_contiguous() else dst.contiguous()
+        n = int(dst.max()) + 1 if num_nodes is None else int(num_nodes)
+        deg = degree(dst, n, dtype=inputs.dtype)
+        if self.fused:
+            out = segment_multi_aggregate(inputs, dst, n, self.aggregators, empty_zero=True)
+        else:
+            out = segment_multi_composed(inputs, dst, n, self.aggregators, empty_zero=True)
+        deg = torch.where(deg > 1, deg, torch.ones_like(deg)).reshape(-1, 1, 1)
+        outs = []
+        for s in self.scalers:
+            if s == 'amplification':
+                out = out * (torch.log(deg + 1) / self.avg_deg['log'])
+            elif s == 'attenuation':
+                out = out * (self.avg_deg['log'] / torch.log(deg + 1))
+            elif s == 'linear':
+                out = out * (deg / self.avg_deg['lin'])
+            elif s == 'inverse_linear':
+                out = out * (self.avg_deg['lin'] / deg)
+            outs.append(out)
+        return torch.cat(outs, dim=-1)
 
 
 class GCNModel(nn.Module):

@@ -40,8 +40,19 @@ def _ops_for(x):
             return cpp_ops.load()
     return _py_ops
 
-__all__ = ["unsorted_segment_sum", "unsorted_segment_mean", "unsorted_segment_max", "segment_sum",
-           "segment_mean", "segment_max", "gspmm", "bspmm", "use_ext", "torch"]
+def _agg_ops_for(x):
+    """The namespace of ``segment_multi`` for `x`: ``torch.ops.ggl_agg`` (registered from C++) where ``_ops_for`` answers
+    ``torch.ops.ggl``, the Python-registered ``torch.ops.gammagl_amd`` otherwise."""
+    ops = _ops_for(x)
+    if ops is not _py_ops:
+        from . import cpp_ops
+
+        return cpp_ops.load_agg()
+    return ops
+
+
+__all__ = ["unsorted_segment_sum", "unsorted_segment_mean", "unsorted_segment_max", "unsorted_segment_min", "segment_sum",
+           "segment_mean", "segment_max", "segment_min", "gspmm", "bspmm", "use_ext", "torch"]
 
 
 def _num_segments(segment_ids, num_segments):
@@ -79,6 +90,29 @@ def unsorted_segment_max(x, segment_ids, num_segments=None):
     n = _num_segments(segment_ids, num_segments)
     assert x.shape[0] == segment_ids.shape[0], "the length of segment_ids should be equal to data.shape[0]."
     return _ops_for(x).segment_max(x, _ids(segment_ids, x), n)[0]
+
+
+def unsorted_segment_min(x, segment_ids, num_segments=None):
+    """Min along segments (what layers/pool/glob.py:89-114 and pna_conv.py:169 call): the mirror of
+    :func:`unsorted_segment_max` — the first element wins ties, NaN never wins, empty segments hold
+    ``numeric_limits<T>::max()``.  f32 runs the multi-statistic walk with the one aggregate ``min`` (no sums are carried;
+    the gradient goes to the witness only, like max's); f16 / bf16 / f64 run ``-unsorted_segment_max(-x)``, which is exact
+    (same winner, same tie and NaN rule, ``-lowest() == max()``); integer dtypes run ``~unsorted_segment_max(~x)``, which
+    reverses the order without overflow."""
+    n = _num_segments(segment_ids, num_segments)
+    assert x.shape[0] == segment_ids.shape[0], "the length of segment_ids should be equal to data.shape[0]."
+    if x.dtype == torch.float32:
+        E = x.shape[0]
+        K = x.numel() // E if E > 0 else int(torch.Size(x.shape[1:]).numel())
+        out = _agg_ops_for(x).segment_multi(x.reshape(E, K), _ids(segment_ids, x), n, [2], max(K, 1), False)
+        return out.reshape((n,) + tuple(x.shape[1:]))
+    if x.dtype.is_floating_point:
+        return -unsorted_segment_max(-x, segment_ids, n)
+    return ~unsorted_segment_max(~x, segment_ids, n)
+
+
+def segment_min(x, segment_ids, num_segments=None):
+    return unsorted_segment_min(x, segment_ids, num_segments)
 
 
 def segment_max(x, segment_ids, num_segments=None):

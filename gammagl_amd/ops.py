@@ -21,6 +21,13 @@ from .plans import GraphPlan, RowsPlan, SegPlan, _PlanCache
 DEFAULT_CHUNK = int(os.environ.get("GGL_LONG_ROW", "0"))  # 0 = automatic, see Engine.auto_chunk
 
 
+def sqrt_rn(t):
+    """The correctly rounded square root of an f32 tensor (taken in float64 and rounded once: 53 >= 2 * 24 + 2 bits make the
+    double rounding exact), as the kernels' sqrt is.  torch.sqrt's vectorised CPU kernel is one ulp off for about 0.6 % of its
+    inputs, which would make the composed statistics differ from the fused walk's in the last bit.  Node-sized tensors only."""
+    return torch.sqrt(t.double()).to(t.dtype) if t.dtype == torch.float32 else torch.sqrt(t)
+
+
 class Engine:
     def __init__(self, lib, require_cuda=True, cpu_only=False):
         self.lib = lib
@@ -48,6 +55,7 @@ class Engine:
         self.gradw_sorted = True    # bspmm weight gradient along the sorted plan with LDS-staged strips (A/B switch)
         self.dot_attn_fused = True  # dot-product attention: the dot inside the aggregate's walk (GPU build only; A/B switch)
         self.gatv2_fused = True     # GATv2 attention: the additive logit inside the aggregate's walk (GPU build only; A/B switch)
+        self.segment_multi_fused = True   # segment_multi: one walk for all statistics; off = composed from the segment ops (A/B switch)
 
     def clear_caches(self):
         """Drop every cached plan, sorted-weight copy and graph-constant (e.g. GCN norms).  Plans are keyed on
@@ -746,6 +754,112 @@ class Engine:
 
     def segment_max_with_arg(self, x, index, N):
         return autograd.SegmentMax.apply(self, *self._seg_args(x, index, N))
+
+    # ---- several statistics of the same rows in one walk (ggl_segment_multi_*, csrc/multiagg.hpp) ----
+    AGG_CODES = {"sum": 0, "mean": 1, "min": 2, "max": 3, "var": 4, "std": 5}   # enum GGL_AGG_* (include/ggl_mpops.h)
+
+    @classmethod
+    def agg_codes(cls, aggs):
+        """names (or codes) -> a tuple of distinct GGL_AGG_* codes, in the caller's order"""
+        codes = []
+        for a in aggs:
+            c = cls.AGG_CODES.get(a) if isinstance(a, str) else (int(a) if 0 <= int(a) <= 5 else None)
+            if c is None:
+                raise ValueError(f"segment_multi: unknown aggregator {a!r}; choose from {sorted(cls.AGG_CODES)}")
+            if c in codes:
+                raise ValueError(f"segment_multi: aggregator {a!r} is given twice")
+            codes.append(c)
+        if not 1 <= len(codes) <= 6:
+            raise ValueError("segment_multi: between 1 and 6 aggregators")
+        return tuple(codes)
+
+    def _segment_multi_fwd(self, x, plan, codes, C, empty_zero, want_mean=False):
+        """(out [N, A * K], mean [N, K] or None, argmin, argmax [N, K] int32 or None) of x [E, K] f32 contiguous"""
+        dev, E, K, A = x.device, int(x.shape[0]), int(x.shape[1]), len(codes)
+        if E != plan.E:
+            raise IndexError("fisrt dimension of x and index should be same")
+        out = torch.empty((plan.N, A * K), dtype=torch.float32, device=dev)
+        mean = torch.empty((plan.N, K), dtype=torch.float32, device=dev) if want_mean else None
+        amin = torch.empty((plan.N, K), dtype=torch.int32, device=dev) if 2 in codes else None
+        amax = torch.empty((plan.N, K), dtype=torch.int32, device=dev) if 3 in codes else None
+        arr = (ctypes.c_int * A)(*codes)
+        part = self._hub_partial(plan, lambda n: self.lib.ggl_segment_multi_partial_bytes(n, K, arr, A), dev)
+        cs = plan.c_struct(part)
+        self._check(self.lib.ggl_segment_multi_fwd(_ptr(x), ctypes.byref(cs), K, C, arr, A, int(bool(empty_zero)), _ptr(out),
+                                                   _ptr(mean), _ptr(amin), _ptr(amax), self._stream(dev)))
+        return out, mean, amin, amax
+
+    def _segment_multi_bwd(self, g, x, out, mean, amin, amax, plan, K, C, codes):
+        dev, A = g.device, len(codes)
+        g = g.contiguous()
+        gx = torch.empty((plan.E, K), dtype=torch.float32, device=dev)
+        arr = (ctypes.c_int * A)(*codes)
+        cs = plan.c_struct(None)
+        self._check(self.lib.ggl_segment_multi_bwd(_ptr(g), _ptr(x), _ptr(out), _ptr(mean), _ptr(amin), _ptr(amax),
+                                                   ctypes.byref(cs), K, C, arr, A, _ptr(gx), self._stream(dev)))
+        return gx
+
+    def _segment_multi_composed(self, x, ids, N, codes, C, empty_zero):
+        """The same statistics from the existing segment ops (the A/B partner of the fused walk and PNAConv's
+        fused=False): mean, sum and max as they are, min = -max(-x), var = mean(x * x) - mean * mean,
+        std = sqrt(relu(var) + 1e-5) (pna_conv.py:159-181)."""
+        E, K = int(x.shape[0]), int(x.shape[1])
+        mean = self.c_segment_mean(x, ids, N) if any(c in codes for c in (1, 4, 5)) else None
+        var = None
+        if 4 in codes or 5 in codes:
+            var = self.c_segment_mean(x * x, ids, N) - mean * mean
+        cnt = None
+        if empty_zero and (2 in codes or 3 in codes):
+            cnt = torch.bincount(ids, minlength=N).unsqueeze(1)
+        outs = []
+        for c in codes:
+            if c == 0:
+                o = self.c_segment_sum(x, ids, N)
+            elif c == 1:
+                o = mean
+            elif c == 2:
+                o = -self.c_segment_max(-x, ids, N)
+            elif c == 3:
+                o = self.c_segment_max(x, ids, N)
+            elif c == 4:
+                o = var
+            else:
+                o = sqrt_rn(torch.relu(var) + 1e-5)
+            if cnt is not None and c in (2, 3):
+                o = torch.where(cnt > 0, o, torch.zeros_like(o))
+            outs.append(o.reshape(N, K // C, 1, C))
+        return torch.cat(outs, 2).reshape(N, len(codes) * K)
+
+    def segment_multi(self, x, ids_or_plan, N=None, aggs=("mean", "min", "max", "std"), C=None, empty_zero=False,
+                      return_witnesses=False):
+        """Several statistics of x [E, K] f32 over the segments of `ids_or_plan` (int64 ids [E], or a SegPlan) in one walk:
+        out [N, K / C, A, C] stored as [N, A * K] — column k of statistic a at (k / C) * A * C + a * C + k % C; C = K (the
+        default) is cat(outs, -1), x [E, T * F] with C = F the per-tower concatenation.  `aggs`: distinct names from sum,
+        mean, min, max, var, std, in output order.  Empty segments: 0 for sum / mean / var, sqrt(1e-5) for std, -+FLT_MAX for
+        max / min or 0 with `empty_zero`.  Differentiable in x; with `return_witnesses` also (argmin, argmax) [N, K] int32
+        (None where not requested).  With `self.segment_multi_fused` off the statistics are composed from the segment ops."""
+        codes = self.agg_codes(aggs)
+        self._check_f32("x", x)
+        if x.dim() != 2:
+            raise RuntimeError(f"segment_multi expects x [E, K], got {tuple(x.shape)}")
+        K = int(x.shape[1])
+        C = K if C is None else int(C)
+        if C <= 0 or (K % C and K > 0):
+            raise RuntimeError(f"segment_multi: C = {C} does not divide K = {K}")
+        if isinstance(ids_or_plan, SegPlan):
+            self._dev(x)
+            plan, ids = ids_or_plan, None
+        else:
+            x, ids, N = self._seg_args(x, ids_or_plan, N)
+            plan = None
+        if not self.segment_multi_fused and ids is not None and not return_witnesses:
+            self.stats["segment_multi"] = {"route": "composed", "saved": ()}
+            return self._segment_multi_composed(x, ids, N, codes, C, empty_zero)
+        if plan is None:
+            plan = self.seg_plan(ids, N)
+        out, amin, amax = autograd.SegmentMulti.apply(self, x.contiguous(), plan, codes, C, bool(empty_zero),
+                                                            bool(x.requires_grad and torch.is_grad_enabled()))
+        return (out, amin, amax) if return_witnesses else out
 
     def segment_softmax_supported(self, x):
         """Does the native edge softmax take `x` (f32, rows of a width the library has a kernel for)?"""

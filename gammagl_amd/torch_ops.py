@@ -21,6 +21,7 @@ points (+ the fused GAT op and the fused epilogue) are dispatcher ops:
     torch.ops.gammagl_amd.edge_softmax_aggregate(index, logits, x, num_nodes, dropout_rate) -> Tensor   (see below)
     torch.ops.gammagl_amd.dot_attention(index, q, k, v, num_nodes, scale, dropout_rate) -> Tensor        (see below)
     torch.ops.gammagl_amd.gatv2_attention(index, xl, xr, att, num_nodes, negative_slope, dropout_rate) -> Tensor  (see below)
+    torch.ops.gammagl_amd.segment_multi(x, index, N, aggs, C, empty_zero) -> Tensor                      (see below)
 
 ``spmm_sum`` / ``spmm_mean`` also take ``x`` stored as bf16 / f16 (the reference is f32 only): the sums are made in f32 and
 rounded once to x's dtype.  ``spmm_*_x16(..., out_f32=True)`` returns those f32 sums unrounded.  ``gat_fused`` does the
@@ -33,6 +34,8 @@ its logits and sums ``alpha * x[src]``): ``out[i, h] = sum_{e -> i} dropout(soft
 (``scale`` defaults to ``1 / sqrt(C)``) and ``x = v``: scaled dot-product attention over a graph, f32.
 ``gatv2_attention`` is that op with GATv2's additive logits, ``logits[e, h] = sum_c att[h, c] * leaky_relu(xl[src_e, h, c] +
 xr[dst_e, h, c])`` and ``x = xl``, f32, differentiable in ``xl``, ``xr`` and ``att``.
+``segment_multi`` returns several statistics of ``x [E, K]`` per segment from one walk: ``aggs`` are distinct GGL_AGG_* codes
+(0 sum, 1 mean, 2 min, 3 max, 4 var, 5 std), the result is ``[N, K / C, A, C]`` stored as ``[N, A * K]``, f32.
 
 Kernels are registered for ``CUDA`` / ``AutogradCUDA`` (= HIP on ROCm: libggl_mpops_hip.so) and for ``CPU`` /
 ``AutogradCPU`` (libggl_mpops_host.so, the host build of the same kernel sources) — the reference's ops dispatch
@@ -70,6 +73,7 @@ _SCHEMAS = {
                      "float dropout_rate=0.0) -> Tensor",
     "gatv2_attention": "(Tensor index, Tensor xl, Tensor xr, Tensor att, int? num_nodes=None, float negative_slope=0.2, "
                        "float dropout_rate=0.0) -> Tensor",
+    "segment_multi": "(Tensor x, Tensor index, int N, int[] aggs, int C, bool empty_zero=False) -> Tensor",
 }
 
 _DEF = Library(NS, "DEF")
@@ -104,6 +108,8 @@ def _kernels(get_engine):
             get_engine().dot_attention(index, q, k, v, num_nodes, scale, dropout_rate, True),
         "gatv2_attention": lambda index, xl, xr, att, num_nodes=None, negative_slope=0.2, dropout_rate=0.0:
             get_engine().gatv2_attention(index, xl, xr, att, num_nodes, negative_slope, dropout_rate, True),
+        "segment_multi": lambda x, index, N, aggs, C, empty_zero=False:
+            get_engine().segment_multi(x, index, N, tuple(aggs), C, empty_zero),
     }
 
 
@@ -176,7 +182,10 @@ def _register_fakes():
         n = xr.shape[0] if num_nodes is None else num_nodes
         return xl.new_empty((n,) + tuple(xl.shape[1:]))
 
-    for name, fn in (("gatv2_attention", gatv2), ("dot_attention", dot), ("edge_softmax_aggregate", esa), ("segment_sum", seg), ("segment_mean", seg), ("segment_max", seg_max),
+    def multi(x, index, N, aggs, C, empty_zero=False):
+        return x.new_empty((N, len(aggs) * x.shape[1]))
+
+    for name, fn in (("segment_multi", multi), ("gatv2_attention", gatv2), ("dot_attention", dot), ("edge_softmax_aggregate", esa), ("segment_sum", seg), ("segment_mean", seg), ("segment_max", seg_max),
                      ("segment_softmax", lambda x, index, N: torch.empty_like(x)),
                      ("spmm_sum", like_x), ("spmm_mean", like_x), ("spmm_max", like_x),
                      ("bspmm_sum", like_x), ("gat_fused", gat),

@@ -75,6 +75,8 @@ extern "C" {
  *   product, formed in registers).  Purely additive again. */
 /* still 11: + ggl_gatv2_supported, ggl_policy_gatv2_fused, ggl_gatv2_fwd, ggl_gatv2_logit_bwd, ggl_gatv2_logit_bwd_partial_bytes
  *   (GATv2's additive attention: the logit formed inside the aggregate's walk, and its backward walk).  Purely additive again. */
+/* still 11: + ggl_segment_multi_fwd, ggl_segment_multi_bwd, ggl_segment_multi_partial_bytes and the codes GGL_AGG_* (sum, mean,
+ *   min, max, var and std of the same message rows in one walk).  Purely additive again. */
 #define GGL_ABI_VERSION 11
 
 /* dtype codes (AT_DISPATCH_ALL_TYPES_AND2(Half, BFloat16), segment_sum_cpu.cpp:32-33) */
@@ -644,6 +646,44 @@ size_t ggl_gatv2_logit_bwd_partial_bytes(int64_t n_chunks, int64_t H, int64_t C,
 int ggl_gatv2_logit_bwd(const ggl_segplan_t *plan, const int32_t *col, const float *other, const float *self,
                         const float *gz, const float *att, float slope, int64_t H, int64_t C, const float *add,
                         float *g_self, float *att_rows, void *stream);
+/* Several statistics of the same message rows in ONE walk of the plan (csrc/multiagg.hpp, every build; f32): what PNA's
+ * aggregate composes from four to five segment ops and an [E, K] tensor of squares (pna_conv.py:159-201).
+ *   aggs : n_aggs (1..6) DISTINCT codes of the enum below, in output order (host memory).  C divides K.
+ *   out  : [N, K / C, A, C] contiguous, A = n_aggs: column k of statistic number a at (k / C) * A * C + a * C + k % C — C = K is
+ *          cat(outs, -1), x [E, T, F] with C = F the per-tower concatenation [N, T, A * F].
+ * Per row i with n elements and per column, positions ascending (e = perm ? perm[p] : p, v = x[e, k]), every step one rounded
+ * f32 operation:
+ *   S = __fadd_rn(S, v) from 0.0f;  Q = __fadd_rn(Q, __fmul_rn(v, v)) from 0.0f
+ *   max: from -FLT_MAX, `if (mx < v) { mx = v; argmax = e; }`;  min: from +FLT_MAX, `if (v < mn) { mn = v; argmin = e; }`
+ *   nf = (float)min(n, 2^24);  mean = n > 1 ? __fdiv_rn(S, nf) : S;  msq = n > 1 ? __fdiv_rn(Q, nf) : Q   (ggl_segment_mean's rule)
+ *   var = __fsub_rn(msq, __fmul_rn(mean, mean));  std = sqrtf(__fadd_rn(fmaxf(var, 0.0f), 1e-5f)), correctly rounded
+ * Empty rows: sum = mean = var = 0, std = sqrt(1e-5f), min / max +-FLT_MAX (0.0f with empty_zero != 0), witnesses E.
+ * mean [N, K] (optional; needs one of sum / mean / var / std among the aggs) and the witnesses argmin / argmax [N, K] int32
+ * (optional; the element index in the caller's order) are written when their pointer is given.
+ * Rows longer than plan->chunk are cut into pieces of chunk positions, each reduced from the start values into a partial
+ * (S, Q, mn, mx, amin, amax: only the panels the aggs need, [n_chunks, K] each, in that order); the partials are merged in
+ * ascending piece order, sums from 0.0f, min / max with the strict rule.  plan->partial =
+ * ggl_segment_multi_partial_bytes(n_chunks, K, aggs, n_aggs) bytes when the plan has long rows.
+ * Backward: g [N, A * K] in out's layout; gx [E, K], every element written.  Per (row, column), n' = max(n, 1),
+ * nf = (float)min(n', 2^24), s0 = sqrtf(1e-5f):
+ *   gv = g_var (0.0f without var);  with std: t = std > s0 ? __fdiv_rn(g_std, __fmul_rn(2.0f, std)) : 0.0f,
+ *        gv = var requested ? __fadd_rn(gv, t) : t             ("var > 0" re-derived from the stored std: var is not stored)
+ *   c1 = __fdiv_rn(__fmul_rn(2.0f, gv), nf)
+ *   c0 = 0.0f; sum: c0 = __fadd_rn(c0, g_sum); mean: c0 = __fadd_rn(c0, __fdiv_rn(g_mean, nf));
+ *        var or std: c0 = __fsub_rn(c0, __fmul_rn(c1, mean))
+ * and per position: t = var or std ? __fadd_rn(c0, __fmul_rn(c1, x[e, k])) : c0; if (argmax == e) t = __fadd_rn(t, g_max);
+ * if (argmin == e) t = __fadd_rn(t, g_min); gx[e, k] = t.  x and mean are read only with var / std, out only with std, the
+ * witnesses only with min / max: the other pointers may be NULL.  No partial buffer.
+ * Refused with GGL_EINVAL: C not dividing K, duplicate or unknown codes, a missing pointer the aggs require (named in the
+ * message), a plan with long rows and no plan->partial (forward). */
+enum { GGL_AGG_SUM = 0, GGL_AGG_MEAN = 1, GGL_AGG_MIN = 2, GGL_AGG_MAX = 3, GGL_AGG_VAR = 4, GGL_AGG_STD = 5 };
+size_t ggl_segment_multi_partial_bytes(int64_t n_chunks, int64_t K, const int *aggs_host, int n_aggs);
+int ggl_segment_multi_fwd(const float *x, const ggl_segplan_t *plan, int64_t K, int64_t C, const int *aggs_host, int n_aggs,
+                          int empty_zero, float *out, float *mean_or_null, int32_t *argmin_or_null, int32_t *argmax_or_null,
+                          void *stream);
+int ggl_segment_multi_bwd(const float *g, const float *x_or_null, const float *out_or_null, const float *mean_or_null,
+                          const int32_t *argmin_or_null, const int32_t *argmax_or_null, const ggl_segplan_t *plan, int64_t K,
+                          int64_t C, const int *aggs_host, int n_aggs, float *gx, void *stream);
 /* Fast path of the same op for heads of C = 4, 8, 16, 32 or 64 channels with H * C <= 256
  * (ggl_gat_fast_supported; e.g. the Reddit GAT's 8 x 8): same walks with ~5x fewer vector-ALU instructions
  * (v_exp_f32, one rescale per 4-8 edges, 16-byte index loads, 32-bit panel offsets, FMA) and a backward that
