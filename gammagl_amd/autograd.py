@@ -304,6 +304,76 @@ class GATFused(torch.autograd.Function):
         return None, None, gel, ger, gx, None, None, None
 
 
+def _esa_forward(eng, gp, v, p_drop, z=None, launch=None):
+    """The forward every logit attention op shares: out [N_dst, H, C], rowmax and rowden, the hub partial, the plan struct and
+    the rng draw, then ggl_edge_softmax_agg_fwd on the given logits z — or launch(cs, rng, out, rmax, rden), a fused kernel
+    of the same walk that forms its logits itself.  The launch happens here: cs points into the partial and the plan's
+    tensors, which this frame keeps alive until the kernel is enqueued.  (out, rowmax, rowden, rng_used)."""
+    dev = v.device
+    N, H, C = gp.N_dst, int(v.shape[1]), int(v.shape[2])
+    out = torch.empty((N, H, C), dtype=torch.float32, device=dev)
+    rmax = torch.empty((N, H), dtype=torch.float32, device=dev)
+    rden = torch.empty((N, H), dtype=torch.float32, device=dev)
+    part = eng._gat_partial(gp.fwd, H, C, dev)
+    cs = gp.fwd.c_struct(part)
+    rng, rng_used = eng._draw(dev, p_drop)
+    if launch is not None:
+        launch(cs, rng, out, rmax, rden)
+    else:
+        eng._check(eng.lib.ggl_edge_softmax_agg_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(z), _ptr(v), H, C, float(p_drop),
+                                                    _ptr(rng), _ptr(out), _ptr(rmax), _ptr(rden), eng._stream(dev)))
+    return out, rmax, rden, rng_used
+
+
+def _esa_backward(eng, gp, z, v, g, out, rmax, rden, p_drop, rng_used, need_gz, need_gv):
+    """The backward every logit attention op shares, on the logits z the forward used: the destination walk (alpha, and gz
+    in the caller's edge order only with need_gz), then — only with need_gv — the source walk.  (gz, gv), None where not
+    needed."""
+    g = g.contiguous()
+    dev = g.device
+    H, C = int(v.shape[1]), int(v.shape[2])
+    st = eng._stream(dev)
+    alpha = torch.empty((max(gp.E, 1), H), dtype=torch.float32, device=dev) if need_gv else None   # sorted positions
+    gz = torch.empty_like(z) if need_gz else None                                                  # caller's order
+    part_f = eng._partial(gp.fwd, torch.float32, H, False, dev)  # must outlive the launch
+    cs = gp.fwd.c_struct(part_f)
+    eng._check(eng.lib.ggl_edge_softmax_agg_bwd_dst(
+        ctypes.byref(cs), _ptr(gp.col), _ptr(z), _ptr(v), _ptr(g), _ptr(out), _ptr(rmax), _ptr(rden), H, C,
+        p_drop, _ptr(rng_used), _ptr(alpha), _ptr(gz), st))
+    gv = None
+    if need_gv:
+        bwd = gp.bwd
+        gv = torch.empty((gp.N_src, H, C), dtype=torch.float32, device=dev)
+        part = eng._partial(bwd, torch.float32, H * C + H, False, dev)
+        csT = bwd.c_struct(part)
+        eng._check(eng.lib.ggl_edge_softmax_agg_bwd_src(ctypes.byref(csT), _ptr(gp.colT), _ptr(gp.posT), _ptr(alpha),
+                                                        _ptr(g), H, C, _ptr(gv), st))
+    return gz, gv
+
+
+def _logit_attention_forward(ctx, name, eng, gp, inputs, v, p_drop, keep_z, fused, compose, launch):
+    """The forward of an op whose logits come from its `inputs` (DotAttention, GATv2Attention), values v.  fused: the op's
+    kernel forms the logits inside the aggregate's walk, launch(z, cs, rng, out, rmax, rden), and stores them to z unless z is
+    None; otherwise compose(z) fills z and ggl_edge_softmax_agg_fwd reads it.  z [E, H] exists only if a backward will read
+    it, the caller asked for it, or the composed route needs it.  Returns (out, z or an empty tensor), z not differentiable."""
+    need = any(ctx.needs_input_grad[2:5])
+    z = None
+    if need or keep_z or not fused:
+        z = torch.empty((gp.E, int(v.shape[1])), dtype=torch.float32, device=v.device)
+    if fused:
+        out, rmax, rden, rng_used = _esa_forward(eng, gp, v, p_drop, launch=lambda *a: launch(z, *a))
+    else:
+        compose(z)
+        out, rmax, rden, rng_used = _esa_forward(eng, gp, v, p_drop, z=z)
+    eng.stats[name] = {"fused": fused, "logits_bytes": 0 if z is None else z.numel() * 4, "logits_saved": bool(need)}
+    ctx.eng, ctx.gp, ctx.p_drop, ctx.rng_used = eng, gp, float(p_drop), rng_used
+    if need:
+        ctx.save_for_backward(z, *inputs, out, rmax, rden)
+    zr = z if (keep_z and z is not None) else out.new_empty(0)
+    ctx.mark_non_differentiable(zr)
+    return out, zr
+
+
 class EdgeSoftmaxAgg(torch.autograd.Function):
     """edge-softmax + aggregate on per-edge logits z [E, H] (ggl_edge_softmax_agg_*): GATFused's general f32 kernels with
     the logit read from z through the plan's perm.  The source walk runs only when x needs a gradient, gz is stored — by
@@ -311,49 +381,19 @@ class EdgeSoftmaxAgg(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eng, gp, z, x, p_drop=0.0):
-        ctx.eng = eng
-        dev = x.device
-        N, H, C = gp.N_dst, int(x.shape[1]), int(x.shape[2])
-        out = torch.empty((N, H, C), dtype=torch.float32, device=dev)
-        rmax = torch.empty((N, H), dtype=torch.float32, device=dev)
-        rden = torch.empty((N, H), dtype=torch.float32, device=dev)
-        part = eng._gat_partial(gp.fwd, H, C, dev)
-        cs = gp.fwd.c_struct(part)
-        rng, rng_used = eng._draw(dev, p_drop)
-        eng._check(eng.lib.ggl_edge_softmax_agg_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(z), _ptr(x), H, C, float(p_drop),
-                                                    _ptr(rng), _ptr(out), _ptr(rmax), _ptr(rden), eng._stream(dev)))
-        ctx.gp, ctx.p_drop, ctx.rng_used = gp, float(p_drop), rng_used
+        out, rmax, rden, rng_used = _esa_forward(eng, gp, x, p_drop, z=z)
+        ctx.eng, ctx.gp, ctx.p_drop, ctx.rng_used = eng, gp, float(p_drop), rng_used
         ctx.save_for_backward(z, x, out, rmax, rden)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        eng = ctx.eng
-        gp = ctx.gp
         z, x, out, rmax, rden = ctx.saved_tensors
         need_z, need_x = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         if not (need_z or need_x):
             return None, None, None, None, None
-        g = g.contiguous()
-        dev = g.device
-        H, C = int(x.shape[1]), int(x.shape[2])
-        st = eng._stream(dev)
-        alpha = torch.empty((max(gp.E, 1), H), dtype=torch.float32, device=dev) if need_x else None   # sorted positions
-        gz = torch.empty_like(z) if need_z else None                                                  # caller's order
-        part_f = eng._partial(gp.fwd, torch.float32, H, False, dev)  # must outlive the launch
-        cs = gp.fwd.c_struct(part_f)
-        eng._check(eng.lib.ggl_edge_softmax_agg_bwd_dst(
-            ctypes.byref(cs), _ptr(gp.col), _ptr(z), _ptr(x), _ptr(g), _ptr(out), _ptr(rmax), _ptr(rden), H, C,
-            ctx.p_drop, _ptr(ctx.rng_used), _ptr(alpha), _ptr(gz), st))
-        gx = None
-        if need_x:
-            bwd = gp.bwd
-            gx = torch.empty((gp.N_src, H, C), dtype=torch.float32, device=dev)
-            part = eng._partial(bwd, torch.float32, H * C + H, False, dev)
-            csT = bwd.c_struct(part)
-            eng._check(eng.lib.ggl_edge_softmax_agg_bwd_src(ctypes.byref(csT), _ptr(gp.colT), _ptr(gp.posT), _ptr(alpha),
-                                                            _ptr(g), H, C, _ptr(gx), st))
+        gz, gx = _esa_backward(ctx.eng, ctx.gp, z, x, g, out, rmax, rden, ctx.p_drop, ctx.rng_used, need_z, need_x)
         return None, None, gz, gx, None
 
 
@@ -375,38 +415,20 @@ class DotAttention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eng, gp, q, k, v, scale, p_drop=0.0, keep_z=False):
-        ctx.eng = eng
-        dev = v.device
-        N, H, C = gp.N_dst, int(v.shape[1]), int(v.shape[2])
-        need = any(ctx.needs_input_grad[2:5])
+        H, C = int(v.shape[1]), int(v.shape[2])
         fused = bool(eng.dot_attn_fused and v.is_cuda and eng.lib.ggl_dot_attn_supported(H, C)
                      and eng.lib.ggl_policy_dot_attn_fused(H, C, gp.E, gp.N_src))
-        out = torch.empty((N, H, C), dtype=torch.float32, device=dev)
-        rmax = torch.empty((N, H), dtype=torch.float32, device=dev)
-        rden = torch.empty((N, H), dtype=torch.float32, device=dev)
-        part = eng._gat_partial(gp.fwd, H, C, dev)
-        cs = gp.fwd.c_struct(part)
-        z = None
-        if need or keep_z or not fused:
-            z = torch.empty((gp.E, H), dtype=torch.float32, device=dev)
-        if not fused:
+
+        def compose(z):
             _edge_dot(eng, gp, k, q, z).mul_(scale)   # one rounded f32 multiply per element
-        rng, rng_used = eng._draw(dev, p_drop)
-        if fused:
+
+        def launch(z, cs, rng, out, rmax, rden):
             eng._check(eng.lib.ggl_dot_attn_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(q), _ptr(k), _ptr(v), float(scale), H, C,
                                                 float(p_drop), _ptr(rng), _ptr(out), _ptr(rmax), _ptr(rden), _ptr(z),
-                                                eng._stream(dev)))
-        else:
-            eng._check(eng.lib.ggl_edge_softmax_agg_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(z), _ptr(v), H, C, float(p_drop),
-                                                        _ptr(rng), _ptr(out), _ptr(rmax), _ptr(rden), eng._stream(dev)))
-        eng.stats["dot_attention"] = {"fused": fused, "logits_bytes": 0 if z is None else z.numel() * 4,
-                                      "logits_saved": bool(need)}
-        ctx.gp, ctx.scale, ctx.p_drop, ctx.rng_used = gp, float(scale), float(p_drop), rng_used
-        if need:
-            ctx.save_for_backward(z, q, k, v, out, rmax, rden)
-        zr = z if (keep_z and z is not None) else out.new_empty(0)
-        ctx.mark_non_differentiable(zr)
-        return out, zr
+                                                eng._stream(v.device)))
+
+        ctx.scale = float(scale)
+        return _logit_attention_forward(ctx, "dot_attention", eng, gp, (q, k, v), v, p_drop, keep_z, fused, compose, launch)
 
     @staticmethod
     @once_differentiable
@@ -417,26 +439,9 @@ class DotAttention(torch.autograd.Function):
         if not (need_q or need_k or need_v):
             return (None,) * 8
         z, q, k, v, out, rmax, rden = ctx.saved_tensors
-        g = g.contiguous()
-        dev = g.device
-        H, C = int(v.shape[1]), int(v.shape[2])
-        st = eng._stream(dev)
         need_z = need_q or need_k
-        alpha = torch.empty((max(gp.E, 1), H), dtype=torch.float32, device=dev) if need_v else None   # sorted positions
-        gs = torch.empty_like(z) if need_z else None                                                  # caller's order
-        part_f = eng._partial(gp.fwd, torch.float32, H, False, dev)  # must outlive the launch
-        cs = gp.fwd.c_struct(part_f)
-        eng._check(eng.lib.ggl_edge_softmax_agg_bwd_dst(
-            ctypes.byref(cs), _ptr(gp.col), _ptr(z), _ptr(v), _ptr(g), _ptr(out), _ptr(rmax), _ptr(rden), H, C,
-            ctx.p_drop, _ptr(ctx.rng_used), _ptr(alpha), _ptr(gs), st))
-        gq = gk = gv = None
-        if need_v:
-            bwd = gp.bwd
-            gv = torch.empty((gp.N_src, H, C), dtype=torch.float32, device=dev)
-            part = eng._partial(bwd, torch.float32, H * C + H, False, dev)
-            csT = bwd.c_struct(part)
-            eng._check(eng.lib.ggl_edge_softmax_agg_bwd_src(ctypes.byref(csT), _ptr(gp.colT), _ptr(gp.posT), _ptr(alpha),
-                                                            _ptr(g), H, C, _ptr(gv), st))
+        gs, gv = _esa_backward(eng, gp, z, v, g, out, rmax, rden, ctx.p_drop, ctx.rng_used, need_z, need_v)
+        gq = gk = None
         if need_z:
             gs.mul_(ctx.scale)   # d z / d <q, k>
         if need_q:
@@ -494,38 +499,21 @@ class GATv2Attention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eng, gp, xl, xr, att, slope, p_drop=0.0, keep_z=False):
-        ctx.eng = eng
-        dev = xl.device
-        N, H, C = gp.N_dst, int(xl.shape[1]), int(xl.shape[2])
-        need = any(ctx.needs_input_grad[2:5])
+        H, C = int(xl.shape[1]), int(xl.shape[2])
         fused = bool(eng.gatv2_fused and xl.is_cuda and eng.lib.ggl_gatv2_supported(H, C)
                      and eng.lib.ggl_policy_gatv2_fused(H, C, gp.E, gp.N_src))
-        out = torch.empty((N, H, C), dtype=torch.float32, device=dev)
-        rmax = torch.empty((N, H), dtype=torch.float32, device=dev)
-        rden = torch.empty((N, H), dtype=torch.float32, device=dev)
-        part = eng._gat_partial(gp.fwd, H, C, dev)
-        cs = gp.fwd.c_struct(part)
-        z = None
-        if need or keep_z or not fused:
-            z = torch.empty((gp.E, H), dtype=torch.float32, device=dev)
-        if not fused:
+
+        def compose(z):
             _gatv2_logits(gp, xl, xr, att, slope, z)
-        rng, rng_used = eng._draw(dev, p_drop)
-        if fused:
+
+        def launch(z, cs, rng, out, rmax, rden):
             eng._check(eng.lib.ggl_gatv2_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(xl), _ptr(xr), _ptr(att), float(slope), H, C,
                                              float(p_drop), _ptr(rng), _ptr(out), _ptr(rmax), _ptr(rden), _ptr(z),
-                                             eng._stream(dev)))
-        else:
-            eng._check(eng.lib.ggl_edge_softmax_agg_fwd(ctypes.byref(cs), _ptr(gp.col), _ptr(z), _ptr(xl), H, C, float(p_drop),
-                                                        _ptr(rng), _ptr(out), _ptr(rmax), _ptr(rden), eng._stream(dev)))
-        eng.stats["gatv2_attention"] = {"fused": fused, "logits_bytes": 0 if z is None else z.numel() * 4,
-                                        "logits_saved": bool(need)}
-        ctx.gp, ctx.slope, ctx.p_drop, ctx.rng_used = gp, float(slope), float(p_drop), rng_used
-        if need:
-            ctx.save_for_backward(z, xl, xr, att, out, rmax, rden)
-        zr = z if (keep_z and z is not None) else out.new_empty(0)
-        ctx.mark_non_differentiable(zr)
-        return out, zr
+                                             eng._stream(xl.device)))
+
+        ctx.slope = float(slope)
+        return _logit_attention_forward(ctx, "gatv2_attention", eng, gp, (xl, xr, att), xl, p_drop, keep_z, fused, compose,
+                                        launch)
 
     @staticmethod
     @once_differentiable
@@ -536,17 +524,8 @@ class GATv2Attention(torch.autograd.Function):
         if not (need_l or need_r or need_a):
             return (None,) * 8
         z, xl, xr, att, out, rmax, rden = ctx.saved_tensors
-        g = g.contiguous()
-        dev = g.device
         H, C = int(xl.shape[1]), int(xl.shape[2])
-        st = eng._stream(dev)
-        alpha = torch.empty((max(gp.E, 1), H), dtype=torch.float32, device=dev) if need_l else None   # sorted positions
-        gz = torch.empty_like(z)                                                                      # caller's order
-        part_f = eng._partial(gp.fwd, torch.float32, H, False, dev)  # must outlive the launch
-        cs = gp.fwd.c_struct(part_f)
-        eng._check(eng.lib.ggl_edge_softmax_agg_bwd_dst(
-            ctypes.byref(cs), _ptr(gp.col), _ptr(z), _ptr(xl), _ptr(g), _ptr(out), _ptr(rmax), _ptr(rden), H, C,
-            ctx.p_drop, _ptr(ctx.rng_used), _ptr(alpha), _ptr(gz), st))
+        gz, gv = _esa_backward(eng, gp, z, xl, g, out, rmax, rden, ctx.p_drop, ctx.rng_used, True, need_l)
         gl = gr = ga = None
         if need_r or need_a:
             gr, rows = _gatv2_logit_bwd(eng, gp.fwd, gp.col, xl, xr, gz, att, ctx.slope, None, need_a)
@@ -555,13 +534,7 @@ class GATv2Attention(torch.autograd.Function):
             if not need_r:
                 gr = None
         if need_l:
-            bwd = gp.bwd
-            gv = torch.empty((gp.N_src, H, C), dtype=torch.float32, device=dev)
-            part = eng._partial(bwd, torch.float32, H * C + H, False, dev)
-            csT = bwd.c_struct(part)
-            eng._check(eng.lib.ggl_edge_softmax_agg_bwd_src(ctypes.byref(csT), _ptr(gp.colT), _ptr(gp.posT), _ptr(alpha),
-                                                            _ptr(g), H, C, _ptr(gv), st))
-            gl, _ = _gatv2_logit_bwd(eng, bwd, gp.colT, xr, xl, gz, att, ctx.slope, gv, False)
+            gl, _ = _gatv2_logit_bwd(eng, gp.bwd, gp.colT, xr, xl, gz, att, ctx.slope, gv, False)
         return None, None, gl, gr, ga, None, None, None
 
 

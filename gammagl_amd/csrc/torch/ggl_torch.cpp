@@ -36,6 +36,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <list>
 #include <memory>
 #include <mutex>
@@ -457,10 +458,19 @@ static std::shared_ptr<GraphPlan> graph_plan(const Tensor &index, int64_t n_dst,
 // ---------------------------------------------------------------------------------------------------------------
 // Forward launches
 // ---------------------------------------------------------------------------------------------------------------
-static Tensor partial_for(const Api &a, const SegPlan &p, const Tensor &like, int64_t K, bool with_arg) {
+// the partial buffer of a plan's long rows: nbytes(n_chunks) bytes + 16 of slack on like's device, undefined for a plan without
+// long rows.  It must outlive the launch that is handed it.
+template <typename Bytes>
+static Tensor hub_partial(const SegPlan &p, const Tensor &like, Bytes nbytes) {
   if (p.n_long == 0) return Tensor();
-  const size_t nb = a.ggl_partial_bytes(dtype_code(like), p.n_chunks, K, with_arg ? 1 : 0);
-  return at::empty({static_cast<int64_t>(nb) + 16}, like.options().dtype(at::kByte));
+  return at::empty({static_cast<int64_t>(nbytes(p.n_chunks)) + 16}, like.options().dtype(at::kByte));
+}
+static Tensor partial_for(const Api &a, const SegPlan &p, const Tensor &like, int64_t K, bool with_arg) {
+  return hub_partial(p, like, [&](int64_t n) { return a.ggl_partial_bytes(dtype_code(like), n, K, with_arg ? 1 : 0); });
+}
+// ... of the GAT forward walks: gat_fused, edge_softmax_aggregate and the ops that form their logits inside that walk
+static Tensor gat_fwd_partial(const Api &a, const SegPlan &p, int64_t H, int64_t C, const Tensor &like) {
+  return hub_partial(p, like, [&](int64_t n) { return a.ggl_gat_partial_bytes(n, H, C); });
 }
 
 static std::vector<int64_t> out_shape(const Tensor &x, int64_t N) {
@@ -1007,9 +1017,7 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor, bool> gat_forward(GraphPlan &g
   TORCH_CHECK(!out_f32 || x16, "out_f32 is for f16 / bf16 rows (x is ", x.scalar_type(), ")");
   Tensor out = at::empty({N, H, C}, out_f32 ? x.options().dtype(at::kFloat) : x.options());
   Tensor rmax = at::empty({N, H}, el.options()), rden = at::empty({N, H}, el.options());
-  Tensor part;
-  if (gp.fwd->n_long > 0)
-    part = at::empty({static_cast<int64_t>(a.ggl_gat_partial_bytes(gp.fwd->n_chunks, H, C)) + 16}, x.options().dtype(at::kByte));
+  Tensor part = gat_fwd_partial(a, *gp.fwd, H, C, x);
   ggl_segplan_t cs = gp.fwd->c(part);
   const Draw d = draw(dev, p);
   static const bool want_fast = env_int("GGL_GAT_FAST", 1) != 0;
@@ -1136,27 +1144,84 @@ static void esa_check(const Tensor &index, const Tensor &z, const Tensor &x) {
               "edge_softmax_aggregate expects logits [E, H] and x [N_src, H, C] (got logits ", z.sizes(), ", x ", x.sizes(),
               " for ", index.size(1), " edges)");
 }
+// The two host cores under edge_softmax_aggregate, dot_attention and gatv2_attention (contiguous f32 tensors on v's device).
+// A fused forward of the same walk, which forms its logits itself and stores them to z unless z is NULL:
+using FusedFwd = std::function<int(const ggl_segplan_t *cs, int64_t *rng, float *out, float *rmax, float *rden, float *z, void *st)>;
+// (out, rowmax, rowden, rng_used): the outputs, the hub partial and the rng draw, then ggl_edge_softmax_agg_fwd on the logits z —
+// or `fused`, handed the same plan struct, draw and outputs, and z (which may be undefined) to write
+static std::tuple<Tensor, Tensor, Tensor, Tensor> esa_forward(GraphPlan &gp, const Tensor &z, const Tensor &v, double p,
+                                                              const FusedFwd &fused = nullptr) {
+  const auto dev = v.device();
+  const Api &a = api_for(dev);
+  const int64_t N = gp.N_dst, H = v.size(1), C = v.size(2);
+  Tensor out = at::empty({N, H, C}, v.options()), rmax = at::empty({N, H}, v.options()), rden = at::empty({N, H}, v.options());
+  Tensor part = gat_fwd_partial(a, *gp.fwd, H, C, v);
+  ggl_segplan_t cs = gp.fwd->c(part);
+  const Draw d = draw(dev, p);
+  float *zp = z.defined() ? z.data_ptr<float>() : nullptr;
+  if (fused)
+    check(a, fused(&cs, d.ptr(), out.data_ptr<float>(), rmax.data_ptr<float>(), rden.data_ptr<float>(), zp, stream_of(dev)));
+  else
+    check(a, a.ggl_edge_softmax_agg_fwd(&cs, gp.col.data_ptr<int32_t>(), zp, v.data_ptr<float>(), H, C, static_cast<float>(p),
+                                        d.ptr(), out.data_ptr<float>(), rmax.data_ptr<float>(), rden.data_ptr<float>(),
+                                        stream_of(dev)));
+  return {out, rmax, rden, d.used};
+}
+// (gz, gv) on the logits z the forward used: the destination walk (alpha by sorted position, gz in the caller's edge order only
+// with need_gz), then — only with need_gv — the source walk.  A gradient that is not needed is not computed and comes back
+// UNDEFINED.
+static std::pair<Tensor, Tensor> esa_backward(GraphPlan &gp, const Tensor &idx, const Tensor &z, const Tensor &v, const Tensor &grad,
+                                              const Tensor &out, const Tensor &rmax, const Tensor &rden, const Tensor &rng_used,
+                                              double p, bool need_gz, bool need_gv) {
+  const auto dev = v.device();
+  const Api &a = api_for(dev);
+  Tensor g = grad.contiguous(), oc = out.contiguous();
+  const int64_t H = v.size(1), C = v.size(2);
+  void *st = stream_of(dev);
+  Tensor alpha = need_gv ? at::empty({std::max<int64_t>(gp.E, 1), H}, v.options()) : Tensor();
+  Tensor gz = need_gz ? at::empty_like(z) : Tensor(), gv;
+  Tensor part_f = partial_for(a, *gp.fwd, z, H, false);
+  ggl_segplan_t cs = gp.fwd->c(part_f);
+  check(a, a.ggl_edge_softmax_agg_bwd_dst(&cs, gp.col.data_ptr<int32_t>(), z.data_ptr<float>(), v.data_ptr<float>(),
+                                          g.data_ptr<float>(), oc.data_ptr<float>(), rmax.data_ptr<float>(),
+                                          rden.data_ptr<float>(), H, C, static_cast<float>(p), used_ptr(p, rng_used),
+                                          need_gv ? alpha.data_ptr<float>() : nullptr,
+                                          need_gz ? gz.data_ptr<float>() : nullptr, st));
+  if (need_gv) {
+    gp.need_bwd(idx);
+    gp.need_posT(idx);
+    gv = at::empty({gp.N_src, H, C}, v.options());
+    Tensor part_t = partial_for(a, *gp.bwd, z, H * C + H, false);
+    ggl_segplan_t csT = gp.bwd->c(part_t);
+    check(a, a.ggl_edge_softmax_agg_bwd_src(&csT, gp.colT.data_ptr<int32_t>(), gp.posT.data_ptr<int32_t>(),
+                                            alpha.data_ptr<float>(), g.data_ptr<float>(), H, C, gv.data_ptr<float>(), st));
+  }
+  return {gz, gv};
+}
+// what an op returns for a gradient nobody needs: EMPTY (a fresh tensor each: outputs of an op may not alias one another)
+static Tensor or_empty(const Tensor &t, const Tensor &like) { return t.defined() ? t : at::empty({0}, like.options()); }
+// (out, rowmax, rowden, rng_used, logits) of an op that forms its logits from its inputs (dot_attention, gatv2_attention):
+// fused, its kernel `launch` forms them in the aggregate's walk and stores them only with keep_logits; otherwise compose(z)
+// fills z [E, H] in front of ggl_edge_softmax_agg_fwd.  logits come back EMPTY without keep_logits.
+template <typename Compose>
+static std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> logit_attention_forward(GraphPlan &gp, const Tensor &v, double p,
+                                                                                  bool keep_logits, bool fused, Compose compose,
+                                                                                  const FusedFwd &launch) {
+  Tensor z = (keep_logits || !fused) ? at::empty({gp.E, v.size(1)}, v.options()) : Tensor();
+  if (!fused) compose(z);
+  static const FusedFwd composed;   // empty: ggl_edge_softmax_agg_fwd on z
+  auto r = esa_forward(gp, z, v, p, fused ? launch : composed);
+  return {std::get<0>(r), std::get<1>(r), std::get<2>(r), std::get<3>(r), keep_logits ? z : at::empty({0}, v.options())};
+}
+
 // (out, rowmax, rowden, rng_used)
 static std::tuple<Tensor, Tensor, Tensor, Tensor> esa_forward_kernel(const Tensor &index, const Tensor &z_, const Tensor &x_,
                                                                      int64_t num_nodes, double p) {
   esa_check(index, z_, x_);
   TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout_rate must be in [0, 1)");
-  const auto dev = x_.device();
-  c10::OptionalDeviceGuard guard(dev);
+  c10::OptionalDeviceGuard guard(x_.device());
   auto gp = gat_plan(index, num_nodes, x_.size(0));
-  const Api &a = api_for(dev);
-  Tensor z = z_.contiguous(), x = x_.contiguous();
-  const int64_t N = gp->N_dst, H = x.size(1), C = x.size(2);
-  Tensor out = at::empty({N, H, C}, x.options()), rmax = at::empty({N, H}, x.options()), rden = at::empty({N, H}, x.options());
-  Tensor part;
-  if (gp->fwd->n_long > 0)
-    part = at::empty({static_cast<int64_t>(a.ggl_gat_partial_bytes(gp->fwd->n_chunks, H, C)) + 16}, x.options().dtype(at::kByte));
-  ggl_segplan_t cs = gp->fwd->c(part);
-  const Draw d = draw(dev, p);
-  check(a, a.ggl_edge_softmax_agg_fwd(&cs, gp->col.data_ptr<int32_t>(), z.data_ptr<float>(), x.data_ptr<float>(), H, C,
-                                      static_cast<float>(p), d.ptr(), out.data_ptr<float>(), rmax.data_ptr<float>(),
-                                      rden.data_ptr<float>(), stream_of(dev)));
-  return {out, rmax, rden, d.used};
+  return esa_forward(*gp, z_.contiguous(), x_.contiguous(), p);
 }
 // (gz, gx); a gradient that is not needed is not computed and comes back EMPTY: need_x = false skips the source walk,
 // need_z = false the gz stores
@@ -1164,33 +1229,12 @@ static std::tuple<Tensor, Tensor> esa_backward_kernel(const Tensor &index, const
                                                       const Tensor &out, const Tensor &rmax, const Tensor &rden,
                                                       const Tensor &rng_used, int64_t num_nodes, double p, bool need_z,
                                                       bool need_x) {
-  const auto dev = x_.device();
-  c10::OptionalDeviceGuard guard(dev);
-  const Api &a = api_for(dev);
-  Tensor idx = index.contiguous(), z = z_.contiguous(), x = x_.contiguous(), g = grad.contiguous(), oc = out.contiguous();
+  c10::OptionalDeviceGuard guard(x_.device());
+  Tensor idx = index.contiguous(), z = z_.contiguous(), x = x_.contiguous();
   auto gp = gat_plan(idx, num_nodes, x.size(0));
-  const int64_t H = x.size(1), C = x.size(2), E = gp->E;
-  Tensor gz = need_z ? at::empty_like(z) : at::empty({0}, z.options());
-  Tensor gx = need_x ? at::empty({gp->N_src, H, C}, x.options()) : at::empty({0}, x.options());
-  if (!need_z && !need_x) return {gz, gx};
-  void *st = stream_of(dev);
-  Tensor alpha = need_x ? at::empty({std::max<int64_t>(E, 1), H}, x.options()) : Tensor();
-  Tensor part_f = partial_for(a, *gp->fwd, z, H, false);
-  ggl_segplan_t cs = gp->fwd->c(part_f);
-  check(a, a.ggl_edge_softmax_agg_bwd_dst(&cs, gp->col.data_ptr<int32_t>(), z.data_ptr<float>(), x.data_ptr<float>(),
-                                          g.data_ptr<float>(), oc.data_ptr<float>(), rmax.data_ptr<float>(),
-                                          rden.data_ptr<float>(), H, C, static_cast<float>(p), used_ptr(p, rng_used),
-                                          need_x ? alpha.data_ptr<float>() : nullptr,
-                                          need_z ? gz.data_ptr<float>() : nullptr, st));
-  if (need_x) {
-    gp->need_bwd(idx);
-    gp->need_posT(idx);
-    Tensor part_t = partial_for(a, *gp->bwd, z, H * C + H, false);
-    ggl_segplan_t csT = gp->bwd->c(part_t);
-    check(a, a.ggl_edge_softmax_agg_bwd_src(&csT, gp->colT.data_ptr<int32_t>(), gp->posT.data_ptr<int32_t>(),
-                                            alpha.data_ptr<float>(), g.data_ptr<float>(), H, C, gx.data_ptr<float>(), st));
-  }
-  return {gz, gx};
+  std::pair<Tensor, Tensor> r;
+  if (need_z || need_x) r = esa_backward(*gp, idx, z, x, grad, out, rmax, rden, rng_used, p, need_z, need_x);
+  return {or_empty(r.first, z), or_empty(r.second, x)};
 }
 
 // Scaled dot-product graph attention (hgt_conv.py:115-153): z[e, h] = scale * <q[dst_e, h, :], k[src_e, h, :]>, then the op above on
@@ -1248,29 +1292,18 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> dot_forward_kernel(con
   TORCH_CHECK(gp->N_dst == q_.size(0), "dot_attention: the graph has ", gp->N_dst, " destinations, q has ", q_.size(0), " rows");
   const Api &a = api_for(dev);
   Tensor q = q_.contiguous(), k = k_.contiguous(), v = v_.contiguous();
-  const int64_t N = gp->N_dst, H = v.size(1), C = v.size(2), E = gp->E;
-  const bool fused = dev.is_cuda() && a.ggl_dot_attn_supported(H, C) && a.ggl_policy_dot_attn_fused(H, C, E, gp->N_src);
-  Tensor out = at::empty({N, H, C}, v.options()), rmax = at::empty({N, H}, v.options()), rden = at::empty({N, H}, v.options());
-  Tensor part;
-  if (gp->fwd->n_long > 0)
-    part = at::empty({static_cast<int64_t>(a.ggl_gat_partial_bytes(gp->fwd->n_chunks, H, C)) + 16}, v.options().dtype(at::kByte));
-  ggl_segplan_t cs = gp->fwd->c(part);
-  Tensor z = (keep_logits || !fused) ? at::empty({E, H}, v.options()) : Tensor();
-  if (!fused) {
-    edge_dot(a, *gp, idx, k, q, z);
-    z.mul_(static_cast<float>(scale));   // one rounded f32 multiply per element
-  }
-  const Draw d = draw(dev, p);
-  if (fused)
-    check(a, a.ggl_dot_attn_fwd(&cs, gp->col.data_ptr<int32_t>(), q.data_ptr<float>(), k.data_ptr<float>(), v.data_ptr<float>(),
-                                static_cast<float>(scale), H, C, static_cast<float>(p), d.ptr(), out.data_ptr<float>(),
-                                rmax.data_ptr<float>(), rden.data_ptr<float>(), z.defined() ? z.data_ptr<float>() : nullptr,
-                                stream_of(dev)));
-  else
-    check(a, a.ggl_edge_softmax_agg_fwd(&cs, gp->col.data_ptr<int32_t>(), z.data_ptr<float>(), v.data_ptr<float>(), H, C,
-                                        static_cast<float>(p), d.ptr(), out.data_ptr<float>(), rmax.data_ptr<float>(),
-                                        rden.data_ptr<float>(), stream_of(dev)));
-  return {out, rmax, rden, d.used, keep_logits ? z : at::empty({0}, v.options())};
+  const int64_t H = v.size(1), C = v.size(2);
+  const bool fused = dev.is_cuda() && a.ggl_dot_attn_supported(H, C) && a.ggl_policy_dot_attn_fused(H, C, gp->E, gp->N_src);
+  return logit_attention_forward(
+      *gp, v, p, keep_logits, fused,
+      [&](Tensor &z) {
+        edge_dot(a, *gp, idx, k, q, z);
+        z.mul_(static_cast<float>(scale));   // one rounded f32 multiply per element
+      },
+      [&](const ggl_segplan_t *cs, int64_t *rng, float *out, float *rmax, float *rden, float *z, void *st) {
+        return a.ggl_dot_attn_fwd(cs, gp->col.data_ptr<int32_t>(), q.data_ptr<float>(), k.data_ptr<float>(), v.data_ptr<float>(),
+                                  static_cast<float>(scale), H, C, static_cast<float>(p), rng, out, rmax, rden, z, st);
+      });
 }
 // (gq, gk, gv) from the saved logits: the edge-softmax aggregate's two backward walks, gs = gz * scale, gq = bspmm_sum(plan, gs, k),
 // gk = bspmm_sum(planT, gs, q).  A gradient that is not needed is not computed and comes back EMPTY.
@@ -1279,41 +1312,22 @@ static std::tuple<Tensor, Tensor, Tensor> dot_backward_kernel(const Tensor &inde
                                                               const Tensor &rmax, const Tensor &rden, const Tensor &rng_used,
                                                               int64_t num_nodes, double scale, double p, bool need_q, bool need_k,
                                                               bool need_v) {
-  const auto dev = v_.device();
-  c10::OptionalDeviceGuard guard(dev);
-  const Api &a = api_for(dev);
-  Tensor idx = index.contiguous(), q = q_.contiguous(), k = k_.contiguous(), v = v_.contiguous(), z = z_.contiguous(),
-         g = grad.contiguous(), oc = out.contiguous();
+  c10::OptionalDeviceGuard guard(v_.device());
+  Tensor idx = index.contiguous(), q = q_.contiguous(), k = k_.contiguous(), v = v_.contiguous(), z = z_.contiguous();
   auto gp = gat_plan(idx, num_nodes, k.size(0));
-  const int64_t H = v.size(1), C = v.size(2), E = gp->E;
-  auto none = [&]() { return at::empty({0}, v.options()); };   // (outputs of an op may not alias one another)
-  if (!need_q && !need_k && !need_v) return {none(), none(), none()};
-  TORCH_CHECK(z.dim() == 2 && z.size(0) == E && z.size(1) == H, "dot_attention_backward needs the forward's logits [E, H]");
-  const bool need_z = need_q || need_k;
-  void *st = stream_of(dev);
-  Tensor alpha = need_v ? at::empty({std::max<int64_t>(E, 1), H}, v.options()) : Tensor();
-  Tensor gs = need_z ? at::empty_like(z) : Tensor();
-  Tensor part_f = partial_for(a, *gp->fwd, z, H, false);
-  ggl_segplan_t cs = gp->fwd->c(part_f);
-  check(a, a.ggl_edge_softmax_agg_bwd_dst(&cs, gp->col.data_ptr<int32_t>(), z.data_ptr<float>(), v.data_ptr<float>(),
-                                          g.data_ptr<float>(), oc.data_ptr<float>(), rmax.data_ptr<float>(),
-                                          rden.data_ptr<float>(), H, C, static_cast<float>(p), used_ptr(p, rng_used),
-                                          need_v ? alpha.data_ptr<float>() : nullptr,
-                                          need_z ? gs.data_ptr<float>() : nullptr, st));
-  Tensor gq = none(), gk = none(), gv = none();
-  if (need_v || need_k) gp->need_bwd(idx);
-  if (need_v) {
-    gp->need_posT(idx);
-    gv = at::empty({gp->N_src, H, C}, v.options());
-    Tensor part_t = partial_for(a, *gp->bwd, z, H * C + H, false);
-    ggl_segplan_t csT = gp->bwd->c(part_t);
-    check(a, a.ggl_edge_softmax_agg_bwd_src(&csT, gp->colT.data_ptr<int32_t>(), gp->posT.data_ptr<int32_t>(),
-                                            alpha.data_ptr<float>(), g.data_ptr<float>(), H, C, gv.data_ptr<float>(), st));
+  Tensor gq, gk, gs, gv;
+  if (need_q || need_k || need_v) {
+    TORCH_CHECK(z.dim() == 2 && z.size(0) == gp->E && z.size(1) == v.size(1),
+                "dot_attention_backward needs the forward's logits [E, H]");
+    std::tie(gs, gv) = esa_backward(*gp, idx, z, v, grad, out, rmax, rden, rng_used, p, need_q || need_k, need_v);
+    if (gs.defined()) gs.mul_(static_cast<float>(scale));
+    if (need_q) gq = bspmm_by_perm(*gp->fwd, gp->col, gs, k, gp->N_dst);
+    if (need_k) {
+      gp->need_bwd(idx);
+      gk = bspmm_by_perm(*gp->bwd, gp->colT, gs, q, gp->N_src);
+    }
   }
-  if (need_z) gs.mul_(static_cast<float>(scale));
-  if (need_q) gq = bspmm_by_perm(*gp->fwd, gp->col, gs, k, gp->N_dst);
-  if (need_k) gk = bspmm_by_perm(*gp->bwd, gp->colT, gs, q, gp->N_src);
-  return {gq, gk, gv};
+  return {or_empty(gq, v), or_empty(gk, v), or_empty(gv, v)};
 }
 
 // GATv2's additive graph attention: z[e, h] = sum_c att[h, c] * LeakyReLU(xl[src_e, h, c] + xr[dst_e, h, c]), then
@@ -1348,10 +1362,7 @@ static std::pair<Tensor, Tensor> gatv2_logit_bwd(const SegPlan &p, const Tensor 
   const Api &a = api_for(self.device());
   const int64_t H = self.size(1), C = self.size(2);
   Tensor g_self = at::empty_like(self), rows = want_rows ? at::empty_like(self) : Tensor();
-  Tensor part;
-  if (p.n_long > 0)
-    part = at::empty({static_cast<int64_t>(a.ggl_gatv2_logit_bwd_partial_bytes(p.n_chunks, H, C, want_rows ? 1 : 0)) + 16},
-                     self.options().dtype(at::kByte));
+  Tensor part = hub_partial(p, self, [&](int64_t n) { return a.ggl_gatv2_logit_bwd_partial_bytes(n, H, C, want_rows ? 1 : 0); });
   ggl_segplan_t cs = p.c(part);
   check(a, a.ggl_gatv2_logit_bwd(&cs, col.data_ptr<int32_t>(), other.data_ptr<float>(), self.data_ptr<float>(),
                                  gz.data_ptr<float>(), att.data_ptr<float>(), static_cast<float>(slope), H, C,
@@ -1372,26 +1383,14 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> gatv2_forward_kernel(c
   TORCH_CHECK(gp->N_dst == xr_.size(0), "gatv2_attention: the graph has ", gp->N_dst, " destinations, xr has ", xr_.size(0), " rows");
   const Api &a = api_for(dev);
   Tensor xl = xl_.contiguous(), xr = xr_.contiguous(), att = att_.contiguous();
-  const int64_t N = gp->N_dst, H = xl.size(1), C = xl.size(2), E = gp->E;
-  const bool fused = dev.is_cuda() && a.ggl_gatv2_supported(H, C) && a.ggl_policy_gatv2_fused(H, C, E, gp->N_src);
-  Tensor out = at::empty({N, H, C}, xl.options()), rmax = at::empty({N, H}, xl.options()), rden = at::empty({N, H}, xl.options());
-  Tensor part;
-  if (gp->fwd->n_long > 0)
-    part = at::empty({static_cast<int64_t>(a.ggl_gat_partial_bytes(gp->fwd->n_chunks, H, C)) + 16}, xl.options().dtype(at::kByte));
-  ggl_segplan_t cs = gp->fwd->c(part);
-  Tensor z = (keep_logits || !fused) ? at::empty({E, H}, xl.options()) : Tensor();
-  if (!fused) gatv2_logits(idx, xl, xr, att, slope, z);
-  const Draw d = draw(dev, p);
-  if (fused)
-    check(a, a.ggl_gatv2_fwd(&cs, gp->col.data_ptr<int32_t>(), xl.data_ptr<float>(), xr.data_ptr<float>(), att.data_ptr<float>(),
-                             static_cast<float>(slope), H, C, static_cast<float>(p), d.ptr(), out.data_ptr<float>(),
-                             rmax.data_ptr<float>(), rden.data_ptr<float>(), z.defined() ? z.data_ptr<float>() : nullptr,
-                             stream_of(dev)));
-  else
-    check(a, a.ggl_edge_softmax_agg_fwd(&cs, gp->col.data_ptr<int32_t>(), z.data_ptr<float>(), xl.data_ptr<float>(), H, C,
-                                        static_cast<float>(p), d.ptr(), out.data_ptr<float>(), rmax.data_ptr<float>(),
-                                        rden.data_ptr<float>(), stream_of(dev)));
-  return {out, rmax, rden, d.used, keep_logits ? z : at::empty({0}, xl.options())};
+  const int64_t H = xl.size(1), C = xl.size(2);
+  const bool fused = dev.is_cuda() && a.ggl_gatv2_supported(H, C) && a.ggl_policy_gatv2_fused(H, C, gp->E, gp->N_src);
+  return logit_attention_forward(
+      *gp, xl, p, keep_logits, fused, [&](Tensor &z) { gatv2_logits(idx, xl, xr, att, slope, z); },
+      [&](const ggl_segplan_t *cs, int64_t *rng, float *out, float *rmax, float *rden, float *z, void *st) {
+        return a.ggl_gatv2_fwd(cs, gp->col.data_ptr<int32_t>(), xl.data_ptr<float>(), xr.data_ptr<float>(), att.data_ptr<float>(),
+                               static_cast<float>(slope), H, C, static_cast<float>(p), rng, out, rmax, rden, z, st);
+      });
 }
 // (g_xl, g_xr, g_att) from the saved logits: the edge-softmax aggregate's two backward walks (alpha, gz, gv), then
 // ggl_gatv2_logit_bwd on the plan (g_xr, R; g_att = ggl_colsum_f32(R)) and on its transpose with add = gv (g_xl).  A gradient
@@ -1404,44 +1403,29 @@ static std::tuple<Tensor, Tensor, Tensor> gatv2_backward_kernel(const Tensor &in
   const auto dev = xl_.device();
   c10::OptionalDeviceGuard guard(dev);
   const Api &a = api_for(dev);
-  Tensor idx = index.contiguous(), xl = xl_.contiguous(), xr = xr_.contiguous(), att = att_.contiguous(), z = z_.contiguous(),
-         g = grad.contiguous(), oc = out.contiguous();
+  Tensor idx = index.contiguous(), xl = xl_.contiguous(), xr = xr_.contiguous(), att = att_.contiguous(), z = z_.contiguous();
   auto gp = gat_plan(idx, num_nodes, xl.size(0));
-  const int64_t H = xl.size(1), C = xl.size(2), E = gp->E;
-  auto none = [&]() { return at::empty({0}, xl.options()); };   // (outputs of an op may not alias one another)
-  if (!need_l && !need_r && !need_a) return {none(), none(), none()};
-  TORCH_CHECK(z.dim() == 2 && z.size(0) == E && z.size(1) == H, "gatv2_attention_backward needs the forward's logits [E, H]");
-  void *st = stream_of(dev);
-  Tensor alpha = need_l ? at::empty({std::max<int64_t>(E, 1), H}, xl.options()) : Tensor();
-  Tensor gz = at::empty_like(z);
-  Tensor part_f = partial_for(a, *gp->fwd, z, H, false);
-  ggl_segplan_t cs = gp->fwd->c(part_f);
-  check(a, a.ggl_edge_softmax_agg_bwd_dst(&cs, gp->col.data_ptr<int32_t>(), z.data_ptr<float>(), xl.data_ptr<float>(),
-                                          g.data_ptr<float>(), oc.data_ptr<float>(), rmax.data_ptr<float>(),
-                                          rden.data_ptr<float>(), H, C, static_cast<float>(p), used_ptr(p, rng_used),
-                                          need_l ? alpha.data_ptr<float>() : nullptr, gz.data_ptr<float>(), st));
-  Tensor gl = none(), gr = none(), ga = none();
-  if (need_r || need_a) {
-    auto r = gatv2_logit_bwd(*gp->fwd, gp->col, xl, xr, gz, att, slope, Tensor(), need_a);
-    if (need_r) gr = r.first;
-    if (need_a) {
-      ga = at::empty({H, C}, xl.options());
-      const size_t wsb = a.ggl_colsum_workspace_bytes(gp->N_dst, H * C);
-      Tensor ws = at::empty({static_cast<int64_t>(std::max<size_t>(wsb, 4))}, xl.options().dtype(at::kByte));
-      check(a, a.ggl_colsum_f32(r.second.data_ptr<float>(), gp->N_dst, H * C, ga.data_ptr<float>(), ws.data_ptr(), wsb, st));
+  const int64_t H = xl.size(1), C = xl.size(2);
+  Tensor gl, gr, ga;
+  if (need_l || need_r || need_a) {
+    TORCH_CHECK(z.dim() == 2 && z.size(0) == gp->E && z.size(1) == H,
+                "gatv2_attention_backward needs the forward's logits [E, H]");
+    Tensor gz, gv;
+    std::tie(gz, gv) = esa_backward(*gp, idx, z, xl, grad, out, rmax, rden, rng_used, p, true, need_l);
+    if (need_r || need_a) {
+      auto r = gatv2_logit_bwd(*gp->fwd, gp->col, xl, xr, gz, att, slope, Tensor(), need_a);
+      if (need_r) gr = r.first;
+      if (need_a) {
+        ga = at::empty({H, C}, xl.options());
+        const size_t wsb = a.ggl_colsum_workspace_bytes(gp->N_dst, H * C);
+        Tensor ws = at::empty({static_cast<int64_t>(std::max<size_t>(wsb, 4))}, xl.options().dtype(at::kByte));
+        check(a, a.ggl_colsum_f32(r.second.data_ptr<float>(), gp->N_dst, H * C, ga.data_ptr<float>(), ws.data_ptr(), wsb,
+                                  stream_of(dev)));
+      }
     }
+    if (need_l) gl = gatv2_logit_bwd(*gp->bwd, gp->colT, xr, xl, gz, att, slope, gv, false).first;
   }
-  if (need_l) {
-    gp->need_bwd(idx);
-    gp->need_posT(idx);
-    Tensor gv = at::empty({gp->N_src, H, C}, xl.options());
-    Tensor part_t = partial_for(a, *gp->bwd, z, H * C + H, false);
-    ggl_segplan_t csT = gp->bwd->c(part_t);
-    check(a, a.ggl_edge_softmax_agg_bwd_src(&csT, gp->colT.data_ptr<int32_t>(), gp->posT.data_ptr<int32_t>(),
-                                            alpha.data_ptr<float>(), g.data_ptr<float>(), H, C, gv.data_ptr<float>(), st));
-    gl = gatv2_logit_bwd(*gp->bwd, gp->colT, xr, xl, gz, att, slope, gv, false).first;
-  }
-  return {gl, gr, ga};
+  return {or_empty(gl, xl), or_empty(gr, xl), or_empty(ga, xl)};
 }
 
 // The same op over a CSR the caller already holds — the argument list of dgNN's GATConvFuse
@@ -2153,26 +2137,35 @@ using DotFwdSig = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor>(const Tenso
 using DotBwdSig = std::tuple<Tensor, Tensor, Tensor>(const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                                                      const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
                                                      int64_t, double, double, bool, bool, bool);
-struct DotFn : public torch::autograd::Function<DotFn> {
-  static Tensor forward(AutogradContext *ctx, const Tensor &index, const Tensor &q, const Tensor &k, const Tensor &v, int64_t n,
-                        double scale, double p, bool need) {
+// the autograd node of an op with three differentiable tensors a, b, c and one scalar s (dot_attention: q, k, v, scale;
+// gatv2_attention: xl, xr, att, slope); Op names its two passes
+struct DotOps {
+  static constexpr const char *fwd = "ggl_attn::dot_attention_forward", *bwd = "ggl_attn::dot_attention_backward";
+};
+struct Gatv2Ops {
+  static constexpr const char *fwd = "ggl_attn::gatv2_attention_forward", *bwd = "ggl_attn::gatv2_attention_backward";
+};
+template <typename Op>
+struct LogitAttnFn : public torch::autograd::Function<LogitAttnFn<Op>> {
+  static Tensor forward(AutogradContext *ctx, const Tensor &index, const Tensor &a, const Tensor &b, const Tensor &c, int64_t n,
+                        double s, double p, bool need) {
     at::AutoDispatchBelowADInplaceOrView below;
-    static auto op = op_handle<DotFwdSig>("ggl_attn::dot_attention_forward");
+    static auto op = op_handle<DotFwdSig>(Op::fwd);
     Tensor out, rmax, rden, used, z;
-    std::tie(out, rmax, rden, used, z) = op.call(index, q, k, v, n, scale, p, need);
-    if (need) ctx->save_for_backward({index, q, k, v, z, out, rmax, rden, used});
+    std::tie(out, rmax, rden, used, z) = op.call(index, a, b, c, n, s, p, need);
+    if (need) ctx->save_for_backward({index, a, b, c, z, out, rmax, rden, used});
     ctx->saved_data["n"] = n;
-    ctx->saved_data["scale"] = scale;
+    ctx->saved_data["s"] = s;
     ctx->saved_data["p"] = p;
     return out;
   }
   static variable_list backward(AutogradContext *ctx, variable_list grads) {
     auto s = ctx->get_saved_variables();
-    static auto op = op_handle<DotBwdSig>("ggl_attn::dot_attention_backward");
-    const bool need_q = ctx->needs_input_grad(1), need_k = ctx->needs_input_grad(2), need_v = ctx->needs_input_grad(3);
+    static auto op = op_handle<DotBwdSig>(Op::bwd);
+    const bool need_a = ctx->needs_input_grad(1), need_b = ctx->needs_input_grad(2), need_c = ctx->needs_input_grad(3);
     auto r = op.call(s[0], s[1], s[2], s[3], s[4], grads[0], s[5], s[6], s[7], s[8], ctx->saved_data["n"].toInt(),
-                     ctx->saved_data["scale"].toDouble(), ctx->saved_data["p"].toDouble(), need_q, need_k, need_v);
-    return {Tensor(), need_q ? std::get<0>(r) : Tensor(), need_k ? std::get<1>(r) : Tensor(), need_v ? std::get<2>(r) : Tensor(),
+                     ctx->saved_data["s"].toDouble(), ctx->saved_data["p"].toDouble(), need_a, need_b, need_c);
+    return {Tensor(), need_a ? std::get<0>(r) : Tensor(), need_b ? std::get<1>(r) : Tensor(), need_c ? std::get<2>(r) : Tensor(),
             Tensor(), Tensor(), Tensor(), Tensor()};
   }
 };
@@ -2186,33 +2179,10 @@ static Tensor dot_autograd(const Tensor &index, const Tensor &q, const Tensor &k
   const int64_t n = num_nodes.has_value() ? *num_nodes : q.size(0);
   const double sc = scale.has_value() ? *scale : 1.0 / std::sqrt(static_cast<double>(q.size(2)));
   const bool need = at::GradMode::is_enabled() && (q.requires_grad() || k.requires_grad() || v.requires_grad());
-  return DotFn::apply(index, q, k, v, n, sc, p, need);
+  return LogitAttnFn<DotOps>::apply(index, q, k, v, n, sc, p, need);
 }
 
 // gatv2_attention: as dot_attention; the logits are kept by the forward only where xl, xr or att requires grad
-struct Gatv2Fn : public torch::autograd::Function<Gatv2Fn> {
-  static Tensor forward(AutogradContext *ctx, const Tensor &index, const Tensor &xl, const Tensor &xr, const Tensor &att, int64_t n,
-                        double slope, double p, bool need) {
-    at::AutoDispatchBelowADInplaceOrView below;
-    static auto op = op_handle<DotFwdSig>("ggl_attn::gatv2_attention_forward");
-    Tensor out, rmax, rden, used, z;
-    std::tie(out, rmax, rden, used, z) = op.call(index, xl, xr, att, n, slope, p, need);
-    if (need) ctx->save_for_backward({index, xl, xr, att, z, out, rmax, rden, used});
-    ctx->saved_data["n"] = n;
-    ctx->saved_data["slope"] = slope;
-    ctx->saved_data["p"] = p;
-    return out;
-  }
-  static variable_list backward(AutogradContext *ctx, variable_list grads) {
-    auto s = ctx->get_saved_variables();
-    static auto op = op_handle<DotBwdSig>("ggl_attn::gatv2_attention_backward");
-    const bool need_l = ctx->needs_input_grad(1), need_r = ctx->needs_input_grad(2), need_a = ctx->needs_input_grad(3);
-    auto r = op.call(s[0], s[1], s[2], s[3], s[4], grads[0], s[5], s[6], s[7], s[8], ctx->saved_data["n"].toInt(),
-                     ctx->saved_data["slope"].toDouble(), ctx->saved_data["p"].toDouble(), need_l, need_r, need_a);
-    return {Tensor(), need_l ? std::get<0>(r) : Tensor(), need_r ? std::get<1>(r) : Tensor(), need_a ? std::get<2>(r) : Tensor(),
-            Tensor(), Tensor(), Tensor(), Tensor()};
-  }
-};
 // xl [N, C], xr [N, C] with att [C] are one head
 static Tensor gatv2_autograd(const Tensor &index, const Tensor &xl, const Tensor &xr, const Tensor &att,
                              c10::optional<int64_t> num_nodes, double slope, double p) {
@@ -2222,7 +2192,7 @@ static Tensor gatv2_autograd(const Tensor &index, const Tensor &xl, const Tensor
   TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout_rate must be in [0, 1)");
   const int64_t n = num_nodes.has_value() ? *num_nodes : xr.size(0);
   const bool need = at::GradMode::is_enabled() && (xl.requires_grad() || xr.requires_grad() || att.requires_grad());
-  return Gatv2Fn::apply(index, xl, xr, att, n, slope, p, need);
+  return LogitAttnFn<Gatv2Ops>::apply(index, xl, xr, att, n, slope, p, need);
 }
 
 using GatCsrFwdSig = std::tuple<Tensor, Tensor, Tensor, Tensor, bool>(const Tensor &, const Tensor &, const Tensor &, const Tensor &,
@@ -2469,35 +2439,25 @@ static Tensor esa_meta(const Tensor &, const Tensor &z, const Tensor &x, c10::op
   if (z.dim() == 1 && x.dim() == 2) return at::empty({N, x.size(1)}, x.options());
   return at::empty({N, x.size(1), x.size(2)}, x.options());
 }
-static std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> dot_fwd_meta(const Tensor &index, const Tensor &q, const Tensor &,
-                                                                       const Tensor &v, int64_t n, double, double, bool keep) {
-  auto o = v.options();
-  return {at::empty({n, v.size(1), v.size(2)}, o), at::empty({n, v.size(1)}, o), at::empty({n, v.size(1)}, o),
-          at::empty({0}, o.dtype(at::kLong)), keep ? at::empty({index.size(1), v.size(1)}, o) : at::empty({0}, o)};
+// the passes of dot_attention (a, b, c = q, k, v) and gatv2_attention (xl, xr, att): every one of q, k, v, xl, xr is [., H, C]
+static std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> logit_attn_fwd_meta(const Tensor &index, const Tensor &a, const Tensor &,
+                                                                              const Tensor &, int64_t n, double, double, bool keep) {
+  auto o = a.options();
+  return {at::empty({n, a.size(1), a.size(2)}, o), at::empty({n, a.size(1)}, o), at::empty({n, a.size(1)}, o),
+          at::empty({0}, o.dtype(at::kLong)), keep ? at::empty({index.size(1), a.size(1)}, o) : at::empty({0}, o)};
 }
-static std::tuple<Tensor, Tensor, Tensor> dot_bwd_meta(const Tensor &, const Tensor &q, const Tensor &k, const Tensor &v, const Tensor &,
-                                                       const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
-                                                       int64_t, double, double, bool need_q, bool need_k, bool need_v) {
-  auto e = [&]() { return at::empty({0}, v.options()); };
-  return {need_q ? at::empty_like(q) : e(), need_k ? at::empty_like(k) : e(), need_v ? at::empty_like(v) : e()};
+static std::tuple<Tensor, Tensor, Tensor> logit_attn_bwd_meta(const Tensor &, const Tensor &a, const Tensor &b, const Tensor &c,
+                                                              const Tensor &, const Tensor &, const Tensor &, const Tensor &,
+                                                              const Tensor &, const Tensor &, int64_t, double, double, bool need_a,
+                                                              bool need_b, bool need_c) {
+  auto e = [&]() { return at::empty({0}, a.options()); };
+  return {need_a ? at::empty_like(a) : e(), need_b ? at::empty_like(b) : e(), need_c ? at::empty_like(c) : e()};
 }
 static Tensor dot_meta(const Tensor &, const Tensor &q, const Tensor &, const Tensor &v, c10::optional<int64_t> n,
                        c10::optional<double>, double) {
   const int64_t N = n.has_value() ? *n : q.size(0);
   if (v.dim() == 2) return at::empty({N, v.size(1)}, v.options());
   return at::empty({N, v.size(1), v.size(2)}, v.options());
-}
-static std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> gatv2_fwd_meta(const Tensor &index, const Tensor &xl, const Tensor &,
-                                                                         const Tensor &, int64_t n, double, double, bool keep) {
-  auto o = xl.options();
-  return {at::empty({n, xl.size(1), xl.size(2)}, o), at::empty({n, xl.size(1)}, o), at::empty({n, xl.size(1)}, o),
-          at::empty({0}, o.dtype(at::kLong)), keep ? at::empty({index.size(1), xl.size(1)}, o) : at::empty({0}, o)};
-}
-static std::tuple<Tensor, Tensor, Tensor> gatv2_bwd_meta(const Tensor &, const Tensor &xl, const Tensor &xr, const Tensor &att,
-                                                         const Tensor &, const Tensor &, const Tensor &, const Tensor &, const Tensor &,
-                                                         const Tensor &, int64_t, double, double, bool need_l, bool need_r, bool need_a) {
-  auto e = [&]() { return at::empty({0}, xl.options()); };
-  return {need_l ? at::empty_like(xl) : e(), need_r ? at::empty_like(xr) : e(), need_a ? at::empty_like(att) : e()};
 }
 static Tensor gatv2_meta(const Tensor &, const Tensor &xl, const Tensor &xr, const Tensor &, c10::optional<int64_t> n, double, double) {
   const int64_t N = n.has_value() ? *n : xr.size(0);
@@ -2926,11 +2886,11 @@ TORCH_LIBRARY_IMPL(ggl_attn, Meta, m) {
   m.impl("edge_softmax_aggregate_forward", ggl_torch::esa_fwd_meta);
   m.impl("edge_softmax_aggregate_backward", ggl_torch::esa_bwd_meta);
   m.impl("dot_attention", ggl_torch::dot_meta);
-  m.impl("dot_attention_forward", ggl_torch::dot_fwd_meta);
-  m.impl("dot_attention_backward", ggl_torch::dot_bwd_meta);
+  m.impl("dot_attention_forward", ggl_torch::logit_attn_fwd_meta);
+  m.impl("dot_attention_backward", ggl_torch::logit_attn_bwd_meta);
   m.impl("gatv2_attention", ggl_torch::gatv2_meta);
-  m.impl("gatv2_attention_forward", ggl_torch::gatv2_fwd_meta);
-  m.impl("gatv2_attention_backward", ggl_torch::gatv2_bwd_meta);
+  m.impl("gatv2_attention_forward", ggl_torch::logit_attn_fwd_meta);
+  m.impl("gatv2_attention_backward", ggl_torch::logit_attn_bwd_meta);
 }
 
 // Several statistics of the same rows in one walk, a namespace of its own for the same reason: the ggl:: surface is pinned.

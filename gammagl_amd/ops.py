@@ -954,6 +954,28 @@ class Engine:
         return self._head_padded(gp, x, lambda xp: autograd.GATFused.apply(
             self, gp, el.contiguous(), er.contiguous(), xp.contiguous(), negative_slope, p, out_dtype))
 
+    def _attn_plan(self, op, index, num_nodes, src, dst, dropout_rate, training):
+        """(gp, p) of a logit attention op: `index` as a GraphPlan over (num_nodes, or dst's rows) destinations and src's rows
+        sources, its rows checked against `dst` and `src` — (name, tensor) pairs, dst None where no tensor has a row per
+        destination — and the attention dropout rate actually applied: 0 outside training, else dropout_rate in [0, 1)."""
+        rows = (dst or src)[1].shape[0]
+        n = rows if num_nodes is None else num_nodes
+        gp = index if isinstance(index, GraphPlan) else self.graph_plan(index, n, src[1].shape[0])
+        if dst is not None and (gp.N_dst != rows or gp.N_src != src[1].shape[0]):
+            raise RuntimeError(f"{op}: the graph has {gp.N_dst} destinations and {gp.N_src} sources, {dst[0]} has "
+                               f"{rows} rows and {src[0]} {src[1].shape[0]}")
+        p = float(dropout_rate) if training else 0.0
+        if not 0.0 <= p < 1.0:
+            raise ValueError("dropout_rate must be in [0, 1)")
+        return gp, p
+
+    @staticmethod
+    def _attn_leaves(*ts):
+        """contiguous inputs; detached when nothing will run backward, so that no logits are kept (or, fused, formed) for it"""
+        if not torch.is_grad_enabled():
+            ts = [t.detach() for t in ts]
+        return [t.contiguous() for t in ts]
+
     def edge_softmax_aggregate(self, index, logits, x, num_nodes=None, dropout_rate=0.0, training=True):
         """out[i,h,:] = sum_{e->i} dropout(softmax_i(logits[:,h]))[e] * x[src_e,h,:] in one kernel per direction
         (ggl_edge_softmax_agg_*): gat_fused with the logit of every edge GIVEN — `logits` [E, H] f32 in the order of
@@ -966,14 +988,10 @@ class Engine:
         self._dev(index, logits, x)
         self._check_f32("logits", logits)
         self._check_f32("x", x)
-        n = x.shape[0] if num_nodes is None else num_nodes
-        gp = index if isinstance(index, GraphPlan) else self.graph_plan(index, n, x.shape[0])
+        gp, p = self._attn_plan("edge_softmax_aggregate", index, num_nodes, ("x", x), None, dropout_rate, training)
         if x.dim() != 3 or logits.dim() != 2 or logits.shape[0] != gp.E or logits.shape[1] != x.shape[1]:
             raise RuntimeError(f"edge_softmax_aggregate expects logits [E, H] and x [N_src, H, C]: got logits "
                                f"{tuple(logits.shape)}, x {tuple(x.shape)} for {gp.E} edges")
-        p = float(dropout_rate) if training else 0.0
-        if not 0.0 <= p < 1.0:
-            raise ValueError("dropout_rate must be in [0, 1)")
         return self._head_padded(gp, x, lambda xp: autograd.EdgeSoftmaxAgg.apply(
             self, gp, logits.contiguous(), xp.contiguous(), p))
 
@@ -1001,19 +1019,9 @@ class Engine:
                                f"k {tuple(k.shape)}, v {tuple(v.shape)}")
         if v.shape[2] != q.shape[2]:
             raise RuntimeError(f"dot_attention needs v of k's head width (Cv == C): got C = {q.shape[2]}, Cv = {v.shape[2]}")
-        n = q.shape[0] if num_nodes is None else num_nodes
-        gp = index if isinstance(index, GraphPlan) else self.graph_plan(index, n, k.shape[0])
-        if gp.N_dst != q.shape[0] or gp.N_src != k.shape[0]:
-            raise RuntimeError(f"dot_attention: the graph has {gp.N_dst} destinations and {gp.N_src} sources, q has "
-                               f"{q.shape[0]} rows and k {k.shape[0]}")
-        p = float(dropout_rate) if training else 0.0
-        if not 0.0 <= p < 1.0:
-            raise ValueError("dropout_rate must be in [0, 1)")
+        gp, p = self._attn_plan("dot_attention", index, num_nodes, ("k", k), ("q", q), dropout_rate, training)
         sc = 1.0 / math.sqrt(q.shape[2]) if scale is None else float(scale)
-        if not torch.is_grad_enabled():   # nothing will run backward: no logits are kept (or, fused, formed) for it
-            q, k, v = q.detach(), k.detach(), v.detach()
-        out, z = autograd.DotAttention.apply(self, gp, q.contiguous(), k.contiguous(), v.contiguous(), sc, p,
-                                             bool(return_logits))
+        out, z = autograd.DotAttention.apply(self, gp, *self._attn_leaves(q, k, v), sc, p, bool(return_logits))
         return (out, z) if return_logits else out
 
     def gatv2_attention(self, index, xl, xr, att, num_nodes=None, negative_slope=0.2, dropout_rate=0.0, training=True,
@@ -1040,18 +1048,9 @@ class Engine:
                                f"xr {tuple(xr.shape)}")
         if att.dim() != 2 or att.shape != xl.shape[1:]:
             raise RuntimeError(f"gatv2_attention expects att [H, C] = {tuple(xl.shape[1:])}: got {tuple(att.shape)}")
-        n = xr.shape[0] if num_nodes is None else num_nodes
-        gp = index if isinstance(index, GraphPlan) else self.graph_plan(index, n, xl.shape[0])
-        if gp.N_dst != xr.shape[0] or gp.N_src != xl.shape[0]:
-            raise RuntimeError(f"gatv2_attention: the graph has {gp.N_dst} destinations and {gp.N_src} sources, xr has "
-                               f"{xr.shape[0]} rows and xl {xl.shape[0]}")
-        p = float(dropout_rate) if training else 0.0
-        if not 0.0 <= p < 1.0:
-            raise ValueError("dropout_rate must be in [0, 1)")
-        if not torch.is_grad_enabled():   # nothing will run backward: no logits are kept (or, fused, formed) for it
-            xl, xr, att = xl.detach(), xr.detach(), att.detach()
-        out, z = autograd.GATv2Attention.apply(self, gp, xl.contiguous(), xr.contiguous(), att.contiguous(),
-                                               float(negative_slope), p, bool(return_logits))
+        gp, p = self._attn_plan("gatv2_attention", index, num_nodes, ("xl", xl), ("xr", xr), dropout_rate, training)
+        out, z = autograd.GATv2Attention.apply(self, gp, *self._attn_leaves(xl, xr, att), float(negative_slope), p,
+                                               bool(return_logits))
         return (out, z) if return_logits else out
 
     def _check_weight(self, weight, gp):

@@ -15,6 +15,24 @@ from .. import mpops
 __all__ = ["edge_softmax_aggregate", "dot_attention", "gatv2_attention"]
 
 
+def _drop_rate(dropout_rate, training):
+    """the rate the op is called with: 0 outside training, else dropout_rate in [0, 1)"""
+    p = float(dropout_rate) if training else 0.0
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout_rate must be in [0, 1)")
+    return p
+
+
+def _attn_ops(x):
+    """``torch.ops.ggl_attn`` when the engine for x's device is the shipped library, the Python-registered operators otherwise"""
+    ops = mpops._ops_for(x)
+    if ops is not mpops._py_ops:
+        from .. import cpp_ops
+
+        ops = cpp_ops.load_attn()
+    return ops
+
+
 def edge_softmax_aggregate(edge_index, logits, x, num_nodes=None, dropout_rate=0.0, training=True):
     """``out[i, h, :] = sum over edges e with dst(e) = i of drop(softmax_i(logits[:, h]))[e] * x[src(e), h, :]``.
 
@@ -37,16 +55,9 @@ def edge_softmax_aggregate(edge_index, logits, x, num_nodes=None, dropout_rate=0
     Route: ``torch.ops.ggl_attn`` (registered from C++) when the engine for x's device is the shipped library, the
     Python-registered ``torch.ops.gammagl_amd`` otherwise — as ``mpops`` chooses for the seven reference operators."""
     _engine(x)._dev(edge_index, logits, x)
-    p = float(dropout_rate) if training else 0.0
-    if not 0.0 <= p < 1.0:
-        raise ValueError("dropout_rate must be in [0, 1)")
-    ops = mpops._ops_for(x)
-    if ops is not mpops._py_ops:
-        from .. import cpp_ops
-
-        ops = cpp_ops.load_attn()
+    p = _drop_rate(dropout_rate, training)
     n = None if num_nodes is None else int(num_nodes)
-    return ops.edge_softmax_aggregate(mpops._ids(edge_index, x), logits, x, n, p)
+    return _attn_ops(x).edge_softmax_aggregate(mpops._ids(edge_index, x), logits, x, n, p)
 
 
 def dot_attention(edge_index, q, k, v, num_nodes=None, scale=None, dropout_rate=0.0, training=True):
@@ -67,16 +78,9 @@ def dot_attention(edge_index, q, k, v, num_nodes=None, scale=None, dropout_rate=
 
     Route: as :func:`edge_softmax_aggregate` (``torch.ops.ggl_attn`` on the shipped library)."""
     _engine(v)._dev(edge_index, q, k, v)
-    p = float(dropout_rate) if training else 0.0
-    if not 0.0 <= p < 1.0:
-        raise ValueError("dropout_rate must be in [0, 1)")
-    ops = mpops._ops_for(v)
-    if ops is not mpops._py_ops:
-        from .. import cpp_ops
-
-        ops = cpp_ops.load_attn()
+    p = _drop_rate(dropout_rate, training)
     n = None if num_nodes is None else int(num_nodes)
-    return ops.dot_attention(mpops._ids(edge_index, v), q, k, v, n, None if scale is None else float(scale), p)
+    return _attn_ops(v).dot_attention(mpops._ids(edge_index, v), q, k, v, n, None if scale is None else float(scale), p)
 
 
 def gatv2_attention(edge_index, xl, xr, att, num_nodes=None, negative_slope=0.2, dropout_rate=0.0, training=True):
@@ -98,13 +102,6 @@ def gatv2_attention(edge_index, xl, xr, att, num_nodes=None, negative_slope=0.2,
 
     Route: as :func:`edge_softmax_aggregate` (``torch.ops.ggl_attn`` on the shipped library)."""
     _engine(xl)._dev(edge_index, xl, xr, att)
-    p = float(dropout_rate) if training else 0.0
-    if not 0.0 <= p < 1.0:
-        raise ValueError("dropout_rate must be in [0, 1)")
-    ops = mpops._ops_for(xl)
-    if ops is not mpops._py_ops:
-        from .. import cpp_ops
-
-        ops = cpp_ops.load_attn()
+    p = _drop_rate(dropout_rate, training)
     n = None if num_nodes is None else int(num_nodes)
-    return ops.gatv2_attention(mpops._ids(edge_index, xl), xl, xr, att, n, float(negative_slope), p)
+    return _attn_ops(xl).gatv2_attention(mpops._ids(edge_index, xl), xl, xr, att, n, float(negative_slope), p)

@@ -182,6 +182,47 @@ def check_one_sided_gradients(eng, dev, H=2, C=16):
             assert (part[2 + i] is None) != n and (not n or same_bits(part[2 + i], full[2 + i])), (need, i)
 
 
+def route_chunks(name):
+    """the engine's plans can be forced to walk the hub row chunked and whole; the operator namespaces build their own"""
+    return CHUNKS if name == "engine" else (None,)
+
+
+def check_single_needs_against_the_aggregate(routes, eng, dev, H=2, C=16, seed=23):
+    """Only v's gradient asked, only q's, only k's, through every route: out and the one gradient have the bits of the SAME
+    route's edge_softmax_aggregate on the returned z under the same rng state — gv its x gradient, gq / gk bspmm of its logits
+    gradient times scale — and the gradients nobody asked for are None.  Pins which of (gz, gv) the shared backward forms."""
+    from gammagl_amd import mpops
+
+    index = make_graph(dev)
+    q, k, v, go = make_qkv(H, C, dev)
+    scale = scale_of(H, C)
+    s32 = float(np.float32(1.0 / math.sqrt(C) if scale is None else scale))
+    aggregate = ec.make_routes(eng)
+    for name, route in routes.items():
+        for chunk in route_chunks(name):
+            with forced_chunk(eng, chunk) if chunk else contextlib.nullcontext():
+                for p in DROPS:
+                    tag = (name, chunk, p)
+                    state = eng._rng_state(dev).clone()
+                    _, z, *_ = run_engine(eng, index, q, k, v, go, scale, p, state, need=(False, False, False))
+                    za, va = z.clone().requires_grad_(True), v.clone().requires_grad_(True)
+                    gc.reseed(eng, seed)
+                    ref = aggregate[name](index, za, va, N_DST, p)
+                    ref.backward(go)
+                    gs = za.grad * s32                      # one rounded f32 multiply per element
+                    want = (lambda: mpops.bspmm(index, gs, square(index, k), "sum")[:N_DST],
+                            lambda: mpops.bspmm(index.flip(0).contiguous(), gs, square(index, q), "sum")[:N_SRC],
+                            lambda: va.grad)
+                    for i in (2, 0, 1):
+                        leaves = [t.clone().requires_grad_(j == i) for j, t in enumerate((q, k, v))]
+                        gc.reseed(eng, seed)
+                        out = route(index, *leaves, N_DST, scale, p)
+                        out.backward(go)
+                        assert same_bits(out.detach(), ref.detach()), (tag, i)
+                        assert same_bits(leaves[i].grad, want[i]()), (tag, i)
+                        assert all(t.grad is None for j, t in enumerate(leaves) if j != i), (tag, i)
+
+
 def run_route(route, eng, index, q, k, v, go, scale, p, seed):
     leaves = [t.clone().requires_grad_(True) for t in (q, k, v)]
     if p > 0:

@@ -10,6 +10,7 @@ ggl_gatv2_logit_bwd, itself held to a serial numpy float32 oracle on the bits.  
 add, one in the slope multiply, one in the product, C - 1 in the sum).
 
 A *route* is a callable ``f(index, xl, xr, att, n_dst, slope, p) -> out`` that records autograd."""
+import contextlib
 import ctypes
 
 import numpy as np
@@ -232,6 +233,43 @@ def check_one_sided_gradients(eng, dev, H=2, C=16):
         assert same_bits(part[0], full[0])
         for i, n in enumerate(need):
             assert (part[2 + i] is None) != n and (not n or same_bits(part[2 + i], full[2 + i])), (need, i)
+
+
+def check_single_needs_against_the_aggregate(routes, eng, dev, H=2, C=16, seed=23):
+    """Only xl's gradient asked, only xr's, only att's, through every route: out has the bits of the SAME route's
+    edge_softmax_aggregate on the returned z under the same rng state, and the one gradient those of ggl_gatv2_logit_bwd on
+    that op's gz (and, for g_xl, with its x gradient gv added — held to the serial oracle as well); the gradients nobody asked
+    for are None.  Pins which of (gz, gv) the shared backward forms."""
+    index = make_graph(dev)
+    xl, xr, att, go = make_inputs(H, C, dev)
+    aggregate = ec.make_routes(eng)
+    for name, route in routes.items():
+        for chunk in dc.route_chunks(name):
+            with forced_chunk(eng, chunk) if chunk else contextlib.nullcontext():
+                gp = eng.graph_plan(index, N_DST, N_SRC)
+                for p in DROPS:
+                    tag = (name, chunk, p)
+                    state = eng._rng_state(dev).clone()
+                    _, z, *_ = run_engine(eng, gp, xl, xr, att, go, p, state, need=(False, False, False))
+                    za, va = z.clone().requires_grad_(True), xl.clone().requires_grad_(True)
+                    gc.reseed(eng, seed)
+                    ref = aggregate[name](index, za, va, N_DST, p)
+                    ref.backward(go)
+                    gz, gv = za.grad, va.grad
+                    want = (lambda: logit_bwd(eng, gp.bwd, gp.colT, xr, xl, gz, att, gv, False)[0],
+                            lambda: logit_bwd(eng, gp.fwd, gp.col, xl, xr, gz, att, None, False)[0],
+                            lambda: eng.colsum(logit_bwd(eng, gp.fwd, gp.col, xl, xr, gz, att, None, True)[1]
+                                               .reshape(N_DST, H * C)).reshape(H, C))
+                    for i in range(3):
+                        leaves = [t.clone().requires_grad_(j == i) for j, t in enumerate((xl, xr, att))]
+                        gc.reseed(eng, seed)
+                        out = route(index, *leaves, N_DST, SLOPE, p)
+                        out.backward(go)
+                        assert same_bits(out.detach(), ref.detach()), (tag, i)
+                        assert same_bits(leaves[i].grad, want[i]()), (tag, i)
+                        assert all(t.grad is None for j, t in enumerate(leaves) if j != i), (tag, i)
+                        if i == 0:
+                            assert same_bits(leaves[0].grad, oracle_logit_bwd(gp.bwd, gp.colT, xr, xl, gz, att, gv)[0]), tag
 
 
 def run_route(route, eng, index, xl, xr, att, go, p, seed):

@@ -61,6 +61,10 @@ def test_one_sided_gradients(eng):
     vc.check_one_sided_gradients(eng, DEV)
 
 
+def test_single_needs_have_the_aggregates_backward_bits(routes, eng):
+    vc.check_single_needs_against_the_aggregate(routes, eng, DEV)
+
+
 def test_routes_agree(routes, eng):
     vc.check_routes_agree(routes, eng, DEV)
 

@@ -75,6 +75,12 @@ def test_one_sided_gradients_gpu(eng, dev):
     vc.check_one_sided_gradients(eng, dev)
 
 
+def test_single_needs_have_the_aggregates_backward_bits_gpu(routes, eng, dev):
+    """on the fused route (2 x 16) and on the composed one (2 x 12)"""
+    vc.check_single_needs_against_the_aggregate(routes, eng, dev)
+    vc.check_single_needs_against_the_aggregate(routes, eng, dev, 2, 12)
+
+
 def test_routes_agree_gpu(routes, eng, dev):
     vc.check_routes_agree(routes, eng, dev)
 
