@@ -17,7 +17,7 @@ HIP_LIB_PATH = os.path.join(_HERE, "lib", "libggl_mpops_hip.so")
 HOST_LIB_PATH = os.path.join(_HERE, "lib", "libggl_mpops_host.so")
 
 GGL_OK, GGL_EINVAL, GGL_EINDEX, GGL_EDTYPE, GGL_EHIP, GGL_EWORKSPACE = 0, -1, -2, -3, -4, -5
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class SegPlanC(ctypes.Structure):
@@ -29,6 +29,7 @@ class SegPlanC(ctypes.Structure):
         ("N", c_int64), ("E", c_int64), ("row_order", c_void_p), ("xcd_run_rows", c_int64),
         ("long_order", c_void_p),
         ("max_len", c_int64),
+        ("partial_bytes", c_size_t),
     ]
 
 
@@ -128,6 +129,9 @@ SIGNATURES = {
     "ggl_segment_epi": (c_int, [_V, _P, c_int64, c_int, _V, c_int64, _V, c_int, c_float, _V, _V, _V]),
     "ggl_gat_fused_fwd": (c_int, [_P, _V, _V, _V, _V, c_float, c_int64, c_int64, c_float, _V, _V, _V, _V, _V]),
     "ggl_gat_partial_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "ggl_gat_bwd_dst_partial_bytes": (c_size_t, [c_int64, c_int64]),
+    "ggl_gat_bwd_src_partial_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "ggl_gat_fast_bwd_dst_partial_bytes": (c_size_t, [c_int64, c_int64]),
     "ggl_gat_fused_bwd_dst": (c_int, [_P, _V, _V, _V, _V, _V, _V, _V, _V, _V, c_float, c_int64, c_int64,
                                       c_float, _V, _V, _V, _V, _V, _V]),
     "ggl_gat_fused_bwd_src": (c_int, [_P, _V, _V, _V, _V, _V, c_int64, c_int64, _V, _V, _V]),
@@ -156,6 +160,8 @@ SIGNATURES = {
                                  _V, _V, _V, _V, _V, _V]),
     "ggl_gat_sh_supported": (c_int, [c_int64, c_int64, c_int64]),
     "ggl_gat_sh_partial_bytes": (c_size_t, [c_int64, c_int64]),
+    "ggl_gat_sh_bwd_dst_partial_bytes": (c_size_t, [c_int64]),
+    "ggl_gat_sh_bwd_src_partial_bytes": (c_size_t, [c_int64, c_int64]),
     "ggl_gat_sh_fwd": (c_int, [_P, _V, _V, _V, _V, c_int64, c_float, c_float, _V, _V, _V, _V, _V]),
     "ggl_gat_sh_stats": (c_int, [_V, _V, _V, _V, _V, c_int64, c_int64, _V, _V]),
     "ggl_gat_sh_bwd": (c_int, [_P, _V, _P, _V, _V, _V, _V, c_int64, _V, _V, _V, _V, c_int64, c_float, c_float, _V,

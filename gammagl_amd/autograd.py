@@ -262,8 +262,8 @@ class GATFused(torch.autograd.Function):
             ger = torch.empty_like(er)
             gx = torch.empty((gp.N_src, H, C), dtype=torch.float32, device=dev)
             gel = torch.empty((gp.N_src, H), dtype=torch.float32, device=dev)
-            part_f = eng._partial(gp.fwd, torch.float32, 8 * H, False, dev)   # four double sums per chunk and head
-            part_t = eng._partial(bwd, torch.float32, H * C + H, False, dev)
+            part_f = eng._gat_fast_bwd_dst_partial(gp.fwd, H, dev)
+            part_t = eng._gat_bwd_src_partial(bwd, H, C, dev)
             cs, csT = gp.fwd.c_struct(part_f), bwd.c_struct(part_t)
             posT = gp.posT if ctx.p_drop > 0 else None
             eng._check(eng.lib.ggl_gat_fast_bwd(
@@ -275,7 +275,7 @@ class GATFused(torch.autograd.Function):
         ad = torch.empty((max(gp.E, 1), H, 2), dtype=torch.float32, device=dev)
         alpha, de = ad.data_ptr(), ad.data_ptr() + 4
         ger = torch.empty_like(er)
-        part_f = eng._partial(gp.fwd, torch.float32, H, False, dev)  # must outlive the launch
+        part_f = eng._gat_bwd_dst_partial(gp.fwd, H, dev)  # must outlive the launch
         cs = gp.fwd.c_struct(part_f)
         xc, gc = _DTYPE_CODE.get(x.dtype), _DTYPE_CODE.get(g.dtype)
         if x16:
@@ -291,7 +291,7 @@ class GATFused(torch.autograd.Function):
         bwd = gp.bwd
         gx = torch.empty((gp.N_src, H, C), dtype=x.dtype, device=dev)
         gel = torch.empty((gp.N_src, H), dtype=torch.float32, device=dev)
-        part = eng._partial(bwd, torch.float32, H * C + H, False, dev)  # gx and gel partials of long rows
+        part = eng._gat_bwd_src_partial(bwd, H, C, dev)
         csT = bwd.c_struct(part)
         if x16:
             eng._check(eng.lib.ggl_gat_fused_bwd_src_x16(ctypes.byref(csT), _ptr(gp.colT), _ptr(gp.posT),
@@ -335,7 +335,7 @@ def _esa_backward(eng, gp, z, v, g, out, rmax, rden, p_drop, rng_used, need_gz, 
     st = eng._stream(dev)
     alpha = torch.empty((max(gp.E, 1), H), dtype=torch.float32, device=dev) if need_gv else None   # sorted positions
     gz = torch.empty_like(z) if need_gz else None                                                  # caller's order
-    part_f = eng._partial(gp.fwd, torch.float32, H, False, dev)  # must outlive the launch
+    part_f = eng._gat_bwd_dst_partial(gp.fwd, H, dev)  # must outlive the launch
     cs = gp.fwd.c_struct(part_f)
     eng._check(eng.lib.ggl_edge_softmax_agg_bwd_dst(
         ctypes.byref(cs), _ptr(gp.col), _ptr(z), _ptr(v), _ptr(g), _ptr(out), _ptr(rmax), _ptr(rden), H, C,
@@ -344,7 +344,7 @@ def _esa_backward(eng, gp, z, v, g, out, rmax, rden, p_drop, rng_used, need_gz, 
     if need_gv:
         bwd = gp.bwd
         gv = torch.empty((gp.N_src, H, C), dtype=torch.float32, device=dev)
-        part = eng._partial(bwd, torch.float32, H * C + H, False, dev)
+        part = eng._gat_bwd_src_partial(bwd, H, C, dev)
         csT = bwd.c_struct(part)
         eng._check(eng.lib.ggl_edge_softmax_agg_bwd_src(ctypes.byref(csT), _ptr(gp.colT), _ptr(gp.posT), _ptr(alpha),
                                                         _ptr(g), H, C, _ptr(gv), st))
@@ -708,7 +708,7 @@ class GATHeadMean(torch.autograd.Function):
         T = torch.empty((N, H, Cp), dtype=torch.float32, device=dev)
         bwd = gp.bwd
         # forward plan's partial: four doubles per hub chunk and head (the destination walk's row sums, round 6)
-        part_f, part_t = eng._gat_sh_partial(gp.fwd, 8, dev), eng._gat_sh_partial(bwd, Cp, dev)
+        part_f, part_t = eng._gat_sh_bwd_dst_partial(gp.fwd, dev), eng._gat_sh_bwd_src_partial(bwd, Cp, dev)
         cs, csT = gp.fwd.c_struct(part_f), bwd.c_struct(part_t)
         posT = gp.posT if ctx.p_drop > 0 else None
         eng._check(eng.lib.ggl_gat_sh_bwd(ctypes.byref(cs), _ptr(gp.col), ctypes.byref(csT), _ptr(gp.colT),

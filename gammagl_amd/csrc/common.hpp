@@ -191,16 +191,25 @@ static inline void dropout_params(float p_drop, uint32_t *thresh, float *scale) 
 }
 
 // What a launcher reads off a plan before it walks it.  n_chunks is 0 and partial NULL for a plan without long rows;
-// how the partial buffer is carved up (pm = pacc + n_chunks * K, ...) belongs to the kernel and stays with the caller.
+// how the partial buffer is carved up (pm = pacc + n_chunks * K, ...) belongs to the kernel and stays with the caller,
+// next to the *_partial_bytes export that sizes it: the caller passes that export's answer for hub_chunks(plan) as `need`.
 struct WalkPlan {
   int64_t N, E, chunk, n_long, n_chunks;
   const int32_t *order;   // the plan's length-sorted row order, or NULL (option row_order = 0)
   float *partial;
 };
+// the chunk count a walk's *_partial_bytes export is asked about: 0 for no plan (rejected next) and no long rows
+static inline int64_t hub_chunks(const ggl_segplan_t *plan) { return (plan && plan->n_long > 0) ? plan->n_chunks : 0; }
+// plan->partial_bytes against what the walk carves out of plan->partial (only asked for a plan with long rows)
+static inline int partial_fits(const ggl_segplan_t *plan, const char *which, size_t need) {
+  GGL_REQUIRE(plan->partial_bytes >= need, GGL_EWORKSPACE, "%s has long rows and a partial of %zu bytes: its walk needs %zu",
+              which, plan->partial_bytes, need);
+  return GGL_OK;
+}
 // The entry points word their rejections differently and the words are part of the ABI: null_text / chunk_text are the
-// caller's, `which` ("plan", "transposed plan") names the plan in the workspace error.
+// caller's, `which` ("plan", "transposed plan") names the plan in the workspace errors.
 static inline int walk_plan(const ggl_segplan_t *plan, const char *which, const char *null_text, const char *chunk_text,
-                            WalkPlan &p) {
+                            size_t need, WalkPlan &p) {
   GGL_REQUIRE(plan && plan->rowptr, GGL_EINVAL, "%s", null_text);
   GGL_REQUIRE(plan->chunk > 0, GGL_EINVAL, "%s", chunk_text);
   p.N = plan->N; p.E = plan->E; p.chunk = plan->chunk;
@@ -211,6 +220,7 @@ static inline int walk_plan(const ggl_segplan_t *plan, const char *which, const 
   if (p.n_long > 0) {
     GGL_REQUIRE(plan->long_rows && plan->chunk_ptr && plan->partial, GGL_EWORKSPACE,
                 "%s has long rows but long_rows/chunk_ptr/partial is NULL", which);
+    if (int rc = partial_fits(plan, which, need)) return rc;
     p.partial = static_cast<float *>(plan->partial);
   }
   return GGL_OK;

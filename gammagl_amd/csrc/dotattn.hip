@@ -90,7 +90,9 @@ extern "C" int ggl_dot_attn_fwd(const ggl_segplan_t *plan, const int32_t *col, c
                                 const float *v, float scale, int64_t H, int64_t C, float p_drop, int64_t *rng_state,
                                 float *out, float *rowmax, float *rowden, float *z_out, void *stream) {
   WalkPlan p;
-  if (int rc = walk_plan(plan, "plan", "plan is NULL", "H, C and chunk must be positive", p)) return rc;
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", "H, C and chunk must be positive",
+                         gat_fwd_partial_bytes(hub_chunks(plan), H, C), p))
+    return rc;
   GGL_REQUIRE(H > 0 && C > 0, GGL_EINVAL, "H, C and chunk must be positive");
   GGL_REQUIRE(ggl_dot_attn_supported(H, C), GGL_EINVAL, "ggl_dot_attn_fwd: C must be 8, 16, 32 or 64 (ggl_dot_attn_supported)");
   const int64_t N = p.N;

@@ -519,9 +519,12 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_src_final16_kernel(
 
 using namespace ggl;
 
-extern "C" size_t ggl_gat_partial_bytes(int64_t n_chunks, int64_t H, int64_t C) {
-  if (n_chunks <= 0) return 0;
-  return (size_t)n_chunks * (size_t)(H * C + 2 * H) * sizeof(float) + 64;
+extern "C" size_t ggl_gat_partial_bytes(int64_t n_chunks, int64_t H, int64_t C) { return gat_fwd_partial_bytes(n_chunks, H, C); }
+// the destination walk's ger partials, [n_chunks, H] floats (gat_bwd_dst_impl; the edge-logit form asks for them and writes none)
+extern "C" size_t ggl_gat_bwd_dst_partial_bytes(int64_t n_chunks, int64_t H) { return ggl_partial_bytes(GGL_F32, n_chunks, H, 0); }
+// the source walk's gx then gel partials, [n_chunks, H * C] and [n_chunks, H] floats (gat_bwd_src_impl, ggl_gat_fast_bwd)
+extern "C" size_t ggl_gat_bwd_src_partial_bytes(int64_t n_chunks, int64_t H, int64_t C) {
+  return ggl_partial_bytes(GGL_F32, n_chunks, H * C + H, 0);
 }
 
 
@@ -536,7 +539,9 @@ static int gat_fwd_impl(const ggl_segplan_t *plan, const int32_t *col, const flo
                         const typename TT<XT>::S *x, float slope, int64_t H, int64_t C, float p_drop,
                         int64_t *rng_state, typename TT<OT>::S *out, float *rowmax, float *rowden, void *stream) {
   WalkPlan p;
-  if (int rc = walk_plan(plan, "plan", "plan is NULL", "H, C and chunk must be positive", p)) return rc;
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", "H, C and chunk must be positive",
+                         gat_fwd_partial_bytes(hub_chunks(plan), H, C), p))
+    return rc;
   GGL_REQUIRE(H > 0 && C > 0, GGL_EINVAL, "H, C and chunk must be positive");
   const int64_t N = p.N;
   if (N == 0) return GGL_OK;
@@ -586,7 +591,9 @@ static int gat_bwd_dst_impl(const ggl_segplan_t *plan, const int32_t *col, const
                             int64_t H, int64_t C, float p_drop, const int64_t *rng_used, float *alpha, float *de,
                             float *ger, void *stream) {
   WalkPlan p;
-  if (int rc = walk_plan(plan, "plan", "plan is NULL", "H, C and chunk must be positive", p)) return rc;
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", "H, C and chunk must be positive",
+                         ggl_gat_bwd_dst_partial_bytes(hub_chunks(plan), H), p))
+    return rc;
   GGL_REQUIRE(H > 0 && C > 0, GGL_EINVAL, "H, C and chunk must be positive");
   const int64_t N = p.N, E = p.E;
   if (N == 0) return GGL_OK;
@@ -694,15 +701,16 @@ extern "C" int ggl_gat_fused_bwd_dst(const ggl_segplan_t *plan, const int32_t *c
                                         alpha, de, ger, stream);
 }
 
-// Source-major half of the backward (gat_bwd_src_kernel above).  planT->partial must hold
-// ggl_partial_bytes(GGL_F32, n_chunks, H*C + H, 0) bytes when the transposed plan has long rows.
+// Source-major half of the backward (gat_bwd_src_kernel above).  planT->partial: ggl_gat_bwd_src_partial_bytes.
 // GEL = false: gx alone (ggl_edge_softmax_agg_bwd_src); de and gel are NULL.
 template <typename GT, typename OT, bool GEL = true>
 static int gat_bwd_src_impl(const ggl_segplan_t *planT, const int32_t *colT, const int32_t *posT, const float *alpha,
                             const float *de, const typename TT<GT>::S *g, int64_t H, int64_t C,
                             typename TT<OT>::S *gx, float *gel, void *stream) {
   WalkPlan p;
-  if (int rc = walk_plan(planT, "transposed plan", "planT is NULL", "H, C and chunk must be positive", p)) return rc;
+  if (int rc = walk_plan(planT, "transposed plan", "planT is NULL", "H, C and chunk must be positive",
+                         ggl_gat_bwd_src_partial_bytes(hub_chunks(planT), H, C), p))
+    return rc;
   GGL_REQUIRE(H > 0 && C > 0, GGL_EINVAL, "H, C and chunk must be positive");
   const int64_t N = p.N;
   if (N == 0) return GGL_OK;
@@ -1213,7 +1221,9 @@ static inline int ssm_logs(const ggl_segplan_t *plan, int64_t K) {
 static inline int ssm_setup(const ggl_segplan_t *plan, int64_t K, SsmDims &d, double *&part, const int32_t *&order,
                             int &logs) {
   WalkPlan p;
-  if (int rc = walk_plan(plan, "plan", "plan is NULL", "chunk must be positive", p)) return rc;
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", "chunk must be positive",
+                         ggl_segment_softmax_partial_bytes(hub_chunks(plan), K), p))
+    return rc;
   GGL_REQUIRE(ggl_segment_softmax_supported(K), GGL_EINVAL, "segment_softmax: K = %lld is outside [1, 64]", (long long)K);
   d.N = p.N; d.K = K;
   d.n_long = p.n_long;

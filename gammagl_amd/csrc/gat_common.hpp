@@ -403,6 +403,11 @@ struct GatFwd {
   float *pacc, *pm, *pd;  // hub-chunk partials: [n_chunks, K] sums, [n_chunks, H] maxima and denominators
   int64_t grid;
 };
+// what gat_fwd_setup carves (and ggl_gat_fast_fwd, which takes the same three panels), + 64 bytes: ggl_gat_partial_bytes
+static inline size_t gat_fwd_partial_bytes(int64_t n_chunks, int64_t H, int64_t C) {
+  if (n_chunks <= 0 || H <= 0 || C <= 0) return 0;
+  return (size_t)n_chunks * (size_t)(H * C + 2 * H) * sizeof(float) + 64;
+}
 static inline int gat_fwd_setup(const WalkPlan &p, float slope, int64_t H, int64_t C, float p_drop,
                                 const int64_t *rng_state, GatFwd &f) {
   GatDims &d = f.d;

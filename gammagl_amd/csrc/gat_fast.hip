@@ -913,7 +913,7 @@ extern "C" int ggl_gat_fast_fwd(const ggl_segplan_t *plan, const int32_t *col, c
                                 int64_t C, float p_drop, int64_t *rng_state, float *out, float *rowmax,
                                 float *rowden, void *stream) {
   WalkPlan p;
-  if (int rc = walk_plan(plan, "plan", "plan is NULL", kFastShape, p)) return rc;
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", kFastShape, gat_fwd_partial_bytes(hub_chunks(plan), H, C), p)) return rc;
   const int c4 = gat_fast_c4(H, C);
   GGL_REQUIRE(c4 > 0, GGL_EINVAL, "%s", kFastShape);
   const int64_t N = p.N;
@@ -948,8 +948,13 @@ extern "C" int ggl_gat_fast_fwd(const ggl_segplan_t *plan, const int32_t *col, c
   return GGL_OK;
 }
 
+// plan->partial of ggl_gat_fast_bwd: the destination walk's four double sums per chunk and head (bwd_dst_final4 merges them)
+extern "C" size_t ggl_gat_fast_bwd_dst_partial_bytes(int64_t n_chunks, int64_t H) {
+  return ggl_partial_bytes(GGL_F32, n_chunks, 8 * H, 0);
+}
+
 // Both walks of the backward.  stats: workspace of N_dst * H * 4 floats (16-byte aligned).  plan->partial:
-// >= n_chunks * H floats; planT->partial: ggl_partial_bytes(GGL_F32, n_chunksT, H*C + H, 0) bytes.
+// ggl_gat_fast_bwd_dst_partial_bytes; planT->partial: ggl_gat_bwd_src_partial_bytes (the general source walk's two panels).
 extern "C" int ggl_gat_fast_bwd(const ggl_segplan_t *plan, const int32_t *col, const ggl_segplan_t *planT,
                                 const int32_t *colT, const int32_t *posT, const float *el, const float *er,
                                 const float *x, const float *g, const float *out, const float *rowmax,
@@ -957,8 +962,11 @@ extern "C" int ggl_gat_fast_bwd(const ggl_segplan_t *plan, const int32_t *col, c
                                 const int64_t *rng_used, float *stats, float *gx, float *gel, float *ger,
                                 void *stream) {
   WalkPlan p, pT;
-  if (int rc = walk_plan(plan, "plan", "plan is NULL", kFastShape, p)) return rc;
-  if (int rc = walk_plan(planT, "transposed plan", "plan is NULL", kFastShape, pT)) return rc;
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", kFastShape, ggl_gat_fast_bwd_dst_partial_bytes(hub_chunks(plan), H), p))
+    return rc;
+  if (int rc = walk_plan(planT, "transposed plan", "plan is NULL", kFastShape,
+                         ggl_gat_bwd_src_partial_bytes(hub_chunks(planT), H, C), pT))
+    return rc;
   const int c4 = gat_fast_c4(H, C);
   GGL_REQUIRE(c4 > 0, GGL_EINVAL, "%s", kFastShape);
   const int64_t N = p.N, NT = pT.N, E = p.E;
@@ -1008,12 +1016,15 @@ extern "C" int ggl_gat_sh_supported(int64_t H, int64_t F, int64_t C) {
   return (H == 8 && F > 0 && F <= 64 && F % 4 == 0 && C > 0 && C <= 64) ? 1 : 0;
 }
 
-// floats of plan->partial the forward needs for a plan with n_chunks hub chunks (the backward needs 8 per chunk
-// on the forward plan and 8 * Cp + 8 per chunk of the transposed plan)
+// plan->partial of ggl_gat_sh_fwd: per chunk 8 * F sums, 8 denominators and 8 maxima (+ 64 bytes)
 extern "C" size_t ggl_gat_sh_partial_bytes(int64_t n_chunks, int64_t F) {
-  if (n_chunks <= 0) return 0;
+  if (n_chunks <= 0 || F <= 0) return 0;
   return (size_t)n_chunks * (size_t)(8 * F + 16) * sizeof(float) + 64;
 }
+// ... of ggl_gat_sh_bwd: the forward plan's four double sums per chunk and head (256 bytes per chunk; the documented rule is
+// the forward's at F = 8), the transposed plan's 8 * Cp sums and 8 gel terms per chunk
+extern "C" size_t ggl_gat_sh_bwd_dst_partial_bytes(int64_t n_chunks) { return ggl_gat_sh_partial_bytes(n_chunks, 8); }
+extern "C" size_t ggl_gat_sh_bwd_src_partial_bytes(int64_t n_chunks, int64_t Cp) { return ggl_gat_sh_partial_bytes(n_chunks, Cp); }
 
 static int sh_dims(ShDims &d, const WalkPlan &p, int64_t F, float slope, float p_drop, const int64_t *rng) {
   d.slope = slope; d.N = p.N; d.F = F; d.E = p.E;
@@ -1026,7 +1037,7 @@ extern "C" int ggl_gat_sh_fwd(const ggl_segplan_t *plan, const int32_t *col, con
                               const float *x, int64_t F, float slope, float p_drop, int64_t *rng_state,
                               float *rowmax, float *A, float *den, void *stream) {
   WalkPlan p;
-  if (int rc = walk_plan(plan, "plan", "plan is NULL", "plan is NULL", p)) return rc;
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", "plan is NULL", ggl_gat_sh_partial_bytes(hub_chunks(plan), F), p)) return rc;
   GGL_REQUIRE(ggl_gat_sh_supported(8, F, 1), GGL_EINVAL, "row width not supported by the shared-row GAT path");
   if (p.N == 0) return GGL_OK;
   GGL_REQUIRE(er && rowmax && A && den, GGL_EINVAL, "NULL pointer");
@@ -1114,8 +1125,10 @@ extern "C" int ggl_gat_sh_bwd(const ggl_segplan_t *plan, const int32_t *col, con
                               float slope, float p_drop, const int64_t *rng_used, float *ger, float *T, float *gel,
                               void *stream) {
   WalkPlan p, pT;   // (this entry names both plans "plan" in its errors)
-  if (int rc = walk_plan(plan, "plan", "plan is NULL", "plan is NULL", p)) return rc;
-  if (int rc = walk_plan(planT, "plan", "plan is NULL", "plan is NULL", pT)) return rc;
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", "plan is NULL", ggl_gat_sh_bwd_dst_partial_bytes(hub_chunks(plan)), p))
+    return rc;
+  if (int rc = walk_plan(planT, "plan", "plan is NULL", "plan is NULL", ggl_gat_sh_bwd_src_partial_bytes(hub_chunks(planT), Cp), pT))
+    return rc;
   GGL_REQUIRE(ggl_gat_sh_supported(8, F, Cp) && Cp % 4 == 0, GGL_EINVAL, "shape not supported by the shared-row GAT path");
   GGL_REQUIRE(pT.E == p.E, GGL_EINVAL, "forward and transposed plans disagree");
   GGL_REQUIRE(p_drop == 0.0f || posT || p.E == 0, GGL_EINVAL, "attention dropout needs posT");
@@ -1124,7 +1137,6 @@ extern "C" int ggl_gat_sh_bwd(const ggl_segplan_t *plan, const int32_t *col, con
     GGL_REQUIRE(ger && G && stats && el && x, GGL_EINVAL, "NULL pointer");
     ShDims d{};
     if (int rc = sh_dims(d, p, F, slope, p_drop, rng_used)) return rc;
-    // (forward plan's partial: FOUR doubles per chunk and head since round 6 = 256 bytes per chunk: ggl_gat_sh_partial_bytes(n_chunks, 8))
     float *pger = p.partial;
     GGL_REQUIRE(aligned16(x) && aligned16(G) && aligned16(stats) && aligned16(col) && aligned16(pger), GGL_EINVAL, "shared-row GAT path needs 16-byte aligned buffers");
     const int64_t grid = ceil_div((d.n_chunks + d.N) * 16, (int64_t)kBlock);

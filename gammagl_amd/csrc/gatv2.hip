@@ -92,7 +92,9 @@ extern "C" int ggl_gatv2_fwd(const ggl_segplan_t *plan, const int32_t *col, cons
                              const float *att, float slope, int64_t H, int64_t C, float p_drop, int64_t *rng_state,
                              float *out, float *rowmax, float *rowden, float *z_out, void *stream) {
   WalkPlan p;
-  if (int rc = walk_plan(plan, "plan", "plan is NULL", "H, C and chunk must be positive", p)) return rc;
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", "H, C and chunk must be positive",
+                         gat_fwd_partial_bytes(hub_chunks(plan), H, C), p))
+    return rc;
   GGL_REQUIRE(H > 0 && C > 0, GGL_EINVAL, "H, C and chunk must be positive");
   GGL_REQUIRE(ggl_gatv2_supported(H, C), GGL_EINVAL, "ggl_gatv2_fwd: C must be 8, 16, 32 or 64 (ggl_gatv2_supported)");
   const int64_t N = p.N;

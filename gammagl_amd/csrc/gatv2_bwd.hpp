@@ -145,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void gatv2_logit_bwd_final_kernel(
 // plan->partial of ggl_gatv2_logit_bwd for a plan with long rows: [n_chunks, H * C] sums of the derivative terms and, with
 // att_rows, as many of the activation terms
 extern "C" size_t ggl_gatv2_logit_bwd_partial_bytes(int64_t n_chunks, int64_t H, int64_t C, int with_att_rows) {
-  if (n_chunks <= 0) return 0;
+  if (n_chunks <= 0 || H <= 0 || C <= 0) return 0;
   return (size_t)n_chunks * (size_t)(H * C) * (with_att_rows ? 2 : 1) * sizeof(float) + 64;
 }
 
@@ -154,7 +154,9 @@ extern "C" int ggl_gatv2_logit_bwd(const ggl_segplan_t *plan, const int32_t *col
                                    const float *add, float *g_self, float *att_rows, void *stream) {
   using namespace ggl;
   WalkPlan p;
-  if (int rc = walk_plan(plan, "plan", "plan is NULL", "H, C and chunk must be positive", p)) return rc;
+  if (int rc = walk_plan(plan, "plan", "plan is NULL", "H, C and chunk must be positive",
+                         ggl_gatv2_logit_bwd_partial_bytes(hub_chunks(plan), H, C, att_rows != nullptr), p))
+    return rc;
   GGL_REQUIRE(H > 0 && C > 0, GGL_EINVAL, "H, C and chunk must be positive");
   const int64_t N = p.N;
   if (N == 0) return GGL_OK;

@@ -10,8 +10,14 @@ namespace ggl { void set_error(const char *fmt, ...); }
 
 extern "C" int ggl_gat_fast_supported(int64_t, int64_t) { return 0; }
 extern "C" int ggl_gat_sh_supported(int64_t, int64_t, int64_t) { return 0; }
+// (the sizers answer as the GPU build's do: a caller may size a buffer before it asks whether the path exists)
 extern "C" size_t ggl_gat_sh_partial_bytes(int64_t n_chunks, int64_t F) {
-  return n_chunks <= 0 ? 0 : (size_t)n_chunks * (size_t)(8 * F + 16) * sizeof(float) + 64;
+  return (n_chunks <= 0 || F <= 0) ? 0 : (size_t)n_chunks * (size_t)(8 * F + 16) * sizeof(float) + 64;
+}
+extern "C" size_t ggl_gat_sh_bwd_dst_partial_bytes(int64_t n_chunks) { return ggl_gat_sh_partial_bytes(n_chunks, 8); }
+extern "C" size_t ggl_gat_sh_bwd_src_partial_bytes(int64_t n_chunks, int64_t Cp) { return ggl_gat_sh_partial_bytes(n_chunks, Cp); }
+extern "C" size_t ggl_gat_fast_bwd_dst_partial_bytes(int64_t n_chunks, int64_t H) {
+  return ggl_partial_bytes(GGL_F32, n_chunks, 8 * H, 0);
 }
 static int no_gpu() {
   ggl::set_error("this GAT path exists in the GPU build only");

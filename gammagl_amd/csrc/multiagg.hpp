@@ -487,6 +487,7 @@ extern "C" int ggl_segment_multi_fwd(const float *x, const ggl_segplan_t *plan, 
   MultiPart part{};
   if (d.n_long > 0) {
     GGL_REQUIRE(plan->partial != nullptr, GGL_EINVAL, "segment_multi_fwd: plan has long rows but plan->partial is NULL");
+    if (int rc = partial_fits(plan, "plan", ggl_segment_multi_partial_bytes(d.n_chunks, K, aggs, n_aggs))) return rc;
     float *w = static_cast<float *>(plan->partial);
     const int64_t panel = d.n_chunks * K;
     if (need.sum) { part.S = w; w += panel; }

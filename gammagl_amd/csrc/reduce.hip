@@ -1119,9 +1119,21 @@ static int launch_x16_cols(int xd, int od, const ReduceArgs &a0, hipStream_t str
       [&](const ReduceArgs &a) { return launch_x16<OP, MODE>(xd, od, a, stream); }, stream);
 }
 
+// plan->partial of every walk behind fill_plan: the [n_chunks, K] value panel (for the serial f32 hub walk: its first n_long
+// <= n_chunks rows), padded to 16 bytes, then for max the [n_chunks, K] int64 witnesses.  ggl_partial_bytes is the sum.
+static size_t value_panel_bytes(int dtype, int64_t n_chunks, int64_t K) {
+  return ((size_t)n_chunks * (size_t)K * dtype_size(dtype) + 15) & ~(size_t)15;
+}
+static size_t reduce_partial_bytes(int dtype, int64_t n_chunks, int64_t K, bool with_arg) {
+  if (n_chunks <= 0 || K <= 0) return 0;
+  return value_panel_bytes(dtype, n_chunks, K) + (with_arg ? (size_t)n_chunks * (size_t)K * 8 : 0);
+}
+
 static int fill_plan(ReduceArgs &a, const ggl_segplan_t *plan, int dtype, int64_t K, bool with_arg) {
   WalkPlan p;   // (the checks; launch_idx has its own row-order rule and the kernels take the plan's raw counts)
-  if (int rc = walk_plan(plan, "plan", "plan / rowptr is NULL", "plan->chunk must be > 0", p)) return rc;
+  if (int rc = walk_plan(plan, "plan", "plan / rowptr is NULL", "plan->chunk must be > 0",
+                         reduce_partial_bytes(dtype, hub_chunks(plan), K, with_arg), p))
+    return rc;
   GGL_REQUIRE(K >= 0 && plan->N >= 0 && plan->E >= 0, GGL_EINVAL, "negative size");
   a.rowptr = plan->rowptr;
   a.perm = plan->perm;
@@ -1139,11 +1151,8 @@ static int fill_plan(ReduceArgs &a, const ggl_segplan_t *plan, int dtype, int64_
   a.n_chunks = plan->n_chunks;
   a.partial = plan->partial;
   a.partial_arg = nullptr;
-  if (plan->n_long > 0 && with_arg) {
-    size_t off = (size_t)plan->n_chunks * (size_t)K * dtype_size(dtype);
-    off = (off + 15) & ~(size_t)15;
-    a.partial_arg = reinterpret_cast<int64_t *>(static_cast<char *>(plan->partial) + off);
-  }
+  if (plan->n_long > 0 && with_arg)
+    a.partial_arg = reinterpret_cast<int64_t *>(static_cast<char *>(plan->partial) + value_panel_bytes(dtype, plan->n_chunks, K));
   return GGL_OK;
 }
 
@@ -1154,11 +1163,7 @@ static int fill_plan(ReduceArgs &a, const ggl_segplan_t *plan, int dtype, int64_
 using namespace ggl;
 
 extern "C" size_t ggl_partial_bytes(int dtype, int64_t n_chunks, int64_t K, int with_arg) {
-  if (n_chunks <= 0 || K <= 0) return 0;
-  size_t b = (size_t)n_chunks * (size_t)K * dtype_size(dtype);
-  b = (b + 15) & ~(size_t)15;
-  if (with_arg) b += (size_t)n_chunks * (size_t)K * 8;
-  return b;
+  return reduce_partial_bytes(dtype, n_chunks, K, with_arg != 0);
 }
 
 // ---- segment ops ---------------------------------------------------------------------------------

@@ -61,7 +61,8 @@ using torch::autograd::variable_list;
   X(ggl_spmm_max) X(ggl_spmm_mean_bwd) X(ggl_spmm_max_bwd) X(ggl_bspmm_sum) X(ggl_bspmm_grad_w)                      \
   X(ggl_bspmm_grad_w_sorted_scratch_bytes) X(ggl_bspmm_grad_w_sorted)                                                \
   X(ggl_spmm_grad_w_scratch_bytes) X(ggl_spmm_grad_w)                                                                \
-  X(ggl_gat_partial_bytes) X(ggl_gat_fused_fwd) X(ggl_gat_fused_bwd_dst) X(ggl_gat_fused_bwd_src)                      \
+  X(ggl_gat_partial_bytes) X(ggl_gat_bwd_dst_partial_bytes) X(ggl_gat_bwd_src_partial_bytes)                          \
+  X(ggl_gat_fast_bwd_dst_partial_bytes) X(ggl_gat_fused_fwd) X(ggl_gat_fused_bwd_dst) X(ggl_gat_fused_bwd_src)         \
   X(ggl_gat_fused_fwd_x16) X(ggl_gat_fused_bwd_dst_x16) X(ggl_gat_fused_bwd_src_x16)                                    \
   X(ggl_edge_softmax_agg_fwd) X(ggl_edge_softmax_agg_bwd_dst) X(ggl_edge_softmax_agg_bwd_src)                          \
   X(ggl_dot_attn_supported) X(ggl_policy_dot_attn_fused) X(ggl_dot_attn_fwd)                                           \
@@ -203,6 +204,7 @@ struct SegPlan {
     s.n_chunks = lng ? n_chunks : 0;
     s.chunk = unsplit ? (int64_t(1) << 62) : chunk;
     s.partial = partial.defined() ? partial.data_ptr() : nullptr;
+    s.partial_bytes = partial.defined() ? partial.nbytes() : 0;
     s.N = N;
     s.E = E;
     if (N > 1) {
@@ -465,12 +467,27 @@ static Tensor hub_partial(const SegPlan &p, const Tensor &like, Bytes nbytes) {
   if (p.n_long == 0) return Tensor();
   return at::empty({static_cast<int64_t>(nbytes(p.n_chunks)) + 16}, like.options().dtype(at::kByte));
 }
+// One sizer per export: a call site names the walk it launches; the library owns the layout and checks plan->partial_bytes.
+// ... of the segment reductions, gspmm / bspmm and their backward walks, partials of like's dtype
 static Tensor partial_for(const Api &a, const SegPlan &p, const Tensor &like, int64_t K, bool with_arg) {
   return hub_partial(p, like, [&](int64_t n) { return a.ggl_partial_bytes(dtype_code(like), n, K, with_arg ? 1 : 0); });
+}
+// ... of the _x16 aggregates: f32 partials under 16-bit rows
+static Tensor partial_f32_for(const Api &a, const SegPlan &p, const Tensor &like, int64_t K) {
+  return hub_partial(p, like, [&](int64_t n) { return a.ggl_partial_bytes(GGL_F32, n, K, 0); });
 }
 // ... of the GAT forward walks: gat_fused, edge_softmax_aggregate and the ops that form their logits inside that walk
 static Tensor gat_fwd_partial(const Api &a, const SegPlan &p, int64_t H, int64_t C, const Tensor &like) {
   return hub_partial(p, like, [&](int64_t n) { return a.ggl_gat_partial_bytes(n, H, C); });
+}
+// ... of their destination walks (fast: ggl_gat_fast_bwd's forward plan) and of the source walk
+static Tensor gat_bwd_dst_partial(const Api &a, const SegPlan &p, int64_t H, bool fast, const Tensor &like) {
+  return hub_partial(p, like, [&](int64_t n) {
+    return fast ? a.ggl_gat_fast_bwd_dst_partial_bytes(n, H) : a.ggl_gat_bwd_dst_partial_bytes(n, H);
+  });
+}
+static Tensor gat_bwd_src_partial(const Api &a, const SegPlan &p, int64_t H, int64_t C, const Tensor &like) {
+  return hub_partial(p, like, [&](int64_t n) { return a.ggl_gat_bwd_src_partial_bytes(n, H, C); });
 }
 
 static std::vector<int64_t> out_shape(const Tensor &x, int64_t N) {
@@ -547,11 +564,7 @@ static Tensor spmm_fwd16(SpOp op, GraphPlan &gp, const SegPlan &p, const Tensor 
   for (int64_t d = 1; d < x.dim(); ++d) K *= x.size(d);
   Tensor out = at::empty(out_shape(x, n_out), out_f32 ? x.options().dtype(at::kFloat) : x.options());
   void *st = stream_of(dev);
-  Tensor part;
-  if (p.n_long > 0) {
-    const size_t nb = a.ggl_partial_bytes(GGL_F32, p.n_chunks, K, 0);
-    part = at::empty({static_cast<int64_t>(nb) + 16}, x.options().dtype(at::kByte));
-  }
+  Tensor part = partial_f32_for(a, p, x, K);
   ggl_segplan_t cs = p.c(part);
   Tensor keep;
   auto [wp, by_pos] = weights_for(a, gp, p, w, keep);
@@ -699,9 +712,7 @@ static std::tuple<Tensor, Tensor> segment_max_kernel(const Tensor &x, const Tens
 // Edge softmax (utils/softmax.py:29-35) as one op each way: ggl_segment_softmax_fwd / _bwd over the id vector's cached plan.
 // y and gx come back in the caller's element order; the backward needs y and grad only.
 static Tensor softmax_partial(const Api &a, const SegPlan &p, const Tensor &like, int64_t K) {
-  if (p.n_long == 0) return Tensor();
-  const size_t nb = a.ggl_segment_softmax_partial_bytes(p.n_chunks, K);
-  return at::empty({static_cast<int64_t>(nb) + 16}, like.options().dtype(at::kByte));
+  return hub_partial(p, like, [&](int64_t n) { return a.ggl_segment_softmax_partial_bytes(n, K); });
 }
 static int64_t softmax_width(const Api &a, const Tensor &x, const SegPlan &p) {
   TORCH_CHECK_INDEX(x.size(0) == p.E, "fisrt dimension of x and index should be same");
@@ -1056,7 +1067,7 @@ static std::tuple<Tensor, Tensor, Tensor> gat_backward(GraphPlan &gp, const Tens
   Tensor ger = at::empty_like(er), gx = at::empty({gp.N_src, H, C}, x.options()), gel = at::empty({gp.N_src, H}, el.options());
   // (the fast destination walk keeps four DOUBLE sums per chunk and head: 8 H floats' worth per chunk, include/ggl_mpops.h;
   //  el is f32: the partials are, whatever x is stored as)
-  Tensor part_f = partial_for(a, fw, el, fast ? 8 * H : H, false), part_t = partial_for(a, bw, el, H * C + H, false);
+  Tensor part_f = gat_bwd_dst_partial(a, fw, H, fast, el), part_t = gat_bwd_src_partial(a, bw, H, C, el);
   ggl_segplan_t cs = fw.c(part_f), csT = bw.c(part_t);
   const int64_t *ru = used_ptr(p, rng_used);
   if (fast) {
@@ -1180,7 +1191,7 @@ static std::pair<Tensor, Tensor> esa_backward(GraphPlan &gp, const Tensor &idx, 
   void *st = stream_of(dev);
   Tensor alpha = need_gv ? at::empty({std::max<int64_t>(gp.E, 1), H}, v.options()) : Tensor();
   Tensor gz = need_gz ? at::empty_like(z) : Tensor(), gv;
-  Tensor part_f = partial_for(a, *gp.fwd, z, H, false);
+  Tensor part_f = gat_bwd_dst_partial(a, *gp.fwd, H, false, z);
   ggl_segplan_t cs = gp.fwd->c(part_f);
   check(a, a.ggl_edge_softmax_agg_bwd_dst(&cs, gp.col.data_ptr<int32_t>(), z.data_ptr<float>(), v.data_ptr<float>(),
                                           g.data_ptr<float>(), oc.data_ptr<float>(), rmax.data_ptr<float>(),
@@ -1191,7 +1202,7 @@ static std::pair<Tensor, Tensor> esa_backward(GraphPlan &gp, const Tensor &idx, 
     gp.need_bwd(idx);
     gp.need_posT(idx);
     gv = at::empty({gp.N_src, H, C}, v.options());
-    Tensor part_t = partial_for(a, *gp.bwd, z, H * C + H, false);
+    Tensor part_t = gat_bwd_src_partial(a, *gp.bwd, H, C, z);
     ggl_segplan_t csT = gp.bwd->c(part_t);
     check(a, a.ggl_edge_softmax_agg_bwd_src(&csT, gp.colT.data_ptr<int32_t>(), gp.posT.data_ptr<int32_t>(),
                                             alpha.data_ptr<float>(), g.data_ptr<float>(), H, C, gv.data_ptr<float>(), st));
@@ -1634,13 +1645,7 @@ static std::tuple<Tensor, Tensor> spmm_epi_forward_kernel(const Tensor &index, c
   }
   const SegPlan &p_ = *s.gp->fwd;
   Tensor y = at::empty({s.gp->N_dst, K}, s.x.options());
-  Tensor part;
-  if (x16) {   // f32 partials, as spmm_fwd16's
-    if (p_.n_long > 0)
-      part = at::empty({static_cast<int64_t>(a.ggl_partial_bytes(GGL_F32, p_.n_chunks, K, 0)) + 16}, s.x.options().dtype(at::kByte));
-  } else {
-    part = partial_for(a, p_, s.x, K, false);
-  }
+  Tensor part = x16 ? partial_f32_for(a, p_, s.x, K) : partial_for(a, p_, s.x, K, false);
   ggl_segplan_t cs = p_.c(part);
   Tensor keep;
   auto [wp, by_pos] = weights_for(a, *s.gp, p_, s.w, keep);
@@ -2571,10 +2576,7 @@ static std::tuple<Tensor, Tensor, Tensor, Tensor> multi_forward_kernel(const Ten
   Tensor mean = want_mean && m.sq ? at::empty({N, K}, o) : at::empty({0}, o);
   Tensor amin = m.mn ? at::empty({N, K}, o.dtype(at::kInt)) : at::empty({0}, o.dtype(at::kInt));
   Tensor amax = m.mx ? at::empty({N, K}, o.dtype(at::kInt)) : at::empty({0}, o.dtype(at::kInt));
-  Tensor part;
-  if (plan->n_long > 0)
-    part = at::empty({static_cast<int64_t>(a.ggl_segment_multi_partial_bytes(plan->n_chunks, K, m.codes.data(), (int)A)) + 16},
-                     o.dtype(at::kByte));
+  Tensor part = hub_partial(*plan, x, [&](int64_t n) { return a.ggl_segment_multi_partial_bytes(n, K, m.codes.data(), (int)A); });
   ggl_segplan_t cs = plan->c(part);
   check(a, a.ggl_segment_multi_fwd(ptr_or_null<float>(x), &cs, K, C, m.codes.data(), (int)A, empty_zero ? 1 : 0,
                                    ptr_or_null<float>(out), ptr_or_null<float>(mean), ptr_or_null<int32_t>(amin),

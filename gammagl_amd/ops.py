@@ -358,7 +358,10 @@ class Engine:
             return None
         return torch.empty(nbytes(plan.n_chunks) + 16, dtype=torch.uint8, device=dev)
 
+    # One sizer per export: a call site names the walk it launches, the library owns that walk's layout and checks the size
+    # SegPlan.c_struct declares (plan->partial_bytes).
     def _partial(self, plan, dtype, K, with_arg, dev):
+        """segment reductions, gspmm / bspmm and their backward walks (ggl_partial_bytes)"""
         return self._hub_partial(
             plan, lambda n: self.lib.ggl_partial_bytes(_DTYPE_CODE[dtype], n, K, 1 if with_arg else 0), dev)
 
@@ -366,10 +369,26 @@ class Engine:
         return self._hub_partial(plan, lambda n: self.lib.ggl_segment_softmax_partial_bytes(n, K), dev)
 
     def _gat_partial(self, plan, H, C, dev):
+        """the forward walks: ggl_gat_fused_fwd[_x16], ggl_gat_fast_fwd, ggl_edge_softmax_agg_fwd, ggl_dot_attn_fwd, ggl_gatv2_fwd"""
         return self._hub_partial(plan, lambda n: self.lib.ggl_gat_partial_bytes(n, H, C), dev)
 
-    def _gat_sh_partial(self, plan, width, dev):
-        return self._hub_partial(plan, lambda n: self.lib.ggl_gat_sh_partial_bytes(n, width), dev)
+    def _gat_bwd_dst_partial(self, plan, H, dev):
+        return self._hub_partial(plan, lambda n: self.lib.ggl_gat_bwd_dst_partial_bytes(n, H), dev)
+
+    def _gat_bwd_src_partial(self, plan, H, C, dev):
+        return self._hub_partial(plan, lambda n: self.lib.ggl_gat_bwd_src_partial_bytes(n, H, C), dev)
+
+    def _gat_fast_bwd_dst_partial(self, plan, H, dev):
+        return self._hub_partial(plan, lambda n: self.lib.ggl_gat_fast_bwd_dst_partial_bytes(n, H), dev)
+
+    def _gat_sh_partial(self, plan, F, dev):
+        return self._hub_partial(plan, lambda n: self.lib.ggl_gat_sh_partial_bytes(n, F), dev)
+
+    def _gat_sh_bwd_dst_partial(self, plan, dev):
+        return self._hub_partial(plan, self.lib.ggl_gat_sh_bwd_dst_partial_bytes, dev)
+
+    def _gat_sh_bwd_src_partial(self, plan, Cp, dev):
+        return self._hub_partial(plan, lambda n: self.lib.ggl_gat_sh_bwd_src_partial_bytes(n, Cp), dev)
 
     def _softmax_width(self, x, plan):
         E = int(x.shape[0])

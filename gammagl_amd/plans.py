@@ -62,7 +62,8 @@ class SegPlan:
             chunk_ptr=(self.chunk_ptr.data_ptr() if n_long else None),
             n_long=n_long, n_chunks=(self.n_chunks if n_long else 0),
             chunk=((1 << 62) if unsplit else self.chunk),
-            partial=(partial.data_ptr() if partial is not None else None), N=self.N, E=self.E,
+            partial=(partial.data_ptr() if partial is not None else None),
+            partial_bytes=(partial.numel() * partial.element_size() if partial is not None else 0), N=self.N, E=self.E,
             row_order=(self.row_order.data_ptr() if self.row_order is not None else None),
             # > 0: XCD runs (a node order with locality); -1: no runs, but the long rows LEAD the id range (a degree-sorted
             # order): the hub walk of a column-blocked aggregate then runs once over the full width (include/ggl_mpops.h)

@@ -77,7 +77,13 @@ extern "C" {
  *   (GATv2's additive attention: the logit formed inside the aggregate's walk, and its backward walk).  Purely additive again. */
 /* still 11: + ggl_segment_multi_fwd, ggl_segment_multi_bwd, ggl_segment_multi_partial_bytes and the codes GGL_AGG_* (sum, mean,
  *   min, max, var and std of the same message rows in one walk).  Purely additive again. */
-#define GGL_ABI_VERSION 11
+/* 12: ggl_segplan_t GREW by `partial_bytes` (appended, as 7 did): the bytes the caller owns at `partial`.  Every entry point
+ *   that carves plan->partial checks it against the *_partial_bytes export that sizes its walk and answers GGL_EWORKSPACE to a
+ *   buffer that is too small; a caller built against <= 11 hands over a shorter struct and is refused by the version check.
+ *   + ggl_gat_bwd_dst_partial_bytes, ggl_gat_bwd_src_partial_bytes, ggl_gat_fast_bwd_dst_partial_bytes,
+ *   ggl_gat_sh_bwd_dst_partial_bytes, ggl_gat_sh_bwd_src_partial_bytes (every walk has a sizer of its own; each returns what
+ *   the header documented for it before). */
+#define GGL_ABI_VERSION 12
 
 /* dtype codes (AT_DISPATCH_ALL_TYPES_AND2(Half, BFloat16), segment_sum_cpu.cpp:32-33) */
 enum {
@@ -118,7 +124,7 @@ typedef struct ggl_segplan {
   int64_t n_long;
   int64_t n_chunks;         /* chunk_ptr[n_long] */
   int64_t chunk;            /* elements per chunk == long-row threshold (> 0) */
-  void *partial;            /* workspace: ggl_partial_bytes(...) bytes, or NULL when n_long == 0 */
+  void *partial;            /* workspace: the entry point's *_partial_bytes(...) bytes, or NULL when n_long == 0 */
   int64_t N;                /* number of segments (output rows) */
   int64_t E;                /* number of elements (edges) */
   const int32_t *row_order; /* [N] rows sorted by length (longest first) or NULL: the order in which
@@ -136,6 +142,8 @@ typedef struct ggl_segplan {
                                exceeds the option `exact_long_max` (2^21 elements; a star graph's centre) keeps the
                                chunked walk — within rounding of the reference instead of its bits — rather than wait
                                for one add chain (ABI 7). */
+  size_t partial_bytes;     /* bytes the caller owns at `partial` (ABI 12); ignored when n_long == 0.  An entry point that
+                               needs more answers GGL_EWORKSPACE and launches nothing. */
 } ggl_segplan_t;
 
 /* bytes of workspace ggl_plan_build needs */
@@ -196,7 +204,10 @@ int ggl_plan_rows_bwd_rowptr(const int64_t *rowptrT, const int32_t *colT, int64_
 int ggl_plan_rows_bwd_fill(const int32_t *colT, const float *w, const int32_t *wperm, int64_t E, const int32_t *rank,
                            const int32_t *pos, int32_t *colT_r, float *w_r, void *stream);
 
-/* bytes of `partial` for n_chunks chunks of K features of dtype (value + int64 arg for max) */
+/* plan->partial of the segment reductions and of gspmm / bspmm and their backward walks, for a plan with n_chunks hub chunks:
+ * K features of dtype per chunk (value + int64 arg for max; K = H * C for bspmm; GGL_F32 for the _x16 entry points, whose
+ * partials are f32).  Every entry point named below checks plan->partial_bytes against the export that sizes its walk, called
+ * with the plan's n_chunks and its own arguments, and answers GGL_EWORKSPACE when the buffer is smaller. */
 size_t ggl_partial_bytes(int dtype, int64_t n_chunks, int64_t K, int with_arg);
 
 /* p[0..n) = v */
@@ -323,7 +334,7 @@ int ggl_spmm_max_bwd(const ggl_segplan_t *planT, const int32_t *colT, const floa
  * bit for bit, under the conditions under which F itself is the serial sum (host build: always; GPU: hub rows through the
  * exact walk, i.e. E < 2^31 and max_len <= option exact_long_max; chunked otherwise, with F32 partials like F's).  Any other
  * dtype pair returns GGL_EDTYPE.  x_ld / out_ld: row strides in elements (0 = K).  plan->partial holds F32 partials:
- * ggl_partial_bytes(GGL_F32, n_chunks, K, 0).  ggl_spmm_mean_bwd_x16 is ggl_spmm_mean_bwd on a 16-bit g (divide and
+ * ggl_partial_bytes(GGL_F32, n_chunks, K, 0), checked.  ggl_spmm_mean_bwd_x16 is ggl_spmm_mean_bwd on a 16-bit g (divide and
  * multiply in f32); the backward of the sum is ggl_spmm_sum_x16 on the transposed plan.
  * Wide rows are cut into column blocks of option "col_block16" columns: ggl_spmm_col_blocks_x16 = launches per call. */
 int ggl_spmm_sum_x16(const ggl_segplan_t *plan, const int32_t *col, const float *w, int w_by_pos, int x_dtype,
@@ -510,7 +521,7 @@ int ggl_segment_epi(const float *x, const ggl_segplan_t *plan, int64_t K, int me
  *       lrelu'(.) -> alpha[E,H], de[E,H] (forward sorted positions); ger[N,H] = row sums of de
  *   ggl_gat_fused_bwd_src: ONE walk of the transposed plan: gx[j,h,:] = sum_p alpha * g[dst,h,:] and
  *       gel[j,h] = sum_p de, reading alpha/de through posT (transposed position -> forward position);
- *       planT->partial = ggl_partial_bytes(GGL_F32, n_chunks, H*C + H, 0) bytes when it has long rows
+ *       planT->partial: ggl_gat_bwd_src_partial_bytes(n_chunks, H, C) bytes, checked
  * ---------------------------------------------------------------------------------------------- */
 /* p_drop > 0: attention dropout (gat_conv.py:104 `dropout(segment_softmax(.))`, GATConvFuse's last
  * argument): edge (sorted position p, head h) is kept when the 32-bit word mix(seed, offset, p * H + h)
@@ -522,12 +533,18 @@ int ggl_gat_fused_fwd(const ggl_segplan_t *plan, const int32_t *col, const float
                       const float *er, const float *x, float slope, int64_t H, int64_t C,
                       float p_drop, int64_t *rng_state, float *out, float *rowmax, float *rowden,
                       void *stream);
-/* plan->partial for ggl_gat_fused_fwd when the plan has long rows (chunk-local softmax partials) */
+/* plan->partial of the forward walks when the plan has long rows (chunk-local softmax partials; checked): ggl_gat_fused_fwd[_x16],
+ * ggl_edge_softmax_agg_fwd, ggl_dot_attn_fwd, ggl_gatv2_fwd, ggl_gat_fast_fwd */
 size_t ggl_gat_partial_bytes(int64_t n_chunks, int64_t H, int64_t C);
+/* ... of the destination walks ggl_gat_fused_bwd_dst[_x16] and ggl_edge_softmax_agg_bwd_dst (the ger partials of the hub chunks,
+ * n_chunks * H floats), and of the source walks ggl_gat_fused_bwd_src[_x16], ggl_edge_softmax_agg_bwd_src and ggl_gat_fast_bwd's
+ * planT (the gx and gel partials, n_chunks * (H*C + H) floats) */
+size_t ggl_gat_bwd_dst_partial_bytes(int64_t n_chunks, int64_t H);
+size_t ggl_gat_bwd_src_partial_bytes(int64_t n_chunks, int64_t H, int64_t C);
 /* alpha / de: two [E,H] f32 arrays, or ONE interleaved [E,H,2] buffer passed as (base, base + 1) — then
  * an edge's alpha and de share a 64-byte line for the source-side walk (same convention in
- * ggl_gat_fused_bwd_src).  rowidx, dot_ws: unused since ABI 3 (may be NULL); plan->partial = ggl_partial_bytes(GGL_F32, n_chunks,
- * H, 0) bytes when the plan has long rows (ger partials of the hub chunks) */
+ * ggl_gat_fused_bwd_src).  rowidx, dot_ws: unused since ABI 3 (may be NULL); plan->partial: ggl_gat_bwd_dst_partial_bytes(n_chunks,
+ * H) bytes, checked */
 int ggl_gat_fused_bwd_dst(const ggl_segplan_t *plan, const int32_t *col, const int32_t *rowidx,
                           const float *el, const float *er, const float *x, const float *g,
                           const float *out, const float *rowmax, const float *rowden, float slope,
@@ -540,8 +557,7 @@ int ggl_gat_fused_bwd_src(const ggl_segplan_t *planT, const int32_t *colT, const
  * purely additive).  x [N_src,H,C] is GGL_BF16 or GGL_F16 (x_dtype); out is x_dtype or GGL_F32 (a last layer's logits); g has
  * out's dtype (g_dtype == out_dtype) and `out` in the backward is the tensor the forward RETURNED (rounded, if it was rounded:
  * no f32 copy is kept); gx has x's dtype.  Any other dtype pair returns GGL_EDTYPE.  el, er, rowmax, rowden, alpha, de, gel, ger
- * and every hub-chunk partial stay f32: plan->partial is sized as for the f32 entry points (ggl_gat_partial_bytes,
- * ggl_partial_bytes(GGL_F32, ...)).  x, g and out are widened at the load (exact), every operation in between is the f32 one
+ * and every hub-chunk partial stay f32: plan->partial is sized, and checked, as for the f32 entry points.  x, g and out are widened at the load (exact), every operation in between is the f32 one
  * of ggl_gat_fused_fwd / _bwd_dst / _bwd_src (call them F) in F's order, and out / gx are rounded ONCE, at the store:
  *   forward   out(x16)          == F.out(x16 as f32) rounded to x_dtype      bit for bit
  *             out(x16, GGL_F32) == F.out(x16 as f32)                         bit for bit
@@ -573,13 +589,13 @@ int ggl_gat_fused_bwd_src_x16(const ggl_segplan_t *planT, const int32_t *colT, c
  * whose logits are all -inf gives zeros like an empty row (no -inf beats the -FLT_MAX start, every exp(-inf + FLT_MAX) is 0),
  * one that holds a NaN keeps the maximum of the others (NaN loses the strict <) and gets NaN sums: what the GAT kernels
  * give for the same s.
- *   ggl_edge_softmax_agg_fwd     : plan->partial = ggl_gat_partial_bytes(n_chunks, H, C) bytes when the plan has long rows.
+ *   ggl_edge_softmax_agg_fwd     : plan->partial: ggl_gat_partial_bytes(n_chunks, H, C) bytes, checked.
  *   ggl_edge_softmax_agg_bwd_dst : alpha[E,H] by SORTED POSITION (what _bwd_src reads through posT), gz[E,H] = alpha (keep/(1-p)
  *       <g_i, x_j> - <g_i, out_i>) by the CALLER's edge number, written by the walk itself.  alpha or gz may be NULL: that
- *       store is skipped (x resp. z needs no gradient).  plan->partial: as ggl_gat_fused_bwd_dst, ggl_partial_bytes(GGL_F32,
- *       n_chunks, H, 0) bytes when the plan has long rows (the shared preamble asks for it; there is no row sum to keep in it).
- *   ggl_edge_softmax_agg_bwd_src : gx[j,h,:] = sum_q alpha[posT[q],h] * g[colT[q],h,:]; planT->partial =
- *       ggl_partial_bytes(GGL_F32, n_chunks, H*C + H, 0) bytes when it has long rows (as ggl_gat_fused_bwd_src). */
+ *       store is skipped (x resp. z needs no gradient).  plan->partial: ggl_gat_bwd_dst_partial_bytes(n_chunks, H) bytes, checked
+ *       (the shared preamble asks for it; there is no row sum to keep in it).
+ *   ggl_edge_softmax_agg_bwd_src : gx[j,h,:] = sum_q alpha[posT[q],h] * g[colT[q],h,:]; planT->partial:
+ *       ggl_gat_bwd_src_partial_bytes(n_chunks, H, C) bytes, checked. */
 int ggl_edge_softmax_agg_fwd(const ggl_segplan_t *plan, const int32_t *col, const float *z, const float *x, int64_t H,
                              int64_t C, float p_drop, int64_t *rng_state, float *out, float *rowmax, float *rowden,
                              void *stream);
@@ -600,8 +616,8 @@ int ggl_edge_softmax_agg_bwd_src(const ggl_segplan_t *planT, const int32_t *colT
  * [E,H] array is touched.  z itself is within gamma_{C+1} |scale| sum_c |q_c k_c| of the exact value (gamma_n = n u / (1 - n u),
  * u = 2^-24); it does not have the bits of ggl_bspmm_grad_w*, which adds the C products serially.  The backward is composed
  * by the caller from ggl_edge_softmax_agg_bwd_dst / _bwd_src on z_out and two ggl_bspmm_sum walks with gz * scale.
- * q, k, v, out and plan->partial must be 16-byte aligned; plan->partial = ggl_gat_partial_bytes(n_chunks, H, C) bytes when the
- * plan has long rows; rng_state as ggl_gat_fused_fwd.
+ * q, k, v, out and plan->partial must be 16-byte aligned; plan->partial: ggl_gat_partial_bytes(n_chunks, H, C) bytes, checked;
+ * rng_state as ggl_gat_fused_fwd.
  *   ggl_dot_attn_supported(H, C)           : 1 for C = 8, 16, 32, 64 and any H > 0.
  *   ggl_policy_dot_attn_fused(H, C, E, N_in): 1 where the fused forward is the default over edge dot + ggl_edge_softmax_agg_fwd
  *       (profiles/dot_attention.txt); never 1 for an unsupported shape. */
@@ -620,8 +636,8 @@ int ggl_dot_attn_fwd(const ggl_segplan_t *plan, const int32_t *col, const float 
  * logits are stored, [E,H] in the CALLER's edge order (through plan->perm), and out / rowmax / rowden are
  * ggl_edge_softmax_agg_fwd(plan, col, z_out, xl, ...)'s bit for bit; with z_out == NULL out has the same bits and no [E,H]
  * array is touched.  z is within gamma_{C+2} sum_c |att_c| |lrelu(xl_c + xr_c)| of the exact value (gamma_n = n u / (1 - n u),
- * u = 2^-24).  xl, xr, att, out and plan->partial must be 16-byte aligned; plan->partial = ggl_gat_partial_bytes(n_chunks, H, C)
- * bytes when the plan has long rows; rng_state as ggl_gat_fused_fwd.
+ * u = 2^-24).  xl, xr, att, out and plan->partial must be 16-byte aligned; plan->partial: ggl_gat_partial_bytes(n_chunks, H, C)
+ * bytes, checked; rng_state as ggl_gat_fused_fwd.
  *   ggl_gatv2_supported(H, C)            : 1 for C = 8, 16, 32, 64 and any H > 0.
  *   ggl_policy_gatv2_fused(H, C, E, N_in): 1 where the fused forward is the default over logits composed in front of
  *       ggl_edge_softmax_agg_fwd (profiles/gatv2_attention.txt); never 1 for an unsupported shape.
@@ -633,8 +649,8 @@ int ggl_dot_attn_fwd(const ggl_segplan_t *plan, const int32_t *col, const float 
  *   accA = __fadd_rn(accA, __fmul_rn(w, s > 0 ? s : __fmul_rn(s, slope)))              (only with att_rows != NULL)
  *   g_self[r,h,c] = add ? __fadd_rn(add[r,h,c], __fmul_rn(att[h,c], accD)) : __fmul_rn(att[h,c], accD);  att_rows[r,h,c] = accA
  * Rows longer than plan->chunk are walked in pieces of chunk positions, each summed from 0.0f, and merged in ascending chunk
- * order from 0.0f before the att multiply and the add; plan->partial = ggl_gatv2_logit_bwd_partial_bytes(n_chunks, H, C,
- * att_rows != NULL) bytes when the plan has long rows.  Forward plan (col, self = xr, other = xl, att_rows = R): g_xr, and
+ * order from 0.0f before the att multiply and the add; plan->partial: ggl_gatv2_logit_bwd_partial_bytes(n_chunks, H, C,
+ * att_rows != NULL) bytes, checked.  Forward plan (col, self = xr, other = xl, att_rows = R): g_xr, and
  * g_att = column sums of R.  Transposed plan (colT, perm = the caller's edge number of every position, self = xl,
  * other = xr, add = gv): the whole g_xl. */
 int ggl_gatv2_supported(int64_t H, int64_t C);
@@ -662,8 +678,8 @@ int ggl_gatv2_logit_bwd(const ggl_segplan_t *plan, const int32_t *col, const flo
  * (optional; the element index in the caller's order) are written when their pointer is given.
  * Rows longer than plan->chunk are cut into pieces of chunk positions, each reduced from the start values into a partial
  * (S, Q, mn, mx, amin, amax: only the panels the aggs need, [n_chunks, K] each, in that order); the partials are merged in
- * ascending piece order, sums from 0.0f, min / max with the strict rule.  plan->partial =
- * ggl_segment_multi_partial_bytes(n_chunks, K, aggs, n_aggs) bytes when the plan has long rows.
+ * ascending piece order, sums from 0.0f, min / max with the strict rule.  plan->partial:
+ * ggl_segment_multi_partial_bytes(n_chunks, K, aggs, n_aggs) bytes, checked (GGL_EWORKSPACE).
  * Backward: g [N, A * K] in out's layout; gx [E, K], every element written.  Per (row, column), n' = max(n, 1),
  * nf = (float)min(n', 2^24), s0 = sqrtf(1e-5f):
  *   gv = g_var (0.0f without var);  with std: t = std > s0 ? __fdiv_rn(g_std, __fmul_rn(2.0f, std)) : 0.0f,
@@ -692,12 +708,12 @@ int ggl_segment_multi_bwd(const float *g, const float *x_or_null, const float *o
  * parity bar of the GAT op, not bit-identical to the kernels above).
  *   ggl_gat_fast_fwd : as ggl_gat_fused_fwd; N_src = rows of x (selects 32-bit offsets when the panel is < 4 GiB)
  *   ggl_gat_fast_bwd : destination walk (stats[N,H,4] = {er, m, 1/(den + 1e-16), <g_i, out_i>}, ger) then
- *                      source walk (gx, gel).  stats: workspace of N * H * 4 floats; plan->partial >=
- *                      n_chunks * H * 4 DOUBLES, 8-byte aligned (ABI 8: the destination walk keeps four double sums per
- *                      row and head, see gat_fast.hip; = ggl_partial_bytes(GGL_F32, n_chunks, 8 * H, 0));
- *                      planT->partial = ggl_partial_bytes(GGL_F32, n_chunksT, H*C + H, 0);
+ *                      source walk (gx, gel).  stats: workspace of N * H * 4 floats; plan->partial:
+ *                      ggl_gat_fast_bwd_dst_partial_bytes(n_chunks, H) bytes, 8-byte aligned (four double sums per chunk and
+ *                      head since ABI 8); planT->partial: ggl_gat_bwd_src_partial_bytes(n_chunksT, H, C); both checked;
  *                      posT is only read with p_drop > 0 (the keep bit lives at the forward position). */
 int ggl_gat_fast_supported(int64_t H, int64_t C);
+size_t ggl_gat_fast_bwd_dst_partial_bytes(int64_t n_chunks, int64_t H);
 int ggl_gat_fast_fwd(const ggl_segplan_t *plan, const int32_t *col, const float *el, const float *er,
                      const float *x, int64_t N_src, float slope, int64_t H, int64_t C, float p_drop,
                      int64_t *rng_state, float *out, float *rowmax, float *rowden, void *stream);
@@ -712,15 +728,17 @@ int ggl_gat_fast_bwd(const ggl_segplan_t *plan, const int32_t *col, const ggl_se
  * backward the source walk gathers the C-float output gradient g_i (dL/dA_ih = g_i W_h^T / H).  H = 8, F and the
  * padded class width Cp <= 64 (multiples of 4): ggl_gat_sh_supported.  GPU build only (DPP row broadcasts and a
  * 16-lane reduce-scatter); parity bar as for the fused GAT op (1e-5 / 1e-4 relative).
- *   ggl_gat_sh_fwd : rowmax[N,8], A[N,8,F] = sum_j alpha_ijh x_j, den[N,8]; plan->partial =
- *                    ggl_gat_sh_partial_bytes(n_chunks, F) when the plan has long rows
+ *   ggl_gat_sh_fwd : rowmax[N,8], A[N,8,F] = sum_j alpha_ijh x_j, den[N,8]; plan->partial:
+ *                    ggl_gat_sh_partial_bytes(n_chunks, F) bytes, checked
  *   ggl_gat_sh_bwd : ger[N,8] (destination walk: G[N,8,F] = dL/dA and stats[N,8,4] = {er, m, 1/(den+1e-16),
  *                    <G_ih, A_ih>} per row, x gathered) and T[N_src,8,Cp] = sum_i alpha_ijh gy_i, gel[N_src,8]
- *                    (source walk: z[N_src,8,Cp] = the rows' own x_j W_h, gy[N,Cp] gathered); partial buffers:
- *                    plan->partial >= n_chunks * 8 * 4 DOUBLES (ABI 9: the destination walk keeps four row sums in double; ggl_gat_sh_partial_bytes(
- *                    n_chunks, 8) is enough), planT->partial = ggl_gat_sh_partial_bytes(n_chunksT, Cp) */
+ *                    (source walk: z[N_src,8,Cp] = the rows' own x_j W_h, gy[N,Cp] gathered); plan->partial:
+ *                    ggl_gat_sh_bwd_dst_partial_bytes(n_chunks) bytes (four double row sums per chunk and head since ABI 9),
+ *                    planT->partial: ggl_gat_sh_bwd_src_partial_bytes(n_chunksT, Cp) bytes; both checked */
 int ggl_gat_sh_supported(int64_t H, int64_t F, int64_t C);
 size_t ggl_gat_sh_partial_bytes(int64_t n_chunks, int64_t F);
+size_t ggl_gat_sh_bwd_dst_partial_bytes(int64_t n_chunks);
+size_t ggl_gat_sh_bwd_src_partial_bytes(int64_t n_chunks, int64_t Cp);
 int ggl_gat_sh_fwd(const ggl_segplan_t *plan, const int32_t *col, const float *el, const float *er, const float *x,
                    int64_t F, float slope, float p_drop, int64_t *rng_state, float *rowmax, float *A, float *den,
                    void *stream);
@@ -747,7 +765,7 @@ int ggl_gat_sh_stats(const float *er, const float *rowmax, const float *den, con
  *        exact arithmetic.  Without it a row dominated by one logit loses its gradient to the cancellation in g - S.
  * No atomics, no host synchronisation, every element of y / gx written exactly once.  Rows longer than plan->chunk go
  * through the long-row table: chunk-local (m, D) — resp. (S, winner) — in plan->partial
- * (ggl_segment_softmax_partial_bytes(n_chunks, K) bytes, 8-byte aligned), merged in chunk order.  A plan presented
+ * (ggl_segment_softmax_partial_bytes(n_chunks, K) bytes, checked; 8-byte aligned), merged in chunk order.  A plan presented
  * WITHOUT its long-row table (n_long == 0) has every row walked in one piece.
  * ggl_segment_softmax_supported(K): 1 <= K <= 64 (one or more lanes per (row, column)); wider rows are the caller's to compose.
  * ---------------------------------------------------------------------------------------------- */

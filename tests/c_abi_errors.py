@@ -52,6 +52,11 @@ ENTRIES = {
     "ggl_gat_fused_bwd_dst_x16": "plan col el er x_dtype x out_dtype g out_dtype saved rowmax rowden slope H C p_drop rng alpha de "
                                  "ger stream",
     "ggl_gat_fused_bwd_src_x16": "plan col posT alpha de out_dtype g H C x_dtype out gel stream",
+    "ggl_edge_softmax_agg_fwd": "plan col z x H C p_drop rng out rowmax rowden stream",
+    "ggl_edge_softmax_agg_bwd_dst": "plan col z x g saved rowmax rowden H C p_drop rng alpha gz stream",
+    "ggl_edge_softmax_agg_bwd_src": "plan col posT alpha g H C out stream",
+    "ggl_gatv2_logit_bwd": "plan col other x gz att slope H C add out att_rows stream",
+    "ggl_segment_multi_fwd": "x plan K C aggs n_aggs empty_zero out none none argmax stream",
     "ggl_segment_softmax_fwd": "x plan K out stream",
     "ggl_segment_softmax_bwd": "x g plan K out stream",
     "ggl_bias_act_fwd": "x bias N K relu p_drop rng out stream",
@@ -63,6 +68,7 @@ CASES = {
     "null_plan": (("plan",), {"plan": "null"}),
     "chunk_0": (("plan",), {"plan": "chunk0"}),
     "long_rows_no_partial": (("plan",), {"plan": "long"}),
+    "partial_too_small": (("plan",), {"plan": "short"}),
     "p_drop_1": (("p_drop",), {"p_drop": 1.0}),
     "p_drop_no_rng": (("p_drop",), {"p_drop": 0.5, "rng": None}),
     "x_ld_below_K": (("x_ld",), {"x_ld": K - 1}),
@@ -95,9 +101,11 @@ def _plans(keep):
         p.max_len = int(np.diff(rowptr).max()) if n else 0
         return p
 
+    short = plan([0, 5, 6, 7, 8], N, E, chunk=2, long_rows=[0], chunk_ptr=[0, 3])
+    short.partial, short.partial_bytes = arr(np.zeros(1 << 12, np.int32), np.int32), 1     # room enough, one byte declared
     return {"ok": plan([0, 2, 4, 6, 8], N, E), "null": None, "chunk0": plan([0, 2, 4, 6, 8], N, E, chunk=0),
             "long": plan([0, 5, 6, 7, 8], N, E, chunk=2, long_rows=[0], chunk_ptr=[0, 3]),     # partial stays NULL
-            "empty": plan([0], 0, 0)}
+            "short": short, "empty": plan([0], 0, 0)}
 
 
 def table(lib):
@@ -106,7 +114,8 @@ def table(lib):
     plans = _plans(keep)
     scalars = {"dtype": F32, "x_dtype": BF16, "out_dtype": BF16, "K": K, "H": H, "C": C, "N": N, "slope": 0.2, "p_drop": 0.0,
                "relu": 1, "stream": None, "w": None, "bias": None, "add": None, "gbias": None, "rng": None, "none": None,
-               "workspace_bytes": 1 << 14}
+               "workspace_bytes": 1 << 14, "n_aggs": 2, "empty_zero": 0}
+    scalars["aggs"] = (ctypes.c_int * 2)(0, 3)                 # GGL_AGG_SUM, GGL_AGG_MAX
     lines = []
     for name, roles in ENTRIES.items():
         roles = roles.split()

@@ -135,6 +135,7 @@ static int run(int64_t N, int64_t E, int64_t chunk, bool sorted, int64_t H, int6
   // ---- forward
   const size_t pfb = ggl_gat_partial_bytes(f.c.n_chunks, H, C);
   f.c.partial = pfb ? std::malloc(pfb) : nullptr;
+  f.c.partial_bytes = pfb;
   float *out_f = block<float>(N * K), *rmax_f = block<float>(N * H), *rden_f = block<float>(N * H);
   float *out = block<float>(N * K), *rmax = block<float>(N * H), *rden = block<float>(N * H);
   CHECK(ggl_gat_fused_fwd(&f.c, col, el, er, x, slope, H, C, p_drop, p_drop > 0 ? rng_f : nullptr, out_f, rmax_f, rden_f,
@@ -148,6 +149,8 @@ static int run(int64_t N, int64_t E, int64_t chunk, bool sorted, int64_t H, int6
   const size_t pdb = ggl_partial_bytes(GGL_F32, f.c.n_chunks, H, 0), psb = ggl_partial_bytes(GGL_F32, t.c.n_chunks, K + H, 0);
   f.c.partial = pdb ? std::malloc(pdb) : nullptr;
   t.c.partial = psb ? std::malloc(psb) : nullptr;
+  f.c.partial_bytes = pdb;
+  t.c.partial_bytes = psb;
   float *alpha_f = block<float>(E * H), *de_f = block<float>(E * H), *ger_f = block<float>(N * H), *gel_f = block<float>(N * H);
   float *gx_f = block<float>(N * K);
   float *alpha = block<float>(E * H), *gz = block<float>(E * H), *gx = block<float>(N * K);

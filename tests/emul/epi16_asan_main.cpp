@@ -90,7 +90,8 @@ static int run_epi(int64_t N, int64_t E, int64_t chunk, int64_t K, int dtype, in
   void *partial = nullptr;
   if (!lr.empty()) {
     plan.long_rows = long_rows; plan.chunk_ptr = chunk_ptr;
-    partial = std::malloc(ggl_partial_bytes(GGL_F32, plan.n_chunks, K, 0));
+    plan.partial_bytes = ggl_partial_bytes(GGL_F32, plan.n_chunks, K, 0);
+    partial = std::malloc(plan.partial_bytes);
     plan.partial = partial;
   }
   const int64_t ld = K + pad;

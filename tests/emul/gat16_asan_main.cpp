@@ -153,6 +153,7 @@ static int run(int64_t N, int64_t E_want, int64_t chunk, int64_t H, int64_t C, i
   // ---- forward: F, then the 16-bit entry point
   const size_t pfb = ggl_gat_partial_bytes(f.c.n_chunks, H, C);
   f.c.partial = pfb ? std::malloc(pfb) : nullptr;
+  f.c.partial_bytes = pfb;
   float *out_f = block<float>(N * K), *rmax_f = block<float>(N * H), *rden_f = block<float>(N * H);
   CHECK(ggl_gat_fused_fwd(&f.c, col, el, er, xf, slope, H, C, p_drop, p_drop > 0 ? rng_f : nullptr, out_f, rmax_f, rden_f,
                           nullptr));
@@ -182,6 +183,8 @@ static int run(int64_t N, int64_t E_want, int64_t chunk, int64_t H, int64_t C, i
   const size_t pdb = ggl_partial_bytes(GGL_F32, f.c.n_chunks, H, 0), psb = ggl_partial_bytes(GGL_F32, t.c.n_chunks, K + H, 0);
   f.c.partial = pdb ? std::malloc(pdb) : nullptr;
   t.c.partial = psb ? std::malloc(psb) : nullptr;
+  f.c.partial_bytes = pdb;
+  t.c.partial_bytes = psb;
   float *ad_f = block<float>(E * H * 2), *ad = block<float>(E * H * 2);
   float *ger_f = block<float>(N * H), *ger = block<float>(N * H), *gel_f = block<float>(N * H), *gel = block<float>(N * H);
   float *gx_f = block<float>(N * K);

@@ -131,6 +131,7 @@ static int walk(Plan &p, const int32_t *col, const float *other, const float *se
   const size_t pb = ggl_gatv2_logit_bwd_partial_bytes(p.c.n_chunks, H, C, with_rows ? 1 : 0);
   EXPECT((pb > 0) == (p.c.n_long > 0));
   p.c.partial = pb ? std::malloc(pb) : nullptr;
+  p.c.partial_bytes = pb;
   float *g_self = block<float>(N * K), *rows = with_rows ? block<float>(N * K) : nullptr;
   float *w_self = block<float>(N * K), *w_rows = block<float>(N * K);
   CHECK(ggl_gatv2_logit_bwd(&p.c, col, other, self, gz, att, slope, H, C, add, g_self, rows, nullptr));

@@ -179,6 +179,7 @@ static int run_case(Plan &p, int64_t K, int64_t C, const std::vector<int> &aggs,
   const size_t pb = ggl_segment_multi_partial_bytes(p.c.n_chunks, K, aggs.data(), A);
   EXPECT((pb > 0) == (p.c.n_long > 0));
   p.c.partial = pb ? std::malloc(pb) : nullptr;
+  p.c.partial_bytes = pb;
   float *out = block<float>(N * A * K);                                  // exactly N * A * K floats
   float *mean = sq ? block<float>(N * K) : nullptr;
   int32_t *amin = mn ? block<int32_t>(N * K) : nullptr, *amax = mx ? block<int32_t>(N * K) : nullptr;   // exactly N * K int32

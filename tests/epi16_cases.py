@@ -543,10 +543,10 @@ def check_dispatcher(eng, dev):
 
 
 def check_c_abi(eng, dev):
-    """the additive entries refuse f32 rows, bf16 -> f16 and f64 with the _x16 family's code; ABI 11"""
+    """the additive entries refuse f32 rows, bf16 -> f16 and f64 with the _x16 family's code; ABI 12"""
     from gammagl_amd import _lib
 
-    assert _lib.ABI_VERSION == 11 and eng.lib.ggl_abi_version() == 11
+    assert _lib.ABI_VERSION == 12 and eng.lib.ggl_abi_version() == 12
     gen = torch.Generator(device=dev).manual_seed(4)
     ei = make_index("uniform", 40, 300, gen, dev)
     gp = eng.graph_plan(ei, 40)

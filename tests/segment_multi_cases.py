@@ -487,7 +487,7 @@ def check_c_abi(eng, dev):
     """the C entry points with exact-size buffers against the oracle; every refusal of the header with its message"""
     from gammagl_amd import _lib
 
-    assert _lib.ABI_VERSION == 11 and eng.lib.ggl_abi_version() == 11
+    assert _lib.ABI_VERSION == 12 and eng.lib.ggl_abi_version() == 12
     for name, n in (("ggl_segment_multi_partial_bytes", 4), ("ggl_segment_multi_fwd", 12), ("ggl_segment_multi_bwd", 13)):
         assert len(_lib.SIGNATURES[name][1]) == n
     full = (ctypes.c_int * 6)(0, 1, 2, 3, 4, 5)

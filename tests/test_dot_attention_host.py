@@ -121,7 +121,7 @@ def test_c_abi_surface(eng):
     "not supported" and fails the launch loudly"""
     from gammagl_amd import _lib
 
-    assert _lib.ABI_VERSION == 11 and eng.lib.ggl_abi_version() == 11
+    assert _lib.ABI_VERSION == 12 and eng.lib.ggl_abi_version() == 12
     for name, n in (("ggl_dot_attn_supported", 2), ("ggl_policy_dot_attn_fused", 4), ("ggl_dot_attn_fwd", 15)):
         assert len(_lib.SIGNATURES[name][1]) == n
     for H, C in dc.SHAPES:

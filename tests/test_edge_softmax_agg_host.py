@@ -137,7 +137,7 @@ def test_c_abi_surface(eng):
 
     from gammagl_amd import _lib
 
-    assert _lib.ABI_VERSION == 11 and eng.lib.ggl_abi_version() == 11
+    assert _lib.ABI_VERSION == 12 and eng.lib.ggl_abi_version() == 12
     for name, n in (("ggl_edge_softmax_agg_fwd", 12), ("ggl_edge_softmax_agg_bwd_dst", 15), ("ggl_edge_softmax_agg_bwd_src", 9)):
         assert len(_lib.SIGNATURES[name][1]) == n
     g = torch.Generator().manual_seed(4)

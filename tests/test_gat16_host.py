@@ -138,7 +138,7 @@ def test_c_abi_surface(eng):
     """the additive entry points: every wrong dtype pair is GGL_EDTYPE, and the ABI number stays"""
     from gammagl_amd import _lib
 
-    assert _lib.ABI_VERSION == 11 and eng.lib.ggl_abi_version() == 11
+    assert _lib.ABI_VERSION == 12 and eng.lib.ggl_abi_version() == 12
     g = torch.Generator().manual_seed(4)
     ei = sc.make_index("uniform", 40, 300, g, DEV)
     gp = eng.graph_plan(ei, 40)

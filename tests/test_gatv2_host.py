@@ -145,7 +145,7 @@ def test_c_abi_surface(eng):
     "not supported", fails the fused launch loudly and has the backward walk"""
     from gammagl_amd import _lib
 
-    assert _lib.ABI_VERSION == 11 and eng.lib.ggl_abi_version() == 11
+    assert _lib.ABI_VERSION == 12 and eng.lib.ggl_abi_version() == 12
     for name, n in (("ggl_gatv2_supported", 2), ("ggl_policy_gatv2_fused", 4), ("ggl_gatv2_fwd", 15),
                     ("ggl_gatv2_logit_bwd_partial_bytes", 4), ("ggl_gatv2_logit_bwd", 13)):
         assert len(_lib.SIGNATURES[name][1]) == n

@@ -105,7 +105,7 @@ def test_dispatcher_contracts(routes):
 def test_abi_10_surface(eng):
     from gammagl_amd import _lib
 
-    assert _lib.ABI_VERSION == 11 and eng.lib.ggl_abi_version() == 11     # (the entry points came with 10; 11 removed forms elsewhere)
+    assert _lib.ABI_VERSION == 12 and eng.lib.ggl_abi_version() == 12     # (the entry points came with 10; 11 removed forms elsewhere)
     assert eng.lib.ggl_segment_softmax_supported(1) == 1 and eng.lib.ggl_segment_softmax_supported(64) == 1
     assert eng.lib.ggl_segment_softmax_supported(65) == 0 and eng.lib.ggl_segment_softmax_supported(0) == 0
     assert eng.lib.ggl_segment_softmax_partial_bytes(0, 8) == 0

@@ -112,7 +112,7 @@ def test_c_abi_surface(eng):
     """the additive entry points: dtype pairs, the block-width option, and the ABI number"""
     from gammagl_amd import _lib
 
-    assert _lib.ABI_VERSION == 11 and eng.lib.ggl_abi_version() == 11     # (they came under 10; 11 removed forms elsewhere)
+    assert _lib.ABI_VERSION == 12 and eng.lib.ggl_abi_version() == 12     # (they came under 10; 11 removed forms elsewhere)
     g = torch.Generator().manual_seed(4)
     ei = sc.make_index("uniform", 40, 300, g, DEV)
     gp = eng.graph_plan(ei, 40)
