@@ -5,87 +5,7 @@
 // perm, no long rows).  Shapes 1 x 1, 3 x 5 (element form), 2 x 12 and 8 x 8 (16-byte loads), with and without attention
 // dropout.  Built and run by tests/test_edge_softmax_agg_sanitized.py; exits 0 when, on z = LeakyReLU(el[src] + er[dst]),
 // out / rowmax / rowden / alpha / gx have the bits of ggl_gat_fused_* and gz is their de in the caller's edge order.
-#include <algorithm>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <numeric>
-#include <vector>
-
-#include "ggl_mpops.h"
-
-#define CHECK(call)                                                                \
-  do {                                                                             \
-    const int rc_ = (call);                                                        \
-    if (rc_ != GGL_OK) {                                                           \
-      std::fprintf(stderr, "%s -> %d: %s\n", #call, rc_, ggl_last_error());        \
-      return 1;                                                                    \
-    }                                                                              \
-  } while (0)
-#define EXPECT(cond)                                                               \
-  do {                                                                             \
-    if (!(cond)) {                                                                 \
-      std::fprintf(stderr, "line %d: %s is false\n", __LINE__, #cond);             \
-      return 1;                                                                    \
-    }                                                                              \
-  } while (0)
-
-static uint32_t rnd_state = 2463534242u;
-static uint32_t rnd() { return rnd_state = rnd_state * 1664525u + 1013904223u; }
-static float rndf() { return (float)((int)(rnd() >> 8) % 4001 - 2000) / 1024.0f; }
-
-template <typename T>
-static T *block(size_t n) { return static_cast<T *>(std::malloc((n ? n : 1) * sizeof(T))); }
-
-static bool same(const float *a, const float *b, size_t n) { return std::memcmp(a, b, n * sizeof(float)) == 0; }
-
-struct Plan {
-  ggl_segplan_t c{};
-  int64_t *rowptr = nullptr, *chunk_ptr = nullptr;
-  int32_t *long_rows = nullptr, *perm = nullptr;
-  void release() { std::free(rowptr); std::free(chunk_ptr); std::free(long_rows); std::free(perm); }
-};
-
-// rowptr / perm / long-row table of `ids` (stable sort; perm stays NULL when the ids arrive sorted)
-static void make_plan(Plan &p, const std::vector<int32_t> &ids, int64_t N, int64_t chunk) {
-  const int64_t E = (int64_t)ids.size();
-  std::vector<int32_t> order(E);
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return ids[a] < ids[b]; });
-  p.rowptr = block<int64_t>(N + 1);
-  std::fill(p.rowptr, p.rowptr + N + 1, 0);
-  for (int32_t d : ids) ++p.rowptr[d + 1];
-  for (int64_t r = 0; r < N; ++r) p.rowptr[r + 1] += p.rowptr[r];
-  if (!std::is_sorted(ids.begin(), ids.end())) {
-    p.perm = block<int32_t>(E);
-    std::memcpy(p.perm, order.data(), E * sizeof(int32_t));
-  }
-  std::vector<int32_t> lr;
-  std::vector<int64_t> cp{0};
-  for (int64_t r = 0; r < N; ++r) {
-    const int64_t len = p.rowptr[r + 1] - p.rowptr[r];
-    if (len > chunk) {
-      lr.push_back((int32_t)r);
-      cp.push_back(cp.back() + (len + chunk - 1) / chunk);
-    }
-  }
-  p.c.rowptr = p.rowptr;
-  p.c.perm = p.perm;
-  p.c.N = N;
-  p.c.E = E;
-  p.c.chunk = chunk;
-  p.c.n_long = (int64_t)lr.size();
-  p.c.n_chunks = cp.back();
-  if (!lr.empty()) {
-    p.long_rows = block<int32_t>(lr.size());
-    p.chunk_ptr = block<int64_t>(cp.size());
-    std::memcpy(p.long_rows, lr.data(), lr.size() * sizeof(int32_t));
-    std::memcpy(p.chunk_ptr, cp.data(), cp.size() * sizeof(int64_t));
-    p.c.long_rows = p.long_rows;
-    p.c.chunk_ptr = p.chunk_ptr;
-  }
-}
+#include "asan_common.hpp"
 
 static int run(int64_t N, int64_t E, int64_t chunk, bool sorted, int64_t H, int64_t C, float p_drop) {
   const int64_t K = H * C;
@@ -133,9 +53,7 @@ static int run(int64_t N, int64_t E, int64_t chunk, bool sorted, int64_t H, int6
   rng[1] = rng_f[1] = rng_used[1] = 3;
 
   // ---- forward
-  const size_t pfb = ggl_gat_partial_bytes(f.c.n_chunks, H, C);
-  f.c.partial = pfb ? std::malloc(pfb) : nullptr;
-  f.c.partial_bytes = pfb;
+  f.set_partial(ggl_gat_partial_bytes(f.c.n_chunks, H, C));
   float *out_f = block<float>(N * K), *rmax_f = block<float>(N * H), *rden_f = block<float>(N * H);
   float *out = block<float>(N * K), *rmax = block<float>(N * H), *rden = block<float>(N * H);
   CHECK(ggl_gat_fused_fwd(&f.c, col, el, er, x, slope, H, C, p_drop, p_drop > 0 ? rng_f : nullptr, out_f, rmax_f, rden_f,
@@ -143,14 +61,10 @@ static int run(int64_t N, int64_t E, int64_t chunk, bool sorted, int64_t H, int6
   CHECK(ggl_edge_softmax_agg_fwd(&f.c, col, z, x, H, C, p_drop, p_drop > 0 ? rng : nullptr, out, rmax, rden, nullptr));
   if (p_drop > 0) EXPECT(rng[1] == 4 && rng_f[1] == 4);
   EXPECT(same(out, out_f, N * K) && same(rmax, rmax_f, N * H) && same(rden, rden_f, N * H));
-  std::free(f.c.partial);
 
   // ---- backward
-  const size_t pdb = ggl_partial_bytes(GGL_F32, f.c.n_chunks, H, 0), psb = ggl_partial_bytes(GGL_F32, t.c.n_chunks, K + H, 0);
-  f.c.partial = pdb ? std::malloc(pdb) : nullptr;
-  t.c.partial = psb ? std::malloc(psb) : nullptr;
-  f.c.partial_bytes = pdb;
-  t.c.partial_bytes = psb;
+  f.set_partial(ggl_partial_bytes(GGL_F32, f.c.n_chunks, H, 0));
+  t.set_partial(ggl_partial_bytes(GGL_F32, t.c.n_chunks, K + H, 0));
   float *alpha_f = block<float>(E * H), *de_f = block<float>(E * H), *ger_f = block<float>(N * H), *gel_f = block<float>(N * H);
   float *gx_f = block<float>(N * K);
   float *alpha = block<float>(E * H), *gz = block<float>(E * H), *gx = block<float>(N * K);
@@ -166,7 +80,7 @@ static int run(int64_t N, int64_t E, int64_t chunk, bool sorted, int64_t H, int6
     for (int64_t h = 0; h < H; ++h) {
       const float ds = gz[e * H + h];
       const float want = positive[e * H + h] ? ds : ds * slope;
-      EXPECT(std::memcmp(&want, &de_f[p * H + h], 4) == 0);
+      EXPECT(same(&want, &de_f[p * H + h], 1));
     }
   }
   // either gradient alone: the other buffer is not touched (NULL)
@@ -174,8 +88,6 @@ static int run(int64_t N, int64_t E, int64_t chunk, bool sorted, int64_t H, int6
   CHECK(ggl_edge_softmax_agg_bwd_dst(&f.c, col, z, x, g, out, rmax, rden, H, C, p_drop, ru, nullptr, gz2, nullptr));
   CHECK(ggl_edge_softmax_agg_bwd_dst(&f.c, col, z, x, g, out, rmax, rden, H, C, p_drop, ru, alpha2, nullptr, nullptr));
   EXPECT(same(gz2, gz, E * H) && same(alpha2, alpha, E * H));
-  std::free(f.c.partial);
-  std::free(t.c.partial);
   for (void *b : {(void *)col, (void *)colT, (void *)posT, (void *)el, (void *)er, (void *)x, (void *)g, (void *)z, (void *)rng,
                   (void *)rng_f, (void *)rng_used, (void *)out_f, (void *)rmax_f, (void *)rden_f, (void *)out, (void *)rmax,
                   (void *)rden, (void *)alpha_f, (void *)de_f, (void *)ger_f, (void *)gel_f, (void *)gx_f, (void *)alpha,

@@ -5,60 +5,7 @@
 // with long rows and once with x / out / add rows ld > K elements apart (the last row is K long: no slack behind it).
 // Built and run by tests/test_epi16_sanitized.py; exits 0 when every result has the bits of the f32 entry points on the
 // widened rows, rounded once.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "ggl_mpops.h"
-
-#define CHECK(call)                                                                \
-  do {                                                                             \
-    const int rc_ = (call);                                                        \
-    if (rc_ != GGL_OK) {                                                           \
-      std::fprintf(stderr, "%s -> %d: %s\n", #call, rc_, ggl_last_error());        \
-      return 1;                                                                    \
-    }                                                                              \
-  } while (0)
-#define EXPECT(cond)                                                               \
-  do {                                                                             \
-    if (!(cond)) {                                                                 \
-      std::fprintf(stderr, "line %d: %s is false\n", __LINE__, #cond);             \
-      return 1;                                                                    \
-    }                                                                              \
-  } while (0)
-
-static uint32_t rnd_state = 2463534242u;
-static uint32_t rnd() { return rnd_state = rnd_state * 1664525u + 1013904223u; }
-static float rndf() { return (float)((int)(rnd() >> 8) % 4001 - 2000) / 1024.0f; }
-
-template <typename T>
-static T *block(size_t n) { return static_cast<T *>(std::malloc((n ? n : 1) * sizeof(T))); }
-
-// 16-bit <-> f32 as the library documents them: exact widening, round-to-nearest-even narrowing
-static float widen(int dtype, uint16_t b) {
-  if (dtype == GGL_BF16) {
-    const uint32_t u = (uint32_t)b << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-  }
-  _Float16 h;
-  std::memcpy(&h, &b, 2);
-  return (float)h;
-}
-static uint16_t narrow(int dtype, float f) {
-  if (dtype == GGL_BF16) {
-    uint32_t x;
-    std::memcpy(&x, &f, 4);
-    return (uint16_t)((x + (((x >> 16) & 1u) + 0x7fffu)) >> 16);   // (no NaNs in this program)
-  }
-  const _Float16 h = (_Float16)f;
-  uint16_t b;
-  std::memcpy(&b, &h, 2);
-  return b;
-}
+#include "asan_common.hpp"
 
 // rows `ld` elements apart, the last one K long: (N - 1) * ld + K elements exactly
 static size_t panel(int64_t N, int64_t K, int64_t ld) { return N > 0 ? (size_t)((N - 1) * ld + K) : 0; }
@@ -68,32 +15,18 @@ static int run_epi(int64_t N, int64_t E, int64_t chunk, int64_t K, int dtype, in
   // a random CSR with a heavy destination (row N - 1), already in destination order (perm = NULL)
   std::vector<std::vector<int32_t>> in(N);
   for (int64_t e = 0; e < E; ++e) in[(e % 3 == 0) ? N - 1 : (int64_t)(rnd() % N)].push_back((int32_t)(rnd() % N));
-  int64_t *rowptr = block<int64_t>(N + 1);
+  Plan plan;
+  plan.rowptr = block<int64_t>(N + 1);
   int32_t *col = block<int32_t>(E);
   float *w = block<float>(E);
   int64_t p = 0;
-  std::vector<int32_t> lr;
-  std::vector<int64_t> cp{0};
   for (int64_t d = 0; d < N; ++d) {
-    rowptr[d] = p;
+    plan.rowptr[d] = p;
     for (int32_t s : in[d]) { col[p] = s; w[p] = (float)(rnd() % 1000) / 1000.0f; ++p; }
-    if ((int64_t)in[d].size() > chunk) { lr.push_back((int32_t)d); cp.push_back(cp.back() + ((int64_t)in[d].size() + chunk - 1) / chunk); }
   }
-  rowptr[N] = p;
-  ggl_segplan_t plan{};
-  plan.rowptr = rowptr; plan.N = N; plan.E = E; plan.chunk = chunk;
-  plan.n_long = (int64_t)lr.size(); plan.n_chunks = cp.back();
-  int32_t *long_rows = block<int32_t>(lr.size());
-  int64_t *chunk_ptr = block<int64_t>(cp.size());
-  std::memcpy(long_rows, lr.data(), lr.size() * sizeof(int32_t));
-  std::memcpy(chunk_ptr, cp.data(), cp.size() * sizeof(int64_t));
-  void *partial = nullptr;
-  if (!lr.empty()) {
-    plan.long_rows = long_rows; plan.chunk_ptr = chunk_ptr;
-    plan.partial_bytes = ggl_partial_bytes(GGL_F32, plan.n_chunks, K, 0);
-    partial = std::malloc(plan.partial_bytes);
-    plan.partial = partial;
-  }
+  plan.rowptr[N] = p;
+  finish_plan(plan, N, E, chunk);
+  plan.set_partial(ggl_partial_bytes(GGL_F32, plan.c.n_chunks, K, 0));
   const int64_t ld = K + pad;
   const size_t n_el = panel(N, K, ld);
   uint16_t *x16 = block<uint16_t>(n_el), *add16 = has_add ? block<uint16_t>(n_el) : nullptr;
@@ -107,22 +40,22 @@ static int run_epi(int64_t N, int64_t E, int64_t chunk, int64_t K, int dtype, in
   uint16_t *got16 = block<uint16_t>(n_el);
   int64_t *rng = block<int64_t>(2);
   rng[0] = 99; rng[1] = 5;
-  CHECK(ggl_spmm_epi_ex(&plan, col, w, 1, x32, ld, K, want, ld, 0, mean, add32, has_add ? ld : 0, bias, 1, p_drop,
+  CHECK(ggl_spmm_epi_ex(&plan.c, col, w, 1, x32, ld, K, want, ld, 0, mean, add32, has_add ? ld : 0, bias, 1, p_drop,
                         p_drop > 0 ? rng : nullptr, 0, 0, 1, nullptr));
   const int64_t moved = rng[1];
   EXPECT(moved == (p_drop > 0 ? 6 : 5));
   rng[1] = 5;
   void *out = out_f32 ? (void *)got32 : (void *)got16;
-  CHECK(ggl_spmm_epi_x16(&plan, col, w, 1, dtype, x16, ld, K, out_f32 ? GGL_F32 : dtype, out, ld, mean, add16, has_add ? ld : 0,
+  CHECK(ggl_spmm_epi_x16(&plan.c, col, w, 1, dtype, x16, ld, K, out_f32 ? GGL_F32 : dtype, out, ld, mean, add16, has_add ? ld : 0,
                          bias, 1, p_drop, p_drop > 0 ? rng : nullptr, 0, 0, 1, nullptr));
   EXPECT(rng[1] == moved);
   for (int64_t r = 0; r < N; ++r)
     for (int64_t k = 0; k < K; ++k) {
       const size_t i = (size_t)(r * ld + k);
-      if (out_f32) EXPECT(std::memcmp(&got32[i], &want[i], 4) == 0);
+      if (out_f32) EXPECT(same(&got32[i], &want[i], 1));
       else EXPECT(got16[i] == narrow(dtype, want[i]));
     }
-  std::free(rowptr); std::free(col); std::free(w); std::free(long_rows); std::free(chunk_ptr); std::free(partial);
+  plan.release(); std::free(col); std::free(w);
   std::free(x16); std::free(add16); std::free(x32); std::free(add32); std::free(bias); std::free(want); std::free(got32);
   std::free(got16); std::free(rng);
   return 0;
@@ -152,7 +85,7 @@ static int run_bias_act(int64_t N, int64_t K, int dtype, int relu, float p_drop,
   CHECK(ggl_bias_act_bwd(g32, yw, N, K, relu, p_drop, ru, ga32, gb32, ws, wsb, nullptr));
   CHECK(ggl_bias_act_bwd_x16(dtype, g16, y16, N, K, relu, p_drop, ru, ga16, gb16, ws, wsb, nullptr));
   for (size_t i = 0; i < n; ++i) EXPECT(ga16[i] == narrow(dtype, ga32[i]));
-  EXPECT(std::memcmp(gb16, gb32, (size_t)K * 4) == 0);
+  EXPECT(same(gb16, gb32, (size_t)K));
   std::free(a16); std::free(y16); std::free(g16); std::free(ga16); std::free(a32); std::free(y32); std::free(g32);
   std::free(ga32); std::free(yw); std::free(bias); std::free(gb16); std::free(gb32); std::free(rng); std::free(used); std::free(ws);
   return 0;

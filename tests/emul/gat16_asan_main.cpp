@@ -5,93 +5,7 @@
 // once with x, g and out starting ONE element into their blocks (2-byte aligned panels: the element form).
 // Built and run by tests/test_gat16_sanitized.py; exits 0 when every result has the bits of the f32 entry points on the
 // widened rows.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "ggl_mpops.h"
-
-#define CHECK(call)                                                                \
-  do {                                                                             \
-    const int rc_ = (call);                                                        \
-    if (rc_ != GGL_OK) {                                                           \
-      std::fprintf(stderr, "%s -> %d: %s\n", #call, rc_, ggl_last_error());        \
-      return 1;                                                                    \
-    }                                                                              \
-  } while (0)
-#define EXPECT(cond)                                                               \
-  do {                                                                             \
-    if (!(cond)) {                                                                 \
-      std::fprintf(stderr, "line %d: %s is false\n", __LINE__, #cond);             \
-      return 1;                                                                    \
-    }                                                                              \
-  } while (0)
-
-static uint32_t rnd_state = 2463534242u;
-static uint32_t rnd() { return rnd_state = rnd_state * 1664525u + 1013904223u; }
-static float rndf() { return (float)((int)(rnd() >> 8) % 4001 - 2000) / 1024.0f; }
-
-template <typename T>
-static T *block(size_t n) { return static_cast<T *>(std::malloc((n ? n : 1) * sizeof(T))); }
-
-// 16-bit <-> f32 as the library documents them: exact widening, round-to-nearest-even narrowing
-static float widen(int dtype, uint16_t b) {
-  if (dtype == GGL_BF16) {
-    const uint32_t u = (uint32_t)b << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-  }
-  _Float16 h;
-  std::memcpy(&h, &b, 2);
-  return (float)h;
-}
-static uint16_t narrow(int dtype, float f) {
-  if (dtype == GGL_BF16) {
-    uint32_t x;
-    std::memcpy(&x, &f, 4);
-    return (uint16_t)((x + (((x >> 16) & 1u) + 0x7fffu)) >> 16);   // (no NaNs in this program)
-  }
-  const _Float16 h = (_Float16)f;
-  uint16_t b;
-  std::memcpy(&b, &h, 2);
-  return b;
-}
-
-struct Plan {
-  ggl_segplan_t c{};
-  int64_t *rowptr = nullptr, *chunk_ptr = nullptr;
-  int32_t *long_rows = nullptr;
-  void release() { std::free(rowptr); std::free(chunk_ptr); std::free(long_rows); }
-};
-
-static void finish_plan(Plan &p, int64_t N, int64_t E, int64_t chunk) {
-  std::vector<int32_t> lr;
-  std::vector<int64_t> cp{0};
-  for (int64_t r = 0; r < N; ++r) {
-    const int64_t len = p.rowptr[r + 1] - p.rowptr[r];
-    if (len > chunk) {
-      lr.push_back((int32_t)r);
-      cp.push_back(cp.back() + (len + chunk - 1) / chunk);
-    }
-  }
-  p.c.rowptr = p.rowptr;
-  p.c.N = N;
-  p.c.E = E;
-  p.c.chunk = chunk;
-  p.c.n_long = (int64_t)lr.size();
-  p.c.n_chunks = cp.back();
-  if (!lr.empty()) {
-    p.long_rows = block<int32_t>(lr.size());
-    p.chunk_ptr = block<int64_t>(cp.size());
-    std::memcpy(p.long_rows, lr.data(), lr.size() * sizeof(int32_t));
-    std::memcpy(p.chunk_ptr, cp.data(), cp.size() * sizeof(int64_t));
-    p.c.long_rows = p.long_rows;
-    p.c.chunk_ptr = p.chunk_ptr;
-  }
-}
+#include "asan_common.hpp"
 
 // shift = 1: the 16-bit panels start one element into their blocks
 static int run(int64_t N, int64_t E_want, int64_t chunk, int64_t H, int64_t C, int dtype, int out_f32, float p_drop, int shift) {
@@ -151,9 +65,7 @@ static int run(int64_t N, int64_t E_want, int64_t chunk, int64_t H, int64_t C, i
   const float slope = 0.2f;
 
   // ---- forward: F, then the 16-bit entry point
-  const size_t pfb = ggl_gat_partial_bytes(f.c.n_chunks, H, C);
-  f.c.partial = pfb ? std::malloc(pfb) : nullptr;
-  f.c.partial_bytes = pfb;
+  f.set_partial(ggl_gat_partial_bytes(f.c.n_chunks, H, C));
   float *out_f = block<float>(N * K), *rmax_f = block<float>(N * H), *rden_f = block<float>(N * H);
   CHECK(ggl_gat_fused_fwd(&f.c, col, el, er, xf, slope, H, C, p_drop, p_drop > 0 ? rng_f : nullptr, out_f, rmax_f, rden_f,
                           nullptr));
@@ -166,25 +78,21 @@ static int run(int64_t N, int64_t E_want, int64_t chunk, int64_t H, int64_t C, i
   CHECK(ggl_gat_fused_fwd_x16(&f.c, col, el, er, dtype, x16, slope, H, C, p_drop, p_drop > 0 ? rng : nullptr, odt, out, rmax,
                               rden, nullptr));
   if (p_drop > 0) EXPECT(rng[1] == 4 && rng_f[1] == 4);
-  EXPECT(std::memcmp(rmax, rmax_f, N * H * 4) == 0 && std::memcmp(rden, rden_f, N * H * 4) == 0);
+  EXPECT(same(rmax, rmax_f, N * H) && same(rden, rden_f, N * H));
   float *seen = block<float>(N * K);      // the widened output the backward reads
   for (int64_t i = 0; i < N * K; ++i) {
     if (out_f32) {
-      EXPECT(std::memcmp(&static_cast<float *>(out)[i], &out_f[i], 4) == 0);
+      EXPECT(same(&static_cast<float *>(out)[i], &out_f[i], 1));
       seen[i] = out_f[i];
     } else {
       EXPECT(static_cast<uint16_t *>(out)[i] == narrow(dtype, out_f[i]));
       seen[i] = widen(dtype, static_cast<uint16_t *>(out)[i]);
     }
   }
-  std::free(f.c.partial);
 
   // ---- backward: destination walk then source walk, F on (xf, gf, seen), then the 16-bit entry points
-  const size_t pdb = ggl_partial_bytes(GGL_F32, f.c.n_chunks, H, 0), psb = ggl_partial_bytes(GGL_F32, t.c.n_chunks, K + H, 0);
-  f.c.partial = pdb ? std::malloc(pdb) : nullptr;
-  t.c.partial = psb ? std::malloc(psb) : nullptr;
-  f.c.partial_bytes = pdb;
-  t.c.partial_bytes = psb;
+  f.set_partial(ggl_partial_bytes(GGL_F32, f.c.n_chunks, H, 0));
+  t.set_partial(ggl_partial_bytes(GGL_F32, t.c.n_chunks, K + H, 0));
   float *ad_f = block<float>(E * H * 2), *ad = block<float>(E * H * 2);
   float *ger_f = block<float>(N * H), *ger = block<float>(N * H), *gel_f = block<float>(N * H), *gel = block<float>(N * H);
   float *gx_f = block<float>(N * K);
@@ -197,11 +105,9 @@ static int run(int64_t N, int64_t E_want, int64_t chunk, int64_t H, int64_t C, i
   CHECK(ggl_gat_fused_bwd_dst_x16(&f.c, col, el, er, dtype, x16, odt, g_in, odt, out, rmax, rden, slope, H, C, p_drop, ru, ad,
                                   ad + 1, ger, nullptr));
   CHECK(ggl_gat_fused_bwd_src_x16(&t.c, colT, posT, ad, ad + 1, odt, g_in, H, C, dtype, gx, gel, nullptr));
-  EXPECT(std::memcmp(ad, ad_f, E * H * 2 * 4) == 0);
-  EXPECT(std::memcmp(ger, ger_f, N * H * 4) == 0 && std::memcmp(gel, gel_f, N * H * 4) == 0);
+  EXPECT(same(ad, ad_f, E * H * 2));
+  EXPECT(same(ger, ger_f, N * H) && same(gel, gel_f, N * H));
   for (int64_t i = 0; i < N * K; ++i) EXPECT(gx[i] == narrow(dtype, gx_f[i]));
-  std::free(f.c.partial);
-  std::free(t.c.partial);
   for (void *b : {(void *)col, (void *)colT, (void *)posT, (void *)el, (void *)er, (void *)x16b, (void *)g16b, (void *)xf,
                   (void *)gf, (void *)rng, (void *)rng_f, (void *)rng_used, (void *)out_f, (void *)rmax_f, (void *)rden_f,
                   (void *)outb, (void *)rmax, (void *)rden, (void *)seen, (void *)ad_f, (void *)ad, (void *)ger_f, (void *)ger,

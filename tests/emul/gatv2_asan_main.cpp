@@ -6,87 +6,7 @@
 // as the backward walks it: the forward plan with self = xr, other = xl and att_rows, and without att_rows; the transposed
 // plan with self = xl, other = xr, with and without add.  Shapes 1 x 1, 3 x 5 (element form), 2 x 12 and 8 x 8 (16-byte
 // loads).  Built and run by tests/test_gatv2_sanitized.py; exits 0 when every output has the bits of the serial loop below.
-#include <algorithm>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <numeric>
-#include <vector>
-
-#include "ggl_mpops.h"
-
-#define CHECK(call)                                                                \
-  do {                                                                             \
-    const int rc_ = (call);                                                        \
-    if (rc_ != GGL_OK) {                                                           \
-      std::fprintf(stderr, "%s -> %d: %s\n", #call, rc_, ggl_last_error());        \
-      return 1;                                                                    \
-    }                                                                              \
-  } while (0)
-#define EXPECT(cond)                                                               \
-  do {                                                                             \
-    if (!(cond)) {                                                                 \
-      std::fprintf(stderr, "line %d: %s is false\n", __LINE__, #cond);             \
-      return 1;                                                                    \
-    }                                                                              \
-  } while (0)
-
-static uint32_t rnd_state = 2463534242u;
-static uint32_t rnd() { return rnd_state = rnd_state * 1664525u + 1013904223u; }
-static float rndf() { return (float)((int)(rnd() >> 8) % 4001 - 2000) / 1024.0f; }
-
-template <typename T>
-static T *block(size_t n) { return static_cast<T *>(std::malloc((n ? n : 1) * sizeof(T))); }
-
-static bool same(const float *a, const float *b, size_t n) { return std::memcmp(a, b, n * sizeof(float)) == 0; }
-
-struct Plan {
-  ggl_segplan_t c{};
-  int64_t *rowptr = nullptr, *chunk_ptr = nullptr;
-  int32_t *long_rows = nullptr, *perm = nullptr;
-  void release() { std::free(rowptr); std::free(chunk_ptr); std::free(long_rows); std::free(perm); }
-};
-
-// rowptr / perm / long-row table of `ids` (stable sort; perm stays NULL when the ids arrive sorted)
-static void make_plan(Plan &p, const std::vector<int32_t> &ids, int64_t N, int64_t chunk) {
-  const int64_t E = (int64_t)ids.size();
-  std::vector<int32_t> order(E);
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return ids[a] < ids[b]; });
-  p.rowptr = block<int64_t>(N + 1);
-  std::fill(p.rowptr, p.rowptr + N + 1, 0);
-  for (int32_t d : ids) ++p.rowptr[d + 1];
-  for (int64_t r = 0; r < N; ++r) p.rowptr[r + 1] += p.rowptr[r];
-  if (!std::is_sorted(ids.begin(), ids.end())) {
-    p.perm = block<int32_t>(E);
-    std::memcpy(p.perm, order.data(), E * sizeof(int32_t));
-  }
-  std::vector<int32_t> lr;
-  std::vector<int64_t> cp{0};
-  for (int64_t r = 0; r < N; ++r) {
-    const int64_t len = p.rowptr[r + 1] - p.rowptr[r];
-    if (len > chunk) {
-      lr.push_back((int32_t)r);
-      cp.push_back(cp.back() + (len + chunk - 1) / chunk);
-    }
-  }
-  p.c.rowptr = p.rowptr;
-  p.c.perm = p.perm;
-  p.c.N = N;
-  p.c.E = E;
-  p.c.chunk = chunk;
-  p.c.n_long = (int64_t)lr.size();
-  p.c.n_chunks = cp.back();
-  if (!lr.empty()) {
-    p.long_rows = block<int32_t>(lr.size());
-    p.chunk_ptr = block<int64_t>(cp.size());
-    std::memcpy(p.long_rows, lr.data(), lr.size() * sizeof(int32_t));
-    std::memcpy(p.chunk_ptr, cp.data(), cp.size() * sizeof(int64_t));
-    p.c.long_rows = p.long_rows;
-    p.c.chunk_ptr = p.chunk_ptr;
-  }
-}
+#include "asan_common.hpp"
 
 // the documented arithmetic, one (row, head, channel) at a time; volatile keeps every step a rounded f32 operation
 static void serial(const Plan &p, const int32_t *col, const float *other, const float *self, const float *gz, const float *att,
@@ -130,16 +50,13 @@ static int walk(Plan &p, const int32_t *col, const float *other, const float *se
   const int64_t K = H * C;
   const size_t pb = ggl_gatv2_logit_bwd_partial_bytes(p.c.n_chunks, H, C, with_rows ? 1 : 0);
   EXPECT((pb > 0) == (p.c.n_long > 0));
-  p.c.partial = pb ? std::malloc(pb) : nullptr;
-  p.c.partial_bytes = pb;
+  p.set_partial(pb);
   float *g_self = block<float>(N * K), *rows = with_rows ? block<float>(N * K) : nullptr;
   float *w_self = block<float>(N * K), *w_rows = block<float>(N * K);
   CHECK(ggl_gatv2_logit_bwd(&p.c, col, other, self, gz, att, slope, H, C, add, g_self, rows, nullptr));
   serial(p, col, other, self, gz, att, slope, H, C, add, w_self, w_rows);
   EXPECT(same(g_self, w_self, N * K));
   if (with_rows) EXPECT(same(rows, w_rows, N * K));
-  std::free(p.c.partial);
-  p.c.partial = nullptr;
   std::free(g_self); std::free(rows); std::free(w_self); std::free(w_rows);
   return 0;
 }

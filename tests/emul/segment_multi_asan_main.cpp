@@ -6,89 +6,12 @@
 // long rows).  Shapes (K, C) = (20, 5) (one column per lane) and (48, 16) (16-byte lanes), four sets of aggregates, empty_zero
 // both ways.  Built and run by tests/test_segment_multi_sanitized.py; exits 0 when every output has the bits of the serial
 // loop below.
-#include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <numeric>
-#include <vector>
 
-#include "ggl_mpops.h"
+#include "asan_common.hpp"
 
-#define CHECK(call)                                                                \
-  do {                                                                             \
-    const int rc_ = (call);                                                        \
-    if (rc_ != GGL_OK) {                                                           \
-      std::fprintf(stderr, "%s -> %d: %s\n", #call, rc_, ggl_last_error());        \
-      return 1;                                                                    \
-    }                                                                              \
-  } while (0)
-#define EXPECT(cond)                                                               \
-  do {                                                                             \
-    if (!(cond)) {                                                                 \
-      std::fprintf(stderr, "line %d: %s is false\n", __LINE__, #cond);             \
-      return 1;                                                                    \
-    }                                                                              \
-  } while (0)
-
-static uint32_t rnd_state = 2463534242u;
-static uint32_t rnd() { return rnd_state = rnd_state * 1664525u + 1013904223u; }
 static float rndq() { return (float)((int)(rnd() >> 8) % 17 - 8) / 4.0f; }       // many equal values, +0.0 among them
-static float rndf() { return (float)((int)(rnd() >> 8) % 4001 - 2000) / 1024.0f; }
-
-template <typename T>
-static T *block(size_t n) { return static_cast<T *>(std::malloc((n ? n : 1) * sizeof(T))); }
-
-static bool same(const void *a, const void *b, size_t bytes) { return std::memcmp(a, b, bytes) == 0; }
-
-struct Plan {
-  ggl_segplan_t c{};
-  int64_t *rowptr = nullptr, *chunk_ptr = nullptr;
-  int32_t *long_rows = nullptr, *perm = nullptr;
-  void release() { std::free(rowptr); std::free(chunk_ptr); std::free(long_rows); std::free(perm); }
-};
-
-static void make_plan(Plan &p, const std::vector<int32_t> &ids, int64_t N, int64_t chunk) {
-  const int64_t E = (int64_t)ids.size();
-  std::vector<int32_t> order(E);
-  std::iota(order.begin(), order.end(), 0);
-  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return ids[a] < ids[b]; });
-  p.rowptr = block<int64_t>(N + 1);
-  std::fill(p.rowptr, p.rowptr + N + 1, 0);
-  for (int32_t d : ids) ++p.rowptr[d + 1];
-  for (int64_t r = 0; r < N; ++r) p.rowptr[r + 1] += p.rowptr[r];
-  if (!std::is_sorted(ids.begin(), ids.end())) {
-    p.perm = block<int32_t>(E);
-    std::memcpy(p.perm, order.data(), E * sizeof(int32_t));
-  }
-  std::vector<int32_t> lr;
-  std::vector<int64_t> cp{0};
-  for (int64_t r = 0; r < N; ++r) {
-    const int64_t len = p.rowptr[r + 1] - p.rowptr[r];
-    if (len > chunk) {
-      lr.push_back((int32_t)r);
-      cp.push_back(cp.back() + (len + chunk - 1) / chunk);
-    }
-  }
-  p.c.rowptr = p.rowptr;
-  p.c.perm = p.perm;
-  p.c.N = N;
-  p.c.E = E;
-  p.c.chunk = chunk;
-  p.c.n_long = (int64_t)lr.size();
-  p.c.n_chunks = cp.back();
-  if (!lr.empty()) {
-    p.long_rows = block<int32_t>(lr.size());
-    p.chunk_ptr = block<int64_t>(cp.size());
-    std::memcpy(p.long_rows, lr.data(), lr.size() * sizeof(int32_t));
-    std::memcpy(p.chunk_ptr, cp.data(), cp.size() * sizeof(int64_t));
-    p.c.long_rows = p.long_rows;
-    p.c.chunk_ptr = p.chunk_ptr;
-  }
-}
 
 struct Acc { float S, Q, mn, mx; int32_t an, ax; };
 
@@ -178,26 +101,24 @@ static int run_case(Plan &p, int64_t K, int64_t C, const std::vector<int> &aggs,
   for (int64_t i = 0; i < N * A * K; ++i) g[i] = rndf();
   const size_t pb = ggl_segment_multi_partial_bytes(p.c.n_chunks, K, aggs.data(), A);
   EXPECT((pb > 0) == (p.c.n_long > 0));
-  p.c.partial = pb ? std::malloc(pb) : nullptr;
-  p.c.partial_bytes = pb;
+  p.set_partial(pb);
   float *out = block<float>(N * A * K);                                  // exactly N * A * K floats
   float *mean = sq ? block<float>(N * K) : nullptr;
   int32_t *amin = mn ? block<int32_t>(N * K) : nullptr, *amax = mx ? block<int32_t>(N * K) : nullptr;   // exactly N * K int32
   float *gx = block<float>(E * K);
   CHECK(ggl_segment_multi_fwd(x, &p.c, K, C, aggs.data(), A, empty_zero, out, mean, amin, amax, nullptr));
-  std::free(p.c.partial);              // the backward needs no partial buffer
-  p.c.partial = nullptr;
+  p.set_partial(0);                    // the backward needs no partial buffer
   // (x, mean, out and the witnesses are handed over only where the aggs read them)
   CHECK(ggl_segment_multi_bwd(g, sq ? x : nullptr, aggs.end() != std::find(aggs.begin(), aggs.end(), (int)GGL_AGG_STD) ? out : nullptr,
                               mean, amin, amax, &p.c, K, C, aggs.data(), A, gx, nullptr));
   float *w_out = block<float>(N * A * K), *w_mean = block<float>(N * K), *w_gx = block<float>(E * K);
   int32_t *w_amin = block<int32_t>(N * K), *w_amax = block<int32_t>(N * K);
   serial(p, x, K, C, aggs.data(), A, empty_zero, g, w_out, w_mean, w_amin, w_amax, w_gx);
-  EXPECT(same(out, w_out, N * A * K * sizeof(float)));
-  if (mean) EXPECT(same(mean, w_mean, N * K * sizeof(float)));
-  if (amin) EXPECT(same(amin, w_amin, N * K * sizeof(int32_t)));
-  if (amax) EXPECT(same(amax, w_amax, N * K * sizeof(int32_t)));
-  EXPECT(same(gx, w_gx, E * K * sizeof(float)));
+  EXPECT(same(out, w_out, N * A * K));
+  if (mean) EXPECT(same(mean, w_mean, N * K));
+  if (amin) EXPECT(same(amin, w_amin, N * K));
+  if (amax) EXPECT(same(amax, w_amax, N * K));
+  EXPECT(same(gx, w_gx, E * K));
   for (void *b : {(void *)x, (void *)g, (void *)out, (void *)mean, (void *)amin, (void *)amax, (void *)gx, (void *)w_out,
                   (void *)w_mean, (void *)w_gx, (void *)w_amin, (void *)w_amax})
     std::free(b);

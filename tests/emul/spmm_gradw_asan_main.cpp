@@ -2,61 +2,10 @@
 // f16 panels) on the host-emulated kernel sources: gw, the scratch and the 16-bit panels are heap blocks of exactly the
 // documented sizes, so a read or write past an end aborts the run.  Built and run by tests/test_spmm_gradw_sanitized.py;
 // exits 0 when every result equals a plain serial restatement, bit for bit.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include "asan_common.hpp"
 
-#include "ggl_mpops.h"
-
-#define CHECK(call)                                                                \
-  do {                                                                             \
-    const int rc_ = (call);                                                        \
-    if (rc_ != GGL_OK) {                                                           \
-      std::fprintf(stderr, "%s -> %d: %s\n", #call, rc_, ggl_last_error());        \
-      return 1;                                                                    \
-    }                                                                              \
-  } while (0)
-#define EXPECT(cond)                                                               \
-  do {                                                                             \
-    if (!(cond)) {                                                                 \
-      std::fprintf(stderr, "line %d: %s is false\n", __LINE__, #cond);             \
-      return 1;                                                                    \
-    }                                                                              \
-  } while (0)
-
-static uint32_t rnd_state = 2463534242u;
-static uint32_t rnd() { return rnd_state = rnd_state * 1664525u + 1013904223u; }
-static float rndf() { return (float)((int)(rnd() >> 8) % 4001 - 2000) / 1024.0f; }
-
-// exact-size heap blocks (never a zero-byte block's NULL)
+// exactly n bytes (never a zero-byte block's NULL)
 static void *bytes(size_t n) { return std::malloc(n ? n : 1); }
-template <typename T>
-static T *block(size_t n) { return static_cast<T *>(bytes(n * sizeof(T))); }
-
-static float widen(int dtype, uint16_t b) {
-  if (dtype == GGL_BF16) {
-    const uint32_t u = (uint32_t)b << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-  }
-  _Float16 h;
-  std::memcpy(&h, &b, 2);
-  return (float)h;
-}
-static uint16_t narrow(int dtype, float f) {
-  if (dtype == GGL_BF16) {
-    uint32_t x;
-    std::memcpy(&x, &f, 4);
-    return (uint16_t)((x + (((x >> 16) & 1u) + 0x7fffu)) >> 16);   // (no NaNs in this program)
-  }
-  const _Float16 h = (_Float16)f;
-  uint16_t b;
-  std::memcpy(&b, &h, 2);
-  return b;
-}
 
 // a panel of `n` elements of `dtype` in a block of exactly n * size bytes, and its widened values
 static void *panel(int dtype, int64_t n, std::vector<float> &wide) {
@@ -115,7 +64,7 @@ static int run(int64_t N_src, int64_t N_dst, int64_t E, int64_t K, int xd, int g
       acc = acc + prod;
     }
     const float got = gw[perm ? perm[q] : q];
-    EXPECT(std::memcmp(&got, &acc, 4) == 0);
+    EXPECT(same(&got, &acc, 1));
   }
   for (void *b : {(void *)rowptr, (void *)col, (void *)rowidx, (void *)perm, x, g, scratch, (void *)gw}) std::free(b);
   return 0;

@@ -1,35 +1,7 @@
 // A stand-alone AddressSanitizer check of the restricted plan pair (ggl_plan_rows_*) and ggl_bias_grad_rows on the host-emulated
 // kernel sources: every buffer is a heap block of exactly the documented size, so a read or write past an end aborts the run.
 // Built and run by tests/test_spmm_rows_sanitized.py; exits 0 when every result equals a plain serial restatement.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
-#include "ggl_mpops.h"
-
-#define CHECK(call)                                                                \
-  do {                                                                             \
-    const int rc_ = (call);                                                        \
-    if (rc_ != GGL_OK) {                                                           \
-      std::fprintf(stderr, "%s -> %d: %s\n", #call, rc_, ggl_last_error());        \
-      return 1;                                                                    \
-    }                                                                              \
-  } while (0)
-#define EXPECT(cond)                                                               \
-  do {                                                                             \
-    if (!(cond)) {                                                                 \
-      std::fprintf(stderr, "line %d: %s is false\n", __LINE__, #cond);             \
-      return 1;                                                                    \
-    }                                                                              \
-  } while (0)
-
-static uint32_t rnd_state = 12345u;
-static uint32_t rnd() { return rnd_state = rnd_state * 1664525u + 1013904223u; }
-
-// exact-size heap blocks (never a zero-byte vector's NULL data())
-template <typename T>
-static T *block(size_t n) { return static_cast<T *>(std::malloc((n ? n : 1) * sizeof(T))); }
+#include "asan_common.hpp"
 
 static int run(int64_t N, int64_t E_want, const std::vector<int64_t> &rows_v, bool weighted, int64_t K) {
   // a random graph as a CSR pair: forward (grouped by destination) and transposed (grouped by source), ascending inside a row
@@ -136,6 +108,7 @@ static int run(int64_t N, int64_t E_want, const std::vector<int64_t> &rows_v, bo
 }
 
 int main() {
+  rnd_state = 12345u;   // this program's own sequence
   const int64_t N = 300;
   std::vector<int64_t> every, some;
   for (int64_t i = 0; i < N; ++i) {

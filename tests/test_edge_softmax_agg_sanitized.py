@@ -3,22 +3,8 @@ tests/emul/edge_softmax_agg_asan_main.cpp (its own main) is compiled with -fsani
 AddressSanitizer build of the host-emulated kernel sources and run directly.  Every buffer it hands the library is a heap
 block of exactly the documented size (z, gz and alpha exactly E * H floats), on a plan with a perm and long rows both ways
 and on one with sorted ids and no perm, so a read or write past an end ends the run with a report."""
-import os
-import subprocess
-import tempfile
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL = os.path.join(HERE, "emul")
-CXX = os.environ.get("CXX", "/opt/rocm/lib/llvm/bin/clang++")
+from sanitized import run_program
 
 
 def test_edge_softmax_agg_entry_points_sanitized():
-    subprocess.check_call([os.path.join(EMUL, "build_asan.sh")], env=dict(os.environ, CXX=CXX))
-    with tempfile.TemporaryDirectory() as d:
-        exe = os.path.join(d, "edge_softmax_agg_asan")
-        subprocess.check_call([CXX, "-std=c++17", "-O1", "-g", "-fsanitize=address", "-fno-omit-frame-pointer",
-                               "-I", os.path.join(HERE, "..", "include"), os.path.join(EMUL, "edge_softmax_agg_asan_main.cpp"),
-                               "-L", EMUL, "-lggl_emul_asan", "-Wl,-rpath," + EMUL, "-o", exe])
-        r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "cases ok" in r.stdout
+    run_program("edge_softmax_agg")

@@ -4,23 +4,8 @@ of the host-emulated kernel sources and run directly.  Every buffer it hands the
 documented size (gz exactly E * H floats, plan->partial exactly ggl_gatv2_logit_bwd_partial_bytes), on a plan pair with a
 perm and long rows both ways and on one with sorted ids and no perm, so a read or write past an end ends the run with a
 report; every output is compared on the bits with a serial loop in the program."""
-import os
-import subprocess
-import tempfile
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL = os.path.join(HERE, "emul")
-CXX = os.environ.get("CXX", "/opt/rocm/lib/llvm/bin/clang++")
+from sanitized import run_program
 
 
 def test_gatv2_logit_backward_sanitized():
-    subprocess.check_call([os.path.join(EMUL, "build_asan.sh")], env=dict(os.environ, CXX=CXX))
-    with tempfile.TemporaryDirectory() as d:
-        exe = os.path.join(d, "gatv2_asan")
-        subprocess.check_call([CXX, "-std=c++17", "-O1", "-g", "-fsanitize=address", "-fno-omit-frame-pointer",
-                               "-ffp-contract=off", "-I", os.path.join(HERE, "..", "include"),
-                               os.path.join(EMUL, "gatv2_asan_main.cpp"), "-L", EMUL, "-lggl_emul_asan",
-                               "-Wl,-rpath," + EMUL, "-o", exe])
-        r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "cases ok" in r.stdout
+    run_program("gatv2", ("-ffp-contract=off",))

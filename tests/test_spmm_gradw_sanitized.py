@@ -1,25 +1,10 @@
 """gspmm's weight gradient (ggl_spmm_grad_w) under AddressSanitizer, as a stand-alone program:
-tests/emul/spmm_gradw_asan_main.cpp (its own main) is compiled with -fsanitize=address together with the host-emulated
-(-DGGL_EMULATE) kernel sources the entry point lives in — edgedot.hip and plan.hip (options, error text), a few seconds
-instead of the whole emulated library — and run directly.  gw, the scratch (carried chain + mean panel) and the 16-bit
-panels are heap blocks of exactly the documented sizes, so a read or write past an end ends the run with a report."""
-import os
-import subprocess
-import tempfile
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL = os.path.join(HERE, "emul")
-CSRC = os.path.join(HERE, "..", "gammagl_amd", "csrc")
-CXX = os.environ.get("CXX", "/opt/rocm/lib/llvm/bin/clang++")
+tests/emul/spmm_gradw_asan_main.cpp (its own main) is compiled with -fsanitize=address, linked against the AddressSanitizer
+build of the host-emulated kernel sources (the entry point lives in edgedot.hip) and run directly.  gw, the scratch (carried
+chain + mean panel) and the 16-bit panels are heap blocks of exactly the documented sizes, so a read or write past an end ends
+the run with a report."""
+from sanitized import run_program
 
 
 def test_spmm_grad_w_sanitized():
-    with tempfile.TemporaryDirectory() as d:
-        exe = os.path.join(d, "spmm_gradw_asan")
-        subprocess.check_call([CXX, "-DGGL_EMULATE", "-x", "c++", "-std=c++17", "-O1", "-g", "-fsanitize=address",
-                               "-fno-omit-frame-pointer", "-ffp-contract=off", "-Wno-unused-function",
-                               "-I", os.path.join(HERE, "..", "include"), os.path.join(CSRC, "plan.hip"),
-                               os.path.join(CSRC, "edgedot.hip"), os.path.join(EMUL, "spmm_gradw_asan_main.cpp"), "-o", exe])
-        r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "cases ok" in r.stdout
+    run_program("spmm_gradw", ("-ffp-contract=off",))

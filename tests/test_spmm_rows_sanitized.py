@@ -2,22 +2,8 @@
 tests/emul/spmm_rows_asan_main.cpp (its own main) is compiled with -fsanitize=address, linked against the AddressSanitizer
 build of the host-emulated kernel sources and run directly.  Every buffer it hands the library is a heap block of exactly
 the documented size, so a read or write past an end ends the run with a report."""
-import os
-import subprocess
-import tempfile
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL = os.path.join(HERE, "emul")
-CXX = os.environ.get("CXX", "/opt/rocm/lib/llvm/bin/clang++")
+from sanitized import run_program
 
 
 def test_rows_plan_and_bias_grad_rows_sanitized():
-    subprocess.check_call([os.path.join(EMUL, "build_asan.sh")], env=dict(os.environ, CXX=CXX))
-    with tempfile.TemporaryDirectory() as d:
-        exe = os.path.join(d, "spmm_rows_asan")
-        subprocess.check_call([CXX, "-std=c++17", "-O1", "-g", "-fsanitize=address", "-fno-omit-frame-pointer",
-                               "-I", os.path.join(HERE, "..", "include"), os.path.join(EMUL, "spmm_rows_asan_main.cpp"),
-                               "-L", EMUL, "-lggl_emul_asan", "-Wl,-rpath," + EMUL, "-o", exe])
-        r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "cases ok" in r.stdout
+    run_program("spmm_rows")
